@@ -11,6 +11,9 @@ T=100 diffusion steps (+5 without noise), U-Net dim_mults (1,2,4,8), unguided, f
 N>1: the single-context plan does not shard (B=100 does not fill a GPU): N independent replicas, no collective in the
 data path (SURVEY.md 8e "replicas only"); value is the aggregate over ranks.  The path that DOES shard (BASELINE
 configs[4]: independent start/goal contexts, one all-gather at the end) is reported beside it in the `sharded` sub-record.
+A plain run measures the headline only: set-up, W warm-up plans, K timed plans, one result line.  Everything else (the roofline, the
+sub-records, the CPU baseline, bench_full.json) runs with --full.  --dump-outputs DIR writes the chain of the last timed plan (rank 0)
+as DIR/chain.npy; the inputs are seeded, so two builds given the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -1177,6 +1180,23 @@ def emit(out):
 
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, chain):
+    """--dump-outputs: the chain [steps+1, B, H, D] the timed path returned in its last plan, as float32 DIR/chain.npy.  A chain over 64 MB
+    (cfg5: 2.4 GB per rank) is written as a fixed sample of whole trajectories: a seeded choice over the batch axis, in batch order."""
+    import numpy as np
+    import torch
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    if chain.numel() * 4 > DUMP_LIMIT_BYTES:
+        B = chain.shape[1]
+        idx = np.sort(np.random.default_rng(0).choice(B, DUMP_LIMIT_BYTES // (chain[:, 0].numel() * 4), replace=False))
+        chain = chain.index_select(1, torch.from_numpy(idx).to(chain.device))
+    np.save(d / "chain.npy", chain.float().cpu().numpy())
+
+
 def _respawn(args):
     """`python bench.py --gpus N` without a torch.distributed.run environment: start the N ranks ourselves."""
     with socket.socket() as s:
@@ -1196,7 +1216,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the `sharded` / `serving` sub-records")
+    ap.add_argument("--full", action="store_true", help="after the headline: roofline, sub-records and CPU baseline (the --no-* options "
+                    "leave parts out), full record to bench_full.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the chain of the last timed plan (rank 0) to DIR/chain.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         _respawn(args)
@@ -1267,6 +1292,8 @@ def main():
     per_rank_dt = [r[0] for r in _all_ranks(dist, [dt], device)]
     dt = max(per_rank_dt)
     assert chain.shape == (T + n0 + 1, B, 64, D) and bool(torch.isfinite(chain[-1]).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, chain)
 
     steps_per_plan = T + n0
     value = world * args.steps * steps_per_plan / dt
@@ -1295,7 +1322,7 @@ def main():
         finally:
             leg_s[name] = round(time.perf_counter() - t_, 1)
     out["leg_seconds"] = leg_s
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         roof, unet_flops = timed("roofline", roofline_leg, dm, B, T)
         out["roofline"] = roof
         # whole-plan view: algorithmic bytes (weights once per step + 4 tensor passes) and FLOPs
@@ -1311,7 +1338,7 @@ def main():
             for c in roof["classes"]:
                 print(f"# {c['us_per_pass']:9.1f} us {c['share']*100:5.1f}%  {c['launches_per_pass']:3d} launches  {c['tflops']:7.2f} TF/s "
                       f"({c['frac']*100:4.1f}% of peak)  {c['class']}", file=sys.stderr)
-    if not args.no_extras and args.config == "cfg2":
+    if args.full and not args.no_extras and args.config == "cfg2":
         # every rank takes part in the sharded sub-record (it ends in a collective when N > 1).  At N > 1 a watchdog stands behind it:
         # should a collective of this leg never return (first contact with the 8-GPU fabric happens in the driver's run), rank 0 still
         # prints the headline line - already complete above - and every rank exits instead of blocking the driver.
@@ -1358,10 +1385,10 @@ def main():
                                                                "fp32_peak_frac": r.get("roofline", {}).get("frac"), "launch_mode": r.get("launch_mode")}
             except Exception as e:
                 out["training"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = timed("cpu_baseline", cpu_baseline_leg, sd, D, T, B, n0)
         out["speedup_vs_cpu_baseline"] = round(value / out["cpu_baseline"]["value"], 1)
-    elif rank == 0:   # the key is always present: a record consumer must not fail on its shape at N > 1
+    elif rank == 0 and args.full:   # the key is always present: a record consumer must not fail on its shape at N > 1
         out["cpu_baseline"] = None
         out["cpu_baseline_reason"] = ("--no-cpu-baseline" if args.no_cpu_baseline else
                                       "measured on rank 0 at N=1 only (the contract: one bounded CPU sample per box, not one per rank)")
@@ -1369,8 +1396,10 @@ def main():
             out.setdefault(k, None)
         if world > 1:
             out["sub_records_reason"] = "guided / serving / planner_baseline / trained / training are single-GPU sub-records: N=1 only"
-    if rank == 0:
+    if rank == 0 and args.full:
         emit(out)
+    elif rank == 0:   # a plain run: the headline record is the whole result line
+        print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -80,3 +80,21 @@ def test_profile_tools_share_the_bench_fingerprint_function():
     for tool in ("pmc_traffic.py", "kernel_stats_json.py"):
         src = (root / "tools" / tool).read_text()
         assert "bench.csrc_fingerprint()" in src and "hashlib" not in src, tool
+
+
+def test_dump_outputs_writes_the_chain_and_a_fixed_sample_of_a_large_one(tmp_path, monkeypatch):
+    """--dump-outputs: the chain as float32 chain.npy; over the size limit, the same seeded choice of whole trajectories on every call."""
+    import numpy as np
+    import torch
+    import bench
+    chain = torch.arange(6 * 10 * 64 * 4, dtype=torch.float32).reshape(6, 10, 64, 4)
+    bench.dump_outputs(tmp_path / "a", chain)
+    got = np.load(tmp_path / "a" / "chain.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, chain.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * 6 * 64 * 4 * 4)   # room for 3 of the 10 trajectories
+    bench.dump_outputs(tmp_path / "b", chain)
+    bench.dump_outputs(tmp_path / "c", chain)
+    b, c = np.load(tmp_path / "b" / "chain.npy"), np.load(tmp_path / "c" / "chain.npy")
+    assert b.shape == (6, 3, 64, 4) and np.array_equal(b, c)
+    idx = [int(b[0, i, 0, 0]) // (64 * 4) for i in range(3)]
+    assert idx == sorted(set(idx)) and np.array_equal(b, chain.numpy()[:, idx])

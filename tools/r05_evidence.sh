@@ -3,8 +3,8 @@
 # Needs build_ab/libmpdx_dev.so (MPDX_BUILD_DEFS=-DMPDX_DEV_HOOKS build) for the cycle-stamp traces.
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05e; mkdir -p $O
-T0=$(date +%s); timeout 900 python bench.py > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "default bench.py wall: $(( $(date +%s) - T0 )) s" | tee $O/bench_default_wall.txt; tail -1 $O/bench_cfg2.json | cut -c1-200
-for c in cfg3 cfg4 cfg5; do timeout 400 python bench.py --config $c --no-cpu-baseline --no-extras > $O/bench_$c.json 2>/dev/null; tail -1 $O/bench_$c.json | cut -c1-160; done
+T0=$(date +%s); timeout 900 python bench.py --full > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "default bench.py wall: $(( $(date +%s) - T0 )) s" | tee $O/bench_default_wall.txt; tail -1 $O/bench_cfg2.json | cut -c1-200
+for c in cfg3 cfg4 cfg5; do timeout 400 python bench.py --full --config $c --no-cpu-baseline --no-extras > $O/bench_$c.json 2>/dev/null; tail -1 $O/bench_$c.json | cut -c1-160; done
 BENCH="python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-extras"
 BENCH1="python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline --no-extras"
 cd /tmp && export TMPDIR=/tmp
@@ -22,7 +22,7 @@ timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_
 timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$O/pmc5_fetch -- $BENCH1 --config cfg5 > /dev/null 2>&1
 timeout 900 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$O/pmc5_write -- $BENCH1 --config cfg5 > /dev/null 2>&1
 timeout 900 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$O/pmc5_sq -- $BENCH1 --config cfg5 > /dev/null 2>&1
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/prof_default -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras > $GRAFT_REPO_ROOT/$O/default_bench_under_rocprof.json 2>/dev/null
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$O/prof_default -- python $OLDPWD/bench.py --full --no-cpu-baseline --no-extras > $OLDPWD/$O/default_bench_under_rocprof.json 2>/dev/null
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/prof_train -- python -c "
 import sys; sys.path.insert(0, '$GRAFT_REPO_ROOT')
 import bench
@@ -61,8 +61,8 @@ if [ -f build_ab/libmpdx_dev.so ]; then
   MPDX_LIB=build_ab/libmpdx_dev.so timeout 300 python tools/ws_trace.py 6400 2>&1 | grep -v amdgpu > $O/ws_trace.txt
   (MPDX_LIB=build_ab/libmpdx_dev.so timeout 300 python tools/guide_trace.py 6400; MPDX_LIB=build_ab/libmpdx_dev.so timeout 300 python tools/guide_trace.py 100) 2>&1 | grep -v "amdgpu\|Warn" > $O/guide_trace.txt
 fi
-MPDX_BENCH_TABLE=1 timeout 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras 2>&1 >/dev/null | grep "^#" > $O/launch_table.txt
-MPDX_BENCH_TABLE=1 timeout 300 python bench.py --config cfg5 --steps 2 --warmup 1 --no-cpu-baseline --no-extras 2>&1 >/dev/null | grep "^#" > $O/launch_table_cfg5.txt
+MPDX_BENCH_TABLE=1 timeout 300 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras 2>&1 >/dev/null | grep "^#" > $O/launch_table.txt
+MPDX_BENCH_TABLE=1 timeout 300 python bench.py --full --config cfg5 --steps 2 --warmup 1 --no-cpu-baseline --no-extras 2>&1 >/dev/null | grep "^#" > $O/launch_table_cfg5.txt
 timeout 600 python -c "
 import json, bench
 print(json.dumps(bench.planner_baseline_leg(), indent=1))
@@ -70,7 +70,7 @@ print(json.dumps(bench.planner_baseline_leg(), indent=1))
 timeout 300 python tools/gpmp_phase_probe.py 2>&1 | grep "solve=\|sigma_obs" > $O/gpmp_probe.txt
 (python tools/train_enqueue_probe.py; python tools/graph_probe_train.py 32; python tools/graph_probe_train.py 128) 2>&1 | grep -v "amdgpu.ids\|Warn" > $O/train_host_vs_gpu.txt
 # multi-GPU dry run on the single-GPU rig (8 ranks share the GPU over gloo): record shape + sharding / gather / checksum code, no fabric
-timeout 1200 python bench.py --gpus 8 --steps 2 --warmup 1 > $O/bench_rig8_single_gpu.json 2> $O/bench_rig8.err; tail -1 $O/bench_rig8_single_gpu.json | cut -c1-200
+timeout 1200 python bench.py --full --gpus 8 --steps 2 --warmup 1 > $O/bench_rig8_single_gpu.json 2> $O/bench_rig8.err; tail -1 $O/bench_rig8_single_gpu.json | cut -c1-200
 head -4 $O/cfg2_kernel_stats.csv | cut -c1-160
 timeout 2400 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; grep -h "passed\|failed" $O/pytest_gpu.log | tail -3 > $O/pytest_gpu_tail.txt; cat $O/pytest_gpu_tail.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -2 $O/smoke.txt

@@ -3,7 +3,7 @@
 # with the `trained` record and the two-form cpu_baseline, the training records and kernel statistics after the launch merges, the GPU tests, smoke.
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05f; mkdir -p $O
-T0=$(date +%s); timeout 900 python bench.py > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "default bench.py wall: $(( $(date +%s) - T0 )) s" | tee $O/bench_default_wall.txt; tail -1 $O/bench_cfg2.json | cut -c1-200
+T0=$(date +%s); timeout 900 python bench.py --full > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "default bench.py wall: $(( $(date +%s) - T0 )) s" | tee $O/bench_default_wall.txt; tail -1 $O/bench_cfg2.json | cut -c1-200
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/prof_train -- python -c "
 import sys; sys.path.insert(0, '$GRAFT_REPO_ROOT')

@@ -3,7 +3,7 @@
 # planning sources are those tools/r06_evidence_c.sh measured (same fingerprint) - plus the default bench line, the GPU tests and smoke.  Outputs: gpurun_out/r06evd.
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06evd; mkdir -p $O
-T0=$(date +%s); timeout 900 python bench.py > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "default bench.py wall: $(( $(date +%s) - T0 )) s" | tee $O/bench_default_wall.txt; cp bench_full.json $O/bench_cfg2_full.json; tail -1 $O/bench_cfg2.json | cut -c1-200; wc -c $O/bench_cfg2.json
+T0=$(date +%s); timeout 900 python bench.py --full > $O/bench_cfg2.json 2> $O/bench_cfg2.err; echo "default bench.py wall: $(( $(date +%s) - T0 )) s" | tee $O/bench_default_wall.txt; cp bench_full.json $O/bench_cfg2_full.json; tail -1 $O/bench_cfg2.json | cut -c1-200; wc -c $O/bench_cfg2.json
 cd /tmp && export TMPDIR=/tmp
 for spec in "train 32 4 1" "train128 128 14 1" "train512 512 14 1" "train128_three_level 128 14 0"; do set -- $spec
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/prof_$1 -- python -c "
