@@ -13,6 +13,7 @@
  *     the hipStream_t it is given (void* here so that the header needs no HIP include).
  *   - tensors are contiguous fp32 row-major.  Trajectories are [B, H, D] exactly as the reference's x.
  *   - one handle per model; a handle is host-side metadata only (layer table, offsets); not thread-safe per handle.
+ *   - the MPDX_* environment switches the library reads are listed in INTEGRATION.md section F (csrc/switches.hpp); none is needed.
  */
 #ifndef MPDX_H
 #define MPDX_H

@@ -24,6 +24,7 @@
 #include "conv_block.hpp"
 #include "conv_ws.hpp"
 #include "fused_level.hpp"
+#include "switches.hpp"
 #include "train_types.hpp"
 
 namespace mpdx {
@@ -36,7 +37,6 @@ int fail(int code, const char* fmt, ...);
         if (e_ != hipSuccess) return ::mpdx::fail((int)e_, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 int raise_lds_limit(const void* kern);   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel)
-int debug_level();                       // MPDX_DEBUG
 
 // final_conv[1] (Conv1d(32 -> D, k=1), temporal_unet.py:113-116) fused with the DDPM posterior step
 // (diffusion_model_base.py:121-155, sample_functions.py:31-62) and hard conditioning (sample_functions.py:5-8).

@@ -20,7 +20,7 @@ static int launch_conv(const ConvArgs& a, hipStream_t st) {
 static bool geo_l8(const Layer& l, const ConvArgs& a) {
     return l.mode == CONV_S1 && l.L_in == 8 && l.L_out == 8 && l.cin_pad == l.c1 + l.c2 && !(l.c1 & 3) && !(l.c2 & 3) && a.rs == l.cin_pad + 8 &&
            (l.cin_pad == 128 || l.cin_pad == 256 || l.cin_pad == 512) && !a.dbg && !(a.Lv_out > 0 && a.Lv_out < l.L_out) &&
-           !(getenv("MPDX_GEO") && atoi(getenv("MPDX_GEO")) == 0);   // MPDX_GEO=0: the runtime-geometry kernels (development A/B)
+           sw::geo();
 }
 template <int NC16, int MT, int NT, int TBRES>
 static int launch_geo_gn(const ConvArgs& a, hipStream_t st) {
@@ -101,7 +101,7 @@ int launch_conv_layer(const Layer& l, ConvArgs& a, int B, hipStream_t st) {
     if (l.mode == CONV_UPT && l.ks == 4) {
         // Upsample1d of the innermost up level (C -> C, 8 -> 16 positions) with compile-time geometry, where instantiated
         if (l.L_in == 8 && l.L_out == 16 && l.cin_pad == l.c1 && l.c2 == 0 && !(l.c1 & 3) && a.rs == l.cin_pad + 4 && !a.dbg && !a.pre && !a.accum && !a.dst2 &&
-            !(a.Lv_out > 0 && a.Lv_out < l.L_out) && !(getenv("MPDX_GEO") && atoi(getenv("MPDX_GEO")) == 0)) {
+            !(a.Lv_out > 0 && a.Lv_out < l.L_out) && sw::geo()) {
             int MT, NT;
             choose_tile(l, B, MT, NT);
             if (l.cout % MT) MT = 16;

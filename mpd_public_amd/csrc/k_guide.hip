@@ -38,7 +38,7 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
     if (gp->clip_grad && gp->clip_rule != 0 && gp->clip_rule != 1) return fail(MPDX_E_INVALID, "clip_rule %d (0 = 'norm', 1 = 'value')", gp->clip_rule);
     a.trace = g_guide_trace;
     // Panda at large batch: the dense variant (no FK table, 128 VGPRs: two workgroups per CU); MPDX_GUIDE_DENSE=0/1 forces it off / on
-    static const int dense_env = getenv("MPDX_GUIDE_DENSE") ? atoi(getenv("MPDX_GUIDE_DENSE")) : -1;
+    const int dense_env = sw::guide_dense();
     const bool dense = gp->robot == MPDX_ROBOT_PANDA && (dense_env >= 0 ? dense_env != 0 : B >= 512) && guide_lds_bytes(*gp, H, D, true) <= 80 * 1024;
     const size_t lds = guide_lds_bytes(*gp, H, D, dense);
     if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "guide needs %zu B of LDS (n_interp %d too large)", lds, gp->n_interp);

@@ -61,7 +61,7 @@ int launch_weight_stationary(int variant, const Layer& l, ConvArgs& a, const Con
             return launch_wsn_t<CONV_S1, 0>(l, a, B, st);
         case 5: return launch_wsn_t<CONV_UPT, 0>(l, a, B, st);
         case 1: {   // 32-position tiles (one duty wave on every SIMD) from 16 tiles per workgroup on
-            static const int ns_env = getenv("MPDX_WS_NS") ? atoi(getenv("MPDX_WS_NS")) : 0;   // dev A/B: 1 / 2 force the tile
+            const int ns_env = sw::ws_ns();   // dev A/B: 1 / 2 force the tile
             const bool big = ns_env ? ns_env == 2 : (long)B * l.L_out >= 32L * kWsGroups * 16;
             if (big && conv_ws_lds_bytes<16, 32, false, 2>(l.L_out, a.rs) <= 160 * 1024) return launch_ws<16, 32, false, 2>(l, a, a2, B, st);
             return launch_ws<16, 32, false>(l, a, a2, B, st);

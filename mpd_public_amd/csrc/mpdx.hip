@@ -30,13 +30,6 @@ int raise_lds_limit(const void* kern) {
     return 0;
 }
 
-// MPDX_DEBUG=1: check hipGetLastError() after every launch group of mpdx_plan (2: also synchronise the stream there, so
-// that an asynchronous fault is attributed to the step that caused it).  Off by default: the plan never synchronises.
-int debug_level() {
-    static const int lv = getenv("MPDX_DEBUG") ? atoi(getenv("MPDX_DEBUG")) : 0;
-    return lv;
-}
-
 static long long* g_conv_trace = nullptr;   // dev tool (mpdx_layer_trace)
 static thread_local int g_plan_chains = 1;  // > 1 while mpdx_plan enqueues a plan as that many concurrent sub-batch chains (tile choice)
 
@@ -467,9 +460,13 @@ static void build_model(mpdx_unet* u) {
 // ------------------------------------------------------------------------------------------------ fused segments
 // Try to turn layers [i0, i1) (an outer U-Net level: 2 residual blocks + resample [+ final_conv[0]]) into one
 // fused_level_kernel program.  Returns false (and leaves the per-layer path) if any shape constraint fails.
-// MPDX_DEBUG_FUSE=1 prints which shape constraint rejected a fused segment (dev aid)
+// MPDX_DEBUG_FUSE: 0 not set, 1 set (the segments built and the shape constraint that rejected one), 2 a value >= 2 (their LDS geometry too)
+static int debug_fuse_level() {
+    const char* e = sw::debug_fuse();
+    return !e ? 0 : (atoi(e) >= 2 ? 2 : 1);
+}
 static bool fuse_reject(int line) {
-    if (getenv("MPDX_DEBUG_FUSE")) fprintf(stderr, "[mpdx] fused segment rejected at mpdx.hip:%d\n", line);
+    if (debug_fuse_level()) fprintf(stderr, "[mpdx] fused segment rejected at mpdx.hip:%d\n", line);
     return false;
 }
 
@@ -599,7 +596,7 @@ static bool build_fused_segment(mpdx_unet* u, int i0, int i1, bool with_final) {
             const Layer* cc = cat_consumer(i + 1, l.dst, l.L_out);
             if (cc) {   // this op's output is the head of a concat: make the buffer wide enough for the skip tensor behind it
                 if (cat_buf >= 0 || cc->c1 != l.cout || (cc->c2 & 3) || (l.cout & 3) || (size_t)cc->L_in * (cc->c2 / 4) > 1024) {
-                    if (getenv("MPDX_DEBUG_FUSE")) fprintf(stderr, "[mpdx] cat: layer %s -> %s cat_buf %d c1 %d c2 %d cout %d L %d\n", l.name.c_str(), cc->name.c_str(), cat_buf, cc->c1, cc->c2, l.cout, cc->L_in);
+                    if (debug_fuse_level()) fprintf(stderr, "[mpdx] cat: layer %s -> %s cat_buf %d c1 %d c2 %d cout %d L %d\n", l.name.c_str(), cc->name.c_str(), cat_buf, cc->c1, cc->c2, l.cout, cc->L_in);
                     return fuse_reject(__LINE__);
                 }
                 ho.dst = buf_for(l.dst, l.L_out, cc->c1 + cc->c2);
@@ -749,8 +746,7 @@ static bool build_fused_segment(mpdx_unet* u, int i0, int i1, bool with_final) {
             for (int k = 0; k < n; ++k) if (a.ops[k].shape != ids[k]) return false;
             return true;
         };
-        static const bool off = getenv("MPDX_STATIC_PROGRAMS") && atoi(getenv("MPDX_STATIC_PROGRAMS")) == 0;
-        if (!off) {
+        if (sw::static_programs()) {
             if (matches(FusedSeqDown::ids, FusedSeqDown::N)) f.program = 0;
             else if (matches(FusedSeqUpA::ids, FusedSeqUpA::N)) f.program = 1;
             else if (matches(FusedSeqUpB::ids, FusedSeqUpB::N)) f.program = 2;
@@ -763,12 +759,12 @@ static bool build_fused_segment(mpdx_unet* u, int i0, int i1, bool with_final) {
             const int sdim = u->cfg.state_dim;
             if ((f.program == 0 && !fused_geom_matches(a, GeomDown::g, sdim)) || (f.program == 3 && !fused_geom_matches(a, GeomUpAB::g, sdim)) ||
                 (f.program == 5 && !fused_geom_matches(a, GeomDown3::g, sdim)) || (f.program == 6 && !fused_geom_matches(a, GeomMid3::g, sdim))) {
-                if (getenv("MPDX_DEBUG_FUSE")) fprintf(stderr, "[mpdx] fused segment: geometry differs from the table of program %d -> generic kernel\n", f.program);
+                if (debug_fuse_level()) fprintf(stderr, "[mpdx] fused segment: geometry differs from the table of program %d -> generic kernel\n", f.program);
                 f.program = -1;
             }
         }
     }
-    if (getenv("MPDX_DEBUG_FUSE") && atoi(getenv("MPDX_DEBUG_FUSE")) >= 2) {   // dev: the segment's LDS geometry as a fused_geom.hpp initialiser
+    if (debug_fuse_level() >= 2) {   // dev: the segment's LDS geometry as a fused_geom.hpp initialiser
         fprintf(stderr, "// program %d: layers [%d,%d) %s..%s, LDS %zu B\n{ %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, {\n", f.program, i0, i1,
                 u->layers[i0].name.c_str(), u->layers[i1 - 1].name.c_str(), f.lds_bytes, a.nops, a.in_off4, a.in_rs4, a.in_rows, a.L0,
                 (a.gc1 == u->cfg.state_dim && a.gc2 == 0) ? -1 : a.gc1, a.gc2, a.c3, a.L3, a.s3_off4, a.s3_rs4, a.s3_col4, a.stat_off, a.par_off, with_final ? -1 : a.par_floats, a.tt_off,
@@ -781,7 +777,7 @@ static bool build_fused_segment(mpdx_unet* u, int i0, int i1, bool with_final) {
         fprintf(stderr, "}},\n");
     }
     u->fused.push_back(f);
-    if (getenv("MPDX_DEBUG_FUSE"))
+    if (debug_fuse_level())
         fprintf(stderr, "[mpdx] fused segment %zu: layers [%d,%d) %s..%s  %d ops  %zu buffers  LDS %zu B  streams+params %zu floats  program %d\n",
                 u->fused.size() - 1, i0, i1, u->layers[i0].name.c_str(), u->layers[i1 - 1].name.c_str(), a.nops, bufs.size(), f.lds_bytes,
                 area - (size_t)a.ops[0].sbase, u->fused.back().program);
@@ -799,6 +795,7 @@ static void build_units(mpdx_unet* u) {
     };
     std::vector<int> owner(n, -1);
     if (u->masked()) { u->owner = owner; return; }   // a horizon in a zero-padded container: every layer as its own (masking) launch
+    const bool merge = !sw::no_merge();
     auto try_seg = [&](const std::string& prefix, bool with_final) {
         int i0, i1;
         if (!range_of(prefix, i0, i1)) return;
@@ -814,7 +811,7 @@ static void build_units(mpdx_unet* u) {
     // levels downs.0 + downs.1 + downs.2 (15 ops; measured cfg 2 23.10 -> 22.47 ms, cfg 5 shard 624 -> 617 ms against two programs;
     // MPDX_MERGE_DOWN3=0 keeps them apart), else downs.0 + downs.1
     bool merged_down = false;
-    if (nl >= 4 && !getenv("MPDX_NO_MERGE") && !(getenv("MPDX_MERGE_DOWN3") && atoi(getenv("MPDX_MERGE_DOWN3")) == 0)) {
+    if (nl >= 4 && merge && sw::merge_down3()) {
         int a0, a1, b0, b1, c0, c1;
         if (range_of("downs.0.", a0, a1) && range_of("downs.1.", b0, b1) && range_of("downs.2.", c0, c1) && a1 == b0 && b1 == c0 &&
             build_fused_segment(u, a0, c1, false)) {
@@ -822,7 +819,7 @@ static void build_units(mpdx_unet* u) {
             merged_down = true;
         }
     }
-    if (!merged_down && nl >= 3 && !getenv("MPDX_NO_MERGE")) {
+    if (!merged_down && nl >= 3 && merge) {
         int a0, a1, b0, b1;
         if (range_of("downs.0.", a0, a1) && range_of("downs.1.", b0, b1) && a1 == b0 && build_fused_segment(u, a0, b1, false)) {
             for (int i = a0; i < b1; ++i) owner[i] = (int)u->fused.size() - 1;
@@ -834,10 +831,10 @@ static void build_units(mpdx_unet* u) {
         if (nl >= 3) try_seg("downs.1.", false);
     }
     // the third down level (C = 128, L = 16: two tile rows per wave) as its own program
-    if (nl >= 4 && !getenv("MPDX_NO_MID2")) try_seg("downs.2.", false);
+    if (nl >= 4 && !sw::no_mid2()) try_seg("downs.2.", false);
     // three levels: the innermost level (no Downsample1d) and the two middle blocks - eight Conv1dBlocks of 128 channels on L / 4 positions - as ONE
     // program (round 6; they were nine launches of ~4.8 us: a training iteration at batch 32 spent 43 us there).  MPDX_NO_MID3=1: per layer as before
-    if (nl == 3 && !getenv("MPDX_NO_MID3")) {
+    if (nl == 3 && !sw::no_mid3()) {
         int a0, a1, b0, b1, c0, c1;
         bool free_ = range_of("downs.2.", a0, a1) && range_of("mid_block1.", b0, b1) && range_of("mid_block2.", c0, c1) && a1 == b0 && b1 == c0;
         for (int i = a0; free_ && i < c1; ++i) free_ = owner[i] < 0;
@@ -846,7 +843,7 @@ static void build_units(mpdx_unet* u) {
     }
     // the two outer up levels + final_conv + DDPM step as ONE program (the second level's skip tensor is staged by the prologue)
     bool merged_up = false;
-    if (nl >= 3 && !getenv("MPDX_NO_MERGE_UP") && !getenv("MPDX_NO_MERGE")) {
+    if (nl >= 3 && !sw::no_merge_up() && merge) {
         int a0, a1, b0, b1;
         if (range_of("ups." + std::to_string(nl - 3) + ".", a0, a1) && range_of("ups." + std::to_string(nl - 2) + ".", b0, b1) && a1 == b0 &&
             b1 == n - 1 && u->layers[n - 1].name.compare(0, 12, "final_conv.0") == 0 && build_fused_segment(u, a0, n, true)) {
@@ -871,8 +868,7 @@ void choose_tile(const Layer& l, int B, int& MT, int& NT) {
     const int min_mt = (l.epi == EPI_GN_MISH && l.gs > 16) ? 32 : 16;
     const int min_nt = std::max(l.mode == CONV_UPT ? 32 : 16, l.L_out);
     const long npos = (long)B * l.L_out;
-    static const char* ov = getenv("MPDX_TILE");
-    if (ov) {
+    if (const char* ov = sw::tile()) {
         int mt = 0, nt = 0;
         if (sscanf(ov, "%dx%d", &mt, &nt) == 2 && mt >= min_mt && nt >= min_nt && l.cout % mt == 0 && nt % l.L_out == 0) { MT = mt; NT = nt; return; }
     }
@@ -881,8 +877,7 @@ void choose_tile(const Layer& l, int B, int& MT, int& NT) {
         MT = (min_mt <= 16 && l.cout % 16 == 0) ? 16 : 32;
         return;
     }
-    static const int target_env = getenv("MPDX_TARGET_WGS") ? atoi(getenv("MPDX_TARGET_WGS")) : 160;
-    const int target = std::max(1, target_env / g_plan_chains);   // concurrent sub-batch chains of a plan share the CUs
+    const int target = std::max(1, sw::target_wgs() / g_plan_chains);   // concurrent sub-batch chains of a plan share the CUs
     auto wgs = [&](int mt, int nt) { return (long)(l.cout / mt) * ((npos + nt - 1) / nt); };
     const int pad = (l.mode == CONV_S1) ? l.ks / 2 : 1;
     auto lds = [&](int mt, int nt) {  // max(staged windows, K-partial buffer), as conv_block_lds_bytes
@@ -893,7 +888,7 @@ void choose_tile(const Layer& l, int B, int& MT, int& NT) {
     const int mts[2] = {32, 16}, nts[3] = {64, 32, 16};
     // largest tile that fits LDS (<= 96 KiB so that a second workgroup can co-reside; MPDX_LDS_CAP_KB overrides) and still
     // yields >= target workgroups; else the smallest legal tile
-    static const size_t cap = (size_t)(getenv("MPDX_LDS_CAP_KB") ? atoi(getenv("MPDX_LDS_CAP_KB")) : 96) * 1024;
+    const size_t cap = (size_t)sw::lds_cap_kb() * 1024;
     for (int nt : nts)
         for (int mt : mts) {
             if (mt < min_mt || nt < min_nt || l.cout % mt || lds(mt, nt) > cap) continue;
@@ -906,8 +901,7 @@ void choose_tile(const Layer& l, int B, int& MT, int& NT) {
 static int layer_ntap(const Layer& l) { return l.mode == CONV_UPT ? 2 : l.ks; }
 bool layer_ksplit(const Layer& l) {
     if (!(l.mode == CONV_S1 && l.ks == 5 && l.epi == EPI_GN_MISH)) return true;
-    static const int forced = getenv("MPDX_KSPLIT") ? atoi(getenv("MPDX_KSPLIT")) : -1;   // dev: 0 = (NT/16) x (8/(NT/16)) waves, 1 = 1 x 8
-    if (forced >= 0) return forced != 0;
+    if (const int forced = sw::ksplit(); forced >= 0) return forced != 0;
     return (l.cin_pad / 16) * layer_ntap(l) >= 16;  // enough K to feed 8 K-split waves
 }
 static double layer_flops(const Layer& l, int B) {
@@ -946,16 +940,13 @@ static int make_conv_args(const mpdx_unet* u, const Layer& l, const float* packe
 // residual 1x1 conv l2: 3 <32,16,R1> (512 -> 128 on a channel concat).  Measured and NOT used (rocprofv3, B = 6400, us per launch,
 // weight-stationary vs per-layer kernels): 128 -> 128 <8,16>: 142.7 vs 95.9; 128 -> 256 + 1x1 <8,32,R1>: 268 vs 234 - with 5 k-groups per
 // wave a tile's 20-40 MFMAs per wave do not cover its barrier and window hand-over; kept: 256 -> 256: 319 vs 332, 512 -> 128 + 1x1: 387 vs 468.
-constexpr int kWsnMinB = 512, kWspMinB = 512;   // (set from the sweep)
 static int weight_stationary_variant(const Layer& l, const Layer* l2, const ConvArgs& a, int B, int dbg) {
-    const char* wsn = getenv("MPDX_WSN");   // dev A/B: 0 = the 128-channel layers stay on the per-layer kernels
+    const int ws_env = sw::ws();   // 0: off, 2: single layers only
     // conv_wsn / conv_wsp load a wave's WHOLE weight slice in their prologue (40-48 KB per wave, ~10 us per launch): they pay from a few tiles per
-    // wave on - batch thresholds from tools/wsn_threshold_sweep.py (profiles/r05_wsn_threshold_sweep.txt); MPDX_WSN_MIN_B / MPDX_WSP_MIN_B override
-    static const int wsn_min_b = getenv("MPDX_WSN_MIN_B") ? atoi(getenv("MPDX_WSN_MIN_B")) : kWsnMinB;
-    static const int wsp_min_b = getenv("MPDX_WSP_MIN_B") ? atoi(getenv("MPDX_WSP_MIN_B")) : kWspMinB;
-    const bool ws_env_on = !(getenv("MPDX_WS") && atoi(getenv("MPDX_WS")) == 0);
-    const bool wsn_on = !(wsn && atoi(wsn) == 0) && ws_env_on && B >= wsn_min_b;
-    const bool wsp_on = ws_env_on && B >= wsp_min_b && !(getenv("MPDX_WSP") && atoi(getenv("MPDX_WSP")) == 0);
+    // wave on - batch thresholds (512, MPDX_WSN_MIN_B / MPDX_WSP_MIN_B) from tools/wsn_threshold_sweep.py (profiles/r05_wsn_threshold_sweep.txt)
+    const int wsn_min_b = sw::wsn_min_b(), wsp_min_b = sw::wsp_min_b();
+    const bool wsn_on = sw::wsn() && ws_env != 0 && B >= wsn_min_b;
+    const bool wsp_on = ws_env != 0 && B >= wsp_min_b && sw::wsp();
     // Upsample1d(128) of the innermost up level, 8 -> 16 positions: conv_wsn_kernel<CONV_UPT> (round 5)
     if (l.mode == CONV_UPT && l.ks == 4 && l.epi == EPI_BIAS && !l2 && l.L_in == 8 && l.L_out == 16 && !l.Lv_out && l.c1 == 128 && l.c2 == 0 &&
         l.cin_pad == 128 && l.cout == 128 && !dbg && !a.pre && !a.accum && !a.dst2 && wsn_on && (long)B * 8 >= 16L * kWsGroups * 8)
@@ -963,9 +954,7 @@ static int weight_stationary_variant(const Layer& l, const Layer* l2, const Conv
     if (!(l.mode == CONV_S1 && l.ks == 5 && l.epi == EPI_GN_MISH && l.L_out == 8 && l.L_in == 8) || l.Lv_out) return 0;
     if (dbg || a.pre || (l.c1 & 3) || (l.c2 & 3) || l.cin_pad != l.c1 + l.c2) return 0;
     if ((long)B * l.L_out < 16L * kWsGroups * 8) return 0;
-    const char* e = getenv("MPDX_WS");
-    if (e && atoi(e) == 0) return 0;
-    if (l2 && e && atoi(e) == 2) return 0;   // dev A/B: 2 = single layers only
+    if (ws_env == 0 || (l2 && ws_env == 2)) return 0;
     if (l2) {
         if (!(l2->mode == CONV_S1 && l2->ks == 1 && l2->epi == EPI_BIAS && l2->cout == l.cout && l2->L_out == 8 && l2->c1 == l.c1 && l2->c2 == l.c2)) return 0;
         if (l.cout == 128 && l.gs == 16 && l.cin_pad == 512) return 3;
@@ -989,8 +978,7 @@ static int run_layer(const mpdx_unet* u, const Layer& l, const float* packed, co
 
 // blocks[0] + residual 1x1 conv of one ResidualTemporalBlock qualify for ONE launch (conv_pair_kernel)?  On success the tile.
 bool pair_tile(const Layer& l1, const Layer& l2, int B, int& MT, int& NT) {
-    static const bool off = getenv("MPDX_PAIR") && atoi(getenv("MPDX_PAIR")) == 0;
-    if (off) return false;
+    if (!sw::pair()) return false;
     if (!(l1.mode == CONV_S1 && l1.ks == 5 && l1.epi == EPI_GN_MISH && l2.mode == CONV_S1 && l2.ks == 1 && l2.epi == EPI_BIAS)) return false;
     if ((l1.gs * l1.L_out != 128 && l1.gs * l1.L_out != 256) || l1.Lv_out) return false;   // general / masked GroupNorm regions: no paired instantiations
     if (l1.src1 != l2.src1 || l1.src2 != l2.src2 || l1.cout != l2.cout || l1.L_out != l2.L_out || !layer_ksplit(l1)) return false;
@@ -1029,12 +1017,7 @@ int check_ready(const mpdx_unet* u) {
 // B~600.)  MPDX_FUSED=0/1 forces none/all, MPDX_FUSED_MASK=<bits> selects segments.
 unsigned fused_mask(int B) {
     (void)B;
-    // read on every call (two getenv per pass): tests and A/B runs switch the path inside one process
-    const char* f = getenv("MPDX_FUSED");
-    const char* m = getenv("MPDX_FUSED_MASK");
-    if (f && atoi(f) == 0) return 0u;
-    if (m) return (unsigned)strtoul(m, nullptr, 0);
-    return ~0u;
+    return sw::fused() ? sw::fused_mask() : 0u;   // both live: tests and A/B runs switch the path inside one process
 }
 // launch units for batch B
 static std::vector<mpdx_unet::Unit> current_units(const mpdx_unet* u, int B, bool* final_in_fused) {
@@ -1448,8 +1431,7 @@ static int plan_side(mpdx_unet* u, mpdx_unet::PlanSide** out) {   // the handle'
 }
 // trajectories of the first chain (0: one chain - the default).  MPDX_PLAN_CHAINS=2 switches the split on (development A/B).
 static int plan_split_point(int B, int npc, int n_ctx) {
-    static const int forced = getenv("MPDX_PLAN_CHAINS") ? atoi(getenv("MPDX_PLAN_CHAINS")) : 0;
-    if (forced != 2 || B < 16) return 0;
+    if (sw::plan_chains() != 2 || B < 16) return 0;
     if (n_ctx >= 2) return (n_ctx / 2) * npc;     // whole contexts per chain: the range-test flags stay per chain
     return std::min(B - 4, ((B / 2) + 3) & ~3);   // one context: both chains publish into its one flag (atomicMax)
 }
@@ -1470,7 +1452,7 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
     const int steps = T + n_without_noise;
     if (n_guide_steps < 0) return fail(MPDX_E_INVALID, "n_guide_steps %d", n_guide_steps);
     if (n_guide_steps == 0) guide = nullptr;   // range(0): the reference runs no guide iteration (sample_functions.py:74)
-    const int dbg = debug_level();
+    const int dbg = sw::debug();
     if (guide) {
         if (!guide_flags) return fail(MPDX_E_INVALID, "guide needs guide_flags");
         if (B % npc) return fail(MPDX_E_INVALID, "B=%d is not a multiple of n_per_ctx=%d", B, npc);

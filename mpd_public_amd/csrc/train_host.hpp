@@ -111,6 +111,24 @@ static size_t wgrad_splits(int M, int N, int B) {
     const int per = (B + S - 1) / S;
     return (size_t)((B + per - 1) / per);
 }
+// make_wgrad's `sdiv` (a divisor of wgrad_splits' count; negative: a multiplier) for the weight gradients that run behind the backward chain, and
+// for the backward programs' layers.  MPDX_WGRAD_LATE_DIV, clamped to >= 1, overrides both rules.
+static int wgrad_late_div_override() {   // 0: not set
+    const int v = sw::wgrad_late_div();
+    return v == sw::kUnset ? 0 : std::max(1, v);
+}
+// fewer batch splits for the weight gradients that run behind the chain (measured, profiles/r06_train_late_div_ab.txt: batch 128 x D = 14 0.898 / 0.84 / 0.82 /
+// 0.81 ms with 1 / 4 / 8 / 16; batch 512 2.027 / 1.94 / 1.96 / 2.01): 8 up to batch 128, 4 beyond
+static int wgrad_late_sdiv(int B) {
+    if (const int o = wgrad_late_div_override()) return o;
+    return B < 64 ? 4 : (B <= 128 ? 8 : 4);
+}
+// the backward programs' layers: the same rule from batch 64 on; below, 4 (measured with the host out of the way, profiles/r06_train_b32_split_ab.txt) unless
+// MPDX_WGRAD_PROG_MUL > 1 asks for up to 4 x MORE splits there
+static int wgrad_prog_sdiv(int B) {
+    const int late_div_env = wgrad_late_div_override(), small_mul = sw::wgrad_prog_mul();
+    return late_div_env ? late_div_env : (B >= 64 ? (B <= 128 ? 8 : 4) : (small_mul > 1 ? -std::min(small_mul, 4) : 4));
+}
 static TrainWs train_ws(const mpdx_unet* u, int B) {
     TrainWs w;
     const size_t n = u->layers.size();
@@ -149,8 +167,7 @@ static TrainWs train_ws(const mpdx_unet* u, int B) {
         tot += wgrad_splits(D, u->cfg.unet_input_dim, B) * D * (size_t)u->cfg.unet_input_dim;
         if (B < 64) tot *= 4;   // (the backward programs' layers may take up to 4 x the rule's splits at small batches: MPDX_WGRAD_PROG_MUL <= 4)
         pv += (size_t)(256 + 64) * D;
-        static const bool off = getenv("MPDX_TRAIN_DEFERRED") && atoi(getenv("MPDX_TRAIN_DEFERRED")) == 0;
-        w.deferred = !off && tot <= ((size_t)96 << 20);   // floats
+        w.deferred = sw::train_deferred() && tot <= ((size_t)96 << 20);   // floats
         w.wparts = take(w.deferred ? tot : 4);
         w.pvecs = take(w.deferred ? pv : 4);
     }
@@ -228,8 +245,7 @@ static int make_wgrad(const float* A, int LA, int lda, int a_off, int M, const f
 }
 // let a (deferred) weight-gradient job add up its convolution's bias gradient too: true if attached (else the caller runs launch_rowsum)
 static bool attach_bias(WgradJob& j, Deferred* df, float* gbias, bool from_b) {
-    static const bool off = getenv("MPDX_TRAIN_BIAS_FOLD") && atoi(getenv("MPDX_TRAIN_BIAS_FOLD")) == 0;   // dev A/B switch
-    if (off || !df || !df->on || !j.deferred || df->col.n >= 120) return false;
+    if (!sw::train_bias_fold() || !df || !df->on || !j.deferred || df->col.n >= 120) return false;
     const int C = from_b ? j.a.N : j.a.M;
     j.a.bias_part = df->ws + df->pcur;
     j.a.bias_from_b = from_b ? 1 : 0;
@@ -264,8 +280,7 @@ static int launch_wgrad(const float* A, int LA, int lda, int a_off, int M, const
 
 // two wave groups per weight-gradient block inside bwd_pair_kernel's 512-thread workgroups (train.hpp wgrad_body, ngrp = 2): shapes of the prefetching loop
 static bool wgrad_two_groups(const WgradJob& j) {
-    static const bool off = getenv("MPDX_WGRAD_TWO") && atoi(getenv("MPDX_WGRAD_TWO")) == 0;   // dev A/B switch
-    if (off) return false;
+    if (!sw::wgrad_two()) return false;
     const int LA = j.a.LA, LB = j.a.LB, nr = LA >> 3;
     return (LA & 7) == 0 && LB == ((j.KS == 3 || j.KS == 4) ? 2 * LA : LA) && (nr == 1 || nr == 2 || nr == 4 || nr == 8);
 }
@@ -393,9 +408,8 @@ static int bwd_down_applicable(const mpdx_unet* u) {
         for (int i = b + (k == 0 ? 2 : 0); i < b + (has_down ? 6 : 5); ++i) if (!tl[i].need_dgrad) return 0;
     }
     if (variant == 2 && (int)u->layers.size() == 34) {   // 3: ... and the two middle blocks (layers 17 .. 20: identity residuals, 128 channels on 16 positions) in front
-        static const bool mid_off = getenv("MPDX_TRAIN_BWD_MID") && atoi(getenv("MPDX_TRAIN_BWD_MID")) == 0;
         const auto& tl = u->tl;
-        bool ok = !mid_off;
+        bool ok = sw::train_bwd_mid();
         for (int i = 17; i <= 20 && ok; ++i) {
             const Layer& l = u->layers[i];
             ok = l.mode == CONV_S1 && l.ks == 5 && l.epi == EPI_GN_MISH && l.c1 == 128 && l.c2 == 0 && l.cout == 128 && l.L_out == 16 && l.gs == 16 && tl[i].src1_l == i - 1 && tl[i].need_dgrad &&
@@ -670,9 +684,7 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
         ta.B = B; ta.packed = const_cast<float*>(packed); ta.jobs = nullptr; ta.n_jobs = 0;
         ta.Hc = masked ? Hc : 0;
         {   // the fused forward programs' weight streams: re-assembled by side blocks of this launch (the pack launch before it wrote `packed`)
-            static const bool fused_fwd_off0 = getenv("MPDX_TRAIN_FUSED_FWD") && atoi(getenv("MPDX_TRAIN_FUSED_FWD")) == 0;
-            static const bool ride_off = getenv("MPDX_TRAIN_RESTREAM_RIDE") && atoi(getenv("MPDX_TRAIN_RESTREAM_RIDE")) == 0;   // dev A/B switch
-            if (!fused_fwd_off0 && !ride_off && fused_mask(B) != 0u && (w.total < ((size_t)1 << 31))) {
+            if (sw::train_fused_fwd() && sw::train_restream_ride() && fused_mask(B) != 0u && (w.total < ((size_t)1 << 31))) {
                 const void* jb = nullptr;
                 int nj = 0;
                 if (int rc = claim_fused_stream_jobs(u, packed, &jb, &nj)) return rc;
@@ -690,8 +702,7 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
     }
     // forward: the fused level programs of the planning path (they additionally keep every op's output and GroupNorm input,
     // FusedArgs::save) for the outer levels, one launch per layer for the rest
-    static const bool fused_fwd_off = getenv("MPDX_TRAIN_FUSED_FWD") && atoi(getenv("MPDX_TRAIN_FUSED_FWD")) == 0;
-    const bool fused_fwd = !fused_fwd_off && fused_mask(B) != 0u && (w.total < ((size_t)1 << 31));
+    const bool fused_fwd = sw::train_fused_fwd() && fused_mask(B) != 0u && (w.total < ((size_t)1 << 31));
     bool eps_done = false;
     for (int i = 0; i < n; ++i) {
         const int seg = fused_fwd ? u->owner[i] : -1;
@@ -743,9 +754,8 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
         if (int rc = layer_args(i, a)) return rc;
         // blocks[0] and the same block's residual 1x1 convolution (the next layer; both read the block input) as ONE launch - the planning path's conv_pair_kernel
         // (round 6: two launches of ~4.8 us less per pass on the four-level network; MPDX_TRAIN_PAIR_FWD=0: one launch per layer)
-        static const bool pair_fwd_off = getenv("MPDX_TRAIN_PAIR_FWD") && atoi(getenv("MPDX_TRAIN_PAIR_FWD")) == 0;
         int MT = 0, NT = 0;
-        if (!pair_fwd_off && !masked && i + 1 < n && !(fused_fwd && u->owner[i + 1] >= 0 && ((fused_mask(B) >> u->owner[i + 1]) & 1u)) && u->tl[i + 1].src1_l == u->tl[i].src1_l &&
+        if (sw::train_pair_fwd() && !masked && i + 1 < n && !(fused_fwd && u->owner[i + 1] >= 0 && ((fused_mask(B) >> u->owner[i + 1]) & 1u)) && u->tl[i + 1].src1_l == u->tl[i].src1_l &&
             u->tl[i + 1].src2_l == u->tl[i].src2_l && pair_tile(l, u->layers[i + 1], B, MT, NT)) {
             ConvArgs a2;
             if (int rc = layer_args(i + 1, a2)) return rc;
@@ -808,15 +818,14 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
     for (int i = n - 1; i >= 0; --i)
         for (int sl : {u->tl[i].src1_l, u->tl[i].src2_l, u->tl[i].res_l})
             if (sl >= 0) first_consumer[sl] = i;
-    static const bool gnfuse_off = getenv("MPDX_TRAIN_GN_FUSE") && atoi(getenv("MPDX_TRAIN_GN_FUSE")) == 0;   // dev A/B switch
+    const bool gnfuse_off = !sw::train_gn_fuse();
     // round 6 EXPERIMENT, OFF by default (MPDX_TRAIN_CHAIN: 0 off (default), 1 auto, 16 / 32 / 64: the smallest level length that chains): the launches of
     // the outer levels' backward chain COLLECTED and run as one bwd_chain_kernel launch per run of chainable steps.  Bit-identical gradients, but SLOWER
     // than the launches it replaces (batch 32: 0.608 -> 0.640 ms with L >= 32, 0.749 ms with L >= 16; batch 128 x D = 14: 0.894 -> 0.921 / 1.002 ms;
     // profiles/r06_train_chain_ab.txt): under a hipGraph a launch boundary costs ~1 us, a chain step still pays the body's own latency chain (operands
     // through L2, staging, K-split reduction, epilogue loads) AND runs a layer's channel tiles one after the other on ONE CU instead of side by side on
     // several.  What would pay is keeping the gradients in LDS between the steps (the forward programs' design) - not built.
-    static const int chain_env = getenv("MPDX_TRAIN_CHAIN") ? atoi(getenv("MPDX_TRAIN_CHAIN")) : 0;
-    static const int chain_max_b = getenv("MPDX_TRAIN_CHAIN_MAX_B") ? atoi(getenv("MPDX_TRAIN_CHAIN_MAX_B")) : 256;
+    const int chain_env = sw::train_chain(), chain_max_b = sw::train_chain_max_b();
     ChainBuilder chain;
     chain.B = B; chain.st = st;
     chain.on = chain_env != 0 && !masked && df.on && B <= chain_max_b;
@@ -826,23 +835,21 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
     written[n - 1] = 1;                 // train_loss_kernel above
     auto first_write = [&](int j) { const bool f = !written[j]; written[j] = 1; return f; };
     // round 6: the backward pass of downs[0..2] as ONE whole-trajectory program (fused_bwd.hpp; MPDX_TRAIN_BWD_PROG=0 switches it off)
-    static const int prog_env = getenv("MPDX_TRAIN_BWD_PROG") ? atoi(getenv("MPDX_TRAIN_BWD_PROG")) : 1;
-    static const int prog_max_b = getenv("MPDX_TRAIN_BWD_PROG_MAX_B") ? atoi(getenv("MPDX_TRAIN_BWD_PROG_MAX_B")) : 512;
-    const int down_variant = (prog_env != 0 && df.on && !masked && B <= prog_max_b && w.total < ((size_t)1 << 31)) ? bwd_down_applicable(u) : 0;
+    const int prog_env = sw::train_bwd_prog();   // (2: the down program only)
+    const bool progs_ok = prog_env != 0 && df.on && !masked && B <= sw::train_bwd_prog_max_b() && w.total < ((size_t)1 << 31);
+    const int down_variant = progs_ok ? bwd_down_applicable(u) : 0;
     const bool prog_down_on = down_variant != 0;
     const int dn_last = down_variant == 3 ? 20 : (down_variant == 2 ? 16 : 17);   // the program covers layers [0, dn_last]
     auto run_down_program = [&]() -> int {   // layers [0, 18) (three-level network: [0, 17)): returns 0 ok, < 0 error, 1 not applicable here (the per-layer path takes over)
         const int n_gn = down_variant == 3 ? 16 : 12;   // GroupNorm ops (three column-sum entries each); dn_last + 1 weight-gradient jobs
         if (!written[dn_last] || df.red.n + dn_last + 1 > 96 || df.col.n + n_gn * 3 + 6 > 120) return 1;
         if (down_variant == 3 && !written[16]) return 1;   // (the skip connection's gradient, an addend of op M5)
-        static const int late_div_env = getenv("MPDX_WGRAD_LATE_DIV") ? std::max(1, atoi(getenv("MPDX_WGRAD_LATE_DIV"))) : 0;
-        static const int small_mul = getenv("MPDX_WGRAD_PROG_MUL") ? atoi(getenv("MPDX_WGRAD_PROG_MUL")) : 1;   // batch < 64: split multiplier of the program layers' weight gradients
-        const int sdiv = late_div_env ? late_div_env : (B >= 64 ? (B <= 128 ? 8 : 4) : (small_mul > 1 ? -std::min(small_mul, 4) : 4));   // (batch < 64: 4 - measured with the host out of the way, profiles/r06_train_b32_split_ab.txt)
+        const int sdiv = wgrad_prog_sdiv(B);
         const BwdProgLayout lay = bwd_down_layout();
         BwdArgs a;
         memset(&a, 0, sizeof(a));
         a.packedT = packedT; a.flat = flat; a.ws = ws; a.B = B; a.dT_stride = u->tt_row; a.stat_off = lay.stat_off;
-        a.dbg = getenv("MPDX_BWD_DBG") ? atoi(getenv("MPDX_BWD_DBG")) : 0;
+        a.dbg = sw::bwd_dbg();
         auto goff = [&](const float* p) { return (int)(p - ws); };
         enum { IN = 0, GB = 1, DUA = 2, DUB = 3, GA = 4 };
         auto rs4_of = [](int C) { return C / 4 + kBwdPad4; };
@@ -991,19 +998,17 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
         }
         return 0;
     };
-    const int up_first = (prog_env != 0 && prog_env != 2 && df.on && !masked && B <= prog_max_b && w.total < ((size_t)1 << 31)) ? bwd_up_applicable(u) : -1;   // (2: the down program only)
+    const int up_first = (progs_ok && prog_env != 2) ? bwd_up_applicable(u) : -1;
     const bool prog_up_on = up_first >= 0;
     const int up_fi = n - 1;   // final_conv[0]
     auto run_up_program = [&]() -> int {   // layers [up_first, n) = [33, 46) ([21, 34) with three levels): final_conv[0] and the two outer up levels; 0 ok, < 0 error, 1 not applicable here
         if (!written[up_fi] || df.red.n + 17 > 96 || df.col.n + 9 * 3 + 4 > 120) return 1;
-        static const int late_div_env = getenv("MPDX_WGRAD_LATE_DIV") ? std::max(1, atoi(getenv("MPDX_WGRAD_LATE_DIV"))) : 0;
-        static const int small_mul = getenv("MPDX_WGRAD_PROG_MUL") ? atoi(getenv("MPDX_WGRAD_PROG_MUL")) : 1;
-        const int sdiv = late_div_env ? late_div_env : (B >= 64 ? (B <= 128 ? 8 : 4) : (small_mul > 1 ? -std::min(small_mul, 4) : 4));   // (batch < 64: 4 - measured with the host out of the way, profiles/r06_train_b32_split_ab.txt)
+        const int sdiv = wgrad_prog_sdiv(B);
         const BwdProgLayout lay = bwd_down_layout();   // (the same five slots: the largest buffer here is 68 rows x 36 floats = 612 float4)
         BwdArgs a;
         memset(&a, 0, sizeof(a));
         a.packedT = packedT; a.flat = flat; a.ws = ws; a.B = B; a.dT_stride = u->tt_row; a.stat_off = lay.stat_off;
-        a.dbg = getenv("MPDX_BWD_DBG") ? atoi(getenv("MPDX_BWD_DBG")) : 0;
+        a.dbg = sw::bwd_dbg();
         auto goff = [&](const float* p) { return (int)(p - ws); };
         enum { IN = 0, GB = 1, DUA = 2, DUB = 3, GA = 4 };
         auto rs4_of = [](int C) { return C / 4 + kBwdPad4; };
@@ -1130,7 +1135,7 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
     // round 6: the dgrad launch of a ResidualTemporalBlock's blocks[1] (with the GroupNorm backward of blocks[0] in its epilogue) WAITS one layer for the block's
     // residual 1x1 convolution (the next layer in backward order): its 1x1 dgrad - and at batch < 48 both layers' weight-gradient blocks - ride on the same
     // launch (BwdPairArgs::cd2): one launch less per such block.  MPDX_TRAIN_PAIR_RES=0: one launch per layer as before
-    static const bool pair_res_off = getenv("MPDX_TRAIN_PAIR_RES") && atoi(getenv("MPDX_TRAIN_PAIR_RES")) == 0;
+    const bool pair_res_off = !sw::train_pair_res();
     struct Pending { bool on = false; int i_next = -1; Layer dg; ConvArgs a; WgradJob jobs[3]; int njobs = 0; } pend;
     auto flush_pending = [&]() -> int {
         if (!pend.on) return 0;
@@ -1158,7 +1163,7 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
         float* gy = grd(i);
         const float* dy = gy;   // gradient wrt the convolution output (after the GroupNorm/Mish backward for Conv1dBlocks)
         if (!written[i]) {   // nothing downstream of this layer carries a gradient: it is zero
-            if (getenv("MPDX_DEBUG_TRAIN")) fprintf(stderr, "[mpdx] backward: layer %d %s has no gradient-carrying consumer (zeroed)\n", i, l.name.c_str());
+            if (sw::debug_train()) fprintf(stderr, "[mpdx] backward: layer %d %s has no gradient-carrying consumer (zeroed)\n", i, l.name.c_str());
             if (int rc = chain.flush()) return rc;
             HIP_TRY(hipMemsetAsync(gy, 0, w.slotB * sizeof(float), st));
             written[i] = 1;
@@ -1198,8 +1203,7 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
             // du IN PLACE for the two kernels whose body allows it (a lane reads its elements before it writes them): grd(i) outlives the pass, the shared
             // dU scratch does not - so this layer's weight gradients can run behind the chain too (dy == gy below).  Round 6: the one 256 -> 256 layer whose
             // GroupNorm backward is its own launch kept its weight-gradient blocks riding on its dgrad launch - 22.6 us against its six siblings' 12.5 at batch 128
-            static const bool gn_inplace_off = getenv("MPDX_TRAIN_GN_INPLACE") && atoi(getenv("MPDX_TRAIN_GN_INPLACE")) == 0;
-            if (!gn_inplace_off && !mrows && (re == 256 || re == 128)) g.du = gy;
+            if (sw::train_gn_inplace() && !mrows && (re == 256 || re == 128)) g.du = gy;
             if (re == 256 && !mrows) hipLaunchKernelGGL(gn_mish_bwd_kernel<4>, ggrid, dim3(256), 0, st, g);
             else if (re == 128 && !mrows) hipLaunchKernelGGL(gn_mish_bwd_kernel<2>, ggrid, dim3(256), 0, st, g);
             else if (re == 256 && l.gs >= 4) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<4, 1>), ggrid, dim3(256), 0, st, g);
@@ -1224,15 +1228,15 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
         float* gw = gflat(l.w);
         WgradJob jobs[2];
         int njobs = 0;
-        static const bool pair_off0 = getenv("MPDX_TRAIN_PAIR") && atoi(getenv("MPDX_TRAIN_PAIR")) == 0;
-        static const int late_env0 = getenv("MPDX_TRAIN_WGRAD_LATE") ? atoi(getenv("MPDX_TRAIN_WGRAD_LATE")) : -1;
-        // fewer batch splits for the weight gradients that run behind the chain (measured, profiles/r06_train_late_div_ab.txt: batch 128 x D = 14 0.898 / 0.84 / 0.82 /
-        // 0.81 ms with 1 / 4 / 8 / 16; batch 512 2.027 / 1.94 / 1.96 / 2.01): 8 up to batch 128, 4 beyond
-        static const int late_div_env = getenv("MPDX_WGRAD_LATE_DIV") ? std::max(1, atoi(getenv("MPDX_WGRAD_LATE_DIV"))) : 0;
-        const int late_div = late_div_env ? late_div_env : (B < 64 ? 4 : (B <= 128 ? 8 : 4));
+        const bool pair_off = !sw::train_pair();
+        // round 6 (MPDX_TRAIN_WGRAD_LATE, dev A/B switch): a layer's weight gradients leave the chain when their dU operand outlives the pass - it does
+        // whenever it sits in the layer's own gradient slot (grd(i): written once, never recycled), not in the shared dU scratch of an un-fused
+        // GroupNorm backward - and run with everybody else's in wgrad_multi_kernel behind the chain
+        const int late_env = sw::train_wgrad_late();   // -1: by batch (measured: batch 32 no gain, 128 -3 %, 512 -4.6 %)
+        const bool late_on = late_env < 0 ? B >= 48 : late_env != 0;   // (batch 48: 0.58 -> 0.543 ms, batch 32: within noise: profiles/r06_train_b32_late_ab.txt)
         // will this layer's weight gradients run behind the chain (decided below, once the jobs exist: the same conditions)?  Then with fewer batch splits.
-        const bool late_cand = (late_env0 < 0 ? B >= 48 : late_env0 != 0) && t.need_dgrad && !pair_off0 && df.on && df.red.n + 2 <= 96 && bwd_pair_has_tile(t.dg, B) && dy == gy;
-        const int sdiv = late_cand ? late_div : 1;
+        const bool late_cand = late_on && t.need_dgrad && !pair_off && df.on && df.red.n + 2 <= 96 && bwd_pair_has_tile(t.dg, B) && dy == gy;
+        const int sdiv = late_cand ? wgrad_late_sdiv(B) : 1;
         if (l.mode == CONV_UPT) {
             if (int rc = make_wgrad(tensor(t.src1_l), l.L_in, l.c1, 0, l.c1, dy, l.L_out, l.cout, 0, l.cout, 2, -1, 4, B, part, gw, l.cout, 0, &df, jobs[njobs++], sdiv)) return rc;
         } else {
@@ -1247,17 +1251,11 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
                 launch_rowsum(gy, (size_t)B * l.L_out, l.cout, rpart, gflat(l.b), st, &df);
             }
         }
-        static const bool pair_off = getenv("MPDX_TRAIN_PAIR") && atoi(getenv("MPDX_TRAIN_PAIR")) == 0;
         // one launch for all of them needs every job on its own partial buffer (the deferred mode)
         const bool paired = t.need_dgrad && !pair_off && jobs[0].deferred && (njobs == 1 || jobs[1].deferred) && bwd_pair_has_tile(t.dg, B);
-        // round 6 (MPDX_TRAIN_WGRAD_LATE, dev A/B switch): a layer's weight gradients leave the chain when their dU operand outlives the pass - it does
-        // whenever it sits in the layer's own gradient slot (grd(i): written once, never recycled), not in the shared dU scratch of an un-fused
-        // GroupNorm backward - and run with everybody else's in wgrad_multi_kernel behind the chain
-        static const int late_env = getenv("MPDX_TRAIN_WGRAD_LATE") ? atoi(getenv("MPDX_TRAIN_WGRAD_LATE")) : -1;   // -1: by batch (measured: batch 32 no gain, 128 -3 %, 512 -4.6 %)
-        const bool late_on = late_env < 0 ? B >= 48 : late_env != 0;   // (batch 48: 0.58 -> 0.543 ms, batch 32: within noise: profiles/r06_train_b32_late_ab.txt)
-        static const bool resamp_fold_off_c = getenv("MPDX_TRAIN_RESAMPLE_FOLD") && atoi(getenv("MPDX_TRAIN_RESAMPLE_FOLD")) == 0;
+        const bool resamp_fold = sw::train_resample_fold();
         // this layer's input-gradient convolution as a step of the backward chain?
-        const bool chain_d = chain.on && paired && dy == gy && ChainBuilder::conv_ok(t.dg, chain_min_L) && !resamp_fold_off_c &&
+        const bool chain_d = chain.on && paired && dy == gy && ChainBuilder::conv_ok(t.dg, chain_min_L) && resamp_fold &&
                              (l.mode != CONV_UPT || t.src1_l >= 0);
         bool late = false;
         if ((late_on || chain_d) && paired && dy == gy) {
@@ -1277,8 +1275,7 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
         if (t.need_dgrad) {
             const Layer& dgl = t.dg;
             const float* din = dy;
-            static const bool resamp_fold_off = getenv("MPDX_TRAIN_RESAMPLE_FOLD") && atoi(getenv("MPDX_TRAIN_RESAMPLE_FOLD")) == 0;   // dev A/B switch
-            const bool fold = !resamp_fold_off;
+            const bool fold = resamp_fold;
             if (l.mode == CONV_DOWN && !fold) {
                 if (int rc = chain.flush()) return rc;
                 const size_t tot = (size_t)B * 2 * l.L_out * l.cout;
@@ -1380,12 +1377,11 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
     }
     if (int rc = flush_pending()) return rc;
     if (int rc = chain.flush()) return rc;
-    if (getenv("MPDX_DEBUG_TRAIN"))   // (tests/test_gpu_train.py reads this line: the programs must RUN on both networks the reference trains)
+    if (sw::debug_train())   // (tests/test_gpu_train.py reads this line: the programs must RUN on both networks the reference trains)
         fprintf(stderr, "[mpdx] backward programs: up %d (layers [%d, %d)), down %d (variant %d, layers [0, %d])\n", ran_up ? 1 : 0, up_first, n, ran_down ? 1 : 0, down_variant, dn_last);
-    if (getenv("MPDX_DEBUG_TRAIN")) fprintf(stderr, "[mpdx] backward: %d chain launch(es) of %d steps, %zu weight-gradient jobs behind them\n", chain.launches, chain.steps, lone.size());
+    if (sw::debug_train()) fprintf(stderr, "[mpdx] backward: %d chain launch(es) of %d steps, %zu weight-gradient jobs behind them\n", chain.launches, chain.steps, lone.size());
     {
-        static const bool multi_off = getenv("MPDX_TRAIN_WGRAD_MULTI") && atoi(getenv("MPDX_TRAIN_WGRAD_MULTI")) == 0;   // dev A/B switch
-        if (!multi_off) {
+        if (sw::train_wgrad_multi()) {
             if (int rc = launch_wgrads_multi(lone, st)) return rc;
         } else
             for (size_t k = 0; k < lone.size(); k += 3)
@@ -1401,8 +1397,7 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
             blocks += (int)(((size_t)e.M * e.N * e.KS + opb - 1) / opb);
         }
         df.red.cstart[df.red.n] = blocks;
-        static const bool join_off = getenv("MPDX_TRAIN_REDUCE_JOIN") && atoi(getenv("MPDX_TRAIN_REDUCE_JOIN")) == 0;   // dev A/B switch
-        if (df.col.n && !join_off) {   // the column sums ride on the same launch (side blocks behind the reduction's)
+        if (df.col.n && sw::train_reduce_join()) {   // the column sums ride on the same launch (side blocks behind the reduction's)
             ReduceColsumArgs rc;   // (8 KB of kernel arguments; the launch copies them)
             rc.red = df.red; rc.col = df.col; rc.n_red_blocks = blocks;
             hipLaunchKernelGGL(wgrad_reduce_colsum_kernel, dim3(blocks + 2 * df.col.n), dim3(256), 0, st, rc);
@@ -1410,8 +1405,7 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
         } else hipLaunchKernelGGL(wgrad_reduce_all_kernel, dim3(blocks), dim3(256), 0, st, df.red);
     }
     if (df.col.n) hipLaunchKernelGGL(colsum_all_kernel, dim3(2, df.col.n), dim3(256), 0, st, df.col);
-    static const bool tail_join = getenv("MPDX_TIME_TAIL_SPLIT") && atoi(getenv("MPDX_TIME_TAIL_SPLIT")) == 0;   // dev A/B switch: the tail inside the launch
-    tb.split_tail = tail_join ? 0 : 1;
+    tb.split_tail = sw::time_tail_split() ? 1 : 0;
     hipLaunchKernelGGL(time_bwd_all_kernel, dim3(B + (tb.row + 31) / 32), dim3(1024), 0, st, tb);   // the time conditioning's backward
     if (tb.split_tail) hipLaunchKernelGGL(time_tail_kernel, dim3(kTimeTailBlocks), dim3(512), 0, st, tb);   // ... and its encoder tail, 8 blocks
     HIP_TRY(hipGetLastError());
