@@ -172,6 +172,7 @@ int mpdx_randn(float* out, size_t n, uint64_t seed, uint64_t offset, void* strea
 #define MPDX_FIELD_OBJECTS   0 /* sdf to sphere/box primitives (task.df_collision_objects / extra objects) */
 #define MPDX_FIELD_WORKSPACE 1 /* workspace-boundary planes */
 #define MPDX_FIELD_SELF      2 /* robot self collision (Panda) */
+#define MPDX_FIELD_GRID      3 /* precomputed signed-distance grid in global memory (guide and metrics kernels only; see below) */
 #define MPDX_ROBOT_POINTMASS 0
 #define MPDX_ROBOT_PANDA     1
 
@@ -181,7 +182,29 @@ typedef struct mpdx_field {
     int32_t sphere_off, n_spheres;      /* float offset into prims, 4 floats each: cx,cy,cz,r (cz unused in 2-D) */
     int32_t box_off, n_boxes;           /* 6 floats each: cx,cy,cz,hx,hy,hz */
     float   ws_min[3], ws_max[3];       /* MPDX_FIELD_WORKSPACE */
+    /* --- MPDX_FIELD_GRID: a sampled signed-distance field (torch_robotics' GridMapSDF; un-vendored, restated: PARITY UNPINNED).
+     * Planes live in mpdx_guide_params.grids (global memory, NOT in prims: every kernel copies prims into LDS):
+     *   sdf plane       [nz][ny][nx] fp32, x fastest
+     *   gradient plane  [nz][ny][nx][4] fp32 (gx, gy, gz, 0): one 16-byte load per node (grids 16-byte aligned, grid_grad_off % 4 == 0)
+     * Lookup of a point p (all in fp32; inv = 1.0f / cell, taken ONCE on the host):
+     *   u_j = (p_j - origin_j) * inv        (one rounded subtraction, one rounded product)
+     *   c_j = min(max(u_j, 0), n_j - 1)     (the point is clamped into the grid box)
+     *   MPDX_GRID_LINEAR : i_j = min((int)floor(c_j), n_j - 2), w_j = c_j - i_j; sdf = bi-/trilinear interpolant of the 4 / 8 nodes around the cell,
+     *                      a + w (b - a) along x, then y, then z; gradient = the analytic derivative of that interpolant (what autograd gives on the
+     *                      same formula: along j the interpolated node difference times inv); an axis on which the point was clamped
+     *                      (c_j != u_j) contributes ZERO gradient.  Needs no gradient plane.
+     *   MPDX_GRID_NEAREST: GridMapSDF AS RECALLED - node i_j = rint(c_j) (half to even, as torch.round / rintf); sdf = the node's value, gradient =
+     *                      the node's STORED gradient (first-order surrogate), the edge node's for a clamped point.
+     * The guide applies the hinge relu(margin - sdf) to it exactly as to an OBJECTS field. */
+    int32_t grid_sdf_off;               /* float offset of the sdf plane in grids */
+    int32_t grid_grad_off;              /* float offset of the gradient plane in grids, or -1: none (LINEAR only) */
+    int32_t n[3];                       /* nodes along x, y, z (>= 2 along a used axis; n[2] = 1 in 2-D) */
+    float   origin[3];                  /* position of node (0, 0, 0) */
+    float   cell;                       /* edge of the cubic cell (> 0) */
+    int32_t mode;                       /* MPDX_GRID_LINEAR | MPDX_GRID_NEAREST */
 } mpdx_field;
+#define MPDX_GRID_LINEAR  0
+#define MPDX_GRID_NEAREST 1
 
 typedef struct mpdx_guide_params {
     int32_t robot;                      /* MPDX_ROBOT_* */
@@ -210,6 +233,8 @@ typedef struct mpdx_guide_params {
                                          * 1: x is ALREADY in robot units (Identity :111-116; no range test): the trajectory optimiser of
                                          *    generate_trajectories (scripts/generate_data/generate_trajectories.py:94-117) works on raw trajectories;
                                          * 2: GaussianNormalizer (:140-141): x * stds + means with means in `mins`, stds in `maxs`, no range test */
+    const float* grids;                 /* device pointer: the planes of the MPDX_FIELD_GRID fields (NULL when there is none); stays in global memory */
+    int32_t n_grid_floats;              /* floats in grids (every plane must lie inside) */
 } mpdx_guide_params;
 
 /* one guide iteration on x[B,H,D] (normalised).  grad_out == NULL: x <- hard_cond(x + guide(x)) in place and
@@ -247,6 +272,14 @@ int mpdx_traj_metrics(const mpdx_guide_params* gp, const float* x_unnormalised, 
 int mpdx_traj_metrics_mask(const mpdx_guide_params* gp, const float* x_unnormalised, float* out4, uint8_t* mask, int n_check, int B,
                            int H, int D, void* stream);
 
+/* ---- bake a signed-distance grid from primitives: replaces GridMapSDF.__init__ (torch_robotics, un-vendored: restated, PARITY UNPINNED), which
+ * samples the fixed objects' SDF (and its gradient) on a regular grid once per environment.  One thread per node: node (ix, iy, iz) sits at
+ * origin_j + (float)i_j * cell (fp32: one rounded product, one rounded sum); sdf_out[iz][iy][ix] = minimum signed distance to the sphere / box tables
+ * of the OBJECTS field gp->fields[field] (the arithmetic of the metrics kernel: IEEE sqrtf); grad_out (or NULL) [iz][iy][ix][4] = the analytic
+ * gradient of the arg-min primitive (gx, gy, gz, 0).  n[2] = 1 in 2-D (gp->ws_dim == 2).  The outputs may be planes of a grids buffer. */
+int mpdx_sdf_grid_bake(const mpdx_guide_params* gp, int field, float* sdf_out, float* grad_out, const int n[3], const float origin[3], float cell,
+                       void* stream);
+
 /* ---- baseline planners of the dataset-generation script: replaces `HybridPlanner(RRTConnect x n via
  * MultiSampleBasedPlanner, GPMP2).optimize()` of scripts/generate_data/generate_trajectories.py:68-120.  The planners are
  * un-vendored in the reference (mp_baselines submodule empty: PARITY UNPINNED); the published algorithms are restated
@@ -261,7 +294,8 @@ int mpdx_traj_metrics_mask(const mpdx_guide_params* gp, const float* x_unnormali
  *   (block-tridiagonal system, banded LDL^T in LDS).  Call iters times with solve = 1 and once more with solve = 0.
  *   A trajectory whose accepted step no longer lowers F (relative 1e-7) or whose lambda reached lambda_max is CONVERGED: its lambda is
  *   stored negated and further calls return at once for it.
- *   adaptive == 0: every candidate is accepted and lambda stays fixed (damped Gauss-Newton with a fixed step). */
+ *   adaptive == 0: every candidate is accepted and lambda stays fixed (damped Gauss-Newton with a fixed step).
+ * The three planner entry points know primitive fields only: a MPDX_FIELD_GRID field is refused with MPDX_E_INVALID (grid fields: guide and metrics only). */
 typedef struct mpdx_gpmp_opts {
     float   sigma_obs;
     float   lambda_up, lambda_down, lambda_min, lambda_max;

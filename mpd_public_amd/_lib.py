@@ -30,13 +30,17 @@ class StepCoefs(C.Structure):
 
 
 MAX_FIELDS = 4
-FIELD_OBJECTS, FIELD_WORKSPACE, FIELD_SELF = 0, 1, 2
+FIELD_OBJECTS, FIELD_WORKSPACE, FIELD_SELF, FIELD_GRID = 0, 1, 2, 3
+GRID_LINEAR, GRID_NEAREST = 0, 1
 ROBOT_POINTMASS, ROBOT_PANDA = 0, 1
 
 
 class Field(C.Structure):
     _fields_ = [("kind", C.c_int32), ("weight", C.c_float), ("sphere_off", C.c_int32), ("n_spheres", C.c_int32),
-                ("box_off", C.c_int32), ("n_boxes", C.c_int32), ("ws_min", C.c_float * 3), ("ws_max", C.c_float * 3)]
+                ("box_off", C.c_int32), ("n_boxes", C.c_int32), ("ws_min", C.c_float * 3), ("ws_max", C.c_float * 3),
+                # MPDX_FIELD_GRID (planes in GuideParams.grids; lookup formulas in include/mpdx.h)
+                ("grid_sdf_off", C.c_int32), ("grid_grad_off", C.c_int32), ("n", C.c_int32 * 3), ("origin", C.c_float * 3),
+                ("cell", C.c_float), ("mode", C.c_int32)]
 
 
 class GuideParams(C.Structure):
@@ -46,7 +50,7 @@ class GuideParams(C.Structure):
                 ("n_fields", C.c_int32), ("fields", Field * MAX_FIELDS), ("use_gp", C.c_int32), ("gp_weight", C.c_float),
                 ("dt", C.c_float), ("sigma_gp", C.c_float), ("prims", C.c_void_p), ("n_prim_floats", C.c_int32),
                 ("clip_rule", C.c_int32), ("max_grad_value", C.c_float), ("gp_half_factor", C.c_int32),
-                ("identity_normalizer", C.c_int32)]
+                ("identity_normalizer", C.c_int32), ("grids", C.c_void_p), ("n_grid_floats", C.c_int32)]
 
 
 class GpmpOpts(C.Structure):
@@ -88,6 +92,7 @@ SIGNATURES = {
     "mpdx_traj_metrics_mask": (_i, [C.POINTER(GuideParams), _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mpdx_guide_trace": (_i, [C.POINTER(GuideParams), _vp, _vp, _i, _i, _i, _vp, C.POINTER(C.c_longlong)]),
     "mpdx_absmax": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "mpdx_sdf_grid_bake": (_i, [C.POINTER(GuideParams), _i, _vp, _vp, C.POINTER(C.c_int * 3), C.POINTER(C.c_float * 3), _f, _vp]),
     "mpdx_unet_profile": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, C.POINTER(C.c_float), C.POINTER(C.c_double),
                                 C.POINTER(C.c_char_p), C.POINTER(C.c_int)]),
     "mpdx_layer_trace": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(C.c_longlong)]),

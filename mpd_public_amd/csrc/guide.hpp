@@ -23,6 +23,7 @@
 
 #include "../../include/mpdx.h"
 #include "conv_block.hpp"
+#include "grid_field.hpp"
 
 namespace mpdx {
 
@@ -41,7 +42,7 @@ __device__ static const int kPandaPA[kPandaNP] = {8, 8, 8, 9, 9, 9, 9, 10, 10, 1
 __device__ static const int kPandaPB[kPandaNP] = {0, 1, 2, 0, 1, 2, 3, 0, 1, 2, 3, 4};
 
 struct GuideArgs {
-    mpdx_guide_params gp;
+    dev_guide_params gp;
     float* x;               // [B][H][D] normalised trajectories (updated in place unless grad_out)
     float* grad_out;        // optional: write the guide increment instead of applying it (API path guide(x))
     const float* hs;        // hard start [B][D] or null
@@ -56,6 +57,7 @@ struct GuideArgs {
     float* chain;           // optional second destination
     NoiseRng rng;           // rng.on: the step's noise is drawn in place (noise pointer ignored)
     long long* trace;       // dev tool: cycle stamps, 16 slots per wave of workgroup 0 (null in production)
+    dev_grids grid;         // MPDX_FIELD_GRID descriptors (grid_field.hpp): last, read by the HAS_GRID instantiations only
 };
 
 // d cost / d p  for  cost = relu(margin - min_prims sdf(p)).
@@ -66,7 +68,7 @@ struct GuideArgs {
 // the 15-sphere objects field of the Panda 60-70 k cycles per launch.)
 // Returns the hinge value relu(margin - sdf) (0 when inactive); `force` = its gradient w.r.t. p.
 template <int DIM>
-__device__ __forceinline__ float objects_force(const float* __restrict__ prims, const mpdx_field& f, const float (&p)[DIM], float margin,
+__device__ __forceinline__ float objects_force(const float* __restrict__ prims, const dev_field& f, const float (&p)[DIM], float margin,
                                                float (&force)[DIM]) {
     float best = 3.0e38f;
     int bi = -1;  // arg-min: sphere index, or n_spheres + box index
@@ -155,7 +157,7 @@ __device__ __forceinline__ float objects_force(const float* __restrict__ prims, 
 // reads are shared by the points, whose distance chains are independent (3 x the instruction-level parallelism of one point's scan,
 // which is a serial min / arg-min chain).  Per point exactly the arithmetic of objects_force: same bits.
 template <int DIM, int NPT, int UB = 2>
-__device__ __forceinline__ void objects_force_n(const float* __restrict__ prims, const mpdx_field& f, const float (&p)[NPT][DIM], const float (&margin)[NPT],
+__device__ __forceinline__ void objects_force_n(const float* __restrict__ prims, const dev_field& f, const float (&p)[NPT][DIM], const float (&margin)[NPT],
                                                 float (&force)[NPT][DIM]) {
     float best[NPT];
     int bi[NPT];
@@ -248,7 +250,7 @@ __device__ __forceinline__ void objects_force_n(const float* __restrict__ prims,
 }
 
 template <int DIM>
-__device__ __forceinline__ void workspace_force(const mpdx_field& f, const float (&p)[DIM], float margin, float (&force)[DIM]) {
+__device__ __forceinline__ void workspace_force(const dev_field& f, const float (&p)[DIM], float margin, float (&force)[DIM]) {
 #pragma unroll
     for (int j = 0; j < DIM; ++j) {
         const float lo = p[j] - f.ws_min[j], hi = f.ws_max[j] - p[j];
@@ -288,7 +290,7 @@ __device__ __forceinline__ void panda_fk(const float (&q)[QD], float (&O)[7][3],
 
 // minimum signed distance of p to the field's primitives (collision checking)
 template <int DIM>
-__device__ __forceinline__ float objects_sdf(const float* __restrict__ prims, const mpdx_field& f, const float (&p)[DIM]) {
+__device__ __forceinline__ float objects_sdf(const float* __restrict__ prims, const dev_field& f, const float (&p)[DIM]) {
     float best = 3.0e38f;
     const float* sp = prims + f.sphere_off;
     for (int s = 0; s < f.n_spheres; ++s) {
@@ -321,9 +323,11 @@ __device__ __forceinline__ float objects_sdf(const float* __restrict__ prims, co
 //   out[b][3] = number of interpolated waypoints checked
 //   mask[b][i] (optional) = 1 if interpolated waypoint i collides (what out[b][0] counts)
 // x is UNNORMALISED [B,H,D] (inference.py:285 un-normalises before computing metrics).
-template <int QD, int DIM, int ROBOT>
-__global__ __launch_bounds__(64) void traj_metrics_kernel(const mpdx_guide_params gp, const float* __restrict__ x, float* __restrict__ out,
-                                                          int B, int H, int n_check, uint8_t* __restrict__ mask) {
+// HAS_GRID (here and in the guide kernels): the instantiation also knows MPDX_FIELD_GRID fields (grid_field.hpp); the launcher picks it when a
+// field is a grid, so that the primitive-only instantiations compile from exactly the code they had before grids existed.
+template <int QD, int DIM, int ROBOT, bool HAS_GRID = false>
+__global__ __launch_bounds__(64) void traj_metrics_kernel(const dev_guide_params gp, const float* __restrict__ x, float* __restrict__ out,
+                                                          int B, int H, int n_check, uint8_t* __restrict__ mask, const dev_grids grid) {
     constexpr int D = 2 * QD;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int lane = threadIdx.x, b = blockIdx.x;
@@ -365,6 +369,7 @@ __global__ __launch_bounds__(64) void traj_metrics_kernel(const mpdx_guide_param
 #pragma unroll
                     for (int j = 0; j < DIM; ++j) hit |= (p[j] - gp.fields[f].ws_min[j] < gp.link_margin) || (gp.fields[f].ws_max[j] - p[j] < gp.link_margin);
                 }
+                else if (HAS_GRID && gp.fields[f].kind == MPDX_FIELD_GRID) hit |= grid_sdf<DIM>(grid.grids, grid.g[f], p) < gp.link_margin;
             }
         } else {
             float O[7][3], Z[7][3];
@@ -382,6 +387,12 @@ __global__ __launch_bounds__(64) void traj_metrics_kernel(const mpdx_guide_param
                         const float dx = P[kPandaPA[pr]][0] - P[kPandaPB[pr]][0], dy = P[kPandaPA[pr]][1] - P[kPandaPB[pr]][1],
                                     dz = P[kPandaPA[pr]][2] - P[kPandaPB[pr]][2];
                         hit |= sqrtf(dx * dx + dy * dy + dz * dz) < kPandaSR[kPandaPA[pr]] + kPandaSR[kPandaPB[pr]];
+                    }
+                } else if (HAS_GRID && kind == MPDX_FIELD_GRID) {
+#pragma unroll
+                    for (int s = 0; s < kPandaNS; ++s) {
+                        const float p3[3] = {P[s][0], P[s][1], P[s][2]};
+                        hit |= grid_sdf<3>(grid.grids, grid.g[f], p3) < kPandaSR[s];
                     }
                 } else {
 #pragma unroll
@@ -414,7 +425,7 @@ __global__ __launch_bounds__(64) void traj_metrics_kernel(const mpdx_guide_param
 //   rule 'norm'  : g * clip(|g + 1e-6|, 0, max_norm) / |g + 1e-6|, norm over ALL D dims
 //   rule 'value' : clip(g, -max_value, max_value) per element
 template <int N>
-__device__ __forceinline__ void clip_waypoint_grad(const mpdx_guide_params& gp, float (&g)[N], int n_zero_dims) {
+__device__ __forceinline__ void clip_waypoint_grad(const dev_guide_params& gp, float (&g)[N], int n_zero_dims) {
     if (!gp.clip_grad) return;
     if (gp.clip_rule == 1) {
 #pragma unroll
@@ -524,13 +535,13 @@ __device__ __forceinline__ void guide_draw_noise(const NoiseRng& rng, unsigned l
 // wave 0 then gathers, clips, adds the GP term and applies the update.  WPT = 8 (2 point halves x up to 4 fields): the
 // single-wave version is a long serial latency chain (2-D: 19 us per launch; 8 waves: 9 us).  The Panda has its own
 // kernel below (guide_step_panda_kernel).
-template <int QD, int DIM, int ROBOT, int WPT>
+template <int QD, int DIM, int ROBOT, int WPT, bool HAS_GRID = false>
 __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a) {
     static_assert(ROBOT == MPDX_ROBOT_POINTMASS, "the Panda has its own kernel (guide_step_panda_kernel)");
     constexpr int D = 2 * QD;
     constexpr int MAXF = MPDX_MAX_FIELDS;
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const mpdx_guide_params& gp = a.gp;
+    const dev_guide_params& gp = a.gp;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr int PW = WPT >= 2 ? 2 : 1, FW = WPT / PW;
@@ -597,6 +608,7 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
                 float force[DIM];
                 if (gp.fields[f].kind == MPDX_FIELD_OBJECTS) objects_force<DIM>(sprim, gp.fields[f], p, margin, force);
                 else if (gp.fields[f].kind == MPDX_FIELD_WORKSPACE) workspace_force<DIM>(gp.fields[f], p, margin, force);
+                else if (HAS_GRID && gp.fields[f].kind == MPDX_FIELD_GRID) grid_force<DIM>(a.grid.grids, a.grid.g[f], p, margin, force);
                 else {
 #pragma unroll
                     for (int j = 0; j < DIM; ++j) force[j] = 0.f;
@@ -719,8 +731,8 @@ constexpr int panda_group_joints(int part) { return part == 0 ? 3 : part == 1 ? 
 // phase 2 of guide_step_panda_kernel for sphere / pair group PART and point half `half`
 // FKREG: the forward kinematics of the point are evaluated HERE from the LDS-staged state (sx, H, D, scale) instead of being read from
 // the per-point FK table of phase 1 (sfk): 4 x the FK work, no 38-KB table - the large-batch variant of the kernel (below).
-template <int PART, bool FKREG>
-__device__ __forceinline__ void panda_group_forces(const mpdx_guide_params& gp, const float* sprim, const float* sfk, float* sG, int half, int lane, int N,
+template <int PART, bool FKREG, bool HAS_GRID = false>
+__device__ __forceinline__ void panda_group_forces(const dev_guide_params& gp, const dev_grids& grid, const float* sprim, const float* sfk, float* sG, int half, int lane, int N,
                                                    long long* tr, const float* sx = nullptr, int H = 0, float scale = 0.f) {
     constexpr int QD = 7, NP = kPandaParts, D = 14;
     constexpr int s_beg = panda_group_first(PART), s_end = panda_group_first(PART + 1), NG = s_end - s_beg;
@@ -799,7 +811,7 @@ __device__ __forceinline__ void panda_group_forces(const mpdx_guide_params& gp, 
         }
         for (int f = 0; f < gp.n_fields; ++f) {
             const int kind = gp.fields[f].kind;
-            if (kind != MPDX_FIELD_OBJECTS && kind != MPDX_FIELD_WORKSPACE) continue;   // (self: above, group 3 only; sG of the other parts is never read)
+            if (kind != MPDX_FIELD_OBJECTS && kind != MPDX_FIELD_WORKSPACE && !(HAS_GRID && kind == MPDX_FIELD_GRID)) continue;   // (self: above, group 3 only; sG of the other parts is never read)
             float FF[7][3], FM[7][3];  // per frame: force on its spheres, their moment about the world origin
 #pragma unroll
             for (int k = 0; k < 7; ++k) { FF[k][0] = FF[k][1] = FF[k][2] = 0.f; FM[k][0] = FM[k][1] = FM[k][2] = 0.f; }
@@ -811,6 +823,7 @@ __device__ __forceinline__ void panda_group_forces(const mpdx_guide_params& gp, 
                 mg[n] = kPandaSR[s_beg + n] + gp.cutoff_margin;
             }
             if (kind == MPDX_FIELD_OBJECTS) objects_force_n<3, NG>(sprim, gp.fields[f], pg, mg, fg);
+            else if (HAS_GRID && kind == MPDX_FIELD_GRID) grid_force_n<3, NG>(grid.grids, grid.g[f], pg, mg, fg);
             else {
 #pragma unroll
                 for (int n = 0; n < NG; ++n) workspace_force<3>(gp.fields[f], pg[n], mg[n], fg[n]);
@@ -832,11 +845,11 @@ __device__ __forceinline__ void panda_group_forces(const mpdx_guide_params& gp, 
 // DENSE (large batches): no FK table in LDS (the forces phase evaluates the FK in registers, four times per point) and registers capped
 // at 128: 70 KB of LDS and 4 waves per SIMD -> TWO workgroups per CU, where the latency-bound phases of one overlap the other's
 // (the default variant: 107 KB, 166 VGPRs, one workgroup per CU; at B = 100 there is one workgroup per CU anyway).  Same arithmetic.
-template <bool DENSE>
+template <bool DENSE, bool HAS_GRID = false>
 __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(const GuideArgs a) {
     constexpr int QD = 7, D = 14, MAXF = MPDX_MAX_FIELDS, NP = kPandaParts, WPT = 8;
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const mpdx_guide_params& gp = a.gp;
+    const dev_guide_params& gp = a.gp;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.x;
@@ -934,10 +947,10 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(co
         const int half = wv & 1;
         long long* trf = (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 8 : nullptr;  // slots 8..: per-field stamps
         switch (wv >> 1) {  // the group is a template parameter: sphere -> frame is static, no per-joint masks
-            case 0: panda_group_forces<0, DENSE>(gp, sprim, sfk, sG, half, lane, N, trf, sx, H, scale); break;
-            case 1: panda_group_forces<1, DENSE>(gp, sprim, sfk, sG, half, lane, N, trf, sx, H, scale); break;
-            case 2: panda_group_forces<2, DENSE>(gp, sprim, sfk, sG, half, lane, N, trf, sx, H, scale); break;
-            default: panda_group_forces<3, DENSE>(gp, sprim, sfk, sG, half, lane, N, trf, sx, H, scale); break;
+            case 0: panda_group_forces<0, DENSE, HAS_GRID>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale); break;
+            case 1: panda_group_forces<1, DENSE, HAS_GRID>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale); break;
+            case 2: panda_group_forces<2, DENSE, HAS_GRID>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale); break;
+            default: panda_group_forces<3, DENSE, HAS_GRID>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale); break;
         }
     }
     G_STAMP();  // 3 this wave's forces done

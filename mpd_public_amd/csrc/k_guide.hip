@@ -26,10 +26,11 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
     if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS) return fail(MPDX_E_INVALID, "n_fields %d", gp->n_fields);
     if (gp->interpolate && (gp->n_interp < H || gp->n_interp > 8 * H)) return fail(MPDX_E_INVALID, "n_interp %d unsupported", gp->n_interp);
     if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
+    if (const char* why = grid_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
     if (gp->robot == MPDX_ROBOT_PANDA && (((uintptr_t)x & 15) || ((size_t)H * D) % 4))
         return fail(MPDX_E_INVALID, "Panda guide: x must be 16-byte aligned with H * D a multiple of 4 (the trajectory is staged with 16-byte loads)");
     GuideArgs a;
-    a.gp = *gp; a.x = x; a.grad_out = grad_out; a.hs = hs; a.hg = hg; a.amax_in = amax_in; a.amax_out = amax_out;
+    a.gp = dev_params_of(*gp); a.x = x; a.grad_out = grad_out; a.hs = hs; a.hg = hg; a.amax_in = amax_in; a.amax_out = amax_out;
     a.B = B; a.H = H; a.D = D; a.n_per_ctx = n_per_ctx > 0 ? n_per_ctx : B;
     a.noise = noise; a.noise_scale = noise_scale; a.noise_extra = noise_extra; a.chain = chain;
     a.guide_scale = guide_scale;
@@ -37,19 +38,31 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
     if (rng) a.rng = *rng;
     if (gp->clip_grad && gp->clip_rule != 0 && gp->clip_rule != 1) return fail(MPDX_E_INVALID, "clip_rule %d (0 = 'norm', 1 = 'value')", gp->clip_rule);
     a.trace = g_guide_trace;
+    // a grid field selects the HAS_GRID instantiations (grid_field.hpp): the primitive-only ones are the code they were before grids existed
+    const bool grid = has_grid_field(*gp);
+    memset(&a.grid, 0, sizeof(a.grid));
+    if (grid) a.grid = dev_grids_of(*gp);
     // Panda at large batch: the dense variant (no FK table, 128 VGPRs: two workgroups per CU); MPDX_GUIDE_DENSE=0/1 forces it off / on
     const int dense_env = sw::guide_dense();
     const bool dense = gp->robot == MPDX_ROBOT_PANDA && (dense_env >= 0 ? dense_env != 0 : B >= 512) && guide_lds_bytes(*gp, H, D, true) <= 80 * 1024;
     const size_t lds = guide_lds_bytes(*gp, H, D, dense);
     if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "guide needs %zu B of LDS (n_interp %d too large)", lds, gp->n_interp);
-    if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 2 && gp->ws_dim == 2)
-        hipLaunchKernelGGL((guide_step_kernel<2, 2, MPDX_ROBOT_POINTMASS, 8>), dim3(B), dim3(512), lds, st, a);
-    else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 3 && gp->ws_dim == 3)
-        hipLaunchKernelGGL((guide_step_kernel<3, 3, MPDX_ROBOT_POINTMASS, 8>), dim3(B), dim3(512), lds, st, a);
-    else if (gp->robot == MPDX_ROBOT_PANDA && gp->q_dim == 7 && gp->ws_dim == 3) {
-        if (dense) {
+    if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 2 && gp->ws_dim == 2) {
+        if (grid) hipLaunchKernelGGL((guide_step_kernel<2, 2, MPDX_ROBOT_POINTMASS, 8, true>), dim3(B), dim3(512), lds, st, a);
+        else hipLaunchKernelGGL((guide_step_kernel<2, 2, MPDX_ROBOT_POINTMASS, 8>), dim3(B), dim3(512), lds, st, a);
+    } else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 3 && gp->ws_dim == 3) {
+        if (grid) hipLaunchKernelGGL((guide_step_kernel<3, 3, MPDX_ROBOT_POINTMASS, 8, true>), dim3(B), dim3(512), lds, st, a);
+        else hipLaunchKernelGGL((guide_step_kernel<3, 3, MPDX_ROBOT_POINTMASS, 8>), dim3(B), dim3(512), lds, st, a);
+    } else if (gp->robot == MPDX_ROBOT_PANDA && gp->q_dim == 7 && gp->ws_dim == 3) {
+        if (dense && grid) {
+            if (int rc = raise_lds_limit((const void*)guide_step_panda_kernel<true, true>)) return rc;
+            hipLaunchKernelGGL((guide_step_panda_kernel<true, true>), dim3(B), dim3(512), lds, st, a);
+        } else if (dense) {
             if (int rc = raise_lds_limit((const void*)guide_step_panda_kernel<true>)) return rc;
             hipLaunchKernelGGL(guide_step_panda_kernel<true>, dim3(B), dim3(512), lds, st, a);
+        } else if (grid) {
+            if (int rc = raise_lds_limit((const void*)guide_step_panda_kernel<false, true>)) return rc;
+            hipLaunchKernelGGL((guide_step_panda_kernel<false, true>), dim3(B), dim3(512), lds, st, a);
         } else {
             if (int rc = raise_lds_limit((const void*)guide_step_panda_kernel<false>)) return rc;
             hipLaunchKernelGGL(guide_step_panda_kernel<false>, dim3(B), dim3(512), lds, st, a);
@@ -92,15 +105,24 @@ int mpdx_traj_metrics_mask(const mpdx_guide_params* gp, const float* x_unnormali
     if (H > 128 || H < 2) return fail(MPDX_E_INVALID, "H=%d unsupported (max 128)", H);
     if (D != 2 * gp->q_dim || D > 16) return fail(MPDX_E_INVALID, "state dim %d != 2*q_dim (%d)", D, gp->q_dim);
     if (n_check < 2) n_check = H;
+    if (const char* why = grid_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
     const size_t lds = (size_t)(H * D + gp->n_prim_floats) * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
-    if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 2 && gp->ws_dim == 2)
-        hipLaunchKernelGGL((traj_metrics_kernel<2, 2, MPDX_ROBOT_POINTMASS>), dim3(B), dim3(64), lds, st, *gp, x_unnormalised, out4, B, H, n_check, mask);
-    else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 3 && gp->ws_dim == 3)
-        hipLaunchKernelGGL((traj_metrics_kernel<3, 3, MPDX_ROBOT_POINTMASS>), dim3(B), dim3(64), lds, st, *gp, x_unnormalised, out4, B, H, n_check, mask);
-    else if (gp->robot == MPDX_ROBOT_PANDA && gp->q_dim == 7 && gp->ws_dim == 3)
-        hipLaunchKernelGGL((traj_metrics_kernel<7, 3, MPDX_ROBOT_PANDA>), dim3(B), dim3(64), lds, st, *gp, x_unnormalised, out4, B, H, n_check, mask);
-    else
+    const bool grid = has_grid_field(*gp);
+    const dev_guide_params g = dev_params_of(*gp);
+    dev_grids gr;
+    memset(&gr, 0, sizeof(gr));
+    if (grid) gr = dev_grids_of(*gp);
+    if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 2 && gp->ws_dim == 2) {
+        if (grid) hipLaunchKernelGGL((traj_metrics_kernel<2, 2, MPDX_ROBOT_POINTMASS, true>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr);
+        else hipLaunchKernelGGL((traj_metrics_kernel<2, 2, MPDX_ROBOT_POINTMASS>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr);
+    } else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 3 && gp->ws_dim == 3) {
+        if (grid) hipLaunchKernelGGL((traj_metrics_kernel<3, 3, MPDX_ROBOT_POINTMASS, true>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr);
+        else hipLaunchKernelGGL((traj_metrics_kernel<3, 3, MPDX_ROBOT_POINTMASS>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr);
+    } else if (gp->robot == MPDX_ROBOT_PANDA && gp->q_dim == 7 && gp->ws_dim == 3) {
+        if (grid) hipLaunchKernelGGL((traj_metrics_kernel<7, 3, MPDX_ROBOT_PANDA, true>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr);
+        else hipLaunchKernelGGL((traj_metrics_kernel<7, 3, MPDX_ROBOT_PANDA>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr);
+    } else
         return fail(MPDX_E_INVALID, "unsupported robot %d / q_dim %d / ws_dim %d", gp->robot, gp->q_dim, gp->ws_dim);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -148,6 +170,38 @@ int mpdx_guide_trace(const mpdx_guide_params* gp, float* x, const uint32_t* absm
     HIP_TRY(hipMemcpy(stamps64, dev, 128 * sizeof(long long), hipMemcpyDeviceToHost));
     (void)hipFree(dev);
     return rc;
+}
+
+int mpdx_sdf_grid_bake(const mpdx_guide_params* gp, int field, float* sdf_out, float* grad_out, const int n[3], const float origin[3], float cell,
+                       void* stream) {
+    if (!gp || !sdf_out || !n || !origin) return fail(MPDX_E_INVALID, "null argument");
+    if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS || field < 0 || field >= gp->n_fields) return fail(MPDX_E_INVALID, "field %d of %d", field, gp->n_fields);
+    const mpdx_field& f = gp->fields[field];
+    if (f.kind != MPDX_FIELD_OBJECTS) return fail(MPDX_E_INVALID, "grid bake: field %d is not an OBJECTS field", field);
+    if (gp->ws_dim != 2 && gp->ws_dim != 3) return fail(MPDX_E_INVALID, "grid bake: ws_dim %d", gp->ws_dim);
+    if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
+    if (f.n_spheres < 0 || f.n_boxes < 0 || f.sphere_off < 0 || f.box_off < 0 || f.sphere_off + 4 * f.n_spheres > gp->n_prim_floats ||
+        f.box_off + 6 * f.n_boxes > gp->n_prim_floats || gp->n_prim_floats > 12 * 1024)
+        return fail(MPDX_E_INVALID, "grid bake: the field's primitive tables do not lie inside prims (%d floats, at most 12288)", gp->n_prim_floats);
+    long long nodes = 1;
+    for (int j = 0; j < 3; ++j) {
+        if (j < gp->ws_dim ? (n[j] < 2 || n[j] > 4096) : n[j] != 1)
+            return fail(MPDX_E_INVALID, "grid bake: n[%d] = %d (2 ... 4096 along a used axis, 1 along an unused one)", j, n[j]);
+        nodes *= n[j];
+    }
+    if (nodes > (1ll << 29)) return fail(MPDX_E_INVALID, "grid bake: %lld nodes", nodes);
+    if (!(cell > 0.f) || !(cell < 3.0e38f)) return fail(MPDX_E_INVALID, "grid bake: cell must be positive and finite");
+    if (grad_out && ((uintptr_t)grad_out & 15)) return fail(MPDX_E_INVALID, "grid bake: grad_out must be 16-byte aligned");
+    GridBakeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.f = dev_field_of(f); a.prims = gp->prims; a.n_prim_floats = gp->n_prim_floats; a.sdf = sdf_out; a.grad = grad_out; a.cell = cell;
+    for (int j = 0; j < 3; ++j) { a.n[j] = n[j]; a.origin[j] = j < gp->ws_dim ? origin[j] : 0.f; }
+    const unsigned blocks = (unsigned)((nodes + 255) / 256);
+    const size_t lds = (size_t)gp->n_prim_floats * sizeof(float);
+    if (gp->ws_dim == 2) hipLaunchKernelGGL(sdf_grid_bake_kernel<2>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(sdf_grid_bake_kernel<3>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 int mpdx_absmax(const float* x, uint32_t* absmax_out, int n_per_ctx, int B, int H, int D, void* stream) {

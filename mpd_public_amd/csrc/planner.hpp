@@ -24,7 +24,7 @@
 namespace mpdx {
 
 struct GpmpArgs {
-    mpdx_guide_params gp;   // robot, fields, margins, dt, sigma_gp, interpolation (identity normaliser: raw robot units)
+    dev_guide_params gp;   // robot, fields, margins, dt, sigma_gp, interpolation (identity normaliser: raw robot units)
     float* x;               // [B][H][D] current trajectories (in/out)
     float* delta;           // [B][H][D] last proposed step (in: candidate = x + delta; out: the new proposal)
     float* state;           // [B][4]: F(x), lambda, accepted steps, F(last candidate)
@@ -55,7 +55,7 @@ __device__ __forceinline__ void gn_accumulate(float c, const float (&j)[QD], flo
 // PART of NPARTS (2 or 4): the point's factors are split over that many threads (of different waves) - Panda: ranges of link spheres and of
 // self-collision pairs, point mass: fields round-robin
 template <int QD, int DIM, int ROBOT, int PART, int NPARTS>
-__device__ __forceinline__ void gn_point(const mpdx_guide_params& gp, const float* sprim, const float (&q)[QD], float* out) {
+__device__ __forceinline__ void gn_point(const dev_guide_params& gp, const float* sprim, const float (&q)[QD], float* out) {
     static_assert(NPARTS == 2 || NPARTS == 4, "two or four parts");
     constexpr int NT = QD * (QD + 1) / 2;
     float M[NT], v[QD], c2 = 0.f;
@@ -439,7 +439,7 @@ template <int QD, int DIM, int ROBOT>
 __global__ __launch_bounds__(kGpmpThreads, 1) void gpmp_lm_kernel(const GpmpArgs a) {
     constexpr int D = 2 * QD, DD = D * D, LSZ = D * (D + 1) / 2, NT = QD * (QD + 1) / 2, MSZ = NT + QD + 1, NTHR = kGpmpThreads;
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const mpdx_guide_params& gp = a.gp;
+    const dev_guide_params& gp = a.gp;
     const int tid = threadIdx.x, b = blockIdx.x, H = a.H;
     const int N = gp.interpolate ? gp.n_interp : H;
     const int n = H - 2, NR = n * D;                 // free support states, unknowns
@@ -707,7 +707,7 @@ __global__ __launch_bounds__(kGpmpThreads, 1) void gpmp_lm_kernel(const GpmpArgs
 // are mirrored to global memory (with the parent links) for the host's path extraction.  All control flow is workgroup-uniform:
 // every decision is an LDS broadcast.
 struct RrtArgs {
-    mpdx_guide_params gp;       // robot + collision fields (edges are checked with the LINK radius only, as traj_metrics_kernel)
+    dev_guide_params gp;       // robot + collision fields (edges are checked with the LINK radius only, as traj_metrics_kernel)
     const float* start;         // [n][QD]
     const float* goal;          // [n][QD]
     float* nodes;               // [n][2][max_nodes][QD]   tree 0 grows from the start, tree 1 from the goal
@@ -735,7 +735,7 @@ __device__ __forceinline__ void philox_uniform4(uint64_t seed, uint64_t ctr, flo
 
 // does configuration q collide?  `part` / `nparts` split the Panda's link spheres and self-collision pairs over threads
 template <int QD, int DIM, int ROBOT>
-__device__ __forceinline__ bool config_hit(const mpdx_guide_params& gp, const float* sprim, const float (&q)[QD], int part, int nparts) {
+__device__ __forceinline__ bool config_hit(const dev_guide_params& gp, const float* sprim, const float (&q)[QD], int part, int nparts) {
     bool hit = false;
     if constexpr (ROBOT == MPDX_ROBOT_POINTMASS) {
         if (part != 0) return false;
@@ -789,7 +789,7 @@ constexpr int kRrtThreads = 256;
 template <int QD, int DIM, int ROBOT>
 __global__ __launch_bounds__(kRrtThreads) void rrt_connect_kernel(const RrtArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const mpdx_guide_params& gp = a.gp;
+    const dev_guide_params& gp = a.gp;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
     const int M = a.max_nodes;
     float* tree = sm;                          // [2][M][QD]
@@ -954,7 +954,7 @@ __global__ __launch_bounds__(kRrtThreads) void rrt_connect_kernel(const RrtArgs 
 // An unsolved problem (link < 0) or a path longer than kPathMax nodes becomes the straight line start -> goal (the optimiser may repair it).
 constexpr int kPathMax = 1024;
 struct RrtPathArgs {
-    mpdx_guide_params gp;
+    dev_guide_params gp;
     const float* start;         // [n][QD]
     const float* goal;          // [n][QD]
     const float* nodes;         // [n][2][max_nodes][QD]
@@ -969,7 +969,7 @@ struct RrtPathArgs {
 template <int QD, int DIM, int ROBOT>
 __global__ __launch_bounds__(kRrtThreads) void rrt_path_kernel(const RrtPathArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const mpdx_guide_params& gp = a.gp;
+    const dev_guide_params& gp = a.gp;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
     const int M = a.max_nodes, H = a.H;
     float* pth = sm;                              // [kPathMax][QD] path nodes

@@ -9,6 +9,8 @@ static int check_planner_params(const mpdx_guide_params* gp, int H, int D) {
     if (D != 2 * gp->q_dim || D > 16) return fail(MPDX_E_INVALID, "state dim %d != 2*q_dim (%d)", D, gp->q_dim);
     if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS) return fail(MPDX_E_INVALID, "n_fields %d", gp->n_fields);
     if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
+    for (int f = 0; f < gp->n_fields; ++f)   // gn_point / config_hit scan primitive tables: a grid field would be skipped silently
+        if (gp->fields[f].kind == MPDX_FIELD_GRID) return fail(MPDX_E_INVALID, "grid fields: guide and metrics only (field %d is a MPDX_FIELD_GRID)", f);
     if (H > 0 && gp->interpolate && (gp->n_interp < 2 || gp->n_interp < H || gp->n_interp > 8 * H))
         return fail(MPDX_E_INVALID, "n_interp %d unsupported for H=%d", gp->n_interp, H);
     return 0;
@@ -27,7 +29,7 @@ int mpdx_gpmp_step(const mpdx_guide_params* gp, const mpdx_gpmp_opts* o, float* 
     if (int rc = check_planner_params(gp, H, D)) return rc;
     GpmpArgs a;
     memset(&a, 0, sizeof(a));
-    a.gp = *gp; a.x = x; a.delta = delta; a.state = state; a.B = B; a.H = H;
+    a.gp = dev_params_of(*gp); a.x = x; a.delta = delta; a.state = state; a.B = B; a.H = H;
     a.sigma_obs = o->sigma_obs; a.lam_up = o->lambda_up; a.lam_down = o->lambda_down; a.lam_min = o->lambda_min; a.lam_max = o->lambda_max;
     a.step = o->step; a.adaptive = o->adaptive; a.solve = solve;
     const int N = gp->interpolate ? gp->n_interp : H;
@@ -61,7 +63,7 @@ int mpdx_rrt_connect(const mpdx_guide_params* gp, const mpdx_rrt_opts* o, const 
     if (int rc = check_planner_params(gp, 0, 2 * gp->q_dim)) return rc;
     RrtArgs a;
     memset(&a, 0, sizeof(a));
-    a.gp = *gp; a.start = start; a.goal = goal; a.nodes = nodes; a.parent = parent; a.count = count; a.link = link; a.iters = iters;
+    a.gp = dev_params_of(*gp); a.start = start; a.goal = goal; a.nodes = nodes; a.parent = parent; a.count = count; a.link = link; a.iters = iters;
     for (int j = 0; j < 8; ++j) { a.q_lo[j] = o->q_lo[j]; a.q_hi[j] = o->q_hi[j]; }
     a.step = o->step; a.max_nodes = o->max_nodes; a.max_iters = o->max_iters; a.max_connect = o->max_connect_steps; a.n_checks = o->n_edge_checks;
     a.seed = o->seed;
@@ -93,7 +95,7 @@ int mpdx_rrt_paths(const mpdx_guide_params* gp, const float* start, const float*
     if (int rc = check_planner_params(gp, 0, 2 * gp->q_dim)) return rc;
     RrtPathArgs a;
     memset(&a, 0, sizeof(a));
-    a.gp = *gp; a.start = start; a.goal = goal; a.nodes = nodes; a.parent = parent; a.link = link; a.out = trajs_out; a.path_len = path_len;
+    a.gp = dev_params_of(*gp); a.start = start; a.goal = goal; a.nodes = nodes; a.parent = parent; a.link = link; a.out = trajs_out; a.path_len = path_len;
     a.max_nodes = max_nodes; a.H = H; a.n_checks = n_edge_checks; a.rounds = rounds; a.dt = dt;
     hipStream_t st = (hipStream_t)stream;
 #define MPDX_RRTP(QD_, DIM_, ROBOT_)                                                                                     \

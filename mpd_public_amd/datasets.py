@@ -136,11 +136,13 @@ class TrajectoryDataset:
     field_key_traj = "traj"
 
     def __init__(self, env_id="EnvDense2D", robot_id="RobotPointMass", n_support_points=64, include_velocity=True,
-                 obstacle_cutoff_margin=0.05, use_extra_objects=True, tensor_args=None, base_dir=None, normalizer="LimitsNormalizer", **kw):
+                 obstacle_cutoff_margin=0.05, use_extra_objects=True, tensor_args=None, base_dir=None, normalizer="LimitsNormalizer",
+                 sdf_grid=None, **kw):
         self.tensor_args = tensor_args or {"device": "cpu", "dtype": torch.float32}
         self.env, self.robot = make_env(env_id), make_robot(robot_id)
+        # sdf_grid (extension, default None: primitive tables): the task's fixed objects as a baked signed-distance grid (planning.PlanningTask)
         self.task = PlanningTask(self.env, self.robot, obstacle_cutoff_margin=obstacle_cutoff_margin,
-                                 use_extra_objects=use_extra_objects, tensor_args=self.tensor_args)
+                                 use_extra_objects=use_extra_objects, tensor_args=self.tensor_args, sdf_grid=sdf_grid)
         self.n_support_points, self.include_velocity = n_support_points, include_velocity
         self.state_dim = self.robot.q_dim * (2 if include_velocity else 1)
         # `normalizer`: one of the reference's five class names (trajectories.py:26,78).  Without a dataset directory the limits are this package's

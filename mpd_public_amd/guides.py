@@ -14,13 +14,15 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .planning import CostCollision, CostComposite, CostGPTrajectory
+from .planning import CostCollision, CostComposite, CostGPTrajectory, GRID_MODES
 
 
 def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight_l, interpolate, n_interp, clip_grad, max_grad_norm, device,
                         clip_grad_rule="norm", max_grad_value=0.1, identity_normalizer=False):
     """Compile cost descriptors into the `mpdx_guide_params` block the HIP kernels take.  Returns (params, primitive
-    table tensor) - the caller keeps the tensor alive (params holds its raw device pointer)."""
+    table tensor) - the caller keeps the tensor alive (params holds its raw device pointer).  The planes of FIELD_GRID fields travel in a second
+    buffer (global memory, not part of the primitive table the kernels stage in LDS): `params.grids_tensor` (None without a grid) holds it and
+    lives as long as the params object; callers keep it next to the primitive table."""
     gp = _lib.GuideParams()
     gp.robot, gp.q_dim, gp.ws_dim = robot.robot_id, robot.q_dim, ws_dim
     gp.interpolate, gp.n_interp = int(bool(interpolate)), int(n_interp)
@@ -36,6 +38,7 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
             gp.mins[d], gp.maxs[d] = float(mins[d]), float(maxs[d])
     gp.cutoff_margin, gp.link_margin = float(cutoff_margin), float(robot.link_margin)
     prims, nf, off = [], 0, 0
+    planes, goff = [], 0     # grid planes, each padded to a multiple of 4 floats (16-byte aligned gradient planes)
     gp.use_gp = 0
     for c, w in zip(cost_l, weight_l):
         if isinstance(c, CostCollision):
@@ -53,6 +56,28 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
             elif fld.kind == _lib.FIELD_WORKSPACE:
                 for j in range(ws_dim):
                     f.ws_min[j], f.ws_max[j] = float(fld.ws_min[j]), float(fld.ws_max[j])
+            elif fld.kind == _lib.FIELD_GRID:
+                g = fld.grid
+                if g is None or g.dim != ws_dim:
+                    raise ValueError(f"FIELD_GRID needs a GridSDF of the workspace dimension {ws_dim}")
+                sdf_p, grad_p = g.planes(device)
+                if g.mode == "nearest" and grad_p is None:
+                    raise ValueError("GridSDF mode 'nearest' needs the gradient plane")
+                f.mode, f.cell = GRID_MODES[g.mode], g.cell
+                for j in range(3):
+                    f.n[j] = g.shape[j] if j < ws_dim else 1
+                    f.origin[j] = float(g.origin[j]) if j < ws_dim else 0.0
+                f.grid_sdf_off, f.grid_grad_off = goff, -1
+                for pl in (sdf_p, grad_p if g.mode == "nearest" else None):
+                    if pl is None:
+                        continue
+                    if pl is grad_p:
+                        f.grid_grad_off = goff
+                    planes.append(pl)
+                    goff += pl.numel()
+                    if goff % 4:
+                        planes.append(torch.zeros(4 - goff % 4, dtype=torch.float32, device=pl.device))
+                        goff += planes[-1].numel()
             nf += 1
         elif isinstance(c, CostGPTrajectory):
             if gp.use_gp:
@@ -66,6 +91,11 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
     table = np.concatenate(prims).astype(np.float32) if n_floats else np.zeros(4, np.float32)
     prim_t = torch.from_numpy(table).to(device)
     gp.prims, gp.n_prim_floats = prim_t.data_ptr(), n_floats
+    grid_t = None
+    if planes:
+        grid_t = planes[0] if len(planes) == 1 else torch.cat(planes)   # (a single plane is used in place: no second copy of a 7.8-MB grid)
+        gp.grids, gp.n_grid_floats = grid_t.data_ptr(), goff
+    gp.grids_tensor = grid_t   # a Python attribute of the ctypes object: the buffer lives as long as the params that point into it
     return gp, prim_t
 
 
@@ -91,6 +121,7 @@ class GuideManagerTrajectoriesWithVelocity(nn.Module):
         self.max_grad_norm, self.max_grad_value = max_grad_norm, max_grad_value
         self._params = None
         self._prims = None
+        self._grids = None
         self._flag = None
 
     # ------------------------------------------------------------------------------------------- compile to device params
@@ -114,6 +145,7 @@ class GuideManagerTrajectoriesWithVelocity(nn.Module):
             self.cost.cost_l, self.cost.weight_cost_l, self.interpolate_trajectories_for_collision, self.num_interpolated_points_for_collision,
             self.clip_grad, self.max_grad_norm, device, clip_grad_rule=self.clip_grad_rule, max_grad_value=self.max_grad_value,
             identity_normalizer=mode)
+        self._grids = self._params.grids_tensor
         return self._params
 
     # ------------------------------------------------------------------------------------------- guide protocol

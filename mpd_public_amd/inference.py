@@ -37,7 +37,10 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
                n_diffusion_steps_without_noise: int = 5, weight_grad_cost_collision: float = 1e-2,
                weight_grad_cost_smoothness: float = 1e-7, factor_num_interpolated_points_for_collision: float = 1.5,
                trajectory_duration: float = 5.0, device: str = "cuda", debug: bool = True, render: bool = False, seed: int = 30,
-               results_dir: str = "logs", model_dir: str = None, model_args: dict = None, **kwargs):
+               results_dir: str = "logs", model_dir: str = None, model_args: dict = None, sdf_grid_cell_size: float = None,
+               sdf_grid_mode: str = "linear", **kwargs):
+    """sdf_grid_cell_size / sdf_grid_mode (extension): None (default) keeps the primitive tables; a cell size makes the task's FIXED objects a
+    signed-distance grid baked on the device ('linear' interpolation or 'nearest' node, planning.PlanningTask(sdf_grid=...))."""
     torch.manual_seed(seed)
     if not torch.cuda.is_available():
         raise RuntimeError("mpd_public_amd.inference needs an AMD GPU (no CPU fallback)")
@@ -58,8 +61,9 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
         args.update(model_args)
     env_id, robot_id = model_id.split("-")
 
+    sdf_grid = None if sdf_grid_cell_size is None else dict(cell_size=float(sdf_grid_cell_size), mode=sdf_grid_mode)
     dataset = TrajectoryDataset(env_id=env_id, robot_id=robot_id, use_extra_objects=True, obstacle_cutoff_margin=0.05,
-                                include_velocity=args["include_velocity"], tensor_args=tensor_args)
+                                include_velocity=args["include_velocity"], tensor_args=tensor_args, sdf_grid=sdf_grid)
     n_support_points, robot, task = dataset.n_support_points, dataset.robot, dataset.task
     dt = trajectory_duration / n_support_points
     robot.dt = dt
@@ -223,5 +227,7 @@ if __name__ == "__main__":
     ap.add_argument("--results_dir", default="logs")
     ap.add_argument("--model_dir", default=None, help="a results directory of mpd_public_amd.train (args.yaml, limits.yaml, checkpoints/): plan with its trained weights")
     ap.add_argument("--n_diffusion_steps_without_noise", type=int, default=5)
+    ap.add_argument("--sdf_grid_cell_size", type=float, default=None, help="fixed objects as a signed-distance grid of this cell size (default: primitive tables)")
+    ap.add_argument("--sdf_grid_mode", default="linear", choices=["linear", "nearest"])
     a = ap.parse_args()
     experiment(**vars(a))

@@ -136,6 +136,119 @@ def make_robot(robot_id: str):
 # ------------------------------------------------------------------------------------------------ collision fields / task
 
 
+GRID_MODES = {"linear": _lib.GRID_LINEAR, "nearest": _lib.GRID_NEAREST}
+
+
+@dataclass
+class GridSDF:
+    """A signed-distance field sampled on a regular grid (torch_robotics' GridMapSDF, un-vendored: the lookup is restated in include/mpdx.h with
+    both plausible forms - `mode` 'linear': bi-/trilinear interpolation, gradient = its analytic derivative; 'nearest': the value and the STORED
+    gradient of the nearest node, GridMapSDF as recalled).
+
+    sdf    [nz, ny, nx] (3-D) or [ny, nx] (2-D) node values, x fastest; node (ix, iy, iz) sits at origin + (ix, iy, iz) * cell
+    grad   None (linear mode needs none) or [..., dim] / [..., 4] node gradients, same leading shape as sdf
+    A grid to be baked on first use from primitives (`PlanningTask(sdf_grid=...)`) has sdf = None and carries `source` / `shape` instead."""
+    sdf: Optional[torch.Tensor]
+    origin: np.ndarray
+    cell: float
+    mode: str = "linear"
+    grad: Optional[torch.Tensor] = None
+    source: Optional[ObjectSet] = None      # bake from these primitives (mpdx_sdf_grid_bake) when sdf is None
+    shape: Optional[tuple] = None           # (nx, ny[, nz]) of a grid still to be baked
+
+    def __post_init__(self):
+        if self.mode not in GRID_MODES:
+            raise ValueError(f"GridSDF mode {self.mode!r}: 'linear' or 'nearest'")
+        self.origin = np.asarray(self.origin, np.float32).reshape(-1)
+        self.cell = float(self.cell)
+        if not self.cell > 0:
+            raise ValueError("GridSDF cell must be positive")
+        if self.sdf is None:
+            if self.source is None or self.shape is None:
+                raise ValueError("GridSDF needs node values (sdf) or primitives to bake them from (source, shape)")
+        else:
+            self.sdf = torch.as_tensor(self.sdf)
+            if self.sdf.dim() not in (2, 3):
+                raise ValueError("GridSDF sdf is [ny, nx] or [nz, ny, nx]")
+            self.shape = tuple(reversed(self.sdf.shape))
+            if self.grad is not None:
+                self.grad = torch.as_tensor(self.grad)
+                if tuple(self.grad.shape[:-1]) != tuple(self.sdf.shape) or self.grad.shape[-1] not in (self.dim, 4):
+                    raise ValueError("GridSDF grad is sdf.shape + (dim,) or sdf.shape + (4,)")
+            elif self.mode == "nearest":
+                raise ValueError("GridSDF mode 'nearest' returns the stored node gradient: give grad")
+        self.shape = tuple(int(v) for v in self.shape)
+        if len(self.shape) != self.origin.size or min(self.shape) < 2:
+            raise ValueError("GridSDF: one origin coordinate per axis and at least 2 nodes along every axis")
+        self._planes = None
+
+    @property
+    def dim(self) -> int:
+        return len(self.shape)
+
+    @property
+    def n_nodes(self) -> int:
+        return int(np.prod(self.shape))
+
+    def planes(self, device):
+        """(sdf plane [n_nodes] fp32, gradient plane [n_nodes * 4] fp32 or None) on `device`, baked there first if need be."""
+        device = torch.device(device)
+        if self._planes is not None and self._planes[0].device == device:
+            return self._planes
+        if self.sdf is None:
+            self._planes = self._bake(device)
+        else:
+            sdf = self.sdf.to(device=device, dtype=torch.float32).contiguous().reshape(-1)
+            grad = None
+            if self.grad is not None:
+                g = self.grad.to(device=device, dtype=torch.float32).reshape(-1, self.grad.shape[-1])
+                grad = torch.zeros((g.shape[0], 4), dtype=torch.float32, device=device)
+                grad[:, :self.dim] = g[:, :self.dim]
+                grad = grad.reshape(-1)
+            self._planes = (sdf, grad)
+        return self._planes
+
+    def _bake(self, device):
+        import ctypes as C
+        if device.type != "cuda":
+            raise RuntimeError("a signed-distance grid is baked on the GPU (mpdx_sdf_grid_bake); there is no CPU fallback")
+        gp = _lib.GuideParams()
+        gp.ws_dim, gp.n_fields = self.dim, 1
+        sp, bx = self.source.prim_floats()
+        f = gp.fields[0]
+        f.kind, f.sphere_off, f.n_spheres, f.box_off, f.n_boxes = _lib.FIELD_OBJECTS, 0, sp.size // 4, sp.size, bx.size // 6
+        table = np.concatenate([sp, bx, np.zeros(4, np.float32)]).astype(np.float32)
+        prims = torch.from_numpy(table).to(device)
+        gp.prims, gp.n_prim_floats = prims.data_ptr(), sp.size + bx.size
+        sdf = torch.empty(self.n_nodes, dtype=torch.float32, device=device)
+        grad = torch.empty(self.n_nodes * 4, dtype=torch.float32, device=device) if self.mode == "nearest" else None   # linear mode reads none
+        n = (C.c_int * 3)(*(list(self.shape) + [1] * (3 - self.dim)))
+        org = (C.c_float * 3)(*([float(v) for v in self.origin] + [0.0] * (3 - self.dim)))
+        with torch.cuda.device(device):
+            _lib.check(_lib.load().mpdx_sdf_grid_bake(C.byref(gp), 0, sdf.data_ptr(), None if grad is None else grad.data_ptr(), C.byref(n), C.byref(org), self.cell,
+                                                      _lib.current_stream()), "mpdx_sdf_grid_bake")
+            torch.cuda.current_stream().synchronize()   # (prims may be freed after this)
+        return sdf, grad
+
+    def node_values(self, device="cuda"):
+        """(sdf [nz, ny, nx] | [ny, nx], grad [..., 4] or None) as the kernels read them (downloaded by the tests for their fp64 reference)."""
+        sdf, grad = self.planes(device)
+        shp = tuple(reversed(self.shape))
+        return sdf.reshape(shp), (None if grad is None else grad.reshape(shp + (4,)))
+
+
+def grid_spec_for(ws_min, ws_max, cell_size, padding=0.3, shift=0.37):
+    """Node counts and origin of the grid box of a workspace: the limits grown by `padding` (default 0.3 m: more than the largest link radius 0.10 +
+    the cutoff margin) with the origin moved down by a further `shift` cells.  The shift keeps geometry that is aligned with the world axes off the
+    node planes - the Panda's first two collision spheres lie on the base axis (x = y = 0 at every configuration); unshifted they sit exactly on
+    a node plane at every waypoint, where the interpolant has its kinks."""
+    cell = float(cell_size)
+    lo = np.asarray(ws_min, np.float64) - padding - shift * cell
+    hi = np.asarray(ws_max, np.float64) + padding
+    n = np.ceil((hi - lo) / cell).astype(np.int64) + 1
+    return tuple(int(v) for v in n), lo.astype(np.float32)
+
+
 @dataclass
 class CollisionField:
     kind: int                       # _lib.FIELD_*
@@ -143,16 +256,33 @@ class CollisionField:
     ws_min: Optional[np.ndarray] = None
     ws_max: Optional[np.ndarray] = None
     name: str = ""
+    grid: Optional[GridSDF] = None  # _lib.FIELD_GRID
 
 
 class PlanningTask:
     """The attribute / method surface inference.py reads from `task` (inference.py:161,191-193,288-297)."""
 
-    def __init__(self, env: Env, robot, obstacle_cutoff_margin=0.05, use_extra_objects=True, tensor_args=None, **kw):
+    def __init__(self, env: Env, robot, obstacle_cutoff_margin=0.05, use_extra_objects=True, tensor_args=None, sdf_grid=None, **kw):
+        """sdf_grid (extension; None = the primitive tables, as before): dict(cell_size=..., mode='linear' | 'nearest', padding=0.3) - the FIXED
+        objects become a signed-distance grid (baked from the primitives on the device on first use, mpdx_sdf_grid_bake) and
+        get_collision_fields() returns a FIELD_GRID field in their place; extra objects, workspace and self fields stay as they are (as
+        torch_robotics does, as recalled: the precomputed grid is for the fixed objects only).  An environment that already carries a grid
+        (env.grid_fixed, set by task_from_torch_robotics) uses it as it is."""
         self.env, self.robot, self.obstacle_cutoff_margin = env, robot, obstacle_cutoff_margin
         self.tensor_args = tensor_args or {"device": "cpu", "dtype": torch.float32}
         self.ws_min, self.ws_max = env.limits
-        self.df_collision_objects = CollisionField(_lib.FIELD_OBJECTS, objects=env.obj_fixed, name="objects")
+        self.sdf_grid = dict(sdf_grid) if sdf_grid is not None else None
+        if getattr(env, "grid_fixed", None) is not None:
+            self.df_collision_objects = CollisionField(_lib.FIELD_GRID, grid=env.grid_fixed, name="objects")
+        elif self.sdf_grid is not None:
+            unknown = set(self.sdf_grid) - {"cell_size", "mode", "padding"}
+            if unknown or "cell_size" not in self.sdf_grid:
+                raise ValueError(f"sdf_grid takes cell_size, mode, padding (got {sorted(self.sdf_grid)})")
+            shape, origin = grid_spec_for(self.ws_min, self.ws_max, self.sdf_grid["cell_size"], float(self.sdf_grid.get("padding", 0.3)))
+            grid = GridSDF(None, origin, self.sdf_grid["cell_size"], mode=self.sdf_grid.get("mode", "linear"), source=env.obj_fixed, shape=shape)
+            self.df_collision_objects = CollisionField(_lib.FIELD_GRID, objects=env.obj_fixed, grid=grid, name="objects")
+        else:
+            self.df_collision_objects = CollisionField(_lib.FIELD_OBJECTS, objects=env.obj_fixed, name="objects")
         self.df_collision_extra_objects = CollisionField(_lib.FIELD_OBJECTS, objects=env.obj_extra, name="extra_objects") if use_extra_objects else None
         self.df_collision_ws_boundaries = CollisionField(_lib.FIELD_WORKSPACE, ws_min=self.ws_min, ws_max=self.ws_max, name="workspace")
         self.df_collision_self = CollisionField(_lib.FIELD_SELF, name="self") if robot.name == "RobotPanda" else None
@@ -171,6 +301,7 @@ class PlanningTask:
             costs = [CostCollision(self.robot, 64, field=f) for f in self.get_collision_fields()]
             self._gp, self._gp_prims = build_device_params(self.robot, self.env.dim, self.obstacle_cutoff_margin, None, None, costs,
                                                            [1.0] * len(costs), True, 128, True, 1.0, device)
+            self._gp_grids = self._gp.grids_tensor   # (None without a grid field) kept alive next to the primitive table
         return self._gp
 
     def trajectory_metrics(self, trajs, n_check=None, return_mask=False):
@@ -249,7 +380,13 @@ def task_from_torch_robotics(tr_task, tensor_args=None, use_extra_objects=True) 
                                        ([margin]) or .link_margin
       tr_task.obstacle_cutoff_margin   float (inference.py:110)
 
-    Signed-distance GRIDS (`GridMapSDF`) and meshes have no primitive form: they raise NotImplementedError (the kernels scan sphere / box tables).
+          GridMapSDF                       .sdf_tensor ([nx, ny(, nz)] node values, indexed as sdf_tensor[ix, iy(, iz)]), .grad_sdf_tensor (the same
+                                           shape + [dim]), .limits ([2, dim]: the position of node 0 and of the last node), .cell_size (float or [dim]
+                                           with equal entries) - AS RECALLED, all four needed: it becomes a `GridSDF` in 'nearest' mode (the recalled
+                                           lookup: value and stored gradient of the node round((p - limits[0]) / cell_size)) with origin = limits[0].
+                                           One grid per objects list, and not next to primitives in the same list (NotImplementedError).
+
+    A field that is neither (a mesh, a grid object without that full surface) has no primitive form: it raises NotImplementedError.
     The arithmetic on the tables (hinge on the SDF, FK, interpolation) is this package's restatement (parity unpinned)."""
     def need(obj, *names):
         for n in names:
@@ -266,8 +403,34 @@ def task_from_torch_robotics(tr_task, tensor_args=None, use_extra_objects=True) 
     if dim not in (2, 3):
         raise NotImplementedError(f"workspace dimension {dim}")
 
-    def object_set(obj_list):
+    GRID_ATTRS = ("sdf_tensor", "grad_sdf_tensor", "limits", "cell_size")
+
+    def grid_of(f):
+        sdf, grad = need(f, "sdf_tensor"), need(f, "grad_sdf_tensor")
+        sdf, grad = torch.as_tensor(sdf).detach().cpu().float(), torch.as_tensor(grad).detach().cpu().float()
+        if sdf.dim() != dim or tuple(grad.shape) != tuple(sdf.shape) + (dim,):
+            raise NotImplementedError(f"GridMapSDF: sdf_tensor {tuple(sdf.shape)} / grad_sdf_tensor {tuple(grad.shape)} for a {dim}-D workspace")
+        cs = np.unique(arr(need(f, "cell_size")))
+        if cs.size != 1:
+            raise NotImplementedError("GridMapSDF with per-axis cell sizes: the grid field has one cubic cell")
+        lim = arr(need(f, "limits"), dim)
+        perm = tuple(reversed(range(dim)))    # [ix, iy(, iz)] -> [(iz,) iy, ix]: x fastest
+        return GridSDF(sdf.permute(*perm).contiguous(), lim[0].copy(), float(cs[0]), mode="nearest", grad=grad.permute(*perm, dim).contiguous())
+
+    grids = {}
+
+    def object_set(obj_list, which="fixed"):
         sc, sr, bc, bh = [], [], [], []
+        n_grid = sum(all(hasattr(f, a) for a in GRID_ATTRS) for obj in (obj_list or []) for f in need(obj, "fields"))
+        n_all = sum(len(need(obj, "fields")) for obj in (obj_list or []))
+        if n_grid:
+            if n_grid != 1 or n_all != 1:
+                raise NotImplementedError("one GridMapSDF per objects list, not mixed with primitive fields in the same list")
+            obj = [o for o in obj_list if len(o.fields)][0]
+            if getattr(obj, "pos", None) is not None and np.abs(arr(obj.pos)).max() > 0:
+                raise NotImplementedError("a GridMapSDF under a shifted ObjectField")
+            grids[which] = grid_of(obj.fields[0])
+            return ObjectSet.empty()
         for obj in (obj_list or []):
             ori = getattr(obj, "ori", None)
             if ori is not None:
@@ -294,7 +457,10 @@ def task_from_torch_robotics(tr_task, tensor_args=None, use_extra_objects=True) 
                          np.concatenate(bc) if bc else z.box_centers, np.concatenate(bh) if bh else z.box_half)
 
     env = Env(str(getattr(env_t, "name", type(env_t).__name__)), dim, object_set(need(env_t, "obj_fixed_list")),
-              object_set(getattr(env_t, "obj_extra_list", None)))
+              object_set(getattr(env_t, "obj_extra_list", None), "extra"))
+    if "extra" in grids:
+        raise NotImplementedError("a GridMapSDF among the EXTRA objects: the grid field stands for the fixed objects")
+    env.grid_fixed = grids.get("fixed")
     lim = arr(need(env_t, "limits"), dim)
     env.limits = (lim[0].copy(), lim[1].copy())
     rob_t = need(tr_task, "robot")
