@@ -80,7 +80,7 @@ struct BwdArgs {
     BwdOp ops[kMaxBwdOps];
 };
 
-// ---- compile-time LDS geometry of the two static programs (train_host.hpp builds the same layout at run time and compares: a mismatch is an error).
+// ---- compile-time LDS geometry of the two static programs (train_bwd_prog.hpp builds the same layout at run time and compares: a mismatch is an error).
 // Five slots of kBwdSlot4 float4 (the largest buffer: 20 rows x (128 + 4) floats): IN, GB, DUA, DUB, GA; a buffer of C channels has rows of C / 4 + 1 float4.
 #ifndef MPDX_BWD_PAD4
 #define MPDX_BWD_PAD4 1
@@ -137,7 +137,7 @@ constexpr BwdGeomOp bwd_up_geom(int i) {
 }
 template <int PROG, int I> struct BwdGeomOf { static constexpr bool has = true; static constexpr BwdGeomOp g = PROG == 0 ? bwd_down_geom(I) : (PROG == 2 ? bwd_down_geom(I, true) : (PROG == 3 ? bwd_down_mid_geom(I) : bwd_up_geom(I))); };
 struct BwdGeomNone { static constexpr bool has = false; static constexpr BwdGeomOp g{0, 0, 0, 0, -1, 0, -1, 0, -1, 0, 0}; };
-// host: does op `o` (as train_host.hpp laid it out) have the table's LDS geometry?
+// host: does op `o` (as train_bwd_prog.hpp laid it out) have the table's LDS geometry?
 inline bool bwd_geom_matches(const BwdOp& o, const BwdGeomOp& g, bool has_rsrc) {
     return o.src_off4 == g.src_off4 && o.src_rs4 == g.src_rs4 && (!has_rsrc || (o.rsrc_off4 == g.rsrc_off4 && o.rsrc_rs4 == g.rsrc_rs4)) && o.add_off4 == g.add_off4 &&
            (g.add_off4 < 0 || o.add_rs4 == g.add_rs4) && o.gy_off4 == g.gy_off4 && (g.gy_off4 < 0 || o.gy_rs4 == g.gy_rs4) && o.dst_off4 == g.dst_off4 &&
@@ -522,7 +522,7 @@ __global__ __launch_bounds__(kFusedThreads) void fused_bwd_program_kernel(const 
     fused_bwd_prologue(a, SEQ::template next_desc<0>(a), ring, smem, tid, lane, wave, b);
     SEQ::template run_from<0>(a, ring, smem, wave, lane, b);
 }
-// the backward pass of downs[0..2] of the standard network (train_host.hpp run_down_program)
+// the backward pass of downs[0..2] of the standard network (train_bwd_prog.hpp run_down_program)
 using BwdSeqDown3 = BwdSeq<0, 0, 1, 1, 1, 2, 3, 4, 4, 4, 5, 6, 7, 7, 7>;
 // the same for the THREE-level network (dim_mults (1, 2, 4)): its innermost level has no Downsample1d - the first op is the GroupNorm backward alone
 using BwdSeqDown3Last = BwdSeq<2, 16, 1, 1, 1, 2, 3, 4, 4, 4, 5, 6, 7, 7, 7>;

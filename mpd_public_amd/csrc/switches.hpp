@@ -27,7 +27,7 @@ constexpr int kUnset = INT_MIN;   // default of an INT switch that has to tell "
     /* ---- diagnostics */ \
     X(debug,               "MPDX_DEBUG",                INT,     0,       ONCE, "1: hipGetLastError() after every launch group of mpdx_plan; 2: also synchronise the stream there, so that an asynchronous fault is attributed to the step that caused it (off: the plan never synchronises)") \
     X(debug_fuse,          "MPDX_DEBUG_FUSE",           STR,     nullptr, LIVE, "set: print every fused segment built and which shape constraint rejected one; a value >= 2 also dumps the segment's LDS geometry as a fused_geom.hpp initialiser") \
-    X(debug_train,         "MPDX_DEBUG_TRAIN",          PRESENT, false,   LIVE, "print which backward programs, chain launches and late weight-gradient jobs a training pass ran (tests/test_gpu_train.py reads these lines)") \
+    X(debug_train,         "MPDX_DEBUG_TRAIN",          PRESENT, false,   LIVE, "print which backward programs a training pass ran and how many late weight-gradient jobs it collected (tests/test_gpu_train.py reads the first line)") \
     X(bwd_dbg,             "MPDX_BWD_DBG",              INT,     0,       LIVE, "BwdArgs::dbg of the backward programs (fused_bwd.hpp debug output)") \
     /* ---- path selection (tests and A/B runs use these) */ \
     X(fused,               "MPDX_FUSED",                ON,      true,    LIVE, "0: no fused level program, every layer its own launch (forward of planning and training)") \
@@ -63,8 +63,6 @@ constexpr int kUnset = INT_MIN;   // default of an INT switch that has to tell "
     X(train_pair_fwd,      "MPDX_TRAIN_PAIR_FWD",       ON,      true,    ONCE, "0: training forward, blocks[0] + residual 1x1 as two launches (paired: two launches of ~4.8 us less per pass on the four-level network)") \
     X(train_gn_fuse,       "MPDX_TRAIN_GN_FUSE",        ON,      true,    ONCE, "0: Mish + GroupNorm backward as its own launch, not the epilogue of the consumer's input-gradient convolution") \
     X(train_gn_inplace,    "MPDX_TRAIN_GN_INPLACE",     ON,      true,    ONCE, "0: an un-fused GroupNorm backward writes the shared dU scratch, not the layer's own gradient slot (in place: 22.6 -> 12.5 us for the one such 256 -> 256 layer at batch 128)") \
-    X(train_chain,         "MPDX_TRAIN_CHAIN",          INT,     0,       ONCE, "backward chain launches (SLOWER, off: batch 32 0.608 -> 0.640 ms, profiles/r06_train_chain_ab.txt): 1 auto, 16 / 32 / 64 the smallest level length that chains") \
-    X(train_chain_max_b,   "MPDX_TRAIN_CHAIN_MAX_B",    INT,     256,     ONCE, "largest batch that MPDX_TRAIN_CHAIN chains") \
     X(train_bwd_prog,      "MPDX_TRAIN_BWD_PROG",       INT,     1,       ONCE, "whole-trajectory backward programs of the outer levels (fused_bwd.hpp): 0 off, 2 the down program only") \
     X(train_bwd_prog_max_b,"MPDX_TRAIN_BWD_PROG_MAX_B", INT,     512,     ONCE, "largest batch that runs the backward programs") \
     X(wgrad_late_div,      "MPDX_WGRAD_LATE_DIV",       INT,     kUnset,  ONCE, "divisor (>= 1) of the batch splits of the weight gradients that run behind the chain and of the backward programs'; unset: 4 / 8 / 4 at batch < 64 / <= 128 / beyond (profiles/r06_train_late_div_ab.txt)") \

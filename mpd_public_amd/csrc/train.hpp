@@ -527,55 +527,6 @@ __global__ __launch_bounds__(512) void bwd_pair_kernel(const BwdPairArgs a) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// The backward CHAIN of the outer levels as ONE launch (round 6).  At the levels whose trajectories own whole tiles (L = 64 / 32 / 16) the
-// input-gradient convolutions - with the Mish + GroupNorm backward of the Conv1dBlock below in their epilogue - and the stand-alone GroupNorm
-// backwards form a chain in which every step needs only what the SAME trajectory's earlier steps produced.  One 512-thread workgroup per
-// trajectory walks the steps the per-layer path would have launched one by one - same bodies (conv_block_body on the dgrad pack with
-// NT = L positions: one trajectory per tile, the channel tiles one after the other; gn_mish_bwd_body), same operands through the same gradient
-// buffers in global memory (L2), same order - separated by workgroup barriers instead of launch boundaries (a barrier orders the workgroup's
-// global stores before its later loads).  The layers' weight gradients do not ride: they run in wgrad_multi_kernel behind the chains.
-constexpr int kChainMaxConv = 22, kChainMaxGn = 6, kChainMaxSteps = kChainMaxConv + kChainMaxGn;
-struct ChainStep { short kind, sel, n_mt, idx; };   // kind 0: dgrad conv (sel = selector below, idx into cd), 1: GroupNorm backward (sel = EPL, idx into gn)
-struct ChainArgs {
-    int n;
-    ChainStep st[kChainMaxSteps];
-    GnBwdArgs gn[kChainMaxGn];
-    ConvArgs cd[kChainMaxConv];
-};
-// selector of a dgrad body: taps (5 / 3 / 1), positions per trajectory (64 / 32 / 16), epilogue (plain / GroupNorm backward); MT = 32
-__host__ __device__ constexpr int chain_sel(int ks, int nt, int gnbwd) { return ((ks == 5 ? 0 : ks == 3 ? 1 : 2) * 3 + (nt == 64 ? 0 : nt == 32 ? 1 : 2)) * 2 + (gnbwd ? 1 : 0); }
-__global__ __launch_bounds__(512) void bwd_chain_kernel(const ChainArgs a) {
-    warm_kernarg<(int)sizeof(ChainArgs)>();
-    const int b = (int)blockIdx.x;
-    const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
-    for (int k = 0; k < a.n; ++k) {
-        const ChainStep s = a.st[k];
-        if (s.kind == 1) {
-            const GnBwdArgs& g = a.gn[s.idx];
-            if (wave < g.n_groups) {
-                if (s.sel == 4) gn_mish_bwd_body<4>(g, b * g.n_groups + wave, lane);
-                else gn_mish_bwd_body<2>(g, b * g.n_groups + wave, lane);
-            }
-            __syncthreads();
-            continue;
-        }
-        const ConvArgs& c = a.cd[s.idx];
-        for (int mt = 0; mt < s.n_mt; ++mt) {
-            const int tile = mt + s.n_mt * b;   // conv_block_body: mt = tile % n_mt, position tile = tile / n_mt = this trajectory
-            switch (s.sel) {
-#define MPDX_CHAIN_CASE(KS, NT, GN) case chain_sel(KS, NT, GN): conv_block_body<CONV_S1, KS, GN ? EPI_GN_BWD : EPI_BIAS, 32, NT, 1, 8>(c, tile); break;
-                MPDX_CHAIN_CASE(5, 64, 0) MPDX_CHAIN_CASE(5, 64, 1) MPDX_CHAIN_CASE(5, 32, 0) MPDX_CHAIN_CASE(5, 32, 1) MPDX_CHAIN_CASE(5, 16, 0) MPDX_CHAIN_CASE(5, 16, 1)
-                MPDX_CHAIN_CASE(3, 64, 0) MPDX_CHAIN_CASE(3, 64, 1) MPDX_CHAIN_CASE(3, 32, 0) MPDX_CHAIN_CASE(3, 32, 1) MPDX_CHAIN_CASE(3, 16, 0) MPDX_CHAIN_CASE(3, 16, 1)
-                MPDX_CHAIN_CASE(1, 64, 0) MPDX_CHAIN_CASE(1, 32, 0) MPDX_CHAIN_CASE(1, 16, 0)
-#undef MPDX_CHAIN_CASE
-                default: break;
-            }
-            __syncthreads();   // the tile's epilogue has stored (workgroup-visible) before anything of this workgroup reads it / restages LDS
-        }
-    }
-}
-
 // MANY weight-gradient GEMMs in ONE launch (round 6): every job keeps its own grid (x = N tiles, y = M tiles, z = batch splits); the blocks of job k
 // are [start[k], start[k + 1]) - found by bisection, as wgrad_reduce_all_body does.  The weight gradients of a layer depend only on the layer's dU and on
 // its (kept) input: nothing in the backward chain waits for them, so they need not ride on the chain's launches (where a dgrad launch lasts as long as

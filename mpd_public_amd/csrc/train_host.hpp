@@ -1,5 +1,6 @@
-// train_host.hpp - host side of the training step (included at the end of mpdx.hip; kernels in train.hpp).
+// train_host.hpp - host side of the training step (included at the end of k_train.hip; kernels in train.hpp).
 // Entry points: mpdx_train_* (include/mpdx.h).  Everything is enqueued on the caller's stream; no synchronisation.
+// mpdx_train_loss_backward runs the stages of TrainPass below; the whole-trajectory backward programs among them live in train_bwd_prog.hpp.
 #pragma once
 
 namespace mpdx {
@@ -370,141 +371,6 @@ static int launch_lone_wgrads(const WgradJob* jobs, int njobs, hipStream_t st) {
     return 0;
 }
 
-// ---- whole-trajectory backward programs (fused_bwd.hpp).  The DOWN program: the backward pass of downs[0..2] of the standard network (three levels of
-// [blocks.0 | residual 1x1 | blocks.1] [blocks.0 | blocks.1 (identity residual)] [Downsample1d], 32 / 64 / 128 channels on 64 / 32 / 16 positions) in
-// ONE launch.  Layer indices: level k occupies [6 k, 6 k + 6) = b0.0, r, b0.1, b1.0, b1.1, down.
-struct BwdProgLayout { int off4[5]; int stat_off; size_t lds_bytes; };
-static BwdProgLayout bwd_down_layout() {
-    // five LDS slots of the largest buffer (20 rows x (128 + 4) floats = 660 float4): IN (the stride-2 layer's zero-stuffed dU), GB, DUa, DUb, GA
-    BwdProgLayout L;
-    const int slot4 = kBwdSlot4;   // >= 20 x 33, 36 x 17, 68 x 9 float4
-    for (int k = 0; k < 5; ++k) L.off4[k] = k * slot4;
-    L.stat_off = 5 * slot4 * 4;
-    L.lds_bytes = (size_t)(L.stat_off + 384) * sizeof(float);
-    return L;
-}
-// is the head of the network the three-level down path the program is written for?  1: layers [0, 18), every level ends in a Downsample1d (dim_mults (1, 2, 4, 8));
-// 2: layers [0, 17), the third level is the innermost one and has none (dim_mults (1, 2, 4): the reference's UNET_DIM_MULTS option 0); 0: neither
-static int bwd_down_applicable(const mpdx_unet* u) {
-    if ((int)u->layers.size() < 19 || u->cfg.n_support_points != 64 || u->masked()) return 0;
-    int variant = 1;
-    for (int k = 0; k < 3; ++k) {
-        const int C = 32 << k, Lk = 64 >> k, b = 6 * k;
-        const int cin = k == 0 ? u->cfg.state_dim : C / 2;
-        auto blk = [&](int i, int c_in) { const Layer& l = u->layers[i]; return l.mode == CONV_S1 && l.ks == 5 && l.epi == EPI_GN_MISH && l.c1 == c_in && l.c2 == 0 && l.cout == C && l.L_out == Lk && l.gs * 8 == C; };
-        if (!blk(b + 0, cin) || !blk(b + 2, C) || !blk(b + 3, C) || !blk(b + 4, C)) return 0;
-        const Layer& r = u->layers[b + 1];
-        if (!(r.mode == CONV_S1 && r.ks == 1 && r.epi == EPI_BIAS && r.c1 == cin && r.cout == C && r.L_out == Lk)) return 0;
-        const Layer& d = u->layers[b + 5];
-        const auto& tl = u->tl;
-        const bool has_down = d.mode == CONV_DOWN && d.ks == 3 && d.epi == EPI_BIAS && d.c1 == C && d.cout == C && d.L_in == Lk && d.L_out == Lk / 2 && tl[b + 5].src1_l == b + 4;
-        if (!has_down) {
-            if (k < 2) return 0;
-            variant = 2;   // (layer 17 is mid_block1's first convolution: the per-layer path has put its gradient into grd(16) by the time the program runs)
-        }
-        if (u->layers[b + 0].tb_off < 0 || u->layers[b + 3].tb_off < 0 || u->layers[b + 2].tb_off >= 0 || u->layers[b + 4].tb_off >= 0) return 0;
-        if (tl[b + 2].res_l != b + 1 || tl[b + 4].res_l != b + 2 || tl[b + 2].src1_l != b || tl[b + 3].src1_l != b + 2 || tl[b + 4].src1_l != b + 3) return 0;
-        if (k > 0 && (tl[b].src1_l != b - 1 || tl[b + 1].src1_l != b - 1)) return 0;
-        for (int i = b + (k == 0 ? 2 : 0); i < b + (has_down ? 6 : 5); ++i) if (!tl[i].need_dgrad) return 0;
-    }
-    if (variant == 2 && (int)u->layers.size() == 34) {   // 3: ... and the two middle blocks (layers 17 .. 20: identity residuals, 128 channels on 16 positions) in front
-        const auto& tl = u->tl;
-        bool ok = sw::train_bwd_mid();
-        for (int i = 17; i <= 20 && ok; ++i) {
-            const Layer& l = u->layers[i];
-            ok = l.mode == CONV_S1 && l.ks == 5 && l.epi == EPI_GN_MISH && l.c1 == 128 && l.c2 == 0 && l.cout == 128 && l.L_out == 16 && l.gs == 16 && tl[i].src1_l == i - 1 && tl[i].need_dgrad &&
-                 ((i & 1) ? l.tb_off >= 0 : l.tb_off < 0);
-        }
-        if (ok && tl[18].res_l == 16 && tl[20].res_l == 18 && tl[17].res_l < 0 && tl[19].res_l < 0) variant = 3;
-    }
-    return variant;
-}
-
-// is the tail of the network [Upsample1d(128) | up level of 64 channels on 16 positions | up level of 32 on 32 | final_conv[0]] the UP program is written for?
-// The four-level network: layers [33, 46) (ups[1], ups[2]); the three-level one: [21, 34) (ups[0], ups[1]).  Returns the first layer of the program, or -1.
-static int bwd_up_applicable(const mpdx_unet* u) {
-    const int n = (int)u->layers.size();
-    if (n < 34 || u->cfg.n_support_points != 64 || u->masked()) return -1;
-    const auto& tl = u->tl;
-    const int fi = n - 1;   // final_conv[0] (final_conv[1], the 1x1, lives in the loss kernel and in final_conv[0]'s epilogue: it is no layer of the list)
-    const Layer& f = u->layers[fi];
-    if (!(f.mode == CONV_S1 && f.ks == 5 && f.epi == EPI_GN_MISH && f.c1 == 32 && f.c2 == 0 && f.cout == 32 && f.L_out == 64 && f.gs == 4 && f.tb_off < 0 && tl[fi].src1_l == fi - 1 && tl[fi].res_l < 0))
-        return -1;
-    const int bases[2] = {fi - 6, fi - 12}, Cs[2] = {32, 64}, Ls[2] = {32, 16}, skips[2] = {10, 16};
-    for (int k = 0; k < 2; ++k) {
-        const int b = bases[k], C = Cs[k], Lk = Ls[k];
-        auto blk = [&](int i, int c1, int c2) { const Layer& l = u->layers[i]; return l.mode == CONV_S1 && l.ks == 5 && l.epi == EPI_GN_MISH && l.c1 == c1 && l.c2 == c2 && l.cout == C && l.L_out == Lk && l.gs * 8 == C; };
-        if (!blk(b, 2 * C, 2 * C) || !blk(b + 2, C, 0) || !blk(b + 3, C, 0) || !blk(b + 4, C, 0)) return -1;
-        const Layer& r = u->layers[b + 1];
-        if (!(r.mode == CONV_S1 && r.ks == 1 && r.epi == EPI_BIAS && r.c1 == 2 * C && r.c2 == 2 * C && r.cout == C && r.L_out == Lk)) return -1;
-        const Layer& up = u->layers[b + 5];
-        if (!(up.mode == CONV_UPT && up.ks == 4 && up.epi == EPI_BIAS && up.c1 == C && up.cout == C && up.L_in == Lk && up.L_out == 2 * Lk)) return -1;
-        if (u->layers[b].tb_off < 0 || u->layers[b + 3].tb_off < 0 || u->layers[b + 2].tb_off >= 0 || u->layers[b + 4].tb_off >= 0) return -1;
-        if (tl[b].src1_l != b - 1 || tl[b + 1].src1_l != b - 1 || tl[b].src2_l != skips[k] || tl[b + 1].src2_l != skips[k]) return -1;
-        if (tl[b + 2].res_l != b + 1 || tl[b + 4].res_l != b + 2 || tl[b + 2].src1_l != b || tl[b + 3].src1_l != b + 2 || tl[b + 4].src1_l != b + 3 || tl[b + 5].src1_l != b + 4) return -1;
-        for (int i = b; i < b + 6; ++i) if (!tl[i].need_dgrad) return -1;
-    }
-    const int first = fi - 12;
-    // the producer of the inner level's x half: 128 channels on 16 positions (the Upsample1d of the level below, or - three levels - mid_block2's blocks.1)
-    const Layer& x = u->layers[first - 1];
-    if (!(x.cout == 128 && x.L_out == 16 && u->layers[16].cout == 128 && u->layers[10].cout == 64 && tl[fi].need_dgrad)) return -1;
-    return first;
-}
-
-// The steps of a backward chain (bwd_chain_kernel) collected in launch order; flush() launches them as ONE kernel (more than it can hold: several)
-struct ChainBuilder {
-    bool on = false;
-    int B = 0;
-    hipStream_t st = nullptr;
-    ChainArgs a;
-    int n_conv = 0, n_gn = 0;
-    size_t lds = 0;
-    int launches = 0, steps = 0;
-    ChainBuilder() { memset(&a, 0, sizeof(a)); }
-    int flush() {
-        if (a.n == 0) return 0;
-        if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "backward chain needs %zu B of LDS", lds);
-        if (lds > 64 * 1024)
-            if (int rc = raise_lds_limit((const void*)bwd_chain_kernel)) return rc;
-        hipLaunchKernelGGL(bwd_chain_kernel, dim3(B), dim3(512), lds, st, a);
-        ++launches;
-        a.n = 0; n_conv = 0; n_gn = 0; lds = 0;
-        return 0;
-    }
-    // can this input-gradient convolution run as a chain step?  (one trajectory per tile, 32-channel tiles, an instantiated body)
-    static bool conv_ok(const Layer& dgl, int min_L) {
-        return dgl.mode == CONV_S1 && (dgl.ks == 5 || dgl.ks == 3 || dgl.ks == 1) && dgl.L_in == dgl.L_out && (dgl.L_out == 64 || dgl.L_out == 32 || dgl.L_out == 16) &&
-               dgl.L_out >= min_L && dgl.cout % 32 == 0;
-    }
-    int add_conv(const Layer& dgl, const ConvArgs& cd, bool gnbwd) {
-        if (gnbwd && dgl.ks == 1) return fail(MPDX_E_INVALID, "chain: no GroupNorm-backward body for a 1-tap convolution");
-        if (n_conv == kChainMaxConv || a.n == kChainMaxSteps)
-            if (int rc = flush()) return rc;
-        ChainStep& s = a.st[a.n++];
-        s.kind = 0; s.sel = (short)chain_sel(dgl.ks, dgl.L_out, gnbwd ? 1 : 0); s.n_mt = (short)(dgl.cout / 32); s.idx = (short)n_conv;
-        a.cd[n_conv] = cd;
-        a.cd[n_conv].n_tiles_n = B;
-        ++n_conv; ++steps;
-        const size_t need = dgl.ks == 5 ? conv_block_lds_bytes<CONV_S1, 5, 32, 64, 8>(dgl.L_in, dgl.L_out, cd.rs)
-                          : dgl.ks == 3 ? conv_block_lds_bytes<CONV_S1, 3, 32, 64, 8>(dgl.L_in, dgl.L_out, cd.rs)
-                                        : conv_block_lds_bytes<CONV_S1, 1, 32, 64, 8>(dgl.L_in, dgl.L_out, cd.rs);
-        // (the staged window of ONE trajectory: NT / L_out = 1, whatever NT the template names; the K-partial buffer: 8 x L_out x 36 floats)
-        const size_t stage = (size_t)(dgl.L_in + 2 * (dgl.ks / 2)) * cd.rs * sizeof(float), red = (size_t)8 * dgl.L_out * 36 * sizeof(float);
-        (void)need;
-        lds = std::max(lds, std::max(stage, red));
-        return 0;
-    }
-    int add_gn(const GnBwdArgs& g, int epl) {
-        if (n_gn == kChainMaxGn || a.n == kChainMaxSteps)
-            if (int rc = flush()) return rc;
-        ChainStep& s = a.st[a.n++];
-        s.kind = 1; s.sel = (short)epl; s.n_mt = 1; s.idx = (short)n_gn;
-        a.gn[n_gn++] = g;
-        ++steps;
-        return 0;
-    }
-};
-
 // any number of deferred weight-gradient GEMMs in launches of up to kWgradMultiMax jobs (wgrad_multi_kernel); the longest blocks first
 static int launch_wgrads_multi(std::vector<WgradJob>& jobs, hipStream_t st) {
     if (jobs.empty()) return 0;
@@ -563,7 +429,585 @@ static void launch_acc(float* dst, const float* src, int B, int L, int Cd, int L
     hipLaunchKernelGGL(acc_slice_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 2048)), dim3(256), 0, st, dst, src, B, L, Cd, Ls, Cs, c_off, step, store);
 }
 
+// Draw mode of the training pass (mpdx_train_draw below): the seed and the device step counter armed for a network
+struct TrainRng { unsigned long long seed; const int* counter; };
+static std::mutex g_train_rng_mu;
+static std::unordered_map<const mpdx_unet*, TrainRng> g_train_rng;
+
+// round 6: the dgrad launch of a ResidualTemporalBlock's blocks[1] (with the GroupNorm backward of blocks[0] in its epilogue) WAITS one layer for the block's
+// residual 1x1 convolution (the next layer in backward order): its 1x1 dgrad - and at batch < 48 both layers' weight-gradient blocks - ride on the same
+// launch (BwdPairArgs::cd2): one launch less per such block.  MPDX_TRAIN_PAIR_RES=0: one launch per layer as before
+struct PendingPair { bool on = false; int i_next = -1; Layer dg; ConvArgs a; WgradJob jobs[3]; int njobs = 0; };
+
+// train_bwd_prog.hpp
+struct BwdProgLayout;
+static int bwd_down_applicable(const mpdx_unet* u);
+static int bwd_up_applicable(const mpdx_unet* u);
+
+// ---- one mpdx_train_loss_backward call: what its stages share, and the stages in the order the entry point runs them.  Every stage enqueues on `st`; the
+// order of the launches and of the first_write / df.red / df.col / df.pcur bookkeeping is behaviour (partial-sum offsets are kernel arguments).
+struct __attribute__((visibility("hidden"))) TrainPass {   // (its members are no symbols of the shared library)
+    mpdx_unet* const u;
+    const float* const flat;
+    const float* const packed;
+    const float* const packedT;
+    float* const grads_flat;
+    float* const ws;
+    const int B;
+    const hipStream_t st;
+    const TrainWs w;
+    const int n;         // layers
+    const bool masked;   // a horizon in a power-of-two container (24, 40, 48, 96 ...): rows [H, Hc) of every activation / gradient tensor are zero
+
+    bool eps_done = false;             // a fused forward program ran final_conv[1] too
+    TimeBwdArgs tb;                    // the time conditioning's backward: filled beside the forward's arguments, launched last
+    Deferred df;
+    std::vector<WgradJob> lone;        // deferred weight-gradient GEMMs without a dgrad convolution to ride on: launched together behind the walk
+    std::vector<int> first_consumer;   // of layer j's output: the reader that comes LAST in backward order (the lowest layer index)
+    std::vector<char> du_ready;        // grd(j) already holds the gradient wrt layer j's CONVOLUTION output
+    std::vector<char> written;         // grd(j) has been written in this pass (launches execute in the order they are enqueued here)
+    int down_variant = 0, dn_last = 0, up_first = -1;   // the backward programs that apply (bwd_down_applicable / bwd_up_applicable): layers [0, dn_last], [up_first, n)
+    bool ran_up = false, ran_down = false;
+    PendingPair pend;
+
+    TrainPass(mpdx_unet* u_, const float* flat_, const float* packed_, const float* packedT_, float* grads_flat_, float* ws_, int B_, hipStream_t st_)
+        : u(u_), flat(flat_), packed(packed_), packedT(packedT_), grads_flat(grads_flat_), ws(ws_), B(B_), st(st_), w(train_ws(u_, B_)), n((int)u_->layers.size()), masked(u_->masked()) {}
+
+    float* xn() const { return ws + w.xn; }
+    float* eps() const { return ws + w.eps; }
+    float* dE() const { return ws + w.dE; }
+    float* part() const { return ws + w.wpart; }   // partial sums of a weight gradient that is not deferred
+    float* out(int i) const { return ws + w.out0 + (size_t)i * w.slotB; }
+    float* pre(int i) const { return ws + w.pre0 + (size_t)i * w.slotB; }
+    float* grd(int i) const { return ws + w.grad0 + (size_t)i * w.slotB; }
+    const float* tensor(int li) const { return li == -1 ? xn() : (li < 0 ? nullptr : out(li)); }
+    float* gflat(int pidx) const { return grads_flat + u->params[pidx].foff; }
+    int goff(const float* p) const { return (int)(p - ws); }
+    // (no memset of the gradient buffers: the first writer of each in the backward pass stores, the later ones add)
+    bool first_write(int j) { const bool f = !written[j]; written[j] = 1; return f; }
+    bool fused_fwd() const { return sw::train_fused_fwd() && fused_mask(B) != 0u && (w.total < ((size_t)1 << 31)); }
+
+    // forward, every layer's output (and GroupNorm input) kept
+    int forward_time_qsample(const float* x_start, const float* noise, const long long* t_dev, const float* sqrt_ac, const float* sqrt_1mac, const float* freqs16,
+                             const float* hard_start, const float* hard_goal, int T);
+    int forward_layers();
+    int forward_fused_segment(const mpdx_unet::Fused& f);
+    int layer_args(int li, ConvArgs& a) const;
+    int loss_and_seed_gradient(const float* target, const float* weights_hd, const float* hard_start, const float* hard_goal, int l1, float loss_scale, float* loss_out);
+    // backward
+    void begin_backward();
+    int backward_final_conv1();
+    int backward_walk();
+    int run_down_program();   // train_bwd_prog.hpp
+    int run_up_program();
+    BwdArgs prog_args(const BwdProgLayout& lay) const;
+    void prog_gn_part(int li, BwdOp& op);
+    int backward_layer(int i);
+    int gn_backward(int i, const float*& dy);
+    int layer_wgrads(int i, const float* dy, int sdiv, WgradJob* jobs, int& njobs);
+    int place_wgrads(int i, const float* dy, WgradJob* jobs, int& njobs, bool& paired);
+    int input_gradient(int i, const float* dy, const WgradJob* jobs, int njobs, bool paired);
+    int gn_epilogue_layer(int i, bool paired) const;
+    int dgrad_with_gn_epilogue(int i, int j, ConvArgs& a, const WgradJob* jobs, int njobs);
+    int dgrad_paired(const Layer& dgl, ConvArgs& a, const WgradJob* jobs, int njobs);
+    int flush_pending();
+    size_t colsum3(const Layer& l);
+    void report() const;
+    int late_wgrads();
+    void finish_reductions();
+    void backward_time();
+};
+
+// the time MLP of every sample, q_sample with its hard conditions and the pass's zero words (the zero bias of the dgrad convolutions + the time backward's
+// ticket) as per-sample side jobs of ONE launch, time_train_fwd_kernel: round 3 spent a memset and a launch on them
+inline int TrainPass::forward_time_qsample(const float* x_start, const float* noise, const long long* t_dev, const float* sqrt_ac, const float* sqrt_1mac,
+                                           const float* freqs16, const float* hard_start, const float* hard_goal, int T) {
+    const mpdx_unet_cfg& c = u->cfg;
+    TimeTrainArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    memset(&tb, 0, sizeof(tb));
+    ta.flat = flat; ta.t = t_dev; ta.freqs = freqs16;
+    ta.emb = ws + w.emb; ta.h1 = ws + w.h1; ta.temb = ws + w.temb; ta.tb = ws + w.tb;
+    ta.tm = ws + w.tm; ta.h1m = ws + w.h1m;
+    ta.w1 = u->params[u->pidx.at("time_mlp.encoder.1.weight")].foff; ta.b1 = u->params[u->pidx.at("time_mlp.encoder.1.bias")].foff;
+    ta.w3 = u->params[u->pidx.at("time_mlp.encoder.3.weight")].foff; ta.b3 = u->params[u->pidx.at("time_mlp.encoder.3.bias")].foff;
+    ta.row = u->tt_row; ta.nblk = (int)u->tt_w.size();
+    if (ta.nblk > 40 || c.time_emb_dim != 32) return fail(MPDX_E_INVALID, "time MLP shape unsupported by the training kernels");
+    for (int i = 0; i < ta.nblk; ++i) {
+        ta.woff[i] = u->params[u->tt_w[i]].foff; ta.boff[i] = u->params[u->tt_b[i]].foff;
+        ta.cout[i] = u->tt_cout[i]; ta.toff[i] = u->tt_off[i];
+    }
+    ta.x0 = x_start; ta.noise = noise; ta.sqrt_ac = sqrt_ac; ta.sqrt_1mac = sqrt_1mac;
+    ta.hs = hard_start; ta.hg = hard_goal; ta.xn = xn(); ta.zero_words = ws + w.zeros; ta.n_zero = 1024 + 4;
+    ta.H = c.n_support_points; ta.D = c.state_dim; ta.T = T;
+    {
+        std::lock_guard<std::mutex> lk(g_train_rng_mu);
+        auto it = g_train_rng.find(u);
+        if (it != g_train_rng.end()) {
+            if ((ta.H * ta.D) & 3) return fail(MPDX_E_INVALID, "draw mode: H * D = %d is not a multiple of 4", ta.H * ta.D);
+            ta.rng_seed = it->second.seed; ta.rng_counter = it->second.counter;
+            ta.t_out = const_cast<long long*>(t_dev); ta.noise_out = const_cast<float*>(noise);
+        }
+    }
+    ta.B = B; ta.packed = const_cast<float*>(packed); ta.jobs = nullptr; ta.n_jobs = 0;
+    ta.Hc = masked ? u->Hc : 0;
+    // the fused forward programs' weight streams: re-assembled by side blocks of this launch (the pack launch before it wrote `packed`)
+    if (fused_fwd() && sw::train_restream_ride()) {
+        const void* jb = nullptr;
+        int nj = 0;
+        if (int rc = claim_fused_stream_jobs(u, packed, &jb, &nj)) return rc;
+        ta.jobs = (const CopyJobDev*)jb; ta.n_jobs = nj;
+    }
+    hipLaunchKernelGGL(time_train_fwd_kernel, dim3(2 * B + kRestreamBlocksPerJob * ta.n_jobs), dim3(512), 0, st, ta);
+    tb.flat = flat; tb.grad = grads_flat; tb.dT = ws + w.dT; tb.emb = ta.emb; tb.h1 = ta.h1; tb.temb = ta.temb; tb.tm = ta.tm; tb.h1m = ta.h1m;
+    tb.dtm = ws + w.dtm; tb.dh1 = ws + w.dh1; tb.ticket = (unsigned*)(ws + w.ticket);
+    if (ta.row > kTimeBwdMaxRow)   // time_bwd_all_kernel carves dTs | roff | red out of LDS at fixed offsets of kTimeBwdMaxRow
+        return fail(MPDX_E_INVALID, "time table row of %d floats (the training kernels take %d)", ta.row, kTimeBwdMaxRow);
+    tb.w1 = ta.w1; tb.b1 = ta.b1; tb.w3 = ta.w3; tb.b3 = ta.b3;
+    tb.B = B; tb.row = ta.row; tb.nblk = ta.nblk;
+    for (int i = 0; i < ta.nblk; ++i) { tb.woff[i] = ta.woff[i]; tb.boff[i] = ta.boff[i]; tb.cout[i] = ta.cout[i]; tb.toff[i] = ta.toff[i]; }
+    return 0;
+}
+
+inline int TrainPass::layer_args(int li, ConvArgs& a) const {
+    const Layer& l = u->layers[li];
+    const auto& t = u->tl[li];
+    memset(&a, 0, sizeof(a));
+    if (int rc = fill_geom(l, B, a)) return rc;
+    a.src1 = tensor(t.src1_l); a.src2 = tensor(t.src2_l);
+    a.wp = packed + u->params[l.w].off;
+    a.bias = packed + u->params[l.b].off;
+    a.gamma = l.gamma >= 0 ? packed + u->params[l.gamma].off : nullptr;
+    a.beta = l.beta >= 0 ? packed + u->params[l.beta].off : nullptr;
+    if (l.tb_off >= 0) { a.tbias = ws + w.tb + l.tb_off; a.tb_stride = u->tt_row; }
+    a.res = tensor(t.res_l);
+    a.dst = out(li);
+    a.pre = l.epi == EPI_GN_MISH ? pre(li) : nullptr;
+    return 0;
+}
+
+// one fused level program of the planning path, in the variant that also keeps every op's output and GroupNorm input (FusedArgs::save)
+inline int TrainPass::forward_fused_segment(const mpdx_unet::Fused& f) {
+    if (int rc = ensure_fused_streams(u, packed, st)) return rc;
+    FusedArgs a = f.tmpl;
+    a.packed = packed;
+    a.tt_row = ws + w.tb; a.tt_stride = u->tt_row;
+    const auto& t0 = u->tl[f.first];
+    a.gsrc1 = tensor(t0.src1_l); a.gsrc2 = tensor(t0.src2_l);
+    a.gsrc3 = f.in3_consumer >= 0 ? tensor(u->tl[f.in3_consumer].src2_l) : a.gsrc1;
+    a.B = B;
+    a.save = ws;
+    int k = 0;
+    for (; k < (int)f.op_layer.size(); ++k) {
+        const int li = f.op_layer[k];
+        a.ops[k].gdst = -1;   // nothing reads the planning path's slots here
+        a.ops[k].save_out = (int)(w.out0 + (size_t)li * w.slotB);
+        a.ops[k].save_pre = u->layers[li].epi == EPI_GN_MISH ? (int)(w.pre0 + (size_t)li * w.slotB) : -1;
+    }
+    for (; k < a.nops; ++k) { a.ops[k].save_out = -1; a.ops[k].save_pre = -1; }
+    if (f.has_final) {   // final_conv[1] -> eps, no DDPM step
+        a.out = eps(); a.fmode = 0; a.n_per_ctx = B;
+        eps_done = true;
+    }
+    return launch_fused_args(f, a, B, st, true);
+}
+
+// the fused level programs for the outer levels, one launch per layer for the rest
+inline int TrainPass::forward_layers() {
+    const bool fused = fused_fwd();
+    for (int i = 0; i < n; ++i) {
+        const int seg = fused ? u->owner[i] : -1;
+        if (seg >= 0 && ((fused_mask(B) >> seg) & 1u) && fused_save_variant(u->fused[seg])) {
+            if (i != u->fused[seg].first) continue;   // the segment's launch covers layers [first, first + count)
+            if (int rc = forward_fused_segment(u->fused[seg])) return rc;
+            continue;
+        }
+        const Layer& l = u->layers[i];
+        ConvArgs a;
+        if (int rc = layer_args(i, a)) return rc;
+        // blocks[0] and the same block's residual 1x1 convolution (the next layer; both read the block input) as ONE launch - the planning path's conv_pair_kernel
+        // (round 6: two launches of ~4.8 us less per pass on the four-level network; MPDX_TRAIN_PAIR_FWD=0: one launch per layer)
+        int MT = 0, NT = 0;
+        if (sw::train_pair_fwd() && !masked && i + 1 < n && !(fused && u->owner[i + 1] >= 0 && ((fused_mask(B) >> u->owner[i + 1]) & 1u)) && u->tl[i + 1].src1_l == u->tl[i].src1_l &&
+            u->tl[i + 1].src2_l == u->tl[i].src2_l && pair_tile(l, u->layers[i + 1], B, MT, NT)) {
+            ConvArgs a2;
+            if (int rc = layer_args(i + 1, a2)) return rc;
+            a.n_tiles_n = a2.n_tiles_n = (int)(((long)B * l.L_out + NT - 1) / NT);
+            const int rc = launch_conv_pair(MT, NT, a, a2, l, u->layers[i + 1], st);
+            if (rc < 0) return rc;
+            if (rc == 1) { ++i; continue; }
+        }
+        if (int rc = launch_layer(l, a, B, st)) return rc;
+    }
+    return 0;
+}
+
+// final_conv[1] -> eps (the network output) unless a fused program has done it; then hard conditions, the loss value, dE and the gradient wrt
+// final_conv[0]'s output (back through final_conv[1]) in one launch
+inline int TrainPass::loss_and_seed_gradient(const float* target, const float* weights_hd, const float* hard_start, const float* hard_goal, int l1, float loss_scale,
+                                             float* loss_out) {
+    const int H = u->cfg.n_support_points, D = u->cfg.state_dim, Hc = u->Hc;
+    FinalArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    fa.h = out(n - 1);
+    fa.w = packed + u->params[u->pidx.at("final_conv.1.weight")].off;
+    fa.bias = packed + u->params[u->pidx.at("final_conv.1.bias")].off;
+    fa.out = eps(); fa.mode = 0; fa.n_per_ctx = 1;
+    fa.B = B; fa.H = H; fa.D = D; fa.C = u->cfg.unet_input_dim;
+    fa.Hc = masked ? Hc : 0;
+    if (!eps_done) launch_final_step(fa, st);
+    {   // train_loss_kernel: state_dim <= 16 in its plain form (padded containers, odd widths), <= 32 in the LDS-staged form (1024 % C == 0, D C <= 1024)
+        const bool staged = !masked && fa.C > 0 && 1024 % fa.C == 0 && 1024 / fa.C <= 64 && D * fa.C <= 1024 && (1024 / fa.C) * D <= 1024;
+        if (fa.C < D || D > 32 || (D > 16 && !staged && !masked))   // (the padded-container form loops over d: any D)
+            return fail(MPDX_E_INVALID, "training: unet_input_dim %d / state_dim %d (the loss kernel takes state_dim <= 32 <= unet_input_dim)", fa.C, D);
+    }
+    const size_t tot = (size_t)B * Hc * fa.C;
+    hipLaunchKernelGGL(train_loss_kernel, dim3((unsigned)std::min<size_t>((tot + 1023) / 1024, 1024) + 16), dim3(1024), 0, st, (const float*)eps(), target, weights_hd,
+                       hard_start, hard_goal, l1, loss_scale, dE(), flat + u->params[u->pidx.at("final_conv.1.weight")].foff, grd(n - 1),
+                       B, H, D, fa.C, loss_out, (double*)(ws + w.lossp), (unsigned*)(ws + w.ticket) + 1, masked ? Hc : 0);   // (ticket word 1: zeroed by the pass's first launch)
+    return 0;
+}
+
+// the bookkeeping of the backward pass, and which backward programs apply
+inline void TrainPass::begin_backward() {
+    df.on = w.deferred; df.ws = ws; df.grads = grads_flat; df.wcur = w.wparts; df.pcur = w.pvecs;
+    df.red.ws = ws; df.red.grad = grads_flat; df.red.n = 0;
+    df.col.ws = ws; df.col.grad = grads_flat; df.col.n = 0;
+    // A Conv1dBlock j whose output feeds exactly one k5 convolution i (blocks[0] -> blocks[1] of a ResidualTemporalBlock) gets its
+    // Mish + GroupNorm backward as the EPILOGUE of i's input-gradient convolution (EPI_GN_BWD): one launch less per residual block.
+    // With several consumers the LAST one in backward order (the lowest layer index) carries the epilogue; the others have added
+    // their gradients to grd(j) by then.
+    first_consumer.assign(n, n);
+    for (int i = n - 1; i >= 0; --i)
+        for (int sl : {u->tl[i].src1_l, u->tl[i].src2_l, u->tl[i].res_l})
+            if (sl >= 0) first_consumer[sl] = i;
+    du_ready.assign(n, 0);
+    written.assign(n, 0);
+    written[n - 1] = 1;   // train_loss_kernel
+    const int prog_env = sw::train_bwd_prog();   // (2: the down program only)
+    const bool progs_ok = prog_env != 0 && df.on && !masked && B <= sw::train_bwd_prog_max_b() && w.total < ((size_t)1 << 31);
+    down_variant = progs_ok ? bwd_down_applicable(u) : 0;
+    dn_last = down_variant == 3 ? 20 : (down_variant == 2 ? 16 : 17);
+    up_first = (progs_ok && prog_env != 2) ? bwd_up_applicable(u) : -1;
+}
+
+// a Conv1dBlock's gamma / beta / bias gradients: three column-sum entries over B partial-sum rows each, carved from the partial area; returns where the rows start
+inline size_t TrainPass::colsum3(const Layer& l) {
+    const size_t at = df.pcur;
+    const int prm[3] = {l.gamma, l.beta, l.b};
+    for (int k = 0; k < 3; ++k) {
+        auto& e = df.col.e[df.col.n++];
+        e.part = at + (size_t)k * B * l.cout; e.out = u->params[prm[k]].foff; e.rows = B; e.C = l.cout;
+    }
+    df.pcur += (size_t)3 * B * l.cout;
+    return at;
+}
+
+// final_conv[1]: weight and bias gradient (grd(n - 1) = dE W was written by train_loss_kernel)
+inline int TrainPass::backward_final_conv1() {
+    const int C = u->cfg.unet_input_dim, D = u->cfg.state_dim, Hc = u->Hc;
+    const int wi = u->pidx.at("final_conv.1.weight"), bi = u->pidx.at("final_conv.1.bias");
+    const size_t rows = (size_t)B * Hc;   // (dE in the container layout: its rows behind the horizon are zero)
+    WgradJob fj;
+    if (int rc = make_wgrad(dE(), Hc, D, 0, D, out(n - 1), Hc, C, 0, C, 1, 0, 1, B, part(), gflat(wi), C, 0, &df, fj)) return rc;
+    const bool fb = attach_bias(fj, &df, gflat(bi), false);
+    if (fj.deferred) lone.push_back(fj);   // rides with the other GEMMs that have no dgrad convolution (one launch behind the walk)
+    else run_wgrad(fj, st);
+    if (!fb) launch_rowsum(dE(), rows, D, ws + w.rpart, gflat(bi), st, &df);
+    return 0;
+}
+
+inline int TrainPass::flush_pending() {
+    if (!pend.on) return 0;
+    pend.on = false;
+    return launch_bwd_pair<5, true>(pend.dg, pend.a, B, pend.jobs, pend.njobs, st);
+}
+
+// the layers from final_conv[0] down to the first: a whole-trajectory program where one applies, else the per-layer step
+inline int TrainPass::backward_walk() {
+    for (int i = n - 1; i >= 0; --i) {
+        if (pend.on && i != pend.i_next)
+            if (int rc = flush_pending()) return rc;
+        if (up_first >= 0 && i == n - 1) {
+            const int rc = run_up_program();
+            if (rc < 0 || rc > 1) return rc;
+            if (rc == 0) { ran_up = true; i = up_first; continue; }   // layers [up_first, n) are done: on with the layer below
+        }
+        if (down_variant != 0 && i == dn_last) {
+            const int rc = run_down_program();
+            if (rc < 0 || rc > 1) return rc;
+            if (rc == 0) { ran_down = true; break; }   // layers [0, dn_last] are done
+        }
+        if (int rc = backward_layer(i)) return rc;
+    }
+    return flush_pending();
+}
+
+inline int TrainPass::backward_layer(int i) {
+    const Layer& l = u->layers[i];
+    float* gy = grd(i);
+    if (!written[i]) {   // nothing downstream of this layer carries a gradient: it is zero
+        if (sw::debug_train()) fprintf(stderr, "[mpdx] backward: layer %d %s has no gradient-carrying consumer (zeroed)\n", i, l.name.c_str());
+        HIP_TRY(hipMemsetAsync(gy, 0, w.slotB * sizeof(float), st));
+        written[i] = 1;
+    }
+    const float* dy = gy;   // gradient wrt the convolution output (after the GroupNorm/Mish backward for Conv1dBlocks)
+    if (l.epi == EPI_GN_MISH && !du_ready[i])
+        if (int rc = gn_backward(i, dy)) return rc;
+    // weight gradient(s) and input gradient: everything below depends only on dy
+    WgradJob jobs[2];
+    int njobs = 0;
+    bool paired = false;
+    if (int rc = place_wgrads(i, dy, jobs, njobs, paired)) return rc;
+    if (u->tl[i].need_dgrad) return input_gradient(i, dy, jobs, njobs, paired);
+    return 0;
+}
+
+// Mish + GroupNorm backward of Conv1dBlock `i` as its own launch (no consumer carries it in its epilogue); dy: where it left dU
+inline int TrainPass::gn_backward(int i, const float*& dy) {
+    const Layer& l = u->layers[i];
+    const auto& t = u->tl[i];
+    float* gy = grd(i);
+    GnBwdArgs g;
+    memset(&g, 0, sizeof(g));
+    if (t.res_l >= 0) { g.gres = grd(t.res_l); g.gres_store = first_write(t.res_l) ? 1 : 0; }
+    g.gy = gy; g.pre = pre(i); g.gamma = flat + u->params[l.gamma].foff; g.beta = flat + u->params[l.beta].foff;
+    g.du = ws + w.dU;
+    g.pg = ws + w.pvec; g.pb = g.pg + (size_t)B * 512; g.pbias = g.pb + (size_t)B * 512;
+    const bool dcol = df.on && df.col.n + 3 <= 120;
+    if (dcol) { g.pg = ws + colsum3(l); g.pb = g.pg + (size_t)B * l.cout; g.pbias = g.pb + (size_t)B * l.cout; }
+    if (l.tb_off >= 0) { g.dT = ws + w.dT + l.tb_off; g.dT_stride = u->tt_row; }
+    g.B = B; g.L = l.L_out; g.C = l.cout; g.gs = l.gs; g.n_groups = l.cout / l.gs;
+    { int k = 0; while ((1 << k) < l.gs) ++k; g.lg_gs = k; }
+    if (l.cout > 512) return fail(MPDX_E_INVALID, "layer %s: more than 512 channels", l.name.c_str());
+    const int re = l.gs * l.L_out, regions = B * g.n_groups;
+    const dim3 ggrid((regions + 3) / 4);
+    g.Lv = l.Lv_out;
+    const bool mrows = l.Lv_out > 0 && l.Lv_out < l.L_out;   // a padded container: the general kernel carries the row mask
+    // du IN PLACE for the two kernels whose body allows it (a lane reads its elements before it writes them): grd(i) outlives the pass, the shared
+    // dU scratch does not - so this layer's weight gradients can run behind the chain too (dy == gy in place_wgrads).  Round 6: the one 256 -> 256 layer whose
+    // GroupNorm backward is its own launch kept its weight-gradient blocks riding on its dgrad launch - 22.6 us against its six siblings' 12.5 at batch 128
+    if (sw::train_gn_inplace() && !mrows && (re == 256 || re == 128)) g.du = gy;
+    if (re == 256 && !mrows) hipLaunchKernelGGL(gn_mish_bwd_kernel<4>, ggrid, dim3(256), 0, st, g);
+    else if (re == 128 && !mrows) hipLaunchKernelGGL(gn_mish_bwd_kernel<2>, ggrid, dim3(256), 0, st, g);
+    else if (re == 256 && l.gs >= 4) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<4, 1>), ggrid, dim3(256), 0, st, g);
+    else if (re == 128 && l.gs >= 2) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<2, 1>), ggrid, dim3(256), 0, st, g);
+    // horizons other than 64 (power-of-two containers 16 ... 128): regions of 64 / 512 / 1024 / 2048 elements
+    else if (re == 64) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<1, 1>), ggrid, dim3(256), 0, st, g);
+    else if (re == 512 && l.gs >= 4) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<4, 2>), ggrid, dim3(256), 0, st, g);
+    else if (re == 1024 && l.gs >= 4) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<4, 4>), ggrid, dim3(256), 0, st, g);
+    else if (re == 2048 && l.gs >= 4) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<4, 8>), ggrid, dim3(256), 0, st, g);
+    else return fail(MPDX_E_INVALID, "layer %s: GroupNorm region of %d elements (group of %d channels)", l.name.c_str(), re, l.gs);
+    if (!dcol) {
+        ColsumArgs cs;
+        memset(&cs, 0, sizeof(cs));
+        cs.part[0] = g.pg; cs.out[0] = gflat(l.gamma);
+        cs.part[1] = g.pb; cs.out[1] = gflat(l.beta);
+        cs.part[2] = g.pbias; cs.out[2] = gflat(l.b);
+        cs.B = B; cs.C = l.cout;
+        hipLaunchKernelGGL(colsum_kernel, dim3((l.cout + 63) / 64, 3), dim3(256), 0, st, cs);
+    }
+    dy = g.du;
+    return 0;
+}
+
+// the weight-gradient GEMM(s) of layer `i` on dU = dy: one job, two where the layer reads a channel concat; a ConvTranspose swaps the operands
+inline int TrainPass::layer_wgrads(int i, const float* dy, int sdiv, WgradJob* jobs, int& njobs) {
+    const Layer& l = u->layers[i];
+    const auto& t = u->tl[i];
+    const int Cin = l.c1 + l.c2;
+    float* gw = gflat(l.w);
+    if (l.mode == CONV_UPT)
+        return make_wgrad(tensor(t.src1_l), l.L_in, l.c1, 0, l.c1, dy, l.L_out, l.cout, 0, l.cout, 2, -1, 4, B, part(), gw, l.cout, 0, &df, jobs[njobs++], sdiv);
+    const int sb = l.mode == CONV_DOWN ? 2 : 1, ob = l.mode == CONV_DOWN ? -1 : -(l.ks / 2);
+    if (int rc = make_wgrad(dy, l.L_out, l.cout, 0, l.cout, tensor(t.src1_l), l.L_in, l.c1, 0, l.c1, sb, ob, l.ks, B, part(), gw, Cin, 0, &df, jobs[njobs++], sdiv)) return rc;
+    if (l.c2 > 0)
+        if (int rc = make_wgrad(dy, l.L_out, l.cout, 0, l.cout, tensor(t.src2_l), l.L_in, l.c2, 0, l.c2, sb, ob, l.ks, B, part(), gw, Cin, l.c1, &df, jobs[njobs++], sdiv)) return rc;
+    return 0;
+}
+
+// builds layer i's weight-gradient jobs and decides where they run: RIDING on the layer's input-gradient launch (they stay in `jobs`; `paired`: that launch
+// is bwd_pair_kernel), LATE (behind the chain, with everybody else's in wgrad_multi_kernel), LONE (no input-gradient launch: three per launch) or at once
+inline int TrainPass::place_wgrads(int i, const float* dy, WgradJob* jobs, int& njobs, bool& paired) {
+    const Layer& l = u->layers[i];
+    const auto& t = u->tl[i];
+    const float* gy = grd(i);
+    const bool pair_off = !sw::train_pair();
+    // round 6 (MPDX_TRAIN_WGRAD_LATE, dev A/B switch): a layer's weight gradients leave the chain when their dU operand outlives the pass - it does
+    // whenever it sits in the layer's own gradient slot (grd(i): written once, never recycled), not in the shared dU scratch of an un-fused
+    // GroupNorm backward - and run with everybody else's in wgrad_multi_kernel behind the chain
+    const int late_env = sw::train_wgrad_late();   // -1: by batch (measured: batch 32 no gain, 128 -3 %, 512 -4.6 %)
+    const bool late_on = late_env < 0 ? B >= 48 : late_env != 0;   // (batch 48: 0.58 -> 0.543 ms, batch 32: within noise: profiles/r06_train_b32_late_ab.txt)
+    // will this layer's weight gradients run behind the chain (decided below, once the jobs exist: the same conditions)?  Then with fewer batch splits.
+    const bool late_cand = late_on && t.need_dgrad && !pair_off && df.on && df.red.n + 2 <= 96 && bwd_pair_has_tile(t.dg, B) && dy == gy;
+    if (int rc = layer_wgrads(i, dy, late_cand ? wgrad_late_sdiv(B) : 1, jobs, njobs)) return rc;
+    // bias gradient = channel sums of dY: rides on the first weight-gradient job, else its own two launches
+    if (l.epi != EPI_GN_MISH && !attach_bias(jobs[0], &df, gflat(l.b), l.mode == CONV_UPT))
+        launch_rowsum(gy, (size_t)B * l.L_out, l.cout, ws + w.rpart, gflat(l.b), st, &df);
+    // one launch for all of them needs every job on its own partial buffer (the deferred mode)
+    paired = t.need_dgrad && !pair_off && jobs[0].deferred && (njobs == 1 || jobs[1].deferred) && bwd_pair_has_tile(t.dg, B);
+    if (late_on && paired && dy == gy) {
+        for (int k = 0; k < njobs; ++k) lone.push_back(jobs[k]);
+        njobs = 0;
+    }
+    if (!paired)
+        for (int k = 0; k < njobs; ++k) {
+            if (!t.need_dgrad && !pair_off && jobs[k].deferred) lone.push_back(jobs[k]);
+            else run_wgrad(jobs[k], st);
+        }
+    return 0;
+}
+
+// the layer j whose Mish + GroupNorm backward runs in the epilogue of layer i's input-gradient convolution (EPI_GN_BWD), or -1
+inline int TrainPass::gn_epilogue_layer(int i, bool paired) const {
+    const Layer& l = u->layers[i];
+    const auto& t = u->tl[i];
+    const int j = t.src1_l;
+    if (!(paired && !masked && sw::train_gn_fuse() && ((l.mode == CONV_S1 && l.ks == 5) || (l.mode == CONV_DOWN && t.dg.ks == 3)) && l.c2 == 0 && j >= 0 && j != n - 1 && first_consumer[j] == i && t.res_l != j &&
+          !(down_variant != 0 && j == dn_last) &&   // (the down program's first op is that layer's GroupNorm backward: it wants G, not dU)
+          u->layers[j].epi == EPI_GN_MISH && u->layers[j].cout == l.c1 && df.on && df.col.n + 3 <= 120))
+        return -1;
+    const Layer& lj = u->layers[j];
+    const int re = lj.gs * lj.L_out;
+    return (re == 256 || re == 128) && lj.L_out == t.dg.L_out ? j : -1;
+}
+
+// layer i's input-gradient convolution with the GroupNorm backward of the Conv1dBlock j below in its epilogue: grd(j) receives dU of layer j
+inline int TrainPass::dgrad_with_gn_epilogue(int i, int j, ConvArgs& a, const WgradJob* jobs, int njobs) {
+    const Layer& l = u->layers[i];
+    const auto& t = u->tl[i];
+    const Layer& lj = u->layers[j];
+    Layer dg2 = t.dg;
+    dg2.epi = EPI_GN_MISH; dg2.gs = lj.gs;
+    a.dst = grd(j); a.dst2 = nullptr; a.c_split = 0;   // (a.accum bit 0 as the caller set it: the other consumers' gradients are in grd(j))
+    if (u->tl[j].res_l >= 0) { a.bw_gres = grd(u->tl[j].res_l); a.bw_gres_store = first_write(u->tl[j].res_l) ? 1 : 0; }
+    a.res = pre(j);
+    a.gamma = flat + u->params[lj.gamma].foff; a.beta = flat + u->params[lj.beta].foff;
+    a.gs = lj.gs; a.lg_gs = 0;
+    while ((1 << a.lg_gs) < lj.gs) ++a.lg_gs;
+    a.bw_pg = ws + colsum3(lj); a.bw_pb = a.bw_pg + (size_t)B * lj.cout; a.bw_pbias = a.bw_pb + (size_t)B * lj.cout;
+    if (lj.tb_off >= 0) { a.bw_dT = ws + w.dT + lj.tb_off; a.bw_dT_stride = u->tt_row; }
+    du_ready[j] = 1;
+    // is the next layer in backward order this block's residual 1x1 convolution?  Then this launch waits for it (PendingPair)
+    bool defer = false;
+    if (sw::train_pair_res() && dg2.ks == 5 && i >= 1 && t.res_l == i - 1 && njobs <= 1) {
+        const Layer& r = u->layers[i - 1];
+        defer = r.mode == CONV_S1 && r.ks == 1 && r.epi == EPI_BIAS && u->tl[i - 1].need_dgrad && r.L_out == l.L_out && !(down_variant != 0 && i - 1 <= dn_last);
+    }
+    if (defer) {
+        pend.on = true; pend.i_next = i - 1; pend.dg = dg2; pend.a = a; pend.njobs = njobs;
+        for (int k = 0; k < njobs; ++k) pend.jobs[k] = jobs[k];
+        return 0;
+    }
+    return dg2.ks == 5 ? launch_bwd_pair<5, true>(dg2, a, B, jobs, njobs, st) : launch_bwd_pair<3, true>(dg2, a, B, jobs, njobs, st);
+}
+
+// an input-gradient convolution with the layer's riding weight-gradient blocks (bwd_pair_kernel); a residual 1x1's rides on the waiting blocks[1] launch
+inline int TrainPass::dgrad_paired(const Layer& dgl, ConvArgs& a, const WgradJob* jobs, int njobs) {
+    if (pend.on && dgl.ks == 1 && pend.njobs + njobs <= 3) {   // the residual 1x1's dgrad (and weight-gradient blocks) ride on the waiting blocks[1] launch
+        WgradJob all[3];
+        int na = 0;
+        for (int k = 0; k < pend.njobs; ++k) all[na++] = pend.jobs[k];
+        for (int k = 0; k < njobs; ++k) all[na++] = jobs[k];
+        const int rc = launch_bwd_pair<5, true>(pend.dg, pend.a, B, all, na, st, &dgl, &a);
+        if (rc != kNoPair2) {
+            pend.on = false;
+            return rc;
+        }
+    }
+    if (int rc = flush_pending()) return rc;
+    if (dgl.ks == 5) return launch_bwd_pair<5>(dgl, a, B, jobs, njobs, st);
+    if (dgl.ks == 3) return launch_bwd_pair<3>(dgl, a, B, jobs, njobs, st);
+    return launch_bwd_pair<1>(dgl, a, B, jobs, njobs, st);
+}
+
+// layer i's input-gradient convolution on dU = dy, stored to / added into the gradient buffer(s) of the layer's input(s)
+inline int TrainPass::input_gradient(int i, const float* dy, const WgradJob* jobs, int njobs, bool paired) {
+    const Layer& l = u->layers[i];
+    const auto& t = u->tl[i];
+    const Layer& dgl = t.dg;
+    const float* din = dy;
+    const bool fold = sw::train_resample_fold();
+    if (l.mode == CONV_DOWN && !fold) {
+        const size_t tot = (size_t)B * 2 * l.L_out * l.cout;
+        hipLaunchKernelGGL(zero_stuff_kernel, dim3((unsigned)std::min<size_t>((tot + 255) / 256, 2048)), dim3(256), 0, st, dy, ws + w.zst, B, l.L_out, l.cout);
+        din = ws + w.zst;
+    }
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = fill_geom(dgl, B, a)) return rc;
+    a.src1 = din;
+    if (l.mode == CONV_DOWN && fold) a.stuff = 1;   // the staging reads dy zero-stuffed (ConvArgs::stuff)
+    a.wp = packedT + t.dgrad_woff;
+    a.bias = ws + w.zeros;
+    if (l.mode == CONV_UPT && fold && t.src1_l >= 0) {   // even output rows straight into the gradient of the layer's input (ConvArgs::decim)
+        a.dst = grd(t.src1_l); a.decim = 1;
+        if (!first_write(t.src1_l)) a.accum |= 1;
+    } else if (l.mode == CONV_UPT) a.dst = ws + w.tmpX;   // full-resolution result, every second position is the gradient
+    else {   // added straight into the gradient buffer(s) of the layer's input(s)
+        a.dst = t.src1_l >= 0 ? grd(t.src1_l) : nullptr;
+        if (t.src1_l >= 0 && !first_write(t.src1_l)) a.accum |= 1;
+        if (l.c2 > 0) {
+            a.c_split = l.c1; a.dst2 = t.src2_l >= 0 ? grd(t.src2_l) : nullptr;
+            if (t.src2_l >= 0 && !first_write(t.src2_l)) a.accum |= 2;
+        }
+    }
+    const int j = gn_epilogue_layer(i, paired);
+    if (j >= 0) {
+        if (int rc = dgrad_with_gn_epilogue(i, j, a, jobs, njobs)) return rc;
+    } else if (paired) {
+        if (int rc = dgrad_paired(dgl, a, jobs, njobs)) return rc;
+    } else if (int rc = launch_layer(dgl, a, B, st)) return rc;
+    if (l.mode == CONV_UPT && t.src1_l >= 0 && !a.decim) launch_acc(grd(t.src1_l), ws + w.tmpX, B, l.L_in, l.c1, dgl.L_out, l.c1 + l.c2, 0, 2, first_write(t.src1_l) ? 1 : 0, st);
+    return 0;
+}
+
+inline void TrainPass::report() const {
+    if (!sw::debug_train()) return;
+    // (tests/test_gpu_train.py reads the first line: the programs must RUN on both networks the reference trains)
+    fprintf(stderr, "[mpdx] backward programs: up %d (layers [%d, %d)), down %d (variant %d, layers [0, %d])\n", ran_up ? 1 : 0, up_first, n, ran_down ? 1 : 0, down_variant, dn_last);
+    fprintf(stderr, "[mpdx] backward: %zu weight-gradient jobs behind the chain\n", lone.size());
+}
+
+// the collected weight-gradient GEMMs: all in one launch, or (MPDX_TRAIN_WGRAD_MULTI=0) three per launch
+inline int TrainPass::late_wgrads() {
+    if (sw::train_wgrad_multi()) return launch_wgrads_multi(lone, st);
+    for (size_t k = 0; k < lone.size(); k += 3)
+        if (int rc = launch_lone_wgrads(lone.data() + k, (int)std::min<size_t>(3, lone.size() - k), st)) return rc;
+    return 0;
+}
+
+// every deferred partial sum -> its gradient: one launch for the weight gradients and (riding as side blocks) the column sums
+inline void TrainPass::finish_reductions() {
+    if (df.red.n) {
+        int blocks = 0;
+        for (int k = 0; k < df.red.n; ++k) {
+            df.red.cstart[k] = blocks;
+            auto& e = df.red.e[k];
+            e.zsl = reduce_zsl(e);
+            const size_t opb = 1024 / (size_t)std::max(1, e.zsl);   // outputs per block
+            blocks += (int)(((size_t)e.M * e.N * e.KS + opb - 1) / opb);
+        }
+        df.red.cstart[df.red.n] = blocks;
+        if (df.col.n && sw::train_reduce_join()) {   // the column sums ride on the same launch (side blocks behind the reduction's)
+            ReduceColsumArgs rc;   // (8 KB of kernel arguments; the launch copies them)
+            rc.red = df.red; rc.col = df.col; rc.n_red_blocks = blocks;
+            hipLaunchKernelGGL(wgrad_reduce_colsum_kernel, dim3(blocks + 2 * df.col.n), dim3(256), 0, st, rc);
+            df.col.n = 0;
+        } else hipLaunchKernelGGL(wgrad_reduce_all_kernel, dim3(blocks), dim3(256), 0, st, df.red);
+    }
+    if (df.col.n) hipLaunchKernelGGL(colsum_all_kernel, dim3(2, df.col.n), dim3(256), 0, st, df.col);
+}
+
+inline void TrainPass::backward_time() {
+    tb.split_tail = sw::time_tail_split() ? 1 : 0;
+    hipLaunchKernelGGL(time_bwd_all_kernel, dim3(B + (tb.row + 31) / 32), dim3(1024), 0, st, tb);   // the time conditioning's backward
+    if (tb.split_tail) hipLaunchKernelGGL(time_tail_kernel, dim3(kTimeTailBlocks), dim3(512), 0, st, tb);   // ... and its encoder tail, 8 blocks
+}
+
 }  // namespace mpdx
+
+#include "train_bwd_prog.hpp"
 
 using namespace mpdx;
 
@@ -607,11 +1051,6 @@ int mpdx_train_pack(mpdx_unet* u, const float* flat, float* packed, float* packe
 /* Draw mode of the training pass (an iteration captured into a hipGraph, trainer.TrainStep.step): with a non-null `step_counter_dev` (a device int
  * that counts the optimiser steps taken: mpdx_adam_step(step < 0) advances it) the NEXT mpdx_train_loss_backward calls treat `t_dev` and `noise` as
  * OUTPUTS and draw them on the device (Philox4x32-10 keyed by `seed`, stream position step * B + sample); null disarms. */
-namespace mpdx {
-struct TrainRng { unsigned long long seed; const int* counter; };
-static std::mutex g_train_rng_mu;
-static std::unordered_map<const mpdx_unet*, TrainRng> g_train_rng;
-}  // namespace mpdx
 int mpdx_train_draw(mpdx_unet* u, unsigned long long seed, const int* step_counter_dev) {
     if (!u) return fail(MPDX_E_INVALID, "null handle");
     std::lock_guard<std::mutex> lk(g_train_rng_mu);
@@ -633,781 +1072,19 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
         return fail(MPDX_E_INVALID, "bad argument");
     build_train_plan(u);
     if (int rc = check_ready(u)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const mpdx_unet_cfg& c = u->cfg;
-    const int H = c.n_support_points, D = c.state_dim, n = (int)u->layers.size();
-    const int Hc = u->Hc;   // rows per trajectory of every activation / gradient tensor: H, or its power-of-two container (24, 40, 48, 96 ...: rows [H, Hc) zero)
-    const bool masked = u->masked();
-    const TrainWs w = train_ws(u, B);
-    float* const xn = ws + w.xn;
-    float* const eps = ws + w.eps;
-    float* const dE = ws + w.dE;
-    auto out = [&](int i) { return ws + w.out0 + (size_t)i * w.slotB; };
-    auto pre = [&](int i) { return ws + w.pre0 + (size_t)i * w.slotB; };
-    auto grd = [&](int i) { return ws + w.grad0 + (size_t)i * w.slotB; };
-    auto tensor = [&](int li) -> const float* { return li == -1 ? xn : (li < 0 ? nullptr : out(li)); };
-    auto gflat = [&](int pidx) { return grads_flat + u->params[pidx].foff; };
-
-    // ---- forward, every layer's output (and GroupNorm input) kept
-    // (no memset of the gradient buffers: the first writer of each in the backward pass stores, the later ones add - `first_write`)
-    // (q_sample with its hard conditions and the pass's zero words - the zero bias of the dgrad convolutions + the time backward's ticket - are
-    //  per-sample side jobs of the first launch, time_train_fwd_kernel: round 3 spent a memset and a launch on them)
     if (!sqrt_alphas_cumprod_dev || !sqrt_one_minus_alphas_cumprod_dev) return fail(MPDX_E_INVALID, "schedule tables missing");
-    TimeTrainArgs ta;
-    memset(&ta, 0, sizeof(ta));
-    TimeBwdArgs tb;
-    memset(&tb, 0, sizeof(tb));
-    {
-        ta.flat = flat; ta.t = t_dev; ta.freqs = freqs16;
-        ta.emb = ws + w.emb; ta.h1 = ws + w.h1; ta.temb = ws + w.temb; ta.tb = ws + w.tb;
-        ta.tm = ws + w.tm; ta.h1m = ws + w.h1m;
-        ta.w1 = u->params[u->pidx.at("time_mlp.encoder.1.weight")].foff; ta.b1 = u->params[u->pidx.at("time_mlp.encoder.1.bias")].foff;
-        ta.w3 = u->params[u->pidx.at("time_mlp.encoder.3.weight")].foff; ta.b3 = u->params[u->pidx.at("time_mlp.encoder.3.bias")].foff;
-        ta.row = u->tt_row; ta.nblk = (int)u->tt_w.size();
-        if (ta.nblk > 40 || c.time_emb_dim != 32) return fail(MPDX_E_INVALID, "time MLP shape unsupported by the training kernels");
-        for (int i = 0; i < ta.nblk; ++i) {
-            ta.woff[i] = u->params[u->tt_w[i]].foff; ta.boff[i] = u->params[u->tt_b[i]].foff;
-            ta.cout[i] = u->tt_cout[i]; ta.toff[i] = u->tt_off[i];
-        }
-        ta.x0 = x_start; ta.noise = noise; ta.sqrt_ac = sqrt_alphas_cumprod_dev; ta.sqrt_1mac = sqrt_one_minus_alphas_cumprod_dev;
-        ta.hs = hard_start; ta.hg = hard_goal; ta.xn = xn; ta.zero_words = ws + w.zeros; ta.n_zero = 1024 + 4;
-        ta.H = H; ta.D = D; ta.T = T;
-        {
-            std::lock_guard<std::mutex> lk(g_train_rng_mu);
-            auto it = g_train_rng.find(u);
-            if (it != g_train_rng.end()) {
-                if ((H * D) & 3) return fail(MPDX_E_INVALID, "draw mode: H * D = %d is not a multiple of 4", H * D);
-                ta.rng_seed = it->second.seed; ta.rng_counter = it->second.counter;
-                ta.t_out = const_cast<long long*>(t_dev); ta.noise_out = const_cast<float*>(noise);
-            }
-        }
-        ta.B = B; ta.packed = const_cast<float*>(packed); ta.jobs = nullptr; ta.n_jobs = 0;
-        ta.Hc = masked ? Hc : 0;
-        {   // the fused forward programs' weight streams: re-assembled by side blocks of this launch (the pack launch before it wrote `packed`)
-            if (sw::train_fused_fwd() && sw::train_restream_ride() && fused_mask(B) != 0u && (w.total < ((size_t)1 << 31))) {
-                const void* jb = nullptr;
-                int nj = 0;
-                if (int rc = claim_fused_stream_jobs(u, packed, &jb, &nj)) return rc;
-                ta.jobs = (const CopyJobDev*)jb; ta.n_jobs = nj;
-            }
-        }
-        hipLaunchKernelGGL(time_train_fwd_kernel, dim3(2 * B + kRestreamBlocksPerJob * ta.n_jobs), dim3(512), 0, st, ta);
-        tb.flat = flat; tb.grad = grads_flat; tb.dT = ws + w.dT; tb.emb = ta.emb; tb.h1 = ta.h1; tb.temb = ta.temb; tb.tm = ta.tm; tb.h1m = ta.h1m;
-        tb.dtm = ws + w.dtm; tb.dh1 = ws + w.dh1; tb.ticket = (unsigned*)(ws + w.ticket);
-        if (ta.row > kTimeBwdMaxRow)   // time_bwd_all_kernel carves dTs | roff | red out of LDS at fixed offsets of kTimeBwdMaxRow
-            return fail(MPDX_E_INVALID, "time table row of %d floats (the training kernels take %d)", ta.row, kTimeBwdMaxRow);
-        tb.w1 = ta.w1; tb.b1 = ta.b1; tb.w3 = ta.w3; tb.b3 = ta.b3;
-        tb.B = B; tb.row = ta.row; tb.nblk = ta.nblk;
-        for (int i = 0; i < ta.nblk; ++i) { tb.woff[i] = ta.woff[i]; tb.boff[i] = ta.boff[i]; tb.cout[i] = ta.cout[i]; tb.toff[i] = ta.toff[i]; }
-    }
-    // forward: the fused level programs of the planning path (they additionally keep every op's output and GroupNorm input,
-    // FusedArgs::save) for the outer levels, one launch per layer for the rest
-    const bool fused_fwd = sw::train_fused_fwd() && fused_mask(B) != 0u && (w.total < ((size_t)1 << 31));
-    bool eps_done = false;
-    for (int i = 0; i < n; ++i) {
-        const int seg = fused_fwd ? u->owner[i] : -1;
-        if (seg >= 0 && ((fused_mask(B) >> seg) & 1u) && fused_save_variant(u->fused[seg])) {
-            const mpdx_unet::Fused& f = u->fused[seg];
-            if (i != f.first) continue;   // the segment's launch covers layers [first, first + count)
-            if (int rc = ensure_fused_streams(u, packed, st)) return rc;
-            FusedArgs a = f.tmpl;
-            a.packed = packed;
-            a.tt_row = ws + w.tb; a.tt_stride = u->tt_row;
-            const auto& t0 = u->tl[f.first];
-            a.gsrc1 = tensor(t0.src1_l); a.gsrc2 = tensor(t0.src2_l);
-            a.gsrc3 = f.in3_consumer >= 0 ? tensor(u->tl[f.in3_consumer].src2_l) : a.gsrc1;
-            a.B = B;
-            a.save = ws;
-            int k = 0;
-            for (; k < (int)f.op_layer.size(); ++k) {
-                const int li = f.op_layer[k];
-                a.ops[k].gdst = -1;   // nothing reads the planning path's slots here
-                a.ops[k].save_out = (int)(w.out0 + (size_t)li * w.slotB);
-                a.ops[k].save_pre = u->layers[li].epi == EPI_GN_MISH ? (int)(w.pre0 + (size_t)li * w.slotB) : -1;
-            }
-            for (; k < a.nops; ++k) { a.ops[k].save_out = -1; a.ops[k].save_pre = -1; }
-            if (f.has_final) {   // final_conv[1] -> eps, no DDPM step
-                a.out = eps; a.fmode = 0; a.n_per_ctx = B;
-                eps_done = true;
-            }
-            if (int rc = launch_fused_args(f, a, B, st, true)) return rc;
-            continue;
-        }
-        auto layer_args = [&](int li, ConvArgs& a) -> int {
-            const Layer& l = u->layers[li];
-            const auto& t = u->tl[li];
-            memset(&a, 0, sizeof(a));
-            if (int rc = fill_geom(l, B, a)) return rc;
-            a.src1 = tensor(t.src1_l); a.src2 = tensor(t.src2_l);
-            a.wp = packed + u->params[l.w].off;
-            a.bias = packed + u->params[l.b].off;
-            a.gamma = l.gamma >= 0 ? packed + u->params[l.gamma].off : nullptr;
-            a.beta = l.beta >= 0 ? packed + u->params[l.beta].off : nullptr;
-            if (l.tb_off >= 0) { a.tbias = ws + w.tb + l.tb_off; a.tb_stride = u->tt_row; }
-            a.res = tensor(t.res_l);
-            a.dst = out(li);
-            a.pre = l.epi == EPI_GN_MISH ? pre(li) : nullptr;
-            return 0;
-        };
-        const Layer& l = u->layers[i];
-        ConvArgs a;
-        if (int rc = layer_args(i, a)) return rc;
-        // blocks[0] and the same block's residual 1x1 convolution (the next layer; both read the block input) as ONE launch - the planning path's conv_pair_kernel
-        // (round 6: two launches of ~4.8 us less per pass on the four-level network; MPDX_TRAIN_PAIR_FWD=0: one launch per layer)
-        int MT = 0, NT = 0;
-        if (sw::train_pair_fwd() && !masked && i + 1 < n && !(fused_fwd && u->owner[i + 1] >= 0 && ((fused_mask(B) >> u->owner[i + 1]) & 1u)) && u->tl[i + 1].src1_l == u->tl[i].src1_l &&
-            u->tl[i + 1].src2_l == u->tl[i].src2_l && pair_tile(l, u->layers[i + 1], B, MT, NT)) {
-            ConvArgs a2;
-            if (int rc = layer_args(i + 1, a2)) return rc;
-            a.n_tiles_n = a2.n_tiles_n = (int)(((long)B * l.L_out + NT - 1) / NT);
-            const int rc = launch_conv_pair(MT, NT, a, a2, l, u->layers[i + 1], st);
-            if (rc < 0) return rc;
-            if (rc == 1) { ++i; continue; }
-        }
-        if (int rc = launch_layer(l, a, B, st)) return rc;
-    }
-    {   // final_conv[1] -> eps (the network output), hard conditions, loss value and its gradient
-        FinalArgs fa;
-        memset(&fa, 0, sizeof(fa));
-        fa.h = out(n - 1);
-        fa.w = packed + u->params[u->pidx.at("final_conv.1.weight")].off;
-        fa.bias = packed + u->params[u->pidx.at("final_conv.1.bias")].off;
-        fa.out = eps; fa.mode = 0; fa.n_per_ctx = 1;
-        fa.B = B; fa.H = H; fa.D = D; fa.C = c.unet_input_dim;
-        fa.Hc = masked ? Hc : 0;
-        if (!eps_done) launch_final_step(fa, st);
-        const float* target = predict_epsilon ? noise : x_start;
-        // loss value + dE + the gradient wrt final_conv[0]'s output (back through final_conv[1]) in one launch
-        {   // train_loss_kernel: state_dim <= 16 in its plain form (padded containers, odd widths), <= 32 in the LDS-staged form (1024 % C == 0, D C <= 1024)
-            const bool staged = !masked && fa.C > 0 && 1024 % fa.C == 0 && 1024 / fa.C <= 64 && D * fa.C <= 1024 && (1024 / fa.C) * D <= 1024;
-            if (fa.C < D || D > 32 || (D > 16 && !staged && !masked))   // (the padded-container form loops over d: any D)
-                return fail(MPDX_E_INVALID, "training: unet_input_dim %d / state_dim %d (the loss kernel takes state_dim <= 32 <= unet_input_dim)", fa.C, D);
-        }
-        const size_t tot = (size_t)B * Hc * fa.C;
-        hipLaunchKernelGGL(train_loss_kernel, dim3((unsigned)std::min<size_t>((tot + 1023) / 1024, 1024) + 16), dim3(1024), 0, st, (const float*)eps, target, weights_hd,
-                           hard_start, hard_goal, l1, loss_scale, dE, flat + u->params[u->pidx.at("final_conv.1.weight")].foff, ws + w.grad0 + (size_t)(n - 1) * w.slotB,
-                           B, H, D, fa.C, loss_out, (double*)(ws + w.lossp), (unsigned*)(ws + w.ticket) + 1, masked ? Hc : 0);   // (ticket word 1: zeroed by the pass's first launch)
-    }
+    TrainPass p(u, flat, packed, packedT, grads_flat, ws, B, (hipStream_t)stream);
+    if (int rc = p.forward_time_qsample(x_start, noise, t_dev, sqrt_alphas_cumprod_dev, sqrt_one_minus_alphas_cumprod_dev, freqs16, hard_start, hard_goal, T)) return rc;
+    if (int rc = p.forward_layers()) return rc;
+    if (int rc = p.loss_and_seed_gradient(predict_epsilon ? noise : x_start, weights_hd, hard_start, hard_goal, l1, loss_scale, loss_out)) return rc;
     HIP_TRY(hipGetLastError());
-
-    // ---- backward
-    float* const part = ws + w.wpart;
-    float* const rpart = ws + w.rpart;
-    Deferred df;
-    df.on = w.deferred; df.ws = ws; df.grads = grads_flat; df.wcur = w.wparts; df.pcur = w.pvecs;
-    df.red.ws = ws; df.red.grad = grads_flat; df.red.n = 0;
-    df.col.ws = ws; df.col.grad = grads_flat; df.col.n = 0;
-    std::vector<WgradJob> lone;   // deferred weight-gradient GEMMs without a dgrad convolution: launched together, three per launch
-    {   // final_conv[1]
-        const int C = c.unet_input_dim;
-        const int wi = u->pidx.at("final_conv.1.weight"), bi = u->pidx.at("final_conv.1.bias");
-        const size_t rows = (size_t)B * Hc;   // (dE in the container layout: its rows behind the horizon are zero)
-        // (grd(n - 1) = dE W was written by train_loss_kernel)
-        WgradJob fj;
-        if (int rc = make_wgrad(dE, Hc, D, 0, D, out(n - 1), Hc, C, 0, C, 1, 0, 1, B, part, gflat(wi), C, 0, &df, fj)) return rc;
-        const bool fb = attach_bias(fj, &df, gflat(bi), false);
-        if (fj.deferred) lone.push_back(fj);   // rides with the other GEMMs that have no dgrad convolution (one launch behind the loop)
-        else run_wgrad(fj, st);
-        if (!fb) launch_rowsum(dE, rows, D, rpart, gflat(bi), st, &df);
-    }
-    // A Conv1dBlock j whose output feeds exactly one k5 convolution i (blocks[0] -> blocks[1] of a ResidualTemporalBlock) gets its
-    // Mish + GroupNorm backward as the EPILOGUE of i's input-gradient convolution (EPI_GN_BWD): one launch less per residual block.
-    // With several consumers the LAST one in backward order (the lowest layer index) carries the epilogue; the others have added
-    // their gradients to grd(j) by then.
-    std::vector<int> first_consumer(n, n);
-    for (int i = n - 1; i >= 0; --i)
-        for (int sl : {u->tl[i].src1_l, u->tl[i].src2_l, u->tl[i].res_l})
-            if (sl >= 0) first_consumer[sl] = i;
-    const bool gnfuse_off = !sw::train_gn_fuse();
-    // round 6 EXPERIMENT, OFF by default (MPDX_TRAIN_CHAIN: 0 off (default), 1 auto, 16 / 32 / 64: the smallest level length that chains): the launches of
-    // the outer levels' backward chain COLLECTED and run as one bwd_chain_kernel launch per run of chainable steps.  Bit-identical gradients, but SLOWER
-    // than the launches it replaces (batch 32: 0.608 -> 0.640 ms with L >= 32, 0.749 ms with L >= 16; batch 128 x D = 14: 0.894 -> 0.921 / 1.002 ms;
-    // profiles/r06_train_chain_ab.txt): under a hipGraph a launch boundary costs ~1 us, a chain step still pays the body's own latency chain (operands
-    // through L2, staging, K-split reduction, epilogue loads) AND runs a layer's channel tiles one after the other on ONE CU instead of side by side on
-    // several.  What would pay is keeping the gradients in LDS between the steps (the forward programs' design) - not built.
-    const int chain_env = sw::train_chain(), chain_max_b = sw::train_chain_max_b();
-    ChainBuilder chain;
-    chain.B = B; chain.st = st;
-    chain.on = chain_env != 0 && !masked && df.on && B <= chain_max_b;
-    const int chain_min_L = chain_env >= 16 ? chain_env : (B >= 64 ? 16 : 32);
-    std::vector<char> du_ready(n, 0);   // grd(j) already holds the gradient wrt layer j's CONVOLUTION output
-    std::vector<char> written(n, 0);    // grd(j) has been written in this pass (launches execute in the order they are enqueued here)
-    written[n - 1] = 1;                 // train_loss_kernel above
-    auto first_write = [&](int j) { const bool f = !written[j]; written[j] = 1; return f; };
-    // round 6: the backward pass of downs[0..2] as ONE whole-trajectory program (fused_bwd.hpp; MPDX_TRAIN_BWD_PROG=0 switches it off)
-    const int prog_env = sw::train_bwd_prog();   // (2: the down program only)
-    const bool progs_ok = prog_env != 0 && df.on && !masked && B <= sw::train_bwd_prog_max_b() && w.total < ((size_t)1 << 31);
-    const int down_variant = progs_ok ? bwd_down_applicable(u) : 0;
-    const bool prog_down_on = down_variant != 0;
-    const int dn_last = down_variant == 3 ? 20 : (down_variant == 2 ? 16 : 17);   // the program covers layers [0, dn_last]
-    auto run_down_program = [&]() -> int {   // layers [0, 18) (three-level network: [0, 17)): returns 0 ok, < 0 error, 1 not applicable here (the per-layer path takes over)
-        const int n_gn = down_variant == 3 ? 16 : 12;   // GroupNorm ops (three column-sum entries each); dn_last + 1 weight-gradient jobs
-        if (!written[dn_last] || df.red.n + dn_last + 1 > 96 || df.col.n + n_gn * 3 + 6 > 120) return 1;
-        if (down_variant == 3 && !written[16]) return 1;   // (the skip connection's gradient, an addend of op M5)
-        const int sdiv = wgrad_prog_sdiv(B);
-        const BwdProgLayout lay = bwd_down_layout();
-        BwdArgs a;
-        memset(&a, 0, sizeof(a));
-        a.packedT = packedT; a.flat = flat; a.ws = ws; a.B = B; a.dT_stride = u->tt_row; a.stat_off = lay.stat_off;
-        a.dbg = sw::bwd_dbg();
-        auto goff = [&](const float* p) { return (int)(p - ws); };
-        enum { IN = 0, GB = 1, DUA = 2, DUB = 3, GA = 4 };
-        auto rs4_of = [](int C) { return C / 4 + kBwdPad4; };
-        a.gin = grd(17); a.in_L = 8; a.in_C = 128; a.in_stuff = 1; a.in_off4 = lay.off4[IN]; a.in_rs4 = rs4_of(128);
-        if (down_variant >= 2) { a.gin = nullptr; a.in_L = 0; a.in_stuff = 0; }   // (no staged input: the first op takes grd(16) / grd(20) as its global addend)
-        int nop = 0;
-        auto gn_part = [&](int li, BwdOp& op) {   // the lower Conv1dBlock `li`: its GroupNorm input, parameters and the partial-sum rows of its gamma / beta / bias gradients
-            const Layer& lj = u->layers[li];
-            op.pre_g = goff(pre(li));
-            op.gamma_f = (int)u->params[lj.gamma].foff; op.beta_f = (int)u->params[lj.beta].foff;
-            op.part_g = (int)df.pcur;
-            const int prm[3] = {lj.gamma, lj.beta, lj.b};
-            for (int k = 0; k < 3; ++k) {
-                auto& e = df.col.e[df.col.n++];
-                e.part = df.pcur + (size_t)k * B * lj.cout; e.out = u->params[prm[k]].foff; e.rows = B; e.C = lj.cout;
-            }
-            df.pcur += (size_t)3 * B * lj.cout;
-            op.dT_g = lj.tb_off >= 0 ? (int)(w.dT + lj.tb_off) : -1;
-        };
-        if (down_variant == 3) {   // M1 .. M4: the two middle blocks (fused_bwd.hpp bwd_down_mid_geom); M5 = the level loop's first op below
-            const int r4 = rs4_of(128);
-            auto mid_op = [&](int nc16) -> BwdOp& {
-                BwdOp& op = a.ops[nop++];
-                memset(&op, 0, sizeof(op));
-                op.shape = bwd_shape_id(CONV_S1, 5, nc16, 0, 128, 16, 1);
-                op.add_off4 = -1; op.gadd = -1; op.gy_off4 = -1; op.gy_g = -1; op.dst_off4 = -1; op.out_g = -1; op.part_g = -1; op.dT_g = -1;
-                return op;
-            };
-            {   // M1: G(layer 20 out) from the up program -> GB (the identity residual of mid_block2 passes it on to layer 18's output); GroupNorm backward of layer 20
-                BwdOp& op = mid_op(0);
-                op.gadd = goff(grd(20));
-                op.gy_off4 = lay.off4[GB]; op.gy_rs4 = r4;
-                op.dst_off4 = lay.off4[DUA]; op.dst_rs4 = r4; op.out_g = goff(grd(20));
-                gn_part(20, op);
-            }
-            {   // M2: dgrad of layer 20 -> G(19 out) (time bias), GroupNorm backward of 19
-                BwdOp& op = mid_op(8);
-                op.src_off4 = lay.off4[DUA]; op.src_rs4 = r4; op.wbase = (int)u->tl[20].dgrad_woff;
-                op.dst_off4 = lay.off4[DUB]; op.dst_rs4 = r4; op.out_g = goff(grd(19));
-                gn_part(19, op);
-            }
-            {   // M3: dgrad of 19 + GB -> G(18 out) -> GA; GroupNorm backward of 18
-                BwdOp& op = mid_op(8);
-                op.src_off4 = lay.off4[DUB]; op.src_rs4 = r4; op.wbase = (int)u->tl[19].dgrad_woff;
-                op.add_off4 = lay.off4[GB]; op.add_rs4 = r4;
-                op.gy_off4 = lay.off4[GA]; op.gy_rs4 = r4;
-                op.dst_off4 = lay.off4[DUA]; op.dst_rs4 = r4; op.out_g = goff(grd(18));
-                gn_part(18, op);
-            }
-            {   // M4: dgrad of 18 -> G(17 out) (time bias), GroupNorm backward of 17
-                BwdOp& op = mid_op(8);
-                op.src_off4 = lay.off4[DUA]; op.src_rs4 = r4; op.wbase = (int)u->tl[18].dgrad_woff;
-                op.dst_off4 = lay.off4[DUB]; op.dst_rs4 = r4; op.out_g = goff(grd(17));
-                gn_part(17, op);
-            }
-        }
-        for (int k = 2; k >= 0; --k) {
-            const int C = 32 << k, Lk = 64 >> k, b0 = 6 * k, r4 = rs4_of(C);
-            auto base_op = [&](int shape_ks, int nc16, int ncr, int cout, int gn) -> BwdOp& {
-                BwdOp& op = a.ops[nop++];
-                memset(&op, 0, sizeof(op));
-                op.shape = bwd_shape_id(CONV_S1, shape_ks, nc16, ncr, cout, Lk, gn);
-                op.add_off4 = -1; op.gadd = -1; op.gy_off4 = -1; op.gy_g = -1; op.dst_off4 = -1; op.out_g = -1; op.part_g = -1; op.dT_g = -1;
-                return op;
-            };
-            if (k == 2 && down_variant == 3) {   // M5: dgrad of layer 17 + GA (mid_block1's identity residual) + the skip connection's gradient -> G(16 out) -> GB; GroupNorm backward of 16
-                BwdOp& op = base_op(5, C / 16, 0, C, 1);
-                op.src_off4 = lay.off4[DUB]; op.src_rs4 = r4; op.wbase = (int)u->tl[17].dgrad_woff;
-                op.add_off4 = lay.off4[GA]; op.add_rs4 = r4;
-                op.gadd = goff(grd(b0 + 4));
-                op.gy_off4 = lay.off4[GB]; op.gy_rs4 = r4;
-                op.dst_off4 = lay.off4[DUA]; op.dst_rs4 = r4; op.out_g = goff(grd(b0 + 4));
-                gn_part(b0 + 4, op);
-            } else if (k == 2 && down_variant == 2) {   // P1 of an innermost level (no Downsample1d): G(b1.1 out) is what the per-layer path accumulated in grd(16)
-                BwdOp& op = base_op(5, 0, 0, C, 1);
-                op.gadd = goff(grd(b0 + 4));
-                op.gy_off4 = lay.off4[GB]; op.gy_rs4 = r4;
-                op.dst_off4 = lay.off4[DUA]; op.dst_rs4 = r4; op.out_g = goff(grd(b0 + 4));
-                gn_part(b0 + 4, op);
-            } else {   // P1: dgrad of the Downsample1d (its dU zero-stuffed in IN) + the skip connection's gradient -> G(b1.1 out) -> GB; GroupNorm backward of b1.1
-                BwdOp& op = base_op(3, C / 16, 0, C, 1);
-                op.src_off4 = lay.off4[IN]; op.src_rs4 = r4;
-                op.wbase = (int)u->tl[b0 + 5].dgrad_woff;
-                if (written[b0 + 4]) op.gadd = goff(grd(b0 + 4));
-                op.gy_off4 = lay.off4[GB]; op.gy_rs4 = r4;
-                op.dst_off4 = lay.off4[DUA]; op.dst_rs4 = r4; op.out_g = goff(grd(b0 + 4));
-                gn_part(b0 + 4, op);
-            }
-            {   // P2: dgrad of b1.1 -> G(b1.0 out) (its time-bias gradient), GroupNorm backward of b1.0
-                BwdOp& op = base_op(5, C / 16, 0, C, 1);
-                op.src_off4 = lay.off4[DUA]; op.src_rs4 = r4;
-                op.wbase = (int)u->tl[b0 + 4].dgrad_woff;
-                op.dst_off4 = lay.off4[DUB]; op.dst_rs4 = r4; op.out_g = goff(grd(b0 + 3));
-                gn_part(b0 + 3, op);
-            }
-            {   // P3: dgrad of b1.0 + the identity residual's G (GB) -> G(b0.1 out) -> GA + the residual 1x1's dY (global); GroupNorm backward of b0.1
-                BwdOp& op = base_op(5, C / 16, 0, C, 1);
-                op.src_off4 = lay.off4[DUB]; op.src_rs4 = r4;
-                op.wbase = (int)u->tl[b0 + 3].dgrad_woff;
-                op.add_off4 = lay.off4[GB]; op.add_rs4 = r4;
-                op.gy_off4 = lay.off4[GA]; op.gy_rs4 = r4; op.gy_g = goff(grd(b0 + 1));
-                op.dst_off4 = lay.off4[DUA]; op.dst_rs4 = r4; op.out_g = goff(grd(b0 + 2));
-                gn_part(b0 + 2, op);
-            }
-            {   // P4: dgrad of b0.1 -> G(b0.0 out) (time bias), GroupNorm backward of b0.0
-                BwdOp& op = base_op(5, C / 16, 0, C, 1);
-                op.src_off4 = lay.off4[DUA]; op.src_rs4 = r4;
-                op.wbase = (int)u->tl[b0 + 2].dgrad_woff;
-                op.dst_off4 = k > 0 ? lay.off4[DUB] : -1; op.dst_rs4 = r4; op.out_g = goff(grd(b0 + 0));
-                gn_part(b0 + 0, op);
-            }
-            if (k > 0) {   // P5: dgrad of b0.0 + the residual 1x1's (from GA) -> dU of the level above's Downsample1d, zero-stuffed into IN
-                const int Cp = C / 2;
-                BwdOp& op = base_op(5, C / 16, C / 16, Cp, 0);
-                op.src_off4 = lay.off4[DUB]; op.src_rs4 = r4;
-                op.rsrc_off4 = lay.off4[GA]; op.rsrc_rs4 = r4;
-                op.wbase = (int)u->tl[b0 + 0].dgrad_woff; op.rwbase = (int)u->tl[b0 + 1].dgrad_woff;
-                op.dst_off4 = lay.off4[IN]; op.dst_rs4 = rs4_of(Cp); op.dst_mode = 1; op.out_g = goff(grd(b0 - 1));
-            }
-        }
-        a.nops = nop;
-        for (int k = 0; k < nop; ++k)
-            if (a.ops[k].shape < 0) return fail(MPDX_E_INVALID, "backward program: op %d has no shape", k);
-        const bool last = down_variant == 2, mid = down_variant == 3;
-        bool is_static = nop == (mid ? BwdSeqDown3Mid::N : BwdSeqDown3::N);
-        for (int k = 0; k < nop && is_static; ++k)
-            is_static = a.ops[k].shape == (mid ? BwdSeqDown3Mid::ids[k] : (last ? BwdSeqDown3Last::ids[k] : BwdSeqDown3::ids[k])) &&
-                        bwd_geom_matches(a.ops[k], mid ? bwd_down_mid_geom(k) : bwd_down_geom(k, last), a.ops[k].shape == 2 || a.ops[k].shape == 5);
-        if (!is_static) return fail(MPDX_E_STATE, "backward program (down): the layout differs from the static program's table");
-        const void* kern = mid ? (const void*)fused_bwd_program_kernel<BwdSeqDown3Mid> : (last ? (const void*)fused_bwd_program_kernel<BwdSeqDown3Last> : (const void*)fused_bwd_program_kernel<BwdSeqDown3>);
-        if (int rc = raise_lds_limit(kern)) return rc;
-        if (mid) hipLaunchKernelGGL(fused_bwd_program_kernel<BwdSeqDown3Mid>, dim3(B), dim3(kFusedThreads), lay.lds_bytes, st, a);
-        else if (last) hipLaunchKernelGGL(fused_bwd_program_kernel<BwdSeqDown3Last>, dim3(B), dim3(kFusedThreads), lay.lds_bytes, st, a);
-        else hipLaunchKernelGGL(fused_bwd_program_kernel<BwdSeqDown3>, dim3(B), dim3(kFusedThreads), lay.lds_bytes, st, a);
-        // the layers' weight gradients (their dY operands now sit in grd(i)) behind the chain; bias gradients of the three convolutions without GroupNorm
-        for (int i = dn_last; i >= 0; --i) {
-            const Layer& l = u->layers[i];
-            const auto& t = u->tl[i];
-            written[i] = 1; du_ready[i] = 1;
-            const int sb = l.mode == CONV_DOWN ? 2 : 1, ob = l.mode == CONV_DOWN ? -1 : -(l.ks / 2);
-            WgradJob j;
-            if (int rc = make_wgrad(grd(i), l.L_out, l.cout, 0, l.cout, tensor(t.src1_l), l.L_in, l.c1, 0, l.c1, sb, ob, l.ks, B, part, gflat(l.w), l.c1, 0, &df, j, sdiv)) return rc;
-            if (!j.deferred) return fail(MPDX_E_STATE, "backward program: no partial-sum storage left for layer %d", i);
-            if (l.epi != EPI_GN_MISH && !attach_bias(j, &df, gflat(l.b), false)) return fail(MPDX_E_STATE, "backward program: no column-sum slot left for layer %d", i);
-            lone.push_back(j);
-        }
-        return 0;
-    };
-    const int up_first = (progs_ok && prog_env != 2) ? bwd_up_applicable(u) : -1;
-    const bool prog_up_on = up_first >= 0;
-    const int up_fi = n - 1;   // final_conv[0]
-    auto run_up_program = [&]() -> int {   // layers [up_first, n) = [33, 46) ([21, 34) with three levels): final_conv[0] and the two outer up levels; 0 ok, < 0 error, 1 not applicable here
-        if (!written[up_fi] || df.red.n + 17 > 96 || df.col.n + 9 * 3 + 4 > 120) return 1;
-        const int sdiv = wgrad_prog_sdiv(B);
-        const BwdProgLayout lay = bwd_down_layout();   // (the same five slots: the largest buffer here is 68 rows x 36 floats = 612 float4)
-        BwdArgs a;
-        memset(&a, 0, sizeof(a));
-        a.packedT = packedT; a.flat = flat; a.ws = ws; a.B = B; a.dT_stride = u->tt_row; a.stat_off = lay.stat_off;
-        a.dbg = sw::bwd_dbg();
-        auto goff = [&](const float* p) { return (int)(p - ws); };
-        enum { IN = 0, GB = 1, DUA = 2, DUB = 3, GA = 4 };
-        auto rs4_of = [](int C) { return C / 4 + kBwdPad4; };
-        auto part3 = [&](int li, int& part_g) {   // partial-sum rows + column-sum entries of a Conv1dBlock's gamma / beta / bias gradients
-            const Layer& lj = u->layers[li];
-            part_g = (int)df.pcur;
-            const int prm[3] = {lj.gamma, lj.beta, lj.b};
-            for (int k = 0; k < 3; ++k) {
-                auto& e = df.col.e[df.col.n++];
-                e.part = df.pcur + (size_t)k * B * lj.cout; e.out = u->params[prm[k]].foff; e.rows = B; e.C = lj.cout;
-            }
-            df.pcur += (size_t)3 * B * lj.cout;
-        };
-        a.gin = nullptr; a.in_L = 64; a.in_C = 32; a.in_stuff = 0; a.in_off4 = lay.off4[IN]; a.in_rs4 = rs4_of(32);   // (no staged input: U0 reads the loss kernel's gradient itself)
-        int nop = 0;
-        auto new_op = [&](int mode, int ks, int nc16, int ncr, int cout, int L, int gn) -> BwdOp& {
-            BwdOp& op = a.ops[nop++];
-            memset(&op, 0, sizeof(op));
-            op.shape = bwd_shape_id(mode, ks, nc16, ncr, cout, L, gn);
-            op.add_off4 = -1; op.gadd = -1; op.gy_off4 = -1; op.gy_g = -1; op.dst_off4 = -1; op.out_g = -1; op.part_g = -1; op.dT_g = -1;
-            return op;
-        };
-        auto gn_part = [&](int li, BwdOp& op) {
-            const Layer& lj = u->layers[li];
-            op.pre_g = goff(pre(li));
-            op.gamma_f = (int)u->params[lj.gamma].foff; op.beta_f = (int)u->params[lj.beta].foff;
-            part3(li, op.part_g);
-            op.dT_g = lj.tb_off >= 0 ? (int)(w.dT + lj.tb_off) : -1;
-        };
-        {   // U0: final_conv[0]'s Mish + GroupNorm backward on the loss kernel's gradient (an op without a convolution: the gradient is its global addend);
-            // dU -> IN and, in place, grd(45) (the operand of final_conv[0]'s weight gradient)
-            BwdOp& op = new_op(CONV_S1, 5, 0, 0, 32, 64, 1);
-            op.gadd = goff(grd(up_fi));
-            op.dst_off4 = lay.off4[IN]; op.dst_rs4 = rs4_of(32); op.out_g = goff(grd(up_fi));
-            gn_part(up_fi, op);
-        }
-        {   // U1: dgrad of final_conv[0] -> dU of ups[2]'s Upsample1d (64 positions)
-            BwdOp& op = new_op(CONV_S1, 5, 2, 0, 32, 64, 0);
-            op.src_off4 = lay.off4[IN]; op.src_rs4 = rs4_of(32);
-            op.wbase = (int)u->tl[up_fi].dgrad_woff;
-            op.dst_off4 = lay.off4[DUA]; op.dst_rs4 = rs4_of(32); op.out_g = goff(grd(up_fi - 1));
-        }
-        const int bases[2] = {up_fi - 6, up_fi - 12}, Cs[2] = {32, 64}, Ls[2] = {32, 16}, skips[2] = {10, 16};
-        int src_slot = DUA;   // where the level's Upsample1d dU sits (2 L positions)
-        for (int k = 0; k < 2; ++k) {
-            const int b0 = bases[k], C = Cs[k], Lk = Ls[k], r4 = rs4_of(C);
-            {   // dgrad of the Upsample1d (its 5-tap pack at stride 2) -> G(b1.1 out) -> GB; GroupNorm backward of b1.1
-                BwdOp& op = new_op(CONV_DOWN, 5, C / 16, 0, C, Lk, 1);
-                op.src_off4 = lay.off4[src_slot]; op.src_rs4 = r4;
-                op.wbase = (int)u->tl[b0 + 5].dgrad_woff;
-                op.gy_off4 = lay.off4[GB]; op.gy_rs4 = r4;
-                op.dst_off4 = lay.off4[DUB]; op.dst_rs4 = r4; op.out_g = goff(grd(b0 + 4));
-                gn_part(b0 + 4, op);
-            }
-            {   // dgrad of b1.1 -> G(b1.0 out) (time bias), GroupNorm backward of b1.0
-                BwdOp& op = new_op(CONV_S1, 5, C / 16, 0, C, Lk, 1);
-                op.src_off4 = lay.off4[DUB]; op.src_rs4 = r4;
-                op.wbase = (int)u->tl[b0 + 4].dgrad_woff;
-                op.dst_off4 = lay.off4[DUA]; op.dst_rs4 = r4; op.out_g = goff(grd(b0 + 3));
-                gn_part(b0 + 3, op);
-            }
-            {   // dgrad of b1.0 + the identity residual's G -> G(b0.1 out) -> GA + the residual 1x1's dY; GroupNorm backward of b0.1
-                BwdOp& op = new_op(CONV_S1, 5, C / 16, 0, C, Lk, 1);
-                op.src_off4 = lay.off4[DUA]; op.src_rs4 = r4;
-                op.wbase = (int)u->tl[b0 + 3].dgrad_woff;
-                op.add_off4 = lay.off4[GB]; op.add_rs4 = r4;
-                op.gy_off4 = lay.off4[GA]; op.gy_rs4 = r4; op.gy_g = goff(grd(b0 + 1));
-                op.dst_off4 = lay.off4[DUB]; op.dst_rs4 = r4; op.out_g = goff(grd(b0 + 2));
-                gn_part(b0 + 2, op);
-            }
-            {   // dgrad of b0.1 -> G(b0.0 out) (time bias), GroupNorm backward of b0.0
-                BwdOp& op = new_op(CONV_S1, 5, C / 16, 0, C, Lk, 1);
-                op.src_off4 = lay.off4[DUB]; op.src_rs4 = r4;
-                op.wbase = (int)u->tl[b0 + 2].dgrad_woff;
-                op.dst_off4 = lay.off4[DUA]; op.dst_rs4 = r4; op.out_g = goff(grd(b0));
-                gn_part(b0, op);
-            }
-            // dgrad of b0.0 + the residual 1x1's (from GA): the gradient of the channel concat [x | skip], one op per half (2 C channels each)
-            const int nblk = (C / 16) * 5, ncr = C / 16, rows_half = 2 * C / 16;
-            for (int half = 0; half < 2; ++half) {
-                BwdOp& op = new_op(CONV_S1, 5, C / 16, C / 16, 2 * C, Lk, 0);
-                op.src_off4 = lay.off4[DUA]; op.src_rs4 = r4;
-                op.rsrc_off4 = lay.off4[GA]; op.rsrc_rs4 = r4;
-                op.wbase = (int)u->tl[b0].dgrad_woff + half * rows_half * nblk * 256;
-                op.rwbase = (int)u->tl[b0 + 1].dgrad_woff + half * rows_half * ncr * 256;
-                if (half == 0) {   // x: the level below's Upsample1d output (its dU); the next level of this program reads it from LDS
-                    op.out_g = goff(grd(b0 - 1));
-                    if (k == 0) { op.dst_off4 = lay.off4[IN]; op.dst_rs4 = rs4_of(2 * C); }
-                } else op.out_g = goff(grd(skips[k]));   // the skip connection's gradient (first writer: stored)
-            }
-            src_slot = IN;
-        }
-        a.nops = nop;
-        for (int k = 0; k < nop; ++k)
-            if (a.ops[k].shape < 0) return fail(MPDX_E_INVALID, "backward program (up): op %d has no shape", k);
-        bool is_static = nop == BwdSeqUp2::N;
-        for (int k = 0; k < nop && is_static; ++k) is_static = a.ops[k].shape == BwdSeqUp2::ids[k] && bwd_geom_matches(a.ops[k], bwd_up_geom(k), a.ops[k].shape == 11 || a.ops[k].shape == 14);
-        if (!is_static) return fail(MPDX_E_STATE, "backward program (up): the layout differs from the static program's table");
-        if (int rc = raise_lds_limit((const void*)fused_bwd_program_kernel<BwdSeqUp2>)) return rc;
-        hipLaunchKernelGGL(fused_bwd_program_kernel<BwdSeqUp2>, dim3(B), dim3(kFusedThreads), lay.lds_bytes, st, a);
-        written[up_first - 1] = written[16] = written[10] = 1;
-        for (int i = up_fi; i >= up_first; --i) {
-            const Layer& l = u->layers[i];
-            const auto& t = u->tl[i];
-            written[i] = 1; du_ready[i] = 1;
-            const int Cin = l.c1 + l.c2;
-            WgradJob jb[2];
-            int nj = 0;
-            if (l.mode == CONV_UPT) {
-                if (int rc = make_wgrad(tensor(t.src1_l), l.L_in, l.c1, 0, l.c1, grd(i), l.L_out, l.cout, 0, l.cout, 2, -1, 4, B, part, gflat(l.w), l.cout, 0, &df, jb[nj++], sdiv)) return rc;
-            } else {
-                const int ob = -(l.ks / 2);
-                if (int rc = make_wgrad(grd(i), l.L_out, l.cout, 0, l.cout, tensor(t.src1_l), l.L_in, l.c1, 0, l.c1, 1, ob, l.ks, B, part, gflat(l.w), Cin, 0, &df, jb[nj++], sdiv)) return rc;
-                if (l.c2 > 0)
-                    if (int rc = make_wgrad(grd(i), l.L_out, l.cout, 0, l.cout, tensor(t.src2_l), l.L_in, l.c2, 0, l.c2, 1, ob, l.ks, B, part, gflat(l.w), Cin, l.c1, &df, jb[nj++], sdiv)) return rc;
-            }
-            for (int k = 0; k < nj; ++k) if (!jb[k].deferred) return fail(MPDX_E_STATE, "backward program: no partial-sum storage left for layer %d", i);
-            if (l.epi != EPI_GN_MISH && !attach_bias(jb[0], &df, gflat(l.b), l.mode == CONV_UPT)) return fail(MPDX_E_STATE, "backward program: no column-sum slot left for layer %d", i);
-            for (int k = 0; k < nj; ++k) lone.push_back(jb[k]);
-        }
-        return 0;
-    };
-    bool ran_up = false, ran_down = false;
-    // round 6: the dgrad launch of a ResidualTemporalBlock's blocks[1] (with the GroupNorm backward of blocks[0] in its epilogue) WAITS one layer for the block's
-    // residual 1x1 convolution (the next layer in backward order): its 1x1 dgrad - and at batch < 48 both layers' weight-gradient blocks - ride on the same
-    // launch (BwdPairArgs::cd2): one launch less per such block.  MPDX_TRAIN_PAIR_RES=0: one launch per layer as before
-    const bool pair_res_off = !sw::train_pair_res();
-    struct Pending { bool on = false; int i_next = -1; Layer dg; ConvArgs a; WgradJob jobs[3]; int njobs = 0; } pend;
-    auto flush_pending = [&]() -> int {
-        if (!pend.on) return 0;
-        pend.on = false;
-        return launch_bwd_pair<5, true>(pend.dg, pend.a, B, pend.jobs, pend.njobs, st);
-    };
-    for (int i = n - 1; i >= 0; --i) {
-        if (pend.on && i != pend.i_next)
-            if (int rc = flush_pending()) return rc;
-        if (prog_up_on && i == up_fi) {
-            if (int rc = chain.flush()) return rc;
-            const int rc = run_up_program();
-            if (rc < 0 || rc > 1) return rc;
-            if (rc == 0) { ran_up = true; i = up_first; continue; }   // layers [up_first, n) are done: on with the layer below
-        }
-        if (prog_down_on && i == dn_last) {
-            if (int rc = chain.flush()) return rc;
-            const int rc = run_down_program();
-            if (rc < 0 || rc > 1) return rc;
-            if (rc == 0) { ran_down = true; break; }   // layers [0, dn_last] are done
-        }
-        const Layer& l = u->layers[i];
-        const auto& t = u->tl[i];
-        const int Cin = l.c1 + l.c2;
-        float* gy = grd(i);
-        const float* dy = gy;   // gradient wrt the convolution output (after the GroupNorm/Mish backward for Conv1dBlocks)
-        if (!written[i]) {   // nothing downstream of this layer carries a gradient: it is zero
-            if (sw::debug_train()) fprintf(stderr, "[mpdx] backward: layer %d %s has no gradient-carrying consumer (zeroed)\n", i, l.name.c_str());
-            if (int rc = chain.flush()) return rc;
-            HIP_TRY(hipMemsetAsync(gy, 0, w.slotB * sizeof(float), st));
-            written[i] = 1;
-        }
-        if (l.epi == EPI_GN_MISH && !du_ready[i]) {
-            GnBwdArgs g;
-            memset(&g, 0, sizeof(g));
-            if (t.res_l >= 0) { g.gres = grd(t.res_l); g.gres_store = first_write(t.res_l) ? 1 : 0; }
-            g.gy = gy; g.pre = pre(i); g.gamma = flat + u->params[l.gamma].foff; g.beta = flat + u->params[l.beta].foff;
-            g.du = ws + w.dU;
-            g.pg = ws + w.pvec; g.pb = g.pg + (size_t)B * 512; g.pbias = g.pb + (size_t)B * 512;
-            const bool dcol = df.on && df.col.n + 3 <= 120;
-            if (dcol) {
-                g.pg = ws + df.pcur; g.pb = g.pg + (size_t)B * l.cout; g.pbias = g.pb + (size_t)B * l.cout;
-                const int prm[3] = {l.gamma, l.beta, l.b};
-                for (int k = 0; k < 3; ++k) {
-                    auto& e = df.col.e[df.col.n++];
-                    e.part = df.pcur + (size_t)k * B * l.cout; e.out = u->params[prm[k]].foff; e.rows = B; e.C = l.cout;
-                }
-                df.pcur += (size_t)3 * B * l.cout;
-            }
-            if (l.tb_off >= 0) { g.dT = ws + w.dT + l.tb_off; g.dT_stride = u->tt_row; }
-            g.B = B; g.L = l.L_out; g.C = l.cout; g.gs = l.gs; g.n_groups = l.cout / l.gs;
-            { int k = 0; while ((1 << k) < l.gs) ++k; g.lg_gs = k; }
-            if (l.cout > 512) return fail(MPDX_E_INVALID, "layer %s: more than 512 channels", l.name.c_str());
-            const int re = l.gs * l.L_out, regions = B * g.n_groups;
-            const dim3 ggrid((regions + 3) / 4);
-            g.Lv = l.Lv_out;
-            const bool mrows = l.Lv_out > 0 && l.Lv_out < l.L_out;   // a padded container: the general kernel carries the row mask
-            const bool gn_chain = chain.on && dcol && !mrows && (re == 256 || re == 128) && g.n_groups <= 8 && l.L_out >= chain_min_L &&
-                                  (l.L_out == 64 || l.L_out == 32 || l.L_out == 16);
-            if (gn_chain) {   // a step of the chain; du IN PLACE (grd(i): it outlives the pass, so the layer's weight gradients can run behind the chains)
-                g.du = gy;
-                if (int rc = chain.add_gn(g, re == 256 ? 4 : 2)) return rc;
-            } else {
-            if (int rc = chain.flush()) return rc;
-            // du IN PLACE for the two kernels whose body allows it (a lane reads its elements before it writes them): grd(i) outlives the pass, the shared
-            // dU scratch does not - so this layer's weight gradients can run behind the chain too (dy == gy below).  Round 6: the one 256 -> 256 layer whose
-            // GroupNorm backward is its own launch kept its weight-gradient blocks riding on its dgrad launch - 22.6 us against its six siblings' 12.5 at batch 128
-            if (sw::train_gn_inplace() && !mrows && (re == 256 || re == 128)) g.du = gy;
-            if (re == 256 && !mrows) hipLaunchKernelGGL(gn_mish_bwd_kernel<4>, ggrid, dim3(256), 0, st, g);
-            else if (re == 128 && !mrows) hipLaunchKernelGGL(gn_mish_bwd_kernel<2>, ggrid, dim3(256), 0, st, g);
-            else if (re == 256 && l.gs >= 4) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<4, 1>), ggrid, dim3(256), 0, st, g);
-            else if (re == 128 && l.gs >= 2) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<2, 1>), ggrid, dim3(256), 0, st, g);
-            // horizons other than 64 (power-of-two containers 16 ... 128): regions of 64 / 512 / 1024 / 2048 elements
-            else if (re == 64) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<1, 1>), ggrid, dim3(256), 0, st, g);
-            else if (re == 512 && l.gs >= 4) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<4, 2>), ggrid, dim3(256), 0, st, g);
-            else if (re == 1024 && l.gs >= 4) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<4, 4>), ggrid, dim3(256), 0, st, g);
-            else if (re == 2048 && l.gs >= 4) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<4, 8>), ggrid, dim3(256), 0, st, g);
-            else return fail(MPDX_E_INVALID, "layer %s: GroupNorm region of %d elements (group of %d channels)", l.name.c_str(), re, l.gs);
-            }
-            ColsumArgs cs;
-            memset(&cs, 0, sizeof(cs));
-            cs.part[0] = g.pg; cs.out[0] = gflat(l.gamma);
-            cs.part[1] = g.pb; cs.out[1] = gflat(l.beta);
-            cs.part[2] = g.pbias; cs.out[2] = gflat(l.b);
-            cs.B = B; cs.C = l.cout;
-            if (!dcol) hipLaunchKernelGGL(colsum_kernel, dim3((l.cout + 63) / 64, 3), dim3(256), 0, st, cs);
-            dy = g.du;
-        }
-        // weight gradient(s) and input gradient: everything below depends only on dy
-        float* gw = gflat(l.w);
-        WgradJob jobs[2];
-        int njobs = 0;
-        const bool pair_off = !sw::train_pair();
-        // round 6 (MPDX_TRAIN_WGRAD_LATE, dev A/B switch): a layer's weight gradients leave the chain when their dU operand outlives the pass - it does
-        // whenever it sits in the layer's own gradient slot (grd(i): written once, never recycled), not in the shared dU scratch of an un-fused
-        // GroupNorm backward - and run with everybody else's in wgrad_multi_kernel behind the chain
-        const int late_env = sw::train_wgrad_late();   // -1: by batch (measured: batch 32 no gain, 128 -3 %, 512 -4.6 %)
-        const bool late_on = late_env < 0 ? B >= 48 : late_env != 0;   // (batch 48: 0.58 -> 0.543 ms, batch 32: within noise: profiles/r06_train_b32_late_ab.txt)
-        // will this layer's weight gradients run behind the chain (decided below, once the jobs exist: the same conditions)?  Then with fewer batch splits.
-        const bool late_cand = late_on && t.need_dgrad && !pair_off && df.on && df.red.n + 2 <= 96 && bwd_pair_has_tile(t.dg, B) && dy == gy;
-        const int sdiv = late_cand ? wgrad_late_sdiv(B) : 1;
-        if (l.mode == CONV_UPT) {
-            if (int rc = make_wgrad(tensor(t.src1_l), l.L_in, l.c1, 0, l.c1, dy, l.L_out, l.cout, 0, l.cout, 2, -1, 4, B, part, gw, l.cout, 0, &df, jobs[njobs++], sdiv)) return rc;
-        } else {
-            const int sb = l.mode == CONV_DOWN ? 2 : 1, ob = l.mode == CONV_DOWN ? -1 : -(l.ks / 2);
-            if (int rc = make_wgrad(dy, l.L_out, l.cout, 0, l.cout, tensor(t.src1_l), l.L_in, l.c1, 0, l.c1, sb, ob, l.ks, B, part, gw, Cin, 0, &df, jobs[njobs++], sdiv)) return rc;
-            if (l.c2 > 0)
-                if (int rc = make_wgrad(dy, l.L_out, l.cout, 0, l.cout, tensor(t.src2_l), l.L_in, l.c2, 0, l.c2, sb, ob, l.ks, B, part, gw, Cin, l.c1, &df, jobs[njobs++], sdiv)) return rc;
-        }
-        if (l.epi != EPI_GN_MISH) {   // bias gradient = channel sums of dY: rides on the first weight-gradient job, else its own two launches
-            if (!attach_bias(jobs[0], &df, gflat(l.b), l.mode == CONV_UPT)) {
-                if (int rc = chain.flush()) return rc;
-                launch_rowsum(gy, (size_t)B * l.L_out, l.cout, rpart, gflat(l.b), st, &df);
-            }
-        }
-        // one launch for all of them needs every job on its own partial buffer (the deferred mode)
-        const bool paired = t.need_dgrad && !pair_off && jobs[0].deferred && (njobs == 1 || jobs[1].deferred) && bwd_pair_has_tile(t.dg, B);
-        const bool resamp_fold = sw::train_resample_fold();
-        // this layer's input-gradient convolution as a step of the backward chain?
-        const bool chain_d = chain.on && paired && dy == gy && ChainBuilder::conv_ok(t.dg, chain_min_L) && resamp_fold &&
-                             (l.mode != CONV_UPT || t.src1_l >= 0);
-        bool late = false;
-        if ((late_on || chain_d) && paired && dy == gy) {
-            late = true;
-            for (int k = 0; k < njobs; ++k) lone.push_back(jobs[k]);
-            njobs = 0;
-        }
-        if (!paired)
-            for (int k = 0; k < njobs; ++k) {
-                if (!t.need_dgrad && !pair_off && jobs[k].deferred) lone.push_back(jobs[k]);
-                else {
-                    if (int rc = chain.flush()) return rc;
-                    run_wgrad(jobs[k], st);
-                }
-            }
-        (void)late;
-        if (t.need_dgrad) {
-            const Layer& dgl = t.dg;
-            const float* din = dy;
-            const bool fold = resamp_fold;
-            if (l.mode == CONV_DOWN && !fold) {
-                if (int rc = chain.flush()) return rc;
-                const size_t tot = (size_t)B * 2 * l.L_out * l.cout;
-                hipLaunchKernelGGL(zero_stuff_kernel, dim3((unsigned)std::min<size_t>((tot + 255) / 256, 2048)), dim3(256), 0, st, dy, ws + w.zst, B, l.L_out, l.cout);
-                din = ws + w.zst;
-            }
-            ConvArgs a;
-            memset(&a, 0, sizeof(a));
-            if (int rc = fill_geom(dgl, B, a)) return rc;
-            a.src1 = din;
-            if (l.mode == CONV_DOWN && fold) a.stuff = 1;   // the staging reads dy zero-stuffed (ConvArgs::stuff)
-            a.wp = packedT + t.dgrad_woff;
-            a.bias = ws + w.zeros;
-            if (l.mode == CONV_UPT && fold && t.src1_l >= 0) {   // even output rows straight into the gradient of the layer's input (ConvArgs::decim)
-                a.dst = grd(t.src1_l); a.decim = 1;
-                if (!first_write(t.src1_l)) a.accum |= 1;
-            } else if (l.mode == CONV_UPT) a.dst = ws + w.tmpX;   // full-resolution result, every second position is the gradient
-            else {   // added straight into the gradient buffer(s) of the layer's input(s)
-                a.dst = t.src1_l >= 0 ? grd(t.src1_l) : nullptr;
-                if (t.src1_l >= 0 && !first_write(t.src1_l)) a.accum |= 1;
-                if (l.c2 > 0) {
-                    a.c_split = l.c1; a.dst2 = t.src2_l >= 0 ? grd(t.src2_l) : nullptr;
-                    if (t.src2_l >= 0 && !first_write(t.src2_l)) a.accum |= 2;
-                }
-            }
-            const int j = t.src1_l;
-            bool gn_fused = false;
-            if (paired && !masked && !gnfuse_off && ((l.mode == CONV_S1 && l.ks == 5) || (l.mode == CONV_DOWN && dgl.ks == 3)) && l.c2 == 0 && j >= 0 && j != n - 1 && first_consumer[j] == i && t.res_l != j &&
-                !(prog_down_on && j == dn_last) &&   // (the down program's first op is that layer's GroupNorm backward: it wants G, not dU)
-                u->layers[j].epi == EPI_GN_MISH && u->layers[j].cout == l.c1 && df.on && df.col.n + 3 <= 120) {
-                const Layer& lj = u->layers[j];
-                const int re = lj.gs * lj.L_out;
-                if ((re == 256 || re == 128) && lj.L_out == dgl.L_out) {
-                    Layer dg2 = dgl;
-                    dg2.epi = EPI_GN_MISH; dg2.gs = lj.gs;
-                    a.dst = grd(j); a.dst2 = nullptr; a.c_split = 0;   // (a.accum bit 0 as set above: the other consumers' gradients are in grd(j))
-                    if (u->tl[j].res_l >= 0) { a.bw_gres = grd(u->tl[j].res_l); a.bw_gres_store = first_write(u->tl[j].res_l) ? 1 : 0; }
-                    a.res = pre(j);
-                    a.gamma = flat + u->params[lj.gamma].foff; a.beta = flat + u->params[lj.beta].foff;
-                    a.gs = lj.gs; a.lg_gs = 0;
-                    while ((1 << a.lg_gs) < lj.gs) ++a.lg_gs;
-                    a.bw_pg = ws + df.pcur; a.bw_pb = a.bw_pg + (size_t)B * lj.cout; a.bw_pbias = a.bw_pb + (size_t)B * lj.cout;
-                    const int prm[3] = {lj.gamma, lj.beta, lj.b};
-                    for (int k = 0; k < 3; ++k) {
-                        auto& e = df.col.e[df.col.n++];
-                        e.part = df.pcur + (size_t)k * B * lj.cout; e.out = u->params[prm[k]].foff; e.rows = B; e.C = lj.cout;
-                    }
-                    df.pcur += (size_t)3 * B * lj.cout;
-                    if (lj.tb_off >= 0) { a.bw_dT = ws + w.dT + lj.tb_off; a.bw_dT_stride = u->tt_row; }
-                    if (chain_d) {
-                        if (int rc = chain.add_conv(dg2, a, true)) return rc;
-                    } else {
-                        if (int rc = chain.flush()) return rc;
-                        // is the next layer in backward order this block's residual 1x1 convolution?  Then this launch waits for it (see `pend`)
-                        bool defer = false;
-                        if (!pair_res_off && dgl.ks == 5 && i >= 1 && t.res_l == i - 1 && njobs <= 1) {
-                            const Layer& r = u->layers[i - 1];
-                            defer = r.mode == CONV_S1 && r.ks == 1 && r.epi == EPI_BIAS && u->tl[i - 1].need_dgrad && r.L_out == l.L_out && !(prog_down_on && i - 1 <= dn_last);
-                        }
-                        if (defer) {
-                            pend.on = true; pend.i_next = i - 1; pend.dg = dg2; pend.a = a; pend.njobs = njobs;
-                            for (int k = 0; k < njobs; ++k) pend.jobs[k] = jobs[k];
-                        } else if (int rc = dgl.ks == 5 ? launch_bwd_pair<5, true>(dg2, a, B, jobs, njobs, st) : launch_bwd_pair<3, true>(dg2, a, B, jobs, njobs, st)) return rc;
-                    }
-                    du_ready[j] = 1;
-                    gn_fused = true;
-                }
-            }
-            if (gn_fused) {
-            } else if (chain_d) {
-                if (int rc = chain.add_conv(dgl, a, false)) return rc;
-            } else if (paired) {
-                if (int rc0 = chain.flush()) return rc0;
-                int rc = kNoPair2;
-                if (pend.on && dgl.ks == 1 && pend.njobs + njobs <= 3) {   // the residual 1x1's dgrad (and weight-gradient blocks) ride on the waiting blocks[1] launch
-                    WgradJob all[3];
-                    int na = 0;
-                    for (int k = 0; k < pend.njobs; ++k) all[na++] = pend.jobs[k];
-                    for (int k = 0; k < njobs; ++k) all[na++] = jobs[k];
-                    rc = launch_bwd_pair<5, true>(pend.dg, pend.a, B, all, na, st, &dgl, &a);
-                    if (rc != kNoPair2) pend.on = false;
-                }
-                if (rc == kNoPair2) {
-                    if (int rc1 = flush_pending()) return rc1;
-                } else if (rc) return rc;
-                if (rc != kNoPair2) {
-                } else
-                if (dgl.ks == 5) rc = launch_bwd_pair<5>(dgl, a, B, jobs, njobs, st);
-                else if (dgl.ks == 3) rc = launch_bwd_pair<3>(dgl, a, B, jobs, njobs, st);
-                else rc = launch_bwd_pair<1>(dgl, a, B, jobs, njobs, st);
-                if (rc) return rc;
-            } else {
-                if (int rc = chain.flush()) return rc;
-                if (int rc = launch_layer(dgl, a, B, st)) return rc;
-            }
-            if (l.mode == CONV_UPT && t.src1_l >= 0 && !a.decim) if (int rc = chain.flush()) return rc;
-            if (l.mode == CONV_UPT && t.src1_l >= 0 && !a.decim) launch_acc(grd(t.src1_l), ws + w.tmpX, B, l.L_in, l.c1, dgl.L_out, Cin, 0, 2, first_write(t.src1_l) ? 1 : 0, st);
-        }
-    }
-    if (int rc = flush_pending()) return rc;
-    if (int rc = chain.flush()) return rc;
-    if (sw::debug_train())   // (tests/test_gpu_train.py reads this line: the programs must RUN on both networks the reference trains)
-        fprintf(stderr, "[mpdx] backward programs: up %d (layers [%d, %d)), down %d (variant %d, layers [0, %d])\n", ran_up ? 1 : 0, up_first, n, ran_down ? 1 : 0, down_variant, dn_last);
-    if (sw::debug_train()) fprintf(stderr, "[mpdx] backward: %d chain launch(es) of %d steps, %zu weight-gradient jobs behind them\n", chain.launches, chain.steps, lone.size());
-    {
-        if (sw::train_wgrad_multi()) {
-            if (int rc = launch_wgrads_multi(lone, st)) return rc;
-        } else
-            for (size_t k = 0; k < lone.size(); k += 3)
-                if (int rc = launch_lone_wgrads(lone.data() + k, (int)std::min<size_t>(3, lone.size() - k), st)) return rc;
-    }
-    if (df.red.n) {
-        int blocks = 0;
-        for (int k = 0; k < df.red.n; ++k) {
-            df.red.cstart[k] = blocks;
-            auto& e = df.red.e[k];
-            e.zsl = reduce_zsl(e);
-            const size_t opb = 1024 / (size_t)std::max(1, e.zsl);   // outputs per block
-            blocks += (int)(((size_t)e.M * e.N * e.KS + opb - 1) / opb);
-        }
-        df.red.cstart[df.red.n] = blocks;
-        if (df.col.n && sw::train_reduce_join()) {   // the column sums ride on the same launch (side blocks behind the reduction's)
-            ReduceColsumArgs rc;   // (8 KB of kernel arguments; the launch copies them)
-            rc.red = df.red; rc.col = df.col; rc.n_red_blocks = blocks;
-            hipLaunchKernelGGL(wgrad_reduce_colsum_kernel, dim3(blocks + 2 * df.col.n), dim3(256), 0, st, rc);
-            df.col.n = 0;
-        } else hipLaunchKernelGGL(wgrad_reduce_all_kernel, dim3(blocks), dim3(256), 0, st, df.red);
-    }
-    if (df.col.n) hipLaunchKernelGGL(colsum_all_kernel, dim3(2, df.col.n), dim3(256), 0, st, df.col);
-    tb.split_tail = sw::time_tail_split() ? 1 : 0;
-    hipLaunchKernelGGL(time_bwd_all_kernel, dim3(B + (tb.row + 31) / 32), dim3(1024), 0, st, tb);   // the time conditioning's backward
-    if (tb.split_tail) hipLaunchKernelGGL(time_tail_kernel, dim3(kTimeTailBlocks), dim3(512), 0, st, tb);   // ... and its encoder tail, 8 blocks
+    p.begin_backward();
+    if (int rc = p.backward_final_conv1()) return rc;
+    if (int rc = p.backward_walk()) return rc;
+    p.report();
+    if (int rc = p.late_wgrads()) return rc;
+    p.finish_reductions();
+    p.backward_time();
     HIP_TRY(hipGetLastError());
     return 0;
 }

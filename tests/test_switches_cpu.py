@@ -16,7 +16,7 @@ CSRC = ROOT / "mpd_public_amd" / "csrc"
 NAMES = """BWD_DBG DEBUG DEBUG_FUSE DEBUG_TRAIN FUSED FUSED_MASK GEO GUIDE_DENSE KSPLIT
    LDS_CAP_KB MERGE_DOWN3 NO_MERGE NO_MERGE_UP NO_MID2 NO_MID3 PAIR PLAN_CHAINS
    STATIC_PROGRAMS TARGET_WGS TILE TIME_TAIL_SPLIT TRAIN_BIAS_FOLD TRAIN_BWD_MID
-   TRAIN_BWD_PROG TRAIN_BWD_PROG_MAX_B TRAIN_CHAIN TRAIN_CHAIN_MAX_B TRAIN_DEFERRED
+   TRAIN_BWD_PROG TRAIN_BWD_PROG_MAX_B TRAIN_DEFERRED
    TRAIN_FUSED_FWD TRAIN_GN_FUSE TRAIN_GN_INPLACE TRAIN_PAIR TRAIN_PAIR_FWD
    TRAIN_PAIR_RES TRAIN_REDUCE_JOIN TRAIN_RESAMPLE_FOLD TRAIN_RESTREAM_RIDE
    TRAIN_WGRAD_LATE TRAIN_WGRAD_MULTI WGRAD_LATE_DIV WGRAD_PROG_MUL WGRAD_TWO WS WSN
@@ -50,7 +50,7 @@ def test_getenv_only_in_switches_hpp():
 
 def test_table_is_the_known_set():
     t = table()
-    assert sorted(t) == sorted("MPDX_" + n for n in NAMES) and len(t) == 48
+    assert sorted(t) == sorted("MPDX_" + n for n in NAMES) and len(t) == 46
     for name, (fn, kind, dflt, timing, doc) in t.items():
         assert fn == name[len("MPDX_"):].lower(), (name, fn)
         assert kind in ("PRESENT", "ON", "INT", "UINT", "STR") and timing in ("ONCE", "LIVE") and doc.strip(), name
@@ -106,8 +106,8 @@ int main(int argc, char** argv) {
     }
     const char* tile = sw::tile();
     printf("no_merge %d pair %d ksplit %d fused_mask %u tile %s\n", (int)sw::no_merge(), (int)sw::pair(), sw::ksplit(), sw::fused_mask(), tile ? tile : "(null)");
-    printf("target_wgs %d lds_cap_kb %d wsn_min_b %d wsp_min_b %d chain_max_b %d bwd_prog_max_b %d\n", sw::target_wgs(), sw::lds_cap_kb(), sw::wsn_min_b(),
-           sw::wsp_min_b(), sw::train_chain_max_b(), sw::train_bwd_prog_max_b());
+    printf("target_wgs %d lds_cap_kb %d wsn_min_b %d wsp_min_b %d bwd_prog_max_b %d\n", sw::target_wgs(), sw::lds_cap_kb(), sw::wsn_min_b(),
+           sw::wsp_min_b(), sw::train_bwd_prog_max_b());
     return 0;
 }
 """
@@ -133,8 +133,8 @@ def probe(tmp_path_factory):
 def test_parse_kinds_on_the_host(probe):
     unset = probe({})
     assert unset["no_merge"] == "0" and unset["pair"] == "1" and unset["ksplit"] == "-1" and unset["fused_mask"] == str(0xffffffff) and unset["tile"] == "(null)"
-    assert (unset["target_wgs"], unset["lds_cap_kb"], unset["wsn_min_b"], unset["wsp_min_b"], unset["chain_max_b"], unset["bwd_prog_max_b"]) == \
-        ("160", "96", "512", "512", "256", "512")
+    assert (unset["target_wgs"], unset["lds_cap_kb"], unset["wsn_min_b"], unset["wsp_min_b"], unset["bwd_prog_max_b"]) == \
+        ("160", "96", "512", "512", "512")
     assert probe({"MPDX_NO_MERGE": "0"})["no_merge"] == "1"      # present: any value counts as set
     assert probe({"MPDX_NO_MERGE": ""})["no_merge"] == "1"
     for off in ("0", "", "x"):                                   # on: off when atoi of the value is 0 - "" and "x" too
