@@ -27,7 +27,7 @@ constexpr int kUnset = INT_MIN;   // default of an INT switch that has to tell "
     /* ---- diagnostics */ \
     X(debug,               "MPDX_DEBUG",                INT,     0,       ONCE, "1: hipGetLastError() after every launch group of mpdx_plan; 2: also synchronise the stream there, so that an asynchronous fault is attributed to the step that caused it (off: the plan never synchronises)") \
     X(debug_fuse,          "MPDX_DEBUG_FUSE",           STR,     nullptr, LIVE, "set: print every fused segment built and which shape constraint rejected one; a value >= 2 also dumps the segment's LDS geometry as a fused_geom.hpp initialiser") \
-    X(debug_train,         "MPDX_DEBUG_TRAIN",          PRESENT, false,   LIVE, "print which backward programs a training pass ran and how many late weight-gradient jobs it collected (tests/test_gpu_train.py reads the first line)") \
+    X(debug_train,         "MPDX_DEBUG_TRAIN",          PRESENT, false,   LIVE, "print which backward programs a training pass ran, how many late weight-gradient jobs it collected and the tiles of its input-gradient convolutions (tests/test_gpu_train.py reads the first line, tests/test_gpu_train_batches.py all three)") \
     X(bwd_dbg,             "MPDX_BWD_DBG",              INT,     0,       LIVE, "BwdArgs::dbg of the backward programs (fused_bwd.hpp debug output)") \
     /* ---- path selection (tests and A/B runs use these) */ \
     X(fused,               "MPDX_FUSED",                ON,      true,    LIVE, "0: no fused level program, every layer its own launch (forward of planning and training)") \

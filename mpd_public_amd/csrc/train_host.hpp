@@ -286,12 +286,27 @@ static bool wgrad_two_groups(const WgradJob& j) {
     return (LA & 7) == 0 && LB == ((j.KS == 3 || j.KS == 4) ? 2 * LA : LA) && (nr == 1 || nr == 2 || nr == 4 || nr == 8);
 }
 
+// the tile of an input-gradient convolution: the forward engine's choice, 16 rows where the layer's channels are no multiple of it (dispatch_tile's rule, k_conv.hip)
+static void dgrad_tile(const Layer& dgl, int B, int& MT, int& NT) {
+    choose_tile(dgl, B, MT, NT);
+    if (dgl.cout % MT) MT = 16;
+}
+// the tiles a backward pass launched its input-gradient convolutions on, counted per convolution; gn: those among them with the GroupNorm backward of the
+// Conv1dBlock below in their epilogue (EPI_GN_BWD: the tile holds NT / L whole trajectories' regions) - TrainPass::report
+struct TileLog {
+    int n[2][4] = {}, gn[2][4] = {};   // MT 16 / 32 x NT 16 / 32 / 64 / 128
+    void add(int MT, int NT, int k, bool gn_bwd) {
+        const int m = MT == 32 ? 1 : 0, c = NT == 16 ? 0 : (NT == 32 ? 1 : (NT == 64 ? 2 : 3));
+        n[m][c] += k;
+        if (gn_bwd) gn[m][c] += 1;
+    }
+};
+
 // does bwd_pair_kernel exist for the tile the forward engine picks for this input-gradient convolution?  (levels of more than 64 positions -
 // n_support_points = 128 - run one trajectory per 128-position tile: per-layer launches there)
 static bool bwd_pair_has_tile(const Layer& dgl, int B) {
     int MT, NT;
-    choose_tile(dgl, B, MT, NT);
-    if (dgl.cout % MT) MT = 16;
+    dgrad_tile(dgl, B, MT, NT);
     if (dgl.cout % MT || NT % dgl.L_out) return false;
     return (MT == 32 || MT == 16) && (NT == 64 || NT == 32 || NT == 16);
 }
@@ -300,13 +315,13 @@ static bool bwd_pair_has_tile(const Layer& dgl, int B) {
 // GN_BWD: the dgrad blocks run the EPI_GN_BWD epilogue (cd carries its operands; `dgl` then has epi = EPI_GN_MISH and the group size
 // of the Conv1dBlock below, so that the tile holds whole GroupNorm regions)
 // dgl2 / cd2 (optional): a second, 1x1 input-gradient convolution on the same tile behind the first one's blocks (BwdPairArgs::cd2); returns kNoPair2 (nothing
-// launched) when that convolution does not fit the first one's tile
+// launched) when that convolution does not fit the first one's tile.  `tiles`: the launch's tile is counted there, once per input-gradient convolution
 constexpr int kNoPair2 = 99;
 template <int KS_D, bool GN_BWD = false>
-static int launch_bwd_pair(const Layer& dgl, ConvArgs& cd, int B, const WgradJob* jobs, int njobs, hipStream_t st, const Layer* dgl2 = nullptr, ConvArgs* cd2 = nullptr) {
+static int launch_bwd_pair(const Layer& dgl, ConvArgs& cd, int B, const WgradJob* jobs, int njobs, hipStream_t st, TileLog& tiles, const Layer* dgl2 = nullptr,
+                           ConvArgs* cd2 = nullptr) {
     int MT, NT;
-    choose_tile(dgl, B, MT, NT);
-    if (dgl.cout % MT) MT = 16;
+    dgrad_tile(dgl, B, MT, NT);
     if (dgl.cout % MT || NT % dgl.L_out) return fail(MPDX_E_INVALID, "layer %s: no tile for C_out=%d L=%d", dgl.name.c_str(), dgl.cout, dgl.L_out);
     if (dgl2 && (dgl2->cout % MT || dgl2->L_out != dgl.L_out || dgl2->ks != 1 || dgl2->mode != CONV_S1 || njobs > 3)) return kNoPair2;
     cd.n_tiles_n = (int)(((long)B * dgl.L_out + NT - 1) / NT);
@@ -338,6 +353,7 @@ static int launch_bwd_pair(const Layer& dgl, ConvArgs& cd, int B, const WgradJob
         if (lds > 64 * 1024)                                                                              \
             if (int rc = raise_lds_limit((const void*)kern)) return rc;                                   \
         hipLaunchKernelGGL(kern, dim3(total), dim3(512), lds, st, a);                                     \
+        tiles.add(mt, nt, dgl2 ? 2 : 1, GN_BWD);                                                          \
         for (int k = 0; k < njobs; ++k) finish_wgrad(jobs[k], st);                                        \
         return 0;                                                                                         \
     }
@@ -469,6 +485,7 @@ struct __attribute__((visibility("hidden"))) TrainPass {   // (its members are n
     int down_variant = 0, dn_last = 0, up_first = -1;   // the backward programs that apply (bwd_down_applicable / bwd_up_applicable): layers [0, dn_last], [up_first, n)
     bool ran_up = false, ran_down = false;
     PendingPair pend;
+    TileLog tiles;                     // of the input-gradient convolutions this pass launched itself (the backward programs' layers are not among them)
 
     TrainPass(mpdx_unet* u_, const float* flat_, const float* packed_, const float* packedT_, float* grads_flat_, float* ws_, int B_, hipStream_t st_)
         : u(u_), flat(flat_), packed(packed_), packedT(packedT_), grads_flat(grads_flat_), ws(ws_), B(B_), st(st_), w(train_ws(u_, B_)), n((int)u_->layers.size()), masked(u_->masked()) {}
@@ -720,7 +737,7 @@ inline int TrainPass::backward_final_conv1() {
 inline int TrainPass::flush_pending() {
     if (!pend.on) return 0;
     pend.on = false;
-    return launch_bwd_pair<5, true>(pend.dg, pend.a, B, pend.jobs, pend.njobs, st);
+    return launch_bwd_pair<5, true>(pend.dg, pend.a, B, pend.jobs, pend.njobs, st, tiles);
 }
 
 // the layers from final_conv[0] down to the first: a whole-trajectory program where one applies, else the per-layer step
@@ -899,7 +916,7 @@ inline int TrainPass::dgrad_with_gn_epilogue(int i, int j, ConvArgs& a, const Wg
         for (int k = 0; k < njobs; ++k) pend.jobs[k] = jobs[k];
         return 0;
     }
-    return dg2.ks == 5 ? launch_bwd_pair<5, true>(dg2, a, B, jobs, njobs, st) : launch_bwd_pair<3, true>(dg2, a, B, jobs, njobs, st);
+    return dg2.ks == 5 ? launch_bwd_pair<5, true>(dg2, a, B, jobs, njobs, st, tiles) : launch_bwd_pair<3, true>(dg2, a, B, jobs, njobs, st, tiles);
 }
 
 // an input-gradient convolution with the layer's riding weight-gradient blocks (bwd_pair_kernel); a residual 1x1's rides on the waiting blocks[1] launch
@@ -909,16 +926,16 @@ inline int TrainPass::dgrad_paired(const Layer& dgl, ConvArgs& a, const WgradJob
         int na = 0;
         for (int k = 0; k < pend.njobs; ++k) all[na++] = pend.jobs[k];
         for (int k = 0; k < njobs; ++k) all[na++] = jobs[k];
-        const int rc = launch_bwd_pair<5, true>(pend.dg, pend.a, B, all, na, st, &dgl, &a);
+        const int rc = launch_bwd_pair<5, true>(pend.dg, pend.a, B, all, na, st, tiles, &dgl, &a);
         if (rc != kNoPair2) {
             pend.on = false;
             return rc;
         }
     }
     if (int rc = flush_pending()) return rc;
-    if (dgl.ks == 5) return launch_bwd_pair<5>(dgl, a, B, jobs, njobs, st);
-    if (dgl.ks == 3) return launch_bwd_pair<3>(dgl, a, B, jobs, njobs, st);
-    return launch_bwd_pair<1>(dgl, a, B, jobs, njobs, st);
+    if (dgl.ks == 5) return launch_bwd_pair<5>(dgl, a, B, jobs, njobs, st, tiles);
+    if (dgl.ks == 3) return launch_bwd_pair<3>(dgl, a, B, jobs, njobs, st, tiles);
+    return launch_bwd_pair<1>(dgl, a, B, jobs, njobs, st, tiles);
 }
 
 // layer i's input-gradient convolution on dU = dy, stored to / added into the gradient buffer(s) of the layer's input(s)
@@ -957,7 +974,12 @@ inline int TrainPass::input_gradient(int i, const float* dy, const WgradJob* job
         if (int rc = dgrad_with_gn_epilogue(i, j, a, jobs, njobs)) return rc;
     } else if (paired) {
         if (int rc = dgrad_paired(dgl, a, jobs, njobs)) return rc;
-    } else if (int rc = launch_layer(dgl, a, B, st)) return rc;
+    } else {   // the un-paired launch: launch_conv_layer picks the tile by the same rule
+        if (int rc = launch_layer(dgl, a, B, st)) return rc;
+        int MT, NT;
+        dgrad_tile(dgl, B, MT, NT);
+        tiles.add(MT, NT, 1, false);
+    }
     if (l.mode == CONV_UPT && t.src1_l >= 0 && !a.decim) launch_acc(grd(t.src1_l), ws + w.tmpX, B, l.L_in, l.c1, dgl.L_out, l.c1 + l.c2, 0, 2, first_write(t.src1_l) ? 1 : 0, st);
     return 0;
 }
@@ -967,6 +989,15 @@ inline void TrainPass::report() const {
     // (tests/test_gpu_train.py reads the first line: the programs must RUN on both networks the reference trains)
     fprintf(stderr, "[mpdx] backward programs: up %d (layers [%d, %d)), down %d (variant %d, layers [0, %d])\n", ran_up ? 1 : 0, up_first, n, ran_down ? 1 : 0, down_variant, dn_last);
     fprintf(stderr, "[mpdx] backward: %zu weight-gradient jobs behind the chain\n", lone.size());
+    // (tests/test_gpu_train_batches.py reads this one: the MTxNT tiles of the input-gradient convolutions the pass launched per layer or paired, xCOUNT each;
+    //  gn K: K of them ran the GroupNorm backward in their epilogue)
+    std::string s;
+    const int mts[2] = {16, 32}, nts[4] = {16, 32, 64, 128};
+    for (int m = 1; m >= 0; --m)
+        for (int k = 3; k >= 0; --k)
+            if (tiles.n[m][k])
+                s += " " + std::to_string(mts[m]) + "x" + std::to_string(nts[k]) + " x" + std::to_string(tiles.n[m][k]) + " (gn " + std::to_string(tiles.gn[m][k]) + ")";
+    fprintf(stderr, "[mpdx] backward: input-gradient tiles:%s\n", s.empty() ? " none" : s.c_str());
 }
 
 // the collected weight-gradient GEMMs: all in one launch, or (MPDX_TRAIN_WGRAD_MULTI=0) three per launch

@@ -170,7 +170,7 @@ class TrainStep:
         self.loss_buf = torch.zeros(1, dtype=torch.float32, device=self.fp.flat.device)
         self.step_count = 0
         self._ws = None
-        self._ws_B = 0
+        self._ws_need = {}   # batch -> floats of the pass's workspace (mpdx_train_workspace_floats)
         half = 16
         self._freqs = torch.exp(torch.arange(half) * -(math.log(10000) / (half - 1))).to(device=self.fp.flat.device, dtype=torch.float32)
 
@@ -215,9 +215,13 @@ class TrainStep:
             noise = m.fill_randn(torch.empty((B, H, D), device=dev, dtype=torch.float32))
         noise = noise.to(torch.float32).contiguous()
         hs, hg = m._hard_tables(hard_conds, B, H, D, dev)
-        if self._ws is None or self._ws_B < B:
-            self._ws = torch.empty(int(lib.mpdx_train_workspace_floats(h, B)), dtype=torch.float32, device=dev)
-            self._ws_B = B
+        # (the workspace does NOT grow with the batch everywhere: the split rules of the weight gradients make a batch of 48 need twice the floats of 64, 512 more
+        #  than 513 - the floats decide, not the batch the buffer was allocated for)
+        need = self._ws_need.get(B)
+        if need is None:
+            need = self._ws_need[B] = int(lib.mpdx_train_workspace_floats(h, B))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.float32, device=dev)
             # graphs captured by step() hold the OLD workspace's address: drop them (they are re-captured after their next eager calls);
             # with no graph captured yet there is nothing to invalidate, and the warm-up count of the running sequence stands
             if self.__dict__.pop("_graphs", None):

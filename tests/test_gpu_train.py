@@ -677,11 +677,13 @@ def test_other_horizons_and_state_dims_vs_reference_golden(golden_dir, H, D, opt
     assert abs(float(norm) - float(g[f"{tag}_total_norm"])) < 3e-4 * float(norm)
 
 
-def test_launch_merges_leave_every_gradient_bit_identical():
+@pytest.mark.parametrize("B", [40, 203])
+def test_launch_merges_leave_every_gradient_bit_identical(B):
     """Round-5 launch merges of the training pass - the time backward's encoder tail as its own 8-block launch (MPDX_TIME_TAIL_SPLIT), the fused programs'
     weight-stream copies as side blocks of the first launch (MPDX_TRAIN_RESTREAM_RIDE), the column sums as side blocks of the weight-gradient reduction
     (MPDX_TRAIN_REDUCE_JOIN): each switched off in its own process (the switches are read once per process), loss + every gradient + the parameters after
-    a clipped Adam step must hash to the same bytes as with all of them on (batch 40: two 32-sample chunks of the tail, the second ragged)."""
+    a clipped Adam step must hash to the same bytes as with all of them on (batch 40: two 32-sample chunks of the tail, the second ragged).
+    Batch 203 (round-6 group only): the same identities on the large input-gradient tiles, the last tile of every level ragged."""
     import hashlib
     import os
     import subprocess
@@ -694,7 +696,7 @@ sys.path.insert(0, "ROOT"); sys.path.insert(0, "ROOT/tests")
 import mpd_public_amd as m
 from mpd_public_amd.trainer import TrainStep
 from helpers import synth_sd, t, DIM_MULTS
-D, opt, B, T = 14, 1, 40, 100
+D, opt, B, T = 14, 1, BATCH, 100
 net = m.TemporalUnet(n_support_points=64, state_dim=D, unet_input_dim=32, dim_mults=DIM_MULTS[opt])
 net.load_state_dict(synth_sd(D, opt), strict=True)
 dm = m.GaussianDiffusionModel(model=net, n_diffusion_steps=T, predict_epsilon=True, loss_type="l2").cuda()
@@ -709,7 +711,7 @@ for it in range(2):
     ts.adam_step(1e-4, max_norm=1.0)
     h.update(ts.fp.flat.detach().cpu().numpy().tobytes())
 print("HASH", h.hexdigest())
-'''.replace("ROOT", str(root))
+'''.replace("ROOT", str(root)).replace("BATCH", str(B))
 
     def run(extra):
         env = dict(os.environ, **extra)
@@ -717,14 +719,22 @@ print("HASH", h.hexdigest())
         lines = [ln for ln in out.stdout.splitlines() if ln.startswith("HASH ")]
         assert out.returncode == 0 and lines, out.stderr[-2000:]
         return lines[-1]
-    ref = run({})
-    for sw in ("MPDX_TIME_TAIL_SPLIT", "MPDX_TRAIN_RESTREAM_RIDE", "MPDX_TRAIN_REDUCE_JOIN"):
-        assert run({sw: "0"}) == ref, sw
+    if B == 40:
+        ref = run({})
+        for sw in ("MPDX_TIME_TAIL_SPLIT", "MPDX_TRAIN_RESTREAM_RIDE", "MPDX_TRAIN_REDUCE_JOIN"):
+            assert run({sw: "0"}) == ref, sw
     # round 6: the weight gradients behind the chain in ONE launch (wgrad_multi_kernel; the default from batch 64 on) instead of riding on the
     # input-gradient launches, and the lone ones three per launch instead of all together - same operands, same summation orders: same bytes
     # (the whole-trajectory backward program of round 6 accumulates a convolution's whole K in one wave - other summation order - so the per-layer path
     #  is the common ground of these runs: MPDX_TRAIN_BWD_PROG=0; late weight gradients with the splits of the riding ones: MPDX_WGRAD_LATE_DIV=1)
     base = {"MPDX_TRAIN_BWD_PROG": "0"}
+    if B != 40:
+        # from batch 48 on the late launch IS the default, with a quarter of the riding weight gradients' batch splits (wgrad_late_sdiv: another summation
+        # order, other bytes): the riding form has to be asked for, and the launch count of the late ones compares against the default
+        riding = run(dict(base, MPDX_TRAIN_WGRAD_LATE="0"))
+        assert run(dict(base, MPDX_TRAIN_WGRAD_LATE="1", MPDX_WGRAD_LATE_DIV="1")) == riding
+        assert run(dict(base, MPDX_TRAIN_WGRAD_MULTI="0")) == run(base)
+        return
     ref0 = run(base)
     for extra in ({"MPDX_TRAIN_WGRAD_LATE": "1", "MPDX_WGRAD_LATE_DIV": "1"}, {"MPDX_TRAIN_WGRAD_MULTI": "0"}):
         assert run(dict(base, **extra)) == ref0, extra
