@@ -254,6 +254,10 @@ __device__ __forceinline__ void conv_block_body(const ConvArgs& a, const int blo
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
+    // (compile-time geometry: every launch has NTHR threads.  hipcc knows tid < 1024 only, keeps the `idx < total` test of the last staging
+    //  load of a pass and SINKS that load into the branch, behind the LDS stores of the others and a vmcnt(0): a second memory round trip
+    //  in series with the first.  With the bound the staging loads of a pass are issued together and the branches are gone.)
+    if constexpr (GK) __builtin_assume(tid < NTHR);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave % WN, wk = wave / WN;
     int tr_i = 0;
