@@ -33,8 +33,22 @@ extern "C" {
 
 typedef struct mpdx_unet mpdx_unet; /* opaque */
 
-/* TemporalUnet.__init__ arguments that shape the network (mpd/models/diffusion_models/temporal_unet.py:22-35),
- * for the only configuration the reference builds: conditioning_type=None, self_attention=False. */
+/* TemporalUnet.__init__ arguments that shape the network (mpd/models/diffusion_models/temporal_unet.py:22-35), for
+ * conditioning_type=None (the only one the reference scripts build); self_attention is either value.
+ *
+ * self_attention = 1 puts a Residual(PreNorm(dim, LinearAttention(dim))) behind the second residual block of every down level, between
+ * the two middle blocks and behind the second residual block of every up level (temporal_unet.py:82,93,104,146,153,162), five more
+ * state-dict tensors each (<p>.fn.fn.to_qkv.weight [384,C,1], <p>.fn.fn.to_out.weight [C,128,1], <p>.fn.fn.to_out.bias [C],
+ * <p>.fn.norm.g / .b [1,C,1]; <p> = downs.<i>.2, mid_attn, ups.<j>.2).  Per trajectory, x [C, L], all in fp32, one launch per block:
+ *   xn  = (x - mean) / sqrt(var + 1e-5) * g + b      mean / biased variance over the C channels of each position (layers.py:194-204)
+ *   qkv = W_qkv xn                                   no bias; q, k, v = 128 rows each = 4 heads x 32 channels (LinearAttention's own
+ *                                                    defaults, layers.py:208; TemporalUnet passes only dim); q *= 32^-0.5 (layers.py:217-219)
+ *   k   = softmax(k) over the L positions of each row, max-subtracted; q is not soft-maxed (layers.py:221)
+ *   context[d][e] = sum_n k[d][n] v[e][n],  out[e][n] = sum_d context[d][e] q[d][n]     per head, 32 x 32 (layers.py:222-224)
+ *   result = W_out out + b_out + x                   (layers.py:226, :180)
+ * In a zero-padded container (H = 24, 40, 48, 96) the softmax and the context sum run over the valid positions and the pad rows stay zero.
+ * Such a network runs every layer as its own launch (no whole-trajectory programs).  It is inference and evaluation only: the
+ * mpdx_train_* entry points refuse its handle (the size functions return 0) - the training pass has no backward for these blocks. */
 typedef struct mpdx_unet_cfg {
     int32_t state_dim;                  /* D */
     int32_t n_support_points;           /* H: 64 in every shipped configuration; 16 ... 128 with H % 2^(n_levels-1) == 0 (powers of two run as they are, 24 / 40 / 48 / 96 ... in the next power-of-two container, zero rows kept zero) */
@@ -42,6 +56,7 @@ typedef struct mpdx_unet_cfg {
     int32_t n_levels;                   /* len(dim_mults) */
     int32_t dim_mults[MPDX_MAX_LEVELS]; /* (1,2,4,8) or (1,2,4): UNET_DIM_MULTS, temporal_unet.py:14-17 */
     int32_t time_emb_dim;               /* 32 */
+    int32_t self_attention;             /* 0 / 1: TemporalUnet(self_attention=...), see above (appended: positional initialisers of the members above leave it 0) */
 } mpdx_unet_cfg;
 
 const char* mpdx_last_error(void);

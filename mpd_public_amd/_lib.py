@@ -18,7 +18,8 @@ MAX_LEVELS = 8
 
 class UnetCfg(C.Structure):
     _fields_ = [("state_dim", C.c_int32), ("n_support_points", C.c_int32), ("unet_input_dim", C.c_int32),
-                ("n_levels", C.c_int32), ("dim_mults", C.c_int32 * MAX_LEVELS), ("time_emb_dim", C.c_int32)]
+                ("n_levels", C.c_int32), ("dim_mults", C.c_int32 * MAX_LEVELS), ("time_emb_dim", C.c_int32),
+                ("self_attention", C.c_int32)]   # appended member, default 0: positional construction of the six above keeps working
 
 
 class StepCoefs(C.Structure):

@@ -1,7 +1,7 @@
 // host.hpp - the host-side model (layer plan, parameter table, fused segments) and the launcher interface between the translation
 // units of libmpdx.so.  The library is built from one host TU (mpdx.hip: model building, the planning loop, the C ABI, the small
 // streaming kernels) and one TU per kernel family - k_conv.hip (conv_block.hpp), k_ws.hip (conv_ws.hpp), k_fused.hip /
-// k_fused_train.hip (fused_level.hpp), k_guide.hip (guide.hpp), k_train.hip (train.hpp + train_host.hpp), k_planner.hip
+// k_fused_train.hip (fused_level.hpp), k_guide.hip (guide.hpp), k_attn.hip (attn.hpp), k_train.hip (train.hpp + train_host.hpp), k_planner.hip
 // (planner.hpp + planner_host.hpp) - so that an edit to one kernel family recompiles that family only (mpd_public_amd/build.py
 // compiles the TUs in parallel and keeps the objects).  A kernel template is instantiated in exactly ONE TU, behind a plain function
 // declared here; no device code crosses a TU (no -fgpu-rdc).
@@ -87,6 +87,14 @@ struct Layer {
     int w = -1, b = -1, gamma = -1, beta = -1;                       // param indices
     int tb_off = -1;                                                 // offset in a time-table row
     int cin_pad = 0, rs = 0;
+    // a Residual(PreNorm(LinearAttention)) block of a self_attention network (attn.hpp), in place on slot `dst` (== src1): w = to_qkv.weight,
+    // w2 / b2 = to_out.weight / bias, gamma / beta = the LayerNorm's g / b; cout channels on L_out positions; no convolution fields apply
+    bool attn = false;
+    int w2 = -1, b2 = -1;
+    // convolutions of a self_attention network: the tile width of a layer WITHOUT the 8-wave K split is pinned (choose_tile), because there the
+    // split of K over the waves - the summation order - follows the width, and the width follows the batch; such a network runs every layer on this
+    // path at every batch and promises results that do not depend on the batch
+    bool pin_nt = false;
     std::string name;
 };
 
@@ -165,6 +173,10 @@ int launch_final_step(const FinalArgs& fa, hipStream_t st);   // final_step_kern
 int launch_conv_layer(const Layer& l, ConvArgs& a, int B, hipStream_t st);
 bool pair_tile(const Layer& l1, const Layer& l2, int B, int& MT, int& NT);   // (mpdx.hip) do blocks[0] + the block's residual 1x1 conv run as one launch, on which tile?
 int launch_conv_pair(int MT, int NT, const ConvArgs& a1, const ConvArgs& a2, const Layer& l1, const Layer& l2, hipStream_t st);   // 1 launched, 0 does not fit, -1 error
+// ---- k_attn.hip: the linear self-attention block (attn.hpp); a.x and the five parameter pointers set by the caller
+struct AttnArgs;
+const char* attn_unsupported(int C, int L);   // null, or why attn_kernel cannot run a level of C channels on L positions
+int launch_attention(const Layer& l, AttnArgs& a, int B, hipStream_t st);
 // ---- k_ws.hip: the weight-stationary persistent kernels
 int launch_weight_stationary(int variant, const Layer& l, ConvArgs& a, const ConvArgs& a2, int B, hipStream_t st);
 // ---- k_fused.hip (planning programs) / k_fused_train.hip (the variants that keep activations for the backward pass)

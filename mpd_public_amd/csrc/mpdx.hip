@@ -2,6 +2,7 @@
 //
 // gfx950 only.  No CUDA shims, no dual paths.  All device memory is caller-owned; nothing here synchronises.
 #include "host.hpp"
+#include "attn.hpp"
 #include "loss.hpp"
 
 namespace mpdx {
@@ -377,6 +378,7 @@ static void build_model(mpdx_unet* u) {
         l.name = wname; l.mode = mode; l.ks = ks; l.epi = epi;
         l.src1 = src1; l.c1 = c1; l.src2 = src2; l.c2 = c2; l.cout = cout; l.L_in = L_in; l.L_out = L_out; l.dst = dst;
         l.Lv_out = (H != Hv) ? (int)((long)L_out * Hv / H) : 0;   // (levels halve container and horizon alike: Hv % 2^(levels-1) == 0)
+        l.pin_nt = c.self_attention != 0;
         if (mode == CONV_UPT) l.w = add_param(u, wname, {c1 + c2, cout, ks}, PK_CONVT);
         else l.w = add_param(u, wname, {cout, c1 + c2, ks}, PK_CONV);
         l.b = add_param(u, bname, {cout});
@@ -421,6 +423,24 @@ static void build_model(mpdx_unet* u) {
         u->layers.back().res = res;
     };
 
+    // Residual(PreNorm(dim, LinearAttention(dim))) (temporal_unet.py:82,93,104; layers.py:174-226) in place on `slot_id`: one launch (attn.hpp).
+    // to_qkv / to_out are 1x1 convolutions: packed into the A-fragment order of the convolutions, one tap
+    auto attention = [&](const std::string& p, int slot_id, int C, int Lc) {
+        if (!c.self_attention) return;
+        Layer l;
+        l.name = p + ".fn.fn.to_qkv.weight"; l.attn = true; l.mode = CONV_S1; l.ks = 0; l.epi = EPI_BIAS;
+        l.src1 = slot_id; l.dst = slot_id; l.c1 = C; l.cout = C; l.L_in = Lc; l.L_out = Lc;
+        l.Lv_out = (H != Hv) ? (int)((long)Lc * Hv / H) : 0;
+        l.w = add_param(u, p + ".fn.fn.to_qkv.weight", {3 * kAttnHid, C, 1}, PK_CONV);
+        l.w2 = add_param(u, p + ".fn.fn.to_out.weight", {C, kAttnHid, 1}, PK_CONV);
+        l.b2 = add_param(u, p + ".fn.fn.to_out.bias", {C});
+        l.gamma = add_param(u, p + ".fn.norm.g", {1, C, 1});
+        l.beta = add_param(u, p + ".fn.norm.b", {1, C, 1});
+        l.cin_pad = pad_cin(C);
+        l.rs = pick_row_stride(l.cin_pad, CONV_S1, Lc, Lc, Lc);
+        u->layers.push_back(l);
+    };
+
     int L = H, cur = SRC_X, curC = D;
     for (int i = 0; i < nl; ++i) {
         const int co = dims[i + 1];
@@ -428,6 +448,7 @@ static void build_model(mpdx_unet* u) {
         const int a = other(cur);
         rtb(p + ".0", cur, curC, SRC_NONE, 0, co, L, a);
         rtb(p + ".1", a, co, SRC_NONE, 0, co, L, S0 + i);
+        attention(p + ".2", S0 + i, co, L);   // (the skip tensor the level pushes is the block's output: temporal_unet.py:146-149)
         cur = S0 + i; curC = co;
         if (i < nl - 1) {
             conv_layer(p + ".4.conv.weight", p + ".4.conv.bias", CONV_DOWN, 3, EPI_BIAS, cur, co, SRC_NONE, 0, co, L, L / 2, P0);
@@ -435,6 +456,7 @@ static void build_model(mpdx_unet* u) {
         }
     }
     rtb("mid_block1", cur, curC, SRC_NONE, 0, curC, L, P0);
+    attention("mid_attn", P0, curC, L);
     rtb("mid_block2", P0, curC, SRC_NONE, 0, curC, L, P1);
     cur = P1;
     for (int j = 0; j < nl - 1; ++j) {
@@ -445,6 +467,7 @@ static void build_model(mpdx_unet* u) {
         rtb(p + ".0", cur, dout, S0 + lv, dout, din, L, a);
         const int b = other(a);
         rtb(p + ".1", a, din, SRC_NONE, 0, din, L, b);
+        attention(p + ".2", b, din, L);
         const int d = other(b);
         conv_layer(p + ".4.conv.weight", p + ".4.conv.bias", CONV_UPT, 4, EPI_BIAS, b, din, SRC_NONE, 0, din, L, 2 * L, d);
         cur = d; L *= 2; curC = din;
@@ -795,6 +818,9 @@ static void build_units(mpdx_unet* u) {
     };
     std::vector<int> owner(n, -1);
     if (u->masked()) { u->owner = owner; return; }   // a horizon in a zero-padded container: every layer as its own (masking) launch
+    // self-attention: a block sits between a level's second residual block and its resample, which the whole-trajectory programs run back to
+    // back in LDS - every layer as its own launch (the convolutions keep their pairs and weight-stationary variants)
+    if (u->cfg.self_attention) { u->owner = owner; return; }
     const bool merge = !sw::no_merge();
     auto try_seg = [&](const std::string& prefix, bool with_final) {
         int i0, i1;
@@ -886,6 +912,13 @@ void choose_tile(const Layer& l, int B, int& MT, int& NT) {
         return std::max(stage, red);
     };
     const int mts[2] = {32, 16}, nts[3] = {64, 32, 16};
+    if (l.pin_nt && !layer_ksplit(l)) {   // (Layer::pin_nt) the narrowest legal width at every batch; the channel tile by the usual rule
+        NT = min_nt;
+        for (int mt : mts)
+            if (mt >= min_mt && l.cout % mt == 0 && lds(mt, NT) <= (size_t)sw::lds_cap_kb() * 1024 && wgs(mt, NT) >= target) { MT = mt; return; }
+        MT = (min_mt <= 16 && l.cout % 16 == 0) ? 16 : 32;
+        return;
+    }
     // largest tile that fits LDS (<= 96 KiB so that a second workgroup can co-reside; MPDX_LDS_CAP_KB overrides) and still
     // yields >= target workgroups; else the smallest legal tile
     const size_t cap = (size_t)sw::lds_cap_kb() * 1024;
@@ -905,6 +938,8 @@ bool layer_ksplit(const Layer& l) {
     return (l.cin_pad / 16) * layer_ntap(l) >= 16;  // enough K to feed 8 K-split waves
 }
 static double layer_flops(const Layer& l, int B) {
+    // attention block: to_qkv 2 * 384 * C + to_out 2 * C * 128 = 1024 C per position, context and out 2 * 2 * 32 * 32 per head and position = 16384
+    if (l.attn) return (double)B * l.L_out * (1024.0 * l.cout + 16384.0);
     return 2.0 * l.cout * (double)B * l.L_out * (l.c1 + l.c2) * layer_ntap(l);
 }
 
@@ -970,6 +1005,14 @@ static int weight_stationary_variant(const Layer& l, const Layer* l2, const Conv
 
 static int run_layer(const mpdx_unet* u, const Layer& l, const float* packed, const float* tt_row, const float* x,
                      float* ws, int B, hipStream_t st, int dbg = 0) {
+    if (l.attn) {
+        AttnArgs aa;
+        memset(&aa, 0, sizeof(aa));
+        aa.x = ws + u->slot_floats * (size_t)B * l.dst;
+        aa.wqkv = packed + u->params[l.w].off; aa.wout = packed + u->params[l.w2].off; aa.bout = packed + u->params[l.b2].off;
+        aa.g = packed + u->params[l.gamma].off; aa.b = packed + u->params[l.beta].off;
+        return launch_attention(l, aa, B, st);
+    }
     ConvArgs a;
     if (int rc = make_conv_args(u, l, packed, tt_row, x, ws, B, dbg, a)) return rc;
     if (const int v = weight_stationary_variant(l, nullptr, a, B, dbg)) return launch_weight_stationary(v, l, a, a, B, st);
@@ -1158,6 +1201,7 @@ static double unit_flops(const mpdx_unet* u, const mpdx_unet::Unit& un, int B) {
 // ALGORITHMIC bytes of a launch unit: every weight / parameter it needs once + the activations that cross its boundary once (inputs,
 // residual, outputs; what stays in LDS inside a fused program does not count) - the denominator of bench.py's traffic_over_algorithmic
 static double layer_param_bytes(const mpdx_unet* u, const Layer& l) {
+    if (l.attn) return 4.0 * ((double)u->params[l.w].n + (double)u->params[l.w2].n + 3.0 * l.cout);
     double n = (double)u->params[l.w].n + l.cout;
     if (l.gamma >= 0) n += 2.0 * l.cout;
     if (l.tb_off >= 0) n += l.cout;
@@ -1231,6 +1275,7 @@ int mpdx_unet_create(const mpdx_unet_cfg* cfg, mpdx_unet** out) {
     if (cfg->unet_input_dim % 16) return fail(MPDX_E_INVALID, "unet_input_dim must be a multiple of 16");
     // final_conv is Conv1dBlock(unet_input_dim, unet_input_dim) on the output of the last up level, which has unet_input_dim * dim_mults[0]
     // channels (temporal_unet.py:98-116): the reference's own forward fails for dim_mults[0] != 1
+    if (cfg->self_attention != 0 && cfg->self_attention != 1) return fail(MPDX_E_INVALID, "self_attention must be 0 or 1");
     if (cfg->dim_mults[0] != 1) return fail(MPDX_E_INVALID, "dim_mults[0] must be 1: final_conv takes unet_input_dim channels (temporal_unet.py:113-116)");
     for (int i = 0; i < cfg->n_levels; ++i)
         if (cfg->dim_mults[i] < 1) return fail(MPDX_E_INVALID, "dim_mults[%d] = %d", i, cfg->dim_mults[i]);
@@ -1255,6 +1300,14 @@ int mpdx_unet_create(const mpdx_unet_cfg* cfg, mpdx_unet** out) {
                 return fail(MPDX_E_INVALID, "layer %s: GroupNorm region of %d elements (group of %d) unsupported", nm.c_str(), re, l.gs);
             }
         }
+    for (const Layer& l : u->layers)
+        if (l.attn)
+            if (const char* why = attn_unsupported(l.cout, l.L_out)) {
+                const std::string nm = l.name;
+                const int ch = l.cout, np = l.L_out;
+                delete u;
+                return fail(MPDX_E_INVALID, "self-attention block %s (%d channels on %d positions): %s", nm.c_str(), ch, np, why);
+            }
     if ((int)u->tt_w.size() > 40) { delete u; return fail(MPDX_E_INVALID, "too many residual blocks"); }
     build_units(u);
     u->packed_floats += 64;   // tail padding
@@ -1819,6 +1872,7 @@ int mpdx_bench_layer(mpdx_unet* u, const float* packed, const float* timetab, co
 int mpdx_unet_layer_tile(const mpdx_unet* u, int i, int B, char* buf, size_t buflen) {
     if (!u || !buf || i < 0 || i >= (int)u->layers.size()) return fail(MPDX_E_INVALID, "bad layer index");
     const Layer& l = u->layers[i];
+    if (l.attn) { snprintf(buf, buflen, "attn %dx%d", attn_cols(l.cout, l.L_out) / l.L_out, l.L_out); return 0; }   // trajectories x positions per workgroup
     int MT, NT;
     ConvArgs dummy;
     memset(&dummy, 0, sizeof(dummy));

@@ -1042,25 +1042,33 @@ inline void TrainPass::backward_time() {
 
 using namespace mpdx;
 
+// a self_attention=True network (attn.hpp) is inference and evaluation only: every training entry point that takes the handle refuses it
+static int train_refuses_attention(const mpdx_unet* u) {
+    if (u && u->cfg.self_attention)
+        return fail(MPDX_E_INVALID, "self-attention network: the training pass has no backward for the self-attention blocks (self_attention=True runs inference and evaluation only)");
+    return 0;
+}
+
 extern "C" {
 
 size_t mpdx_train_flat_floats(mpdx_unet* u) {
-    if (!u) return 0;
+    if (!u || train_refuses_attention(u)) return 0;
     build_train_plan(u);
     return u->flat_floats;
 }
 size_t mpdx_train_dgrad_pack_floats(mpdx_unet* u) {
-    if (!u) return 0;
+    if (!u || train_refuses_attention(u)) return 0;
     build_train_plan(u);
     return std::max<size_t>(u->packedT_floats, 4);
 }
 size_t mpdx_train_workspace_floats(mpdx_unet* u, int B) {
-    if (!u || B <= 0) return 0;
+    if (!u || B <= 0 || train_refuses_attention(u)) return 0;
     build_train_plan(u);
     return train_ws(u, B).total;
 }
 int mpdx_train_param_offset(mpdx_unet* u, int idx, size_t* off, size_t* n) {
     if (!u || idx < 0 || idx >= (int)u->params.size() || !off || !n) return fail(MPDX_E_INVALID, "bad argument");
+    if (int rc = train_refuses_attention(u)) return rc;
     build_train_plan(u);
     *off = u->params[idx].foff; *n = u->params[idx].n;
     return 0;
@@ -1069,6 +1077,7 @@ int mpdx_train_param_offset(mpdx_unet* u, int idx, size_t* off, size_t* n) {
 /* flat parameter vector (reference layout) -> forward pack (+ the dgrad pack when packedT is given): one launch */
 int mpdx_train_pack(mpdx_unet* u, const float* flat, float* packed, float* packedT, void* stream) {
     if (!u || !flat || !packed) return fail(MPDX_E_INVALID, "null argument");
+    if (int rc = train_refuses_attention(u)) return rc;
     build_train_plan(u);
     if (int rc = ensure_pack_descs(u)) return rc;
     hipLaunchKernelGGL(pack_train_kernel, dim3((unsigned)u->n_pack_chunks), dim3(256), 0, (hipStream_t)stream, (const PackDesc*)u->pack_descs_dev,
@@ -1084,6 +1093,7 @@ int mpdx_train_pack(mpdx_unet* u, const float* flat, float* packed, float* packe
  * OUTPUTS and draw them on the device (Philox4x32-10 keyed by `seed`, stream position step * B + sample); null disarms. */
 int mpdx_train_draw(mpdx_unet* u, unsigned long long seed, const int* step_counter_dev) {
     if (!u) return fail(MPDX_E_INVALID, "null handle");
+    if (int rc = train_refuses_attention(u)) return rc;
     std::lock_guard<std::mutex> lk(g_train_rng_mu);
     if (step_counter_dev) g_train_rng[u] = TrainRng{seed, step_counter_dev};
     else g_train_rng.erase(u);
@@ -1101,6 +1111,7 @@ int mpdx_train_loss_backward(mpdx_unet* u, const float* flat, const float* packe
                              void* stream) {
     if (!u || !flat || !packed || !packedT || !grads_flat || !x_start || !noise || !t_dev || !freqs16 || !loss_out || !ws || B <= 0)
         return fail(MPDX_E_INVALID, "bad argument");
+    if (int rc = train_refuses_attention(u)) return rc;
     build_train_plan(u);
     if (int rc = check_ready(u)) return rc;
     if (!sqrt_alphas_cumprod_dev || !sqrt_one_minus_alphas_cumprod_dev) return fail(MPDX_E_INVALID, "schedule tables missing");

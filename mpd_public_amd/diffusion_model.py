@@ -456,7 +456,8 @@ class GaussianDiffusionModel(nn.Module):
         it is the forward value only."""
         t = torch.randint(0, self.n_diffusion_steps, (x.shape[0],), device=x.device).long()
         if torch.is_grad_enabled() and context is None and any(p.requires_grad for p in self.model.parameters()):
-            from .trainer import loss_with_grad
+            from .trainer import loss_with_grad, refuse_self_attention
+            refuse_self_attention(self.model)   # (before the timestep draw's consumer touches the device: no backward for the attention blocks)
             hard_conds = args[0] if args else None
             return loss_with_grad(self, x, hard_conds, t=t), {}
         return self.p_losses(x, context, t, *args)

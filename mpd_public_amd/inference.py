@@ -69,7 +69,8 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
     robot.dt = dt
 
     unet = TemporalUnet(state_dim=dataset.state_dim, n_support_points=n_support_points, unet_input_dim=args["unet_input_dim"],
-                        dim_mults=UNET_DIM_MULTS[args["unet_dim_mults_option"]])
+                        dim_mults=UNET_DIM_MULTS[args["unet_dim_mults_option"]],
+                        self_attention=bool(args.get("self_attention", False)))   # (the key of a run that built TemporalUnet(self_attention=True); absent: False)
     model = GaussianDiffusionModel(model=unet, variance_schedule=args["variance_schedule"], n_diffusion_steps=args["n_diffusion_steps"],
                                    predict_epsilon=args["predict_epsilon"])
     if ckpt is not None and os.path.exists(ckpt):

@@ -60,14 +60,14 @@ def synth_param(name: str, shape: Tuple[int, ...]) -> np.ndarray:
 
     * conv / linear ``weight``: U(-b, b) with b = 1/sqrt(fan_in) (the scale torch's default init uses,
       so activations stay O(1) through the 33 conv blocks);
-    * GroupNorm ``block.2.weight``: 1 + 0.1 u,  ``block.2.bias``: 0.1 u;
+    * GroupNorm ``block.2.weight``: 1 + 0.1 u,  ``block.2.bias``: 0.1 u; the self-attention blocks' LayerNorm ``norm.g`` / ``norm.b`` alike;
     * other ``bias``: U(-b, b) with b = 1/sqrt(fan_out-ish) -> use 0.05 so biases matter but do not dominate.
     """
     n = int(np.prod(shape)) if len(shape) else 1
     u = hash_uniform(name, n)
-    if name.endswith("block.2.weight"):
+    if name.endswith("block.2.weight") or name.endswith("norm.g"):
         v = 1.0 + 0.1 * u
-    elif name.endswith("block.2.bias"):
+    elif name.endswith("block.2.bias") or name.endswith("norm.b"):
         v = 0.1 * u
     elif name.endswith("weight"):
         if len(shape) == 3:  # Conv1d [Co,Ci,k] / ConvTranspose1d [Ci,Co,k]: fan_in = shape[1]*k either way is fine

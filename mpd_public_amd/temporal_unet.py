@@ -4,8 +4,9 @@ Same constructor arguments, same module tree / state-dict keys (so a reference c
 inference.py:145-148), same call protocol ``model(x[B,H,D], time[B] int64, context=None) -> eps[B,H,D]``.
 The forward does NOT run the torch modules: they only hold the parameters.  On first use the parameters are
 repacked once into MFMA fragment order and every call runs the hand-written gfx950 kernels in libmpdx.so.
-Only the configuration the reference ever builds is supported: conditioning_type=None, self_attention=False
-(inference.py:132-141, train.py:94-107).
+conditioning_type=None only (what the reference scripts build: inference.py:132-141, train.py:94-107).  self_attention=True adds the
+reference's Residual(PreNorm(dim, LinearAttention(dim))) blocks (temporal_unet.py:82,93,104; layers.py:174-226), one HIP launch each
+(csrc/attn.hpp) - for inference and evaluation; the training step refuses such a network (no backward for those blocks).
 """
 from __future__ import annotations
 
@@ -56,6 +57,30 @@ def _res_block(cin, cout, cond_dim):
     return m
 
 
+SELF_ATTENTION_TRAINING_REFUSAL = ("self-attention network: the training pass has no backward for the self-attention blocks "
+                                   "(self_attention=True runs inference and evaluation only)")
+
+
+class _LayerNormHolder(_Holder):   # layers.py:194-204
+    def __init__(self, dim):
+        super().__init__()
+        self.g = nn.Parameter(torch.ones(1, dim, 1))
+        self.b = nn.Parameter(torch.zeros(1, dim, 1))
+
+
+def _self_attention(dim, heads=4, dim_head=32):
+    """Residual(PreNorm(dim, LinearAttention(dim))) (layers.py:174-226) as parameter holders: <p>.fn.fn.to_qkv / to_out, <p>.fn.norm.g / .b.
+    heads / dim_head are LinearAttention's own defaults - TemporalUnet passes only dim (temporal_unet.py:82,93,104)."""
+    hidden = heads * dim_head
+    res, pre, att = _Holder(), _Holder(), _Holder()
+    att.to_qkv = nn.Conv1d(dim, hidden * 3, 1, bias=False)
+    att.to_out = nn.Conv1d(hidden, dim, 1)
+    pre.fn = att            # (registration order fn, norm: the reference's state-dict order)
+    pre.norm = _LayerNormHolder(dim)
+    res.fn = pre
+    return res
+
+
 def _resample(dim, up):
     m = _Holder()
     m.conv = nn.ConvTranspose1d(dim, dim, 4, 2, 1) if up else nn.Conv1d(dim, dim, 3, 2, 1)
@@ -70,8 +95,8 @@ class TemporalUnet(nn.Module):
         if conditioning_type not in (None, "None"):
             raise NotImplementedError("mpd_public_amd.TemporalUnet: only conditioning_type=None is supported "
                                       "(the only configuration the reference scripts build)")
-        if self_attention:
-            raise NotImplementedError("mpd_public_amd.TemporalUnet: self_attention=True is not supported")
+        self.self_attention = bool(self_attention)
+        attn = (lambda dim: _self_attention(dim)) if self.self_attention else (lambda dim: nn.Identity())
         self.state_dim = state_dim
         self.conditioning_type = None
         self.n_support_points = n_support_points
@@ -88,17 +113,17 @@ class TemporalUnet(nn.Module):
         self.downs = nn.ModuleList()
         for i, (ci, co) in enumerate(in_out):
             last = i >= n_res - 1
-            self.downs.append(nn.ModuleList([_res_block(ci, co, time_emb_dim), _res_block(co, co, time_emb_dim), nn.Identity(),
+            self.downs.append(nn.ModuleList([_res_block(ci, co, time_emb_dim), _res_block(co, co, time_emb_dim), attn(co),
                                              nn.Identity(), _resample(co, up=False) if not last else nn.Identity()]))
+        self.ups = nn.ModuleList()   # registered ahead of the middle blocks, as the reference does (temporal_unet.py:72-73): state_dict() lists the same order
+        for ci, co in reversed(in_out[1:]):  # every up stage upsamples (temporal_unet.py:98-107)
+            self.ups.append(nn.ModuleList([_res_block(co * 2, ci, time_emb_dim), _res_block(ci, ci, time_emb_dim), attn(ci),
+                                           nn.Identity(), _resample(ci, up=True)]))
         mid = dims[-1]
         self.mid_block1 = _res_block(mid, mid, time_emb_dim)
-        self.mid_attn = nn.Identity()
+        self.mid_attn = attn(mid)
         self.mid_attention = nn.Identity()
         self.mid_block2 = _res_block(mid, mid, time_emb_dim)
-        self.ups = nn.ModuleList()
-        for ci, co in reversed(in_out[1:]):  # every up stage upsamples (temporal_unet.py:98-107)
-            self.ups.append(nn.ModuleList([_res_block(co * 2, ci, time_emb_dim), _res_block(ci, ci, time_emb_dim), nn.Identity(),
-                                           nn.Identity(), _resample(ci, up=True)]))
         self.final_conv = nn.Sequential(_conv_block(unet_input_dim, unet_input_dim), nn.Conv1d(unet_input_dim, state_dim, 1))
 
         # device-side state (created lazily on the parameters' device)
@@ -146,7 +171,7 @@ class TemporalUnet(nn.Module):
             lib = _lib.load()
             mults = (C.c_int32 * _lib.MAX_LEVELS)(*self.dim_mults)
             cfg = _lib.UnetCfg(int(self.state_dim), int(self.n_support_points), int(self.unet_input_dim), len(self.dim_mults),
-                               mults, int(self.time_emb_dim))
+                               mults, int(self.time_emb_dim), int(self.self_attention))
             h = C.c_void_p()
             _lib.check(lib.mpdx_unet_create(C.byref(cfg), C.byref(h)), "mpdx_unet_create")
             self._h = h

@@ -85,6 +85,9 @@ def experiment(dataset_subdir: str = "EnvSimple2D-RobotPointMass", include_veloc
                use_ema: bool = True, use_amp: bool = False, steps_til_summary: int = 10, summary_class: str = "SummaryTrajectoryGeneration",
                steps_til_ckpt: int = 50000, device: str = "cuda", debug: bool = True, seed: int = 0, results_dir: str = "logs",
                data_dir: str = "data_trajectories", **kwargs):
+    if kwargs.get("self_attention"):   # (not an argument of the reference's train.py; named here so that it is refused, not swallowed by **kwargs)
+        from .temporal_unet import SELF_ATTENTION_TRAINING_REFUSAL
+        raise NotImplementedError(SELF_ATTENTION_TRAINING_REFUSAL)
     if diffusion_model_class != "GaussianDiffusionModel" or loss_class != "GaussianDiffusionLoss":
         raise NotImplementedError("only GaussianDiffusionModel / GaussianDiffusionLoss (the classes train.py's defaults name)")
     torch.manual_seed(seed)

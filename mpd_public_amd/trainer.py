@@ -55,11 +55,19 @@ class EarlyStopper:
         return False
 
 
+def refuse_self_attention(unet):
+    """A self_attention=True network is inference and evaluation only (csrc/attn.hpp has no backward): refused before any device work."""
+    if getattr(unet, "self_attention", False):
+        from .temporal_unet import SELF_ATTENTION_TRAINING_REFUSAL
+        raise NotImplementedError(SELF_ATTENTION_TRAINING_REFUSAL)
+
+
 class FlatParams:
     """The parameters of a TemporalUnet as ONE flat fp32 tensor in the layout libmpdx differentiates (parameter i of
     mpdx_unet_param_info at mpdx_train_param_offset(i)), with every nn.Parameter (and its .grad) a view into it."""
 
     def __init__(self, unet):
+        refuse_self_attention(unet)
         self.unet = unet
         lib, h = _lib.load(), unet._handle()
         dev = next(unet.parameters()).device
@@ -161,6 +169,7 @@ class TrainStep:
     """loss + gradient of GaussianDiffusionModel.loss (diffusion_model_base.py:331-357) and the optimiser step, native."""
 
     def __init__(self, model):
+        refuse_self_attention(model.model)
         self.model = model
         self.unet = model.model
         self.fp = flat_params(self.unet)
