@@ -194,7 +194,8 @@ int mpdx_randn(float* out, size_t n, uint64_t seed, uint64_t offset, void* strea
 typedef struct mpdx_field {
     int32_t kind;                       /* MPDX_FIELD_* */
     float   weight;                     /* weight_grad_cost_collision (inference.py:55) */
-    int32_t sphere_off, n_spheres;      /* float offset into prims, 4 floats each: cx,cy,cz,r (cz unused in 2-D) */
+    int32_t sphere_off, n_spheres;      /* float offset into prims, 4 floats each: cx,cy,cz,r (cz unused in 2-D); with several scenes: offset into the
+                                         * staged image of a scene and the table's CAPACITY (mpdx_guide_params.n_scenes) */
     int32_t box_off, n_boxes;           /* 6 floats each: cx,cy,cz,hx,hy,hz */
     float   ws_min[3], ws_max[3];       /* MPDX_FIELD_WORKSPACE */
     /* --- MPDX_FIELD_GRID: a sampled signed-distance field (torch_robotics' GridMapSDF; un-vendored, restated: PARITY UNPINNED).
@@ -238,7 +239,7 @@ typedef struct mpdx_guide_params {
     float   gp_weight;                  /* weight_grad_cost_smoothness (inference.py:56) */
     float   dt;                         /* trajectory_duration / n_support_points (inference.py:120) */
     float   sigma_gp;                   /* 1.0 */
-    const float* prims;                 /* device pointer: primitive table */
+    const float* prims;                 /* device pointer: primitive table (n_scenes > 1: the scene blocks + the shared tail, see the scene members below) */
     int32_t n_prim_floats;
     /* --- switches for what the reference's empty submodules leave undecidable / for options of guides.py --- */
     int32_t clip_rule;                  /* 0: clip_grad_rule 'norm' (guides.py:224-230); 1: 'value' (guides.py:232-236) */
@@ -250,7 +251,33 @@ typedef struct mpdx_guide_params {
                                          * 2: GaussianNormalizer (:140-141): x * stds + means with means in `mins`, stds in `maxs`, no range test */
     const float* grids;                 /* device pointer: the planes of the MPDX_FIELD_GRID fields (NULL when there is none); stays in global memory */
     int32_t n_grid_floats;              /* floats in grids (every plane must lie inside) */
+    /* --- several obstacle scenes in one batch (an extension: the reference plans one task per call).  All four members zero (or n_scenes = 1):
+     * one scene, prims as described above - the block behaves exactly as before these members existed.
+     * n_scenes > 1: the trajectories of one launch see different primitive tables.  prims then holds
+     *     [ scene block 0 | scene block 1 | ... | scene block n_scenes-1 | shared tail ]
+     *   scene block s   scene_stride floats at prims + s * scene_stride:
+     *                     words 0 .. 2*MPDX_MAX_FIELDS-1 (int32 bit patterns, the block header): n_spheres of field 0 .. MPDX_MAX_FIELDS-1 IN THIS
+     *                     SCENE, then n_boxes of field 0 .. MPDX_MAX_FIELDS-1 in this scene (entries of fields that are not OBJECTS fields: ignored);
+     *                     then the sphere (4 floats each) and box (6 floats each) tables of the per-scene fields, unused capacity zero
+     *   shared tail     the n_prim_floats - n_scenes * scene_stride floats behind the last block: tables every scene sees (may be empty)
+     * A workgroup (= one trajectory) of scene s stages block s and, directly behind it, the shared tail: scene_stride + tail floats.  sphere_off /
+     * box_off of an OBJECTS field are offsets into THAT image, the same for every scene: a table at an offset < scene_stride lies in the scene
+     * block (it must start behind the header and end inside the block) and differs per scene; a table at an offset >= scene_stride lies in the
+     * shared tail.  n_spheres / n_boxes of the field are the CAPACITY of its table (the maximum over the scenes); a scene scans
+     * min(header count, capacity) primitives, in table order - the result is, bit for bit, that of a single-scene block holding those primitives.
+     * WORKSPACE, SELF and GRID fields are the same for every scene (a grid stands for the fixed environment).
+     * Trajectory b uses scene scene_of_ctx[b / scene_n_per_ctx], clamped into [0, n_scenes) by the kernels: a bad entry reads another scene, never
+     * out of bounds.  The caller sizes scene_of_ctx: ceil(B / scene_n_per_ctx) entries for a batch of B.
+     * Entry points that take scenes: mpdx_guide_step, mpdx_guide_step_scaled, mpdx_guide_time, mpdx_traj_metrics, mpdx_traj_metrics_mask, mpdx_plan
+     * (checked on the host before any launch: MPDX_E_INVALID, message naming the scene member at fault); mpdx_gpmp_step, mpdx_rrt_connect,
+     * mpdx_rrt_paths and mpdx_sdf_grid_bake refuse n_scenes > 1. */
+    int32_t n_scenes;                   /* 0 or 1: one scene */
+    int32_t scene_stride;               /* floats per scene block: a multiple of 4, >= 2*MPDX_MAX_FIELDS + the per-scene tables */
+    const int32_t* scene_of_ctx;        /* device array: scene index per group of scene_n_per_ctx consecutive trajectories */
+    int32_t scene_n_per_ctx;            /* trajectories per entry of scene_of_ctx (a member: the metrics entry points have no n_per_ctx argument) */
 } mpdx_guide_params;
+#define MPDX_SCENE_HEADER_WORDS 8            /* 2 * MPDX_MAX_FIELDS */
+#define MPDX_SCENE_MAX_STAGED_FLOATS 12288   /* scene_stride + shared tail: the kernels' LDS budget for one staged table */
 
 /* one guide iteration on x[B,H,D] (normalised).  grad_out == NULL: x <- hard_cond(x + guide(x)) in place and
  * absmax_out[ctx] <- atomicMax(max|x_new|) ; grad_out != NULL: grad_out <- guide(x), x untouched.

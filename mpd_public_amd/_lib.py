@@ -31,6 +31,8 @@ class StepCoefs(C.Structure):
 
 
 MAX_FIELDS = 4
+SCENE_HEADER_WORDS = 2 * MAX_FIELDS      # MPDX_SCENE_HEADER_WORDS
+SCENE_MAX_STAGED_FLOATS = 12 * 1024      # MPDX_SCENE_MAX_STAGED_FLOATS
 FIELD_OBJECTS, FIELD_WORKSPACE, FIELD_SELF, FIELD_GRID = 0, 1, 2, 3
 GRID_LINEAR, GRID_NEAREST = 0, 1
 ROBOT_POINTMASS, ROBOT_PANDA = 0, 1
@@ -51,7 +53,9 @@ class GuideParams(C.Structure):
                 ("n_fields", C.c_int32), ("fields", Field * MAX_FIELDS), ("use_gp", C.c_int32), ("gp_weight", C.c_float),
                 ("dt", C.c_float), ("sigma_gp", C.c_float), ("prims", C.c_void_p), ("n_prim_floats", C.c_int32),
                 ("clip_rule", C.c_int32), ("max_grad_value", C.c_float), ("gp_half_factor", C.c_int32),
-                ("identity_normalizer", C.c_int32), ("grids", C.c_void_p), ("n_grid_floats", C.c_int32)]
+                ("identity_normalizer", C.c_int32), ("grids", C.c_void_p), ("n_grid_floats", C.c_int32),
+                # several obstacle scenes in one batch (layout of the scene blocks in include/mpdx.h); all zero: one scene
+                ("n_scenes", C.c_int32), ("scene_stride", C.c_int32), ("scene_of_ctx", C.c_void_p), ("scene_n_per_ctx", C.c_int32)]
 
 
 class GpmpOpts(C.Structure):

@@ -24,6 +24,7 @@
 #include "../../include/mpdx.h"
 #include "conv_block.hpp"
 #include "grid_field.hpp"
+#include "scene_table.hpp"
 
 namespace mpdx {
 
@@ -57,7 +58,8 @@ struct GuideArgs {
     float* chain;           // optional second destination
     NoiseRng rng;           // rng.on: the step's noise is drawn in place (noise pointer ignored)
     long long* trace;       // dev tool: cycle stamps, 16 slots per wave of workgroup 0 (null in production)
-    dev_grids grid;         // MPDX_FIELD_GRID descriptors (grid_field.hpp): last, read by the HAS_GRID instantiations only
+    dev_grids grid;         // MPDX_FIELD_GRID descriptors (grid_field.hpp): read by the HAS_GRID instantiations only
+    dev_scenes scene;       // per-scene primitive tables (scene_table.hpp): last, read by the MULTI_SCENE instantiations only
 };
 
 // d cost / d p  for  cost = relu(margin - min_prims sdf(p)).
@@ -325,15 +327,24 @@ __device__ __forceinline__ float objects_sdf(const float* __restrict__ prims, co
 // x is UNNORMALISED [B,H,D] (inference.py:285 un-normalises before computing metrics).
 // HAS_GRID (here and in the guide kernels): the instantiation also knows MPDX_FIELD_GRID fields (grid_field.hpp); the launcher picks it when a
 // field is a grid, so that the primitive-only instantiations compile from exactly the code they had before grids existed.
-template <int QD, int DIM, int ROBOT, bool HAS_GRID = false>
+// MULTI_SCENE (here and in the guide kernels): the workgroup stages the block of ITS scene (scene_table.hpp) and scans the OBJECTS fields with that
+// scene's counts; chosen by the launcher when n_scenes > 1, for the same reason.
+template <int QD, int DIM, int ROBOT, bool HAS_GRID = false, bool MULTI_SCENE = false>
 __global__ __launch_bounds__(64) void traj_metrics_kernel(const dev_guide_params gp, const float* __restrict__ x, float* __restrict__ out,
-                                                          int B, int H, int n_check, uint8_t* __restrict__ mask, const dev_grids grid) {
+                                                          int B, int H, int n_check, uint8_t* __restrict__ mask, const dev_grids grid, const dev_scenes scene) {
     constexpr int D = 2 * QD;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int lane = threadIdx.x, b = blockIdx.x;
     float* sx = sm;
     float* sprim = sx + H * D;
-    for (int i = lane; i < gp.n_prim_floats; i += 64) sprim[i] = gp.prims[i];
+    SceneCounts sc_n;
+    if constexpr (MULTI_SCENE) {
+        const int s = scene_of_traj(scene, b);
+        sc_n = scene_counts(gp, gp.prims + (size_t)s * scene.stride);
+        stage_scene_table(gp, scene, s, sprim, lane, 64);
+    } else {
+        for (int i = lane; i < gp.n_prim_floats; i += 64) sprim[i] = gp.prims[i];
+    }
     for (int i = lane; i < H * D; i += 64) sx[i] = x[(size_t)b * H * D + i];
     __syncthreads();
     float plen = 0.f, smooth = 0.f;
@@ -364,7 +375,10 @@ __global__ __launch_bounds__(64) void traj_metrics_kernel(const dev_guide_params
 #pragma unroll
             for (int j = 0; j < DIM; ++j) p[j] = q[j];
             for (int f = 0; f < gp.n_fields; ++f) {
-                if (gp.fields[f].kind == MPDX_FIELD_OBJECTS) hit |= objects_sdf<DIM>(sprim, gp.fields[f], p) < gp.link_margin;
+                if (gp.fields[f].kind == MPDX_FIELD_OBJECTS) {
+                    if constexpr (MULTI_SCENE) hit |= objects_sdf<DIM>(sprim, scene_field(gp, sc_n, f), p) < gp.link_margin;
+                    else hit |= objects_sdf<DIM>(sprim, gp.fields[f], p) < gp.link_margin;
+                }
                 else if (gp.fields[f].kind == MPDX_FIELD_WORKSPACE) {
 #pragma unroll
                     for (int j = 0; j < DIM; ++j) hit |= (p[j] - gp.fields[f].ws_min[j] < gp.link_margin) || (gp.fields[f].ws_max[j] - p[j] < gp.link_margin);
@@ -398,7 +412,10 @@ __global__ __launch_bounds__(64) void traj_metrics_kernel(const dev_guide_params
 #pragma unroll
                     for (int s = 0; s < kPandaNS; ++s) {
                         const float p3[3] = {P[s][0], P[s][1], P[s][2]};
-                        if (kind == MPDX_FIELD_OBJECTS) hit |= objects_sdf<3>(sprim, gp.fields[f], p3) < kPandaSR[s];
+                        if (kind == MPDX_FIELD_OBJECTS) {
+                            if constexpr (MULTI_SCENE) hit |= objects_sdf<3>(sprim, scene_field(gp, sc_n, f), p3) < kPandaSR[s];
+                            else hit |= objects_sdf<3>(sprim, gp.fields[f], p3) < kPandaSR[s];
+                        }
                         else {
 #pragma unroll
                             for (int j = 0; j < 3; ++j) hit |= (p3[j] - gp.fields[f].ws_min[j] < kPandaSR[s]) || (gp.fields[f].ws_max[j] - p3[j] < kPandaSR[s]);
@@ -535,7 +552,7 @@ __device__ __forceinline__ void guide_draw_noise(const NoiseRng& rng, unsigned l
 // wave 0 then gathers, clips, adds the GP term and applies the update.  WPT = 8 (2 point halves x up to 4 fields): the
 // single-wave version is a long serial latency chain (2-D: 19 us per launch; 8 waves: 9 us).  The Panda has its own
 // kernel below (guide_step_panda_kernel).
-template <int QD, int DIM, int ROBOT, int WPT, bool HAS_GRID = false>
+template <int QD, int DIM, int ROBOT, int WPT, bool HAS_GRID = false, bool MULTI_SCENE = false>
 __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a) {
     static_assert(ROBOT == MPDX_ROBOT_POINTMASS, "the Panda has its own kernel (guide_step_panda_kernel)");
     constexpr int D = 2 * QD;
@@ -560,7 +577,14 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
     float* sA = sx + H * D;
     float* sB = sA + MAXF * N * QD;
     float* sprim = sB + MAXF * N * QD;
-    for (int i = threadIdx.x; i < gp.n_prim_floats; i += 64 * WPT) sprim[i] = gp.prims[i];
+    SceneCounts sc_n;
+    if constexpr (MULTI_SCENE) {
+        const int s = scene_of_traj(a.scene, b);
+        sc_n = scene_counts(gp, gp.prims + (size_t)s * a.scene.stride);
+        stage_scene_table(gp, a.scene, s, sprim, threadIdx.x, 64 * WPT);
+    } else {
+        for (int i = threadIdx.x; i < gp.n_prim_floats; i += 64 * WPT) sprim[i] = gp.prims[i];
+    }
 
     // ---- load + unnormalise (normalization.py:156-167)
     const int ctx = b / a.n_per_ctx;
@@ -606,7 +630,10 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
             for (int f = 0; f < gp.n_fields; ++f) {
                 if ((f % FW) != wv / PW) continue;
                 float force[DIM];
-                if (gp.fields[f].kind == MPDX_FIELD_OBJECTS) objects_force<DIM>(sprim, gp.fields[f], p, margin, force);
+                if (gp.fields[f].kind == MPDX_FIELD_OBJECTS) {
+                    if constexpr (MULTI_SCENE) objects_force<DIM>(sprim, scene_field(gp, sc_n, f), p, margin, force);
+                    else objects_force<DIM>(sprim, gp.fields[f], p, margin, force);
+                }
                 else if (gp.fields[f].kind == MPDX_FIELD_WORKSPACE) workspace_force<DIM>(gp.fields[f], p, margin, force);
                 else if (HAS_GRID && gp.fields[f].kind == MPDX_FIELD_GRID) grid_force<DIM>(a.grid.grids, a.grid.g[f], p, margin, force);
                 else {
@@ -731,9 +758,10 @@ constexpr int panda_group_joints(int part) { return part == 0 ? 3 : part == 1 ? 
 // phase 2 of guide_step_panda_kernel for sphere / pair group PART and point half `half`
 // FKREG: the forward kinematics of the point are evaluated HERE from the LDS-staged state (sx, H, D, scale) instead of being read from
 // the per-point FK table of phase 1 (sfk): 4 x the FK work, no 38-KB table - the large-batch variant of the kernel (below).
-template <int PART, bool FKREG, bool HAS_GRID = false>
+// MULTI_SCENE: the OBJECTS fields are scanned with the counts of the workgroup's scene (sc_n; scene_table.hpp)
+template <int PART, bool FKREG, bool HAS_GRID = false, bool MULTI_SCENE = false>
 __device__ __forceinline__ void panda_group_forces(const dev_guide_params& gp, const dev_grids& grid, const float* sprim, const float* sfk, float* sG, int half, int lane, int N,
-                                                   long long* tr, const float* sx = nullptr, int H = 0, float scale = 0.f) {
+                                                   long long* tr, const float* sx = nullptr, int H = 0, float scale = 0.f, const SceneCounts* sc_n = nullptr) {
     constexpr int QD = 7, NP = kPandaParts, D = 14;
     constexpr int s_beg = panda_group_first(PART), s_end = panda_group_first(PART + 1), NG = s_end - s_beg;
     constexpr int NJ = panda_group_joints(PART);
@@ -822,7 +850,10 @@ __device__ __forceinline__ void panda_group_forces(const dev_guide_params& gp, c
                 pg[n][0] = P[s_beg + n][0]; pg[n][1] = P[s_beg + n][1]; pg[n][2] = P[s_beg + n][2];
                 mg[n] = kPandaSR[s_beg + n] + gp.cutoff_margin;
             }
-            if (kind == MPDX_FIELD_OBJECTS) objects_force_n<3, NG>(sprim, gp.fields[f], pg, mg, fg);
+            if (kind == MPDX_FIELD_OBJECTS) {
+                if constexpr (MULTI_SCENE) objects_force_n<3, NG>(sprim, scene_field(gp, *sc_n, f), pg, mg, fg);
+                else objects_force_n<3, NG>(sprim, gp.fields[f], pg, mg, fg);
+            }
             else if (HAS_GRID && kind == MPDX_FIELD_GRID) grid_force_n<3, NG>(grid.grids, grid.g[f], pg, mg, fg);
             else {
 #pragma unroll
@@ -845,7 +876,7 @@ __device__ __forceinline__ void panda_group_forces(const dev_guide_params& gp, c
 // DENSE (large batches): no FK table in LDS (the forces phase evaluates the FK in registers, four times per point) and registers capped
 // at 128: 70 KB of LDS and 4 waves per SIMD -> TWO workgroups per CU, where the latency-bound phases of one overlap the other's
 // (the default variant: 107 KB, 166 VGPRs, one workgroup per CU; at B = 100 there is one workgroup per CU anyway).  Same arithmetic.
-template <bool DENSE, bool HAS_GRID = false>
+template <bool DENSE, bool HAS_GRID = false, bool MULTI_SCENE = false>
 __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(const GuideArgs a) {
     constexpr int QD = 7, D = 14, MAXF = MPDX_MAX_FIELDS, NP = kPandaParts, WPT = 8;
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -869,7 +900,14 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(co
     float* snz = sC + ((MAXF * H * QD + (int)((sC - sm) & 3) + 3) & ~3) - (int)((sC - sm) & 3);   // 16-byte aligned: [H * D + 4] the step's noise of this
     float* snz_x = snz + H * D + 4;           //                    trajectory (last guide iteration of a step, rng.on) | [H * D] the normalised state
     float* sprim = snz_x + H * D;
-    for (int i = threadIdx.x; i < gp.n_prim_floats; i += 64 * WPT) sprim[i] = gp.prims[i];
+    SceneCounts sc_n;
+    if constexpr (MULTI_SCENE) {
+        const int s = scene_of_traj(a.scene, b);
+        sc_n = scene_counts(gp, gp.prims + (size_t)s * a.scene.stride);
+        stage_scene_table(gp, a.scene, s, sprim, threadIdx.x, 64 * WPT);
+    } else {
+        for (int i = threadIdx.x; i < gp.n_prim_floats; i += 64 * WPT) sprim[i] = gp.prims[i];
+    }
     float* shc = sprim + ((gp.n_prim_floats + 3) & ~3);   // [2][D] this trajectory's hard conditions (apply mode), staged here: their loads fly with the state's
     if (!a.grad_out && (int)threadIdx.x < 2 * D) {
         const int which = (int)threadIdx.x >= D ? 1 : 0, d = (int)threadIdx.x - which * D;
@@ -947,10 +985,10 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(co
         const int half = wv & 1;
         long long* trf = (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 8 : nullptr;  // slots 8..: per-field stamps
         switch (wv >> 1) {  // the group is a template parameter: sphere -> frame is static, no per-joint masks
-            case 0: panda_group_forces<0, DENSE, HAS_GRID>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale); break;
-            case 1: panda_group_forces<1, DENSE, HAS_GRID>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale); break;
-            case 2: panda_group_forces<2, DENSE, HAS_GRID>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale); break;
-            default: panda_group_forces<3, DENSE, HAS_GRID>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale); break;
+            case 0: panda_group_forces<0, DENSE, HAS_GRID, MULTI_SCENE>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale, &sc_n); break;
+            case 1: panda_group_forces<1, DENSE, HAS_GRID, MULTI_SCENE>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale, &sc_n); break;
+            case 2: panda_group_forces<2, DENSE, HAS_GRID, MULTI_SCENE>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale, &sc_n); break;
+            default: panda_group_forces<3, DENSE, HAS_GRID, MULTI_SCENE>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale, &sc_n); break;
         }
     }
     G_STAMP();  // 3 this wave's forces done

@@ -27,10 +27,11 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
     if (gp->interpolate && (gp->n_interp < H || gp->n_interp > 8 * H)) return fail(MPDX_E_INVALID, "n_interp %d unsupported", gp->n_interp);
     if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
     if (const char* why = grid_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
+    if (const char* why = scene_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
     if (gp->robot == MPDX_ROBOT_PANDA && (((uintptr_t)x & 15) || ((size_t)H * D) % 4))
         return fail(MPDX_E_INVALID, "Panda guide: x must be 16-byte aligned with H * D a multiple of 4 (the trajectory is staged with 16-byte loads)");
     GuideArgs a;
-    a.gp = dev_params_of(*gp); a.x = x; a.grad_out = grad_out; a.hs = hs; a.hg = hg; a.amax_in = amax_in; a.amax_out = amax_out;
+    a.gp = dev_params_staged(*gp); a.x = x; a.grad_out = grad_out; a.hs = hs; a.hg = hg; a.amax_in = amax_in; a.amax_out = amax_out;
     a.B = B; a.H = H; a.D = D; a.n_per_ctx = n_per_ctx > 0 ? n_per_ctx : B;
     a.noise = noise; a.noise_scale = noise_scale; a.noise_extra = noise_extra; a.chain = chain;
     a.guide_scale = guide_scale;
@@ -42,32 +43,44 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
     const bool grid = has_grid_field(*gp);
     memset(&a.grid, 0, sizeof(a.grid));
     if (grid) a.grid = dev_grids_of(*gp);
+    // several scenes select the MULTI_SCENE instantiations (scene_table.hpp), for the same reason; a workgroup stages one scene block + the shared tail
+    const bool multi = has_scenes(*gp);
+    a.scene = dev_scenes_of(*gp);
+    mpdx_guide_params staged = *gp;   // (the LDS carve is sized by what a workgroup stages)
+    staged.n_prim_floats = staged_prim_floats(*gp);
     // Panda at large batch: the dense variant (no FK table, 128 VGPRs: two workgroups per CU); MPDX_GUIDE_DENSE=0/1 forces it off / on
     const int dense_env = sw::guide_dense();
-    const bool dense = gp->robot == MPDX_ROBOT_PANDA && (dense_env >= 0 ? dense_env != 0 : B >= 512) && guide_lds_bytes(*gp, H, D, true) <= 80 * 1024;
-    const size_t lds = guide_lds_bytes(*gp, H, D, dense);
+    const bool dense = gp->robot == MPDX_ROBOT_PANDA && (dense_env >= 0 ? dense_env != 0 : B >= 512) && guide_lds_bytes(staged, H, D, true) <= 80 * 1024;
+    const size_t lds = guide_lds_bytes(staged, H, D, dense);
     if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "guide needs %zu B of LDS (n_interp %d too large)", lds, gp->n_interp);
-    if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 2 && gp->ws_dim == 2) {
-        if (grid) hipLaunchKernelGGL((guide_step_kernel<2, 2, MPDX_ROBOT_POINTMASS, 8, true>), dim3(B), dim3(512), lds, st, a);
-        else hipLaunchKernelGGL((guide_step_kernel<2, 2, MPDX_ROBOT_POINTMASS, 8>), dim3(B), dim3(512), lds, st, a);
-    } else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 3 && gp->ws_dim == 3) {
-        if (grid) hipLaunchKernelGGL((guide_step_kernel<3, 3, MPDX_ROBOT_POINTMASS, 8, true>), dim3(B), dim3(512), lds, st, a);
-        else hipLaunchKernelGGL((guide_step_kernel<3, 3, MPDX_ROBOT_POINTMASS, 8>), dim3(B), dim3(512), lds, st, a);
-    } else if (gp->robot == MPDX_ROBOT_PANDA && gp->q_dim == 7 && gp->ws_dim == 3) {
-        if (dense && grid) {
-            if (int rc = raise_lds_limit((const void*)guide_step_panda_kernel<true, true>)) return rc;
-            hipLaunchKernelGGL((guide_step_panda_kernel<true, true>), dim3(B), dim3(512), lds, st, a);
-        } else if (dense) {
-            if (int rc = raise_lds_limit((const void*)guide_step_panda_kernel<true>)) return rc;
-            hipLaunchKernelGGL(guide_step_panda_kernel<true>, dim3(B), dim3(512), lds, st, a);
-        } else if (grid) {
-            if (int rc = raise_lds_limit((const void*)guide_step_panda_kernel<false, true>)) return rc;
-            hipLaunchKernelGGL((guide_step_panda_kernel<false, true>), dim3(B), dim3(512), lds, st, a);
-        } else {
-            if (int rc = raise_lds_limit((const void*)guide_step_panda_kernel<false>)) return rc;
-            hipLaunchKernelGGL(guide_step_panda_kernel<false>, dim3(B), dim3(512), lds, st, a);
-        }
+#define MPDX_GUIDE_PM(QD_)                                                                                                                      \
+    {                                                                                                                                           \
+        if (multi && grid) hipLaunchKernelGGL((guide_step_kernel<QD_, QD_, MPDX_ROBOT_POINTMASS, 8, true, true>), dim3(B), dim3(512), lds, st, a);   \
+        else if (multi) hipLaunchKernelGGL((guide_step_kernel<QD_, QD_, MPDX_ROBOT_POINTMASS, 8, false, true>), dim3(B), dim3(512), lds, st, a); \
+        else if (grid) hipLaunchKernelGGL((guide_step_kernel<QD_, QD_, MPDX_ROBOT_POINTMASS, 8, true>), dim3(B), dim3(512), lds, st, a);         \
+        else hipLaunchKernelGGL((guide_step_kernel<QD_, QD_, MPDX_ROBOT_POINTMASS, 8>), dim3(B), dim3(512), lds, st, a);                         \
     }
+#define MPDX_GUIDE_PANDA(...)                                                                          \
+    {                                                                                                  \
+        if (int rc = raise_lds_limit((const void*)guide_step_panda_kernel<__VA_ARGS__>)) return rc;    \
+        hipLaunchKernelGGL((guide_step_panda_kernel<__VA_ARGS__>), dim3(B), dim3(512), lds, st, a);    \
+    }
+    if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 2 && gp->ws_dim == 2) MPDX_GUIDE_PM(2)
+    else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 3 && gp->ws_dim == 3) MPDX_GUIDE_PM(3)
+    else if (gp->robot == MPDX_ROBOT_PANDA && gp->q_dim == 7 && gp->ws_dim == 3) {
+        if (multi) {
+            if (dense && grid) MPDX_GUIDE_PANDA(true, true, true)
+            else if (dense) MPDX_GUIDE_PANDA(true, false, true)
+            else if (grid) MPDX_GUIDE_PANDA(false, true, true)
+            else MPDX_GUIDE_PANDA(false, false, true)
+        }
+        else if (dense && grid) MPDX_GUIDE_PANDA(true, true)
+        else if (dense) MPDX_GUIDE_PANDA(true)
+        else if (grid) MPDX_GUIDE_PANDA(false, true)
+        else MPDX_GUIDE_PANDA(false)
+    }
+#undef MPDX_GUIDE_PM
+#undef MPDX_GUIDE_PANDA
     else
         return fail(MPDX_E_INVALID, "unsupported robot %d / q_dim %d / ws_dim %d", gp->robot, gp->q_dim, gp->ws_dim);
     return 0;
@@ -105,24 +118,30 @@ int mpdx_traj_metrics_mask(const mpdx_guide_params* gp, const float* x_unnormali
     if (H > 128 || H < 2) return fail(MPDX_E_INVALID, "H=%d unsupported (max 128)", H);
     if (D != 2 * gp->q_dim || D > 16) return fail(MPDX_E_INVALID, "state dim %d != 2*q_dim (%d)", D, gp->q_dim);
     if (n_check < 2) n_check = H;
+    if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS) return fail(MPDX_E_INVALID, "n_fields %d", gp->n_fields);
+    if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
     if (const char* why = grid_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
-    const size_t lds = (size_t)(H * D + gp->n_prim_floats) * sizeof(float);
+    if (const char* why = scene_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
     hipStream_t st = (hipStream_t)stream;
-    const bool grid = has_grid_field(*gp);
-    const dev_guide_params g = dev_params_of(*gp);
+    const bool grid = has_grid_field(*gp), multi = has_scenes(*gp);
+    const dev_guide_params g = dev_params_staged(*gp);   // (n_prim_floats = what a workgroup stages: the table, or one scene block + the shared tail)
+    const size_t lds = (size_t)(H * D + g.n_prim_floats) * sizeof(float);
     dev_grids gr;
     memset(&gr, 0, sizeof(gr));
     if (grid) gr = dev_grids_of(*gp);
-    if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 2 && gp->ws_dim == 2) {
-        if (grid) hipLaunchKernelGGL((traj_metrics_kernel<2, 2, MPDX_ROBOT_POINTMASS, true>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr);
-        else hipLaunchKernelGGL((traj_metrics_kernel<2, 2, MPDX_ROBOT_POINTMASS>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr);
-    } else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 3 && gp->ws_dim == 3) {
-        if (grid) hipLaunchKernelGGL((traj_metrics_kernel<3, 3, MPDX_ROBOT_POINTMASS, true>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr);
-        else hipLaunchKernelGGL((traj_metrics_kernel<3, 3, MPDX_ROBOT_POINTMASS>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr);
-    } else if (gp->robot == MPDX_ROBOT_PANDA && gp->q_dim == 7 && gp->ws_dim == 3) {
-        if (grid) hipLaunchKernelGGL((traj_metrics_kernel<7, 3, MPDX_ROBOT_PANDA, true>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr);
-        else hipLaunchKernelGGL((traj_metrics_kernel<7, 3, MPDX_ROBOT_PANDA>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr);
-    } else
+    const dev_scenes sc = dev_scenes_of(*gp);
+#define MPDX_METRICS(QD_, DIM_, ROBOT_)                                                                                                                                          \
+    {                                                                                                                                                                            \
+        if (multi && grid) hipLaunchKernelGGL((traj_metrics_kernel<QD_, DIM_, ROBOT_, true, true>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr, sc);    \
+        else if (multi) hipLaunchKernelGGL((traj_metrics_kernel<QD_, DIM_, ROBOT_, false, true>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr, sc);  \
+        else if (grid) hipLaunchKernelGGL((traj_metrics_kernel<QD_, DIM_, ROBOT_, true>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr, sc);          \
+        else hipLaunchKernelGGL((traj_metrics_kernel<QD_, DIM_, ROBOT_>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr, sc);                          \
+    }
+    if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 2 && gp->ws_dim == 2) MPDX_METRICS(2, 2, MPDX_ROBOT_POINTMASS)
+    else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 3 && gp->ws_dim == 3) MPDX_METRICS(3, 3, MPDX_ROBOT_POINTMASS)
+    else if (gp->robot == MPDX_ROBOT_PANDA && gp->q_dim == 7 && gp->ws_dim == 3) MPDX_METRICS(7, 3, MPDX_ROBOT_PANDA)
+#undef MPDX_METRICS
+    else
         return fail(MPDX_E_INVALID, "unsupported robot %d / q_dim %d / ws_dim %d", gp->robot, gp->q_dim, gp->ws_dim);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -131,6 +150,7 @@ int mpdx_traj_metrics_mask(const mpdx_guide_params* gp, const float* x_unnormali
 int mpdx_guide_time(const mpdx_guide_params* gp, float* x, float* grad_out, const uint32_t* absmax_in, int n_per_ctx, int B, int H, int D,
                     int reps, void* stream, float* ms_avg) {
     if (!gp || !x || !grad_out || !absmax_in || !ms_avg || reps < 1) return fail(MPDX_E_INVALID, "bad argument");
+    if (const char* why = scene_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);   // (before the events: nothing is created for a refused block)
     hipStream_t st = (hipStream_t)stream;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
@@ -178,6 +198,7 @@ int mpdx_sdf_grid_bake(const mpdx_guide_params* gp, int field, float* sdf_out, f
     if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS || field < 0 || field >= gp->n_fields) return fail(MPDX_E_INVALID, "field %d of %d", field, gp->n_fields);
     const mpdx_field& f = gp->fields[field];
     if (f.kind != MPDX_FIELD_OBJECTS) return fail(MPDX_E_INVALID, "grid bake: field %d is not an OBJECTS field", field);
+    if (has_scenes(*gp)) return fail(MPDX_E_INVALID, "grid bake: one scene only (n_scenes = %d): a grid stands for the fixed environment", gp->n_scenes);
     if (gp->ws_dim != 2 && gp->ws_dim != 3) return fail(MPDX_E_INVALID, "grid bake: ws_dim %d", gp->ws_dim);
     if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
     if (f.n_spheres < 0 || f.n_boxes < 0 || f.sphere_off < 0 || f.box_off < 0 || f.sphere_off + 4 * f.n_spheres > gp->n_prim_floats ||

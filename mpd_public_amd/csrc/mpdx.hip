@@ -4,6 +4,7 @@
 #include "host.hpp"
 #include "attn.hpp"
 #include "loss.hpp"
+#include "scene_table.hpp"
 
 namespace mpdx {
 
@@ -1496,6 +1497,8 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
               uint64_t rng_seed, uint64_t rng_offset, void* stream) {
     if (!u || !packed || !timetab || !coefs || !x || !ws || T <= 0 || n_without_noise < 0 || B <= 0)
         return fail(MPDX_E_INVALID, "bad argument");
+    if (guide)   // the scene members are checked here, before the first launch of the loop (launch_guide checks them again per launch)
+        if (const char* why = scene_params_problem(*guide)) return fail(MPDX_E_INVALID, "%s", why);
     if (int rc = check_ready(u)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int H = u->cfg.n_support_points, D = u->cfg.state_dim;

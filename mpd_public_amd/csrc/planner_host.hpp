@@ -9,6 +9,7 @@ static int check_planner_params(const mpdx_guide_params* gp, int H, int D) {
     if (D != 2 * gp->q_dim || D > 16) return fail(MPDX_E_INVALID, "state dim %d != 2*q_dim (%d)", D, gp->q_dim);
     if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS) return fail(MPDX_E_INVALID, "n_fields %d", gp->n_fields);
     if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
+    if (gp->n_scenes > 1) return fail(MPDX_E_INVALID, "the baseline planners take one scene (n_scenes = %d): scene batches are for the guide and metrics kernels", gp->n_scenes);
     for (int f = 0; f < gp->n_fields; ++f)   // gn_point / config_hit scan primitive tables: a grid field would be skipped silently
         if (gp->fields[f].kind == MPDX_FIELD_GRID) return fail(MPDX_E_INVALID, "grid fields: guide and metrics only (field %d is a MPDX_FIELD_GRID)", f);
     if (H > 0 && gp->interpolate && (gp->n_interp < 2 || gp->n_interp < H || gp->n_interp > 8 * H))

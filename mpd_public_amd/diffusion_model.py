@@ -168,12 +168,14 @@ class GaussianDiffusionModel(nn.Module):
             noise_ptr = noise[1:].data_ptr()
         coefs = self._coef_table(noise_std_extra_schedule_fn, scale_grad_by_std)
         chain = torch.empty((steps + 1, B, H, D), device=dev, dtype=torch.float32) if return_chain else None
-        npc = int(n_per_context or B)
+        npc = int(n_per_context or getattr(guide, "_n_per_context", None) or B)   # (a guide bound to obstacle scenes carries its trajectories per context)
         gp_ref, flags, n_gs, t_sg = None, None, 0, 0
         if int(n_guide_steps) <= 0:
             guide = None   # range(0): the reference runs no guide iteration
         if guide is not None:
             import ctypes as C
+            if hasattr(guide, "check_batch"):
+                guide.check_batch(B, npc)   # (a guide bound to obstacle scenes serves the batch shape it was bound to)
             gp_ref = C.byref(guide.device_params(dev))
             n_gs = int(n_guide_steps)
             t_sg = int(min(t_start_guide, T + 1)) if t_start_guide != float("inf") else T + 1

@@ -18,11 +18,15 @@ from .planning import CostCollision, CostComposite, CostGPTrajectory, GRID_MODES
 
 
 def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight_l, interpolate, n_interp, clip_grad, max_grad_norm, device,
-                        clip_grad_rule="norm", max_grad_value=0.1, identity_normalizer=False):
+                        clip_grad_rule="norm", max_grad_value=0.1, identity_normalizer=False, scenes=None):
     """Compile cost descriptors into the `mpdx_guide_params` block the HIP kernels take.  Returns (params, primitive
     table tensor) - the caller keeps the tensor alive (params holds its raw device pointer).  The planes of FIELD_GRID fields travel in a second
     buffer (global memory, not part of the primitive table the kernels stage in LDS): `params.grids_tensor` (None without a grid) holds it and
-    lives as long as the params object; callers keep it next to the primitive table."""
+    lives as long as the params object; callers keep it next to the primitive table.
+    scenes (a planning.PlanningScenes, or None = one scene, the table as before): the OBJECTS fields it varies get one table per scene - the blocked
+    layout of include/mpdx.h (per-scene header + tables at the same offsets in every scene block, capacity = the largest scene, the other OBJECTS
+    fields once in the shared tail).  n_scenes / scene_stride are set; the caller binds scene_of_ctx / scene_n_per_ctx per call
+    (`params.table_host`: the host copy of the table, for tests)."""
     gp = _lib.GuideParams()
     gp.robot, gp.q_dim, gp.ws_dim = robot.robot_id, robot.q_dim, ws_dim
     gp.interpolate, gp.n_interp = int(bool(interpolate)), int(n_interp)
@@ -38,6 +42,8 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
             gp.mins[d], gp.maxs[d] = float(mins[d]), float(maxs[d])
     gp.cutoff_margin, gp.link_margin = float(cutoff_margin), float(robot.link_margin)
     prims, nf, off = [], 0, 0
+    varied = []    # scenes: (field index, [ObjectSet per scene]) of the fields that differ per scene
+    shared = []    # scenes: (field index, sphere floats, box floats) of the OBJECTS fields every scene sees
     planes, goff = [], 0     # grid planes, each padded to a multiple of 4 floats (16-byte aligned gradient planes)
     gp.use_gp = 0
     for c, w in zip(cost_l, weight_l):
@@ -46,7 +52,13 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
                 raise NotImplementedError(f"at most {_lib.MAX_FIELDS} collision fields")
             f, fld = gp.fields[nf], c.field
             f.kind, f.weight = fld.kind, float(w)
-            if fld.kind == _lib.FIELD_OBJECTS:
+            per_scene = scenes.objects_for(fld) if scenes is not None else None
+            if fld.kind == _lib.FIELD_OBJECTS and scenes is not None:
+                if per_scene is not None:
+                    varied.append((nf, per_scene))
+                else:
+                    shared.append((nf,) + tuple(fld.objects.prim_floats()))
+            elif fld.kind == _lib.FIELD_OBJECTS:
                 sp, bx = fld.objects.prim_floats()
                 f.sphere_off, f.n_spheres = off, sp.size // 4
                 off += sp.size
@@ -87,8 +99,12 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
         else:
             raise NotImplementedError(type(c))
     gp.n_fields = nf
-    n_floats = int(sum(p.size for p in prims))
-    table = np.concatenate(prims).astype(np.float32) if n_floats else np.zeros(4, np.float32)
+    if scenes is not None:
+        table, n_floats = _scene_table(gp, scenes.n_scenes, varied, shared)
+    else:
+        n_floats = int(sum(p.size for p in prims))
+        table = np.concatenate(prims).astype(np.float32) if n_floats else np.zeros(4, np.float32)
+    gp.table_host = table
     prim_t = torch.from_numpy(table).to(device)
     gp.prims, gp.n_prim_floats = prim_t.data_ptr(), n_floats
     grid_t = None
@@ -97,6 +113,53 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
         gp.grids, gp.n_grid_floats = grid_t.data_ptr(), goff
     gp.grids_tensor = grid_t   # a Python attribute of the ctypes object: the buffer lives as long as the params that point into it
     return gp, prim_t
+
+
+def _scene_table(gp, n_scenes, varied, shared):
+    """The blocked primitive table of include/mpdx.h: n_scenes blocks of gp.scene_stride floats ([header: n_spheres per field, n_boxes per field,
+    int32 | the per-scene tables at fixed offsets, capacity = the largest scene, unused rows zero]) followed by the shared tail (the OBJECTS
+    fields that are the same in every scene, stored once).  Sets the fields' offsets / capacities and gp.n_scenes / gp.scene_stride; returns
+    (table, floats in it)."""
+    off = _lib.SCENE_HEADER_WORDS
+    slots = []
+    for fi, sets in varied:
+        tabs = [o.prim_floats() for o in sets]
+        f = gp.fields[fi]
+        f.n_spheres, f.n_boxes = max(sp.size // 4 for sp, _ in tabs), max(bx.size // 6 for _, bx in tabs)
+        f.sphere_off = off
+        f.box_off = off + 4 * f.n_spheres
+        off = f.box_off + 6 * f.n_boxes
+        slots.append((fi, tabs))
+    stride = (off + 3) & ~3
+    off = stride
+    for fi, sp, bx in shared:     # offsets into the staged image [scene block | shared tail]
+        f = gp.fields[fi]
+        f.sphere_off, f.n_spheres = off, sp.size // 4
+        off += sp.size
+        f.box_off, f.n_boxes = off, bx.size // 6
+        off += bx.size
+    tail = off - stride
+    if stride + tail > _lib.SCENE_MAX_STAGED_FLOATS:
+        raise ValueError(f"a scene block of {stride} floats + {tail} shared floats exceeds the kernels' table budget of {_lib.SCENE_MAX_STAGED_FLOATS} floats")
+    table = np.zeros(n_scenes * stride + tail + 4, np.float32)   # (+4: never an empty allocation; not part of n_prim_floats)
+    hdr = table.view(np.int32)
+    for s in range(n_scenes):
+        b0 = s * stride
+        for fi, tabs in slots:
+            sp, bx = tabs[s]
+            f = gp.fields[fi]
+            hdr[b0 + fi], hdr[b0 + _lib.MAX_FIELDS + fi] = sp.size // 4, bx.size // 6
+            table[b0 + f.sphere_off: b0 + f.sphere_off + sp.size] = sp
+            table[b0 + f.box_off: b0 + f.box_off + bx.size] = bx
+        for fi, sp, bx in shared:   # a shared field has its capacity in every scene
+            hdr[b0 + fi], hdr[b0 + _lib.MAX_FIELDS + fi] = sp.size // 4, bx.size // 6
+    for fi, sp, bx in shared:
+        f = gp.fields[fi]
+        g0 = n_scenes * stride - stride   # image offset -> table offset of the tail
+        table[g0 + f.sphere_off: g0 + f.sphere_off + sp.size] = sp
+        table[g0 + f.box_off: g0 + f.box_off + bx.size] = bx
+    gp.n_scenes, gp.scene_stride = n_scenes, stride
+    return table, n_scenes * stride + tail
 
 
 class GuideManagerTrajectoriesWithVelocity(nn.Module):
@@ -123,6 +186,39 @@ class GuideManagerTrajectoriesWithVelocity(nn.Module):
         self._prims = None
         self._grids = None
         self._flag = None
+        # a guide bound to obstacle scenes (with_scenes): the scenes, the host assignment, trajectories per context, the device index table
+        self._scenes = None
+        self._scene_of_context = None
+        self._n_per_context = None
+        self._scene_table = None
+
+    def with_scenes(self, scenes, scene_of_context, n_per_context):
+        """A guide with the same cost terms and options whose trajectories see different obstacle scenes (an extension, planning.PlanningScenes):
+        the c-th group of `n_per_context` consecutive trajectories uses scene `scene_of_context[c]`.  The returned guide owns the device index
+        table; it is what `guide=` of GaussianDiffusionModel.plan / the step-by-step loop takes, for batches of len(scene_of_context) *
+        n_per_context trajectories.  Its whole-tensor range test (LimitsNormalizer.unnormalize) is evaluated per context, as one call per context
+        would.  The reference's constructor signature is untouched: the binding is this method."""
+        if not self.is_native:
+            raise NotImplementedError("scenes need the HIP guide (a CostComposite of the reference's cost terms); a guide that differentiates a Python cost "
+                                      "with autograd has one set of obstacles, inside that cost")
+        if scenes.task is not self.dataset.task:
+            raise ValueError("the scenes were built for another task than this guide's dataset.task")
+        soc = scenes.check_assignment(scene_of_context, None, n_per_context)
+        g = GuideManagerTrajectoriesWithVelocity(self.dataset, self.cost, clip_grad=self.clip_grad, clip_grad_rule=self.clip_grad_rule,
+                                                 max_grad_norm=self.max_grad_norm, max_grad_value=self.max_grad_value,
+                                                 interpolate_trajectories_for_collision=self.interpolate_trajectories_for_collision,
+                                                 num_interpolated_points_for_collision=self.num_interpolated_points_for_collision)
+        g._scenes, g._scene_of_context, g._n_per_context = scenes, soc, int(n_per_context)
+        return g
+
+    def check_batch(self, B, n_per_context=None):
+        """A scene-bound guide serves batches of exactly the shape it was bound to."""
+        if self._scenes is None:
+            return
+        if B != len(self._scene_of_context) * self._n_per_context:
+            raise ValueError(f"this guide is bound to {len(self._scene_of_context)} contexts of {self._n_per_context} trajectories, not to a batch of {B}")
+        if n_per_context is not None and int(n_per_context) != self._n_per_context:
+            raise ValueError(f"n_per_context={n_per_context} differs from the {self._n_per_context} the guide's scenes were bound with")
 
     # ------------------------------------------------------------------------------------------- compile to device params
     def device_params(self, device) -> "_lib.GuideParams":
@@ -144,8 +240,11 @@ class GuideManagerTrajectoriesWithVelocity(nn.Module):
             ds.robot, ds.env.dim, ds.task.obstacle_cutoff_margin, lo, hi,
             self.cost.cost_l, self.cost.weight_cost_l, self.interpolate_trajectories_for_collision, self.num_interpolated_points_for_collision,
             self.clip_grad, self.max_grad_norm, device, clip_grad_rule=self.clip_grad_rule, max_grad_value=self.max_grad_value,
-            identity_normalizer=mode)
+            identity_normalizer=mode, scenes=self._scenes)
         self._grids = self._params.grids_tensor
+        if self._scenes is not None:
+            self._scene_table = torch.tensor(self._scene_of_context, dtype=torch.int32, device=device)
+            self._params.scene_of_ctx, self._params.scene_n_per_ctx = self._scene_table.data_ptr(), self._n_per_context
         return self._params
 
     # ------------------------------------------------------------------------------------------- guide protocol
@@ -184,11 +283,13 @@ class GuideManagerTrajectoriesWithVelocity(nn.Module):
             return self._forward_autograd(x_normalized)
         x = x_normalized.to(torch.float32).contiguous()
         B, H, D = x.shape
+        self.check_batch(B)
         gp = self.device_params(x.device)
         lib, st = _lib.load(), _lib.current_stream()
-        flag = torch.zeros(1, dtype=torch.int32, device=x.device)
-        _lib.check(lib.mpdx_absmax(x.data_ptr(), flag.data_ptr(), B, B, H, D, st), "mpdx_absmax")
+        npc = self._n_per_context if self._scenes is not None else B   # scenes: the range test per context, as one call per context would
+        flag = torch.zeros(B // npc, dtype=torch.int32, device=x.device)
+        _lib.check(lib.mpdx_absmax(x.data_ptr(), flag.data_ptr(), npc, B, H, D, st), "mpdx_absmax")
         out = torch.empty_like(x)
-        _lib.check(lib.mpdx_guide_step(C.byref(gp), x.data_ptr(), out.data_ptr(), None, None, flag.data_ptr(), None, B, B, H, D, st),
+        _lib.check(lib.mpdx_guide_step(C.byref(gp), x.data_ptr(), out.data_ptr(), None, None, flag.data_ptr(), None, npc, B, H, D, st),
                    "mpdx_guide_step")
         return out

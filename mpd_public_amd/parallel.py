@@ -29,14 +29,26 @@ def expand_contexts(start: torch.Tensor, goal: torch.Tensor, n_samples: int):
 
 
 def plan_contexts(model, start: torch.Tensor, goal: torch.Tensor, n_samples: int, *, rank: int = 0, world_size: int = 1,
-                  max_batch: int = 8192, planner=None, **plan_kwargs) -> Tuple[torch.Tensor, Tuple[int, int]]:
+                  max_batch: int = 8192, planner=None, scenes=None, scene_of_context=None, **plan_kwargs) -> Tuple[torch.Tensor, Tuple[int, int]]:
     """Plan this rank's block of contexts.  start/goal: normalised [C_total, D] tables (identical on every rank).
     Returns (final trajectories [C_local*n_samples, H, D], (lo, hi) context range).  Contexts are processed in chunks of
     at most `max_batch` trajectories; the whole-tensor range test of the normaliser is evaluated per context
     (n_per_context=n_samples), as one reference run_inference call per context would.
-    `planner(hard_conds, B, n_per_context, **kw) -> x` defaults to model.plan (tests inject a stub)."""
+    `planner(hard_conds, B, n_per_context, **kw) -> x` defaults to model.plan (tests inject a stub).
+    scenes / scene_of_context (an extension; None = one obstacle scene, the path as it was): a planning.PlanningScenes and the scene of every one
+    of the C_total contexts (identical on every rank).  The `guide=` of plan_kwargs is then bound, chunk by chunk, to this rank's slice of the
+    assignment (GuideManagerTrajectoriesWithVelocity.with_scenes): contexts with different obstacles share one batch."""
     C_total = start.shape[0]
     lo, hi = shard_range(C_total, world_size, rank)
+    if scenes is not None:
+        if scene_of_context is None:
+            raise ValueError("scenes need scene_of_context (the scene of every context)")
+        scene_of_context = scenes.check_assignment(scene_of_context, C_total * n_samples, n_samples)
+        base_guide = plan_kwargs.get("guide")
+        if base_guide is None or not hasattr(base_guide, "with_scenes"):
+            raise ValueError("scenes differ in what the cost guide sees: pass guide=GuideManagerTrajectoriesWithVelocity(...)")
+    elif scene_of_context is not None:
+        raise ValueError("scene_of_context without scenes")
     H = plan_kwargs.pop("horizon", None)
     outs = []
     per_chunk = max(1, max_batch // n_samples)
@@ -48,6 +60,8 @@ def plan_contexts(model, start: torch.Tensor, goal: torch.Tensor, n_samples: int
         c1 = min(hi, c0 + per_chunk)
         hs, hg = expand_contexts(start[c0:c1], goal[c0:c1], n_samples)
         horizon_idx = (H or getattr(getattr(model, "model", None), "n_support_points", 64)) - 1
+        if scenes is not None:
+            plan_kwargs["guide"] = base_guide.with_scenes(scenes, scene_of_context[c0:c1], n_samples)
         outs.append(planner({0: hs, horizon_idx: hg}, (c1 - c0) * n_samples, n_samples, **plan_kwargs))
     if not outs:
         D = start.shape[1]

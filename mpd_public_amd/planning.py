@@ -362,6 +362,156 @@ class PlanningTask:
         return torch.tensor(lo[:qd], device=device), torch.tensor(hi[:qd], device=device)
 
 
+def _check_object_set(o, dim, what):
+    """An ObjectSet as the primitive tables need it: [n, 3] centres (unused axes zero), [n] positive radii, [n, 3] positive half extents."""
+    if not isinstance(o, ObjectSet):
+        raise TypeError(f"{what}: an ObjectSet is expected, got {type(o).__name__}")
+    sc, sr, bc, bh = (np.asarray(a, np.float32) for a in (o.sphere_centers, o.sphere_radii, o.box_centers, o.box_half))
+    if sc.ndim != 2 or sc.shape[1] != 3 or bc.ndim != 2 or bc.shape[1] != 3 or bh.shape != bc.shape or sr.shape != (sc.shape[0],):
+        raise ValueError(f"{what}: sphere_centers [n, 3], sphere_radii [n], box_centers / box_half [m, 3] (rows padded to 3-D) are expected, got "
+                         f"{sc.shape}, {sr.shape}, {bc.shape}, {bh.shape}")
+    if not (np.isfinite(sc).all() and np.isfinite(sr).all() and np.isfinite(bc).all() and np.isfinite(bh).all()):
+        raise ValueError(f"{what}: non-finite primitive")
+    if (sr <= 0).any() or (bh <= 0).any():
+        raise ValueError(f"{what}: radii and half extents must be positive")
+    if dim < 3 and (np.abs(sc[:, dim:]).max(initial=0.0) > 0 or np.abs(bc[:, dim:]).max(initial=0.0) > 0):
+        raise ValueError(f"{what}: a primitive of a {dim}-D workspace has a centre off the unused axes (wrong dimension)")
+
+
+class PlanningScenes:
+    """Several obstacle scenes of ONE task, for contexts that are planned and evaluated in one batch (an extension: the reference builds one
+    PlanningTask per run_inference call, inference.py:107-123).  Scene s is `task` with its extra-objects field replaced by `extra_objects[s]`
+    (an empty ObjectSet is a scene without extra obstacles) and, if `fixed_objects` is given, its fixed-objects field by `fixed_objects[s]`.
+    Workspace limits, the robot, the self-collision field and a signed-distance grid are the same in every scene (a grid stands for the fixed
+    environment: `fixed_objects` with a grid task raises ValueError).
+
+    The guide takes scenes through `GuideManagerTrajectoriesWithVelocity.with_scenes(scenes, scene_of_context, n_per_context)`, the metrics through
+    the methods below, which take the assignment per call: `scene_of_context[c]` is the scene of the c-th group of `n_per_context` consecutive
+    trajectories.  Both run the MULTI_SCENE instantiations of the HIP guide / metrics kernels on one blocked primitive table
+    (guides.build_device_params(scenes=...), layout in include/mpdx.h)."""
+
+    def __init__(self, task: PlanningTask, extra_objects, fixed_objects=None):
+        if task.df_collision_extra_objects is None:
+            raise ValueError("PlanningScenes replaces the task's extra-objects field: build the task with use_extra_objects=True")
+        extra_objects = list(extra_objects)
+        if not extra_objects:
+            raise ValueError("at least one scene")
+        dim = task.env.dim
+        for s, o in enumerate(extra_objects):
+            _check_object_set(o, dim, f"extra_objects[{s}]")
+        if fixed_objects is not None:
+            if task.df_collision_objects.kind == _lib.FIELD_GRID:
+                raise ValueError("the task's fixed field is a signed-distance grid, which every scene shares: fixed_objects cannot replace it")
+            fixed_objects = list(fixed_objects)
+            if len(fixed_objects) != len(extra_objects):
+                raise ValueError(f"{len(fixed_objects)} fixed object sets for {len(extra_objects)} scenes")
+            for s, o in enumerate(fixed_objects):
+                _check_object_set(o, dim, f"fixed_objects[{s}]")
+        self.task, self.extra_objects, self.fixed_objects = task, extra_objects, fixed_objects
+        self._gp = None
+        # sizes: what a workgroup stages must fit the kernels' table budget (the same rule the launchers apply)
+        staged = _lib.SCENE_HEADER_WORDS
+        for sets in (extra_objects, fixed_objects):
+            if sets is not None:
+                staged += 4 * max(len(o.sphere_radii) for o in sets) + 6 * max(len(o.box_centers) for o in sets)
+        if fixed_objects is None and task.df_collision_objects.kind == _lib.FIELD_OBJECTS:
+            o = task.df_collision_objects.objects
+            staged += 4 * len(o.sphere_radii) + 6 * len(o.box_centers)
+        if staged + 3 > _lib.SCENE_MAX_STAGED_FLOATS:
+            raise ValueError(f"a scene needs {staged} table floats; the kernels stage at most {_lib.SCENE_MAX_STAGED_FLOATS}")
+
+    @property
+    def n_scenes(self) -> int:
+        return len(self.extra_objects)
+
+    def objects_for(self, field):
+        """The per-scene ObjectSets that stand for `field` of the task (None: the field is the same in every scene)."""
+        if field is self.task.df_collision_extra_objects:
+            return self.extra_objects
+        if self.fixed_objects is not None and field is self.task.df_collision_objects:
+            return self.fixed_objects
+        return None
+
+    def scene_task(self, s: int) -> PlanningTask:
+        """Scene s as a single-scene PlanningTask (what one call per scene would use; the tests' reference)."""
+        import copy
+        t = copy.copy(self.task)
+        t._gp = None
+        t.df_collision_extra_objects = CollisionField(_lib.FIELD_OBJECTS, objects=self.extra_objects[s], name="extra_objects")
+        if self.fixed_objects is not None:
+            t.df_collision_objects = CollisionField(_lib.FIELD_OBJECTS, objects=self.fixed_objects[s], name="objects")
+        return t
+
+    def check_assignment(self, scene_of_context, n_trajs, n_per_context):
+        """scene_of_context as a host int list, validated against the scenes and the batch: one entry per context, each in [0, n_scenes)."""
+        npc = int(n_per_context)
+        if npc <= 0:
+            raise ValueError(f"n_per_context={n_per_context}")
+        soc = [int(v) for v in (scene_of_context.tolist() if hasattr(scene_of_context, "tolist") else scene_of_context)]
+        if n_trajs is not None:
+            if n_trajs % npc:
+                raise ValueError(f"{n_trajs} trajectories are not a multiple of n_per_context={npc}")
+            if len(soc) != n_trajs // npc:
+                raise ValueError(f"scene_of_context has {len(soc)} entries for {n_trajs // npc} contexts of {npc} trajectories")
+        bad = [v for v in soc if not 0 <= v < self.n_scenes]
+        if bad:
+            raise ValueError(f"scene_of_context entries {bad} outside [0, {self.n_scenes})")
+        return soc
+
+    @staticmethod
+    def bind(gp, scene_of_context, n_per_context, device):
+        """A copy of the parameter block `gp` bound to one assignment: (params, device index table - keep it alive as long as the params)."""
+        table = torch.tensor(scene_of_context, dtype=torch.int32, device=device)
+        out = type(gp).from_buffer_copy(gp)
+        out.scene_of_ctx, out.scene_n_per_ctx = table.data_ptr(), int(n_per_context)
+        return out, table
+
+    def _params(self, device):
+        if self._gp is None or self._gp_prims.device != torch.device(device):
+            from .guides import build_device_params
+            costs = [CostCollision(self.task.robot, 64, field=f) for f in self.task.get_collision_fields()]
+            self._gp, self._gp_prims = build_device_params(self.task.robot, self.task.env.dim, self.task.obstacle_cutoff_margin, None, None, costs,
+                                                           [1.0] * len(costs), True, 128, True, 1.0, device, scenes=self)
+            self._gp_grids = self._gp.grids_tensor
+        return self._gp
+
+    # ---- the metrics of PlanningTask with a scene per context; arithmetic in csrc/guide.hpp::traj_metrics_kernel<..., MULTI_SCENE>
+    def trajectory_metrics(self, trajs, scene_of_context, n_per_context, n_check=None, return_mask=False):
+        """PlanningTask.trajectory_metrics where the c-th group of n_per_context trajectories is checked against scene scene_of_context[c]."""
+        import ctypes as C
+        trajs = trajs.to(torch.float32).contiguous()
+        if not trajs.is_cuda:
+            raise RuntimeError("trajectory metrics run on the GPU (libmpdx); there is no CPU fallback")
+        B, H, D = trajs.shape
+        soc = self.check_assignment(scene_of_context, B, n_per_context)
+        n_check = int(n_check or 4 * H)
+        out = torch.empty((B, 4), dtype=torch.float32, device=trajs.device)
+        mask = torch.empty((B, n_check), dtype=torch.uint8, device=trajs.device) if return_mask else None
+        gp, table = self.bind(self._params(trajs.device), soc, n_per_context, trajs.device)
+        _lib.check(_lib.load().mpdx_traj_metrics_mask(C.byref(gp), trajs.data_ptr(), out.data_ptr(), mask.data_ptr() if return_mask else None,
+                                                      n_check, B, H, D, _lib.current_stream()), "mpdx_traj_metrics_mask")
+        table.record_stream(torch.cuda.current_stream())   # (the launch is asynchronous: the allocator must not hand the table out before it ran)
+        return (out, mask.bool()) if return_mask else out
+
+    def get_trajs_collision_and_free(self, trajs, scene_of_context, n_per_context, return_indices=False, **kw):
+        m = self.trajectory_metrics(trajs, scene_of_context, n_per_context)
+        coll = m[:, 0] > 0
+        idx_c, idx_f = torch.nonzero(coll).flatten(), torch.nonzero(~coll).flatten()
+        tc = trajs[idx_c] if idx_c.numel() else None
+        tf = trajs[idx_f] if idx_f.numel() else None
+        if return_indices:
+            return tc, idx_c, tf, idx_f, None
+        return tc, tf
+
+    def compute_fraction_free_trajs(self, trajs, scene_of_context, n_per_context, **kw):
+        m = self.trajectory_metrics(trajs, scene_of_context, n_per_context)
+        return float((m[:, 0] == 0).float().mean())
+
+    def compute_collision_intensity_trajs(self, trajs, scene_of_context, n_per_context, **kw):
+        m = self.trajectory_metrics(trajs, scene_of_context, n_per_context)
+        return float((m[:, 0] / m[:, 3]).mean())
+
+
 def task_from_torch_robotics(tr_task, tensor_args=None, use_extra_objects=True) -> PlanningTask:
     """Adapter: a REAL `torch_robotics.tasks.tasks.PlanningTask` (what `inference.py:161,181,191-201` builds) -> this package's `PlanningTask`, i.e. the
     primitive tables the guide / metrics kernels read.  torch_robotics is an empty submodule in the reference checkout (`deps/torch_robotics`,
