@@ -432,6 +432,13 @@ int mpdx_bench_layer(mpdx_unet* u, const float* packed_dev, const float* timetab
                      float* ws, void* stream, int reps, int dbg, float* ms_per_launch);
 /* tile the dispatcher picks for launch i at batch B: writes "MTxNT/WNxWK" into buf */
 int mpdx_unet_layer_tile(const mpdx_unet* u, int i, int B, char* buf, size_t buflen);
+/* dev / test entry: ONE Residual(PreNorm(C, LinearAttention(C))) block (layers.py:174-226) outside a network, in place on x [B][L][C]
+ * (channel-last; rows Lv..L-1 of each trajectory zero on entry and on return: a horizon of Lv positions in its power-of-two container L).
+ * Parameters in state-dict layout: to_qkv.weight [384,C,1], to_out.weight [C,128,1], to_out.bias [C], norm.g / norm.b [1,C,1].  Runs what a
+ * network runs (the same weight packing, layer description and launch); MPDX_E_INVALID, before any launch, for every (C, L) that
+ * mpdx_unet_create refuses for a self-attention level.  Synchronises the stream. */
+int mpdx_attention_block(float* x, const float* to_qkv_w, const float* to_out_w, const float* to_out_b, const float* norm_g, const float* norm_b,
+                         int B, int L, int Lv, int C, void* stream);
 
 #ifdef __cplusplus
 }

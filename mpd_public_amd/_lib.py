@@ -110,6 +110,7 @@ SIGNATURES = {
     "mpdx_unet_fused_program": (_i, [_vp, _i]),
     "mpdx_bench_layer": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, C.POINTER(C.c_float)]),
     "mpdx_unet_layer_tile": (_i, [_vp, _i, _i, C.c_char_p, _sz]),
+    "mpdx_attention_block": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mpdx_randn": (_i, [_vp, _sz, C.c_uint64, C.c_uint64, _vp]),
     "mpdx_train_flat_floats": (_sz, [_vp]),
     "mpdx_train_dgrad_pack_floats": (_sz, [_vp]),

@@ -1903,5 +1903,41 @@ int mpdx_randn(float* out, size_t n, uint64_t seed, uint64_t offset, void* strea
     return 0;
 }
 
+// dev entry: ONE Residual(PreNorm(LinearAttention)) block on a caller-owned activation, through the code a network runs (pack_conv_weights_kernel,
+// a Layer filled as build_model's `attention` lambda fills it, launch_attention).  Synchronises the stream (it frees its packed weights).
+int mpdx_attention_block(float* x, const float* to_qkv_w, const float* to_out_w, const float* to_out_b, const float* norm_g, const float* norm_b,
+                         int B, int L, int Lv, int C, void* stream) {
+    if (!x || !to_qkv_w || !to_out_w || !to_out_b || !norm_g || !norm_b) return fail(MPDX_E_INVALID, "null argument");
+    if (B <= 0) return fail(MPDX_E_INVALID, "batch must be positive");
+    if (const char* why = attn_unsupported(C, L)) return fail(MPDX_E_INVALID, "self-attention block (%d channels on %d positions): %s", C, L, why);
+    if (Lv < 1 || Lv > L) return fail(MPDX_E_INVALID, "valid positions must be in [1, %d]", L);
+    hipStream_t st = (hipStream_t)stream;
+    Layer l;
+    l.name = "mpdx_attention_block"; l.attn = true; l.mode = CONV_S1; l.ks = 0; l.epi = EPI_BIAS;
+    l.c1 = C; l.cout = C; l.L_in = L; l.L_out = L;
+    l.Lv_out = Lv != L ? Lv : 0;
+    l.cin_pad = pad_cin(C);
+    l.rs = pick_row_stride(l.cin_pad, CONV_S1, L, L, L);
+    const int hid_pad = pad_cin(kAttnHid);
+    const size_t n_qkv = (size_t)(3 * kAttnHid / 16) * (l.cin_pad / 16) * 256, n_out = (size_t)(C / 16) * (hid_pad / 16) * 256;
+    float* packed = nullptr;
+    HIP_TRY(hipMalloc(&packed, (n_qkv + n_out) * sizeof(float)));
+    hipLaunchKernelGGL(pack_conv_weights_kernel, dim3((unsigned)std::min<size_t>((n_qkv + 255) / 256, 2048)), dim3(256), 0, st, to_qkv_w, packed,
+                       3 * kAttnHid, C, 1, l.cin_pad, 1, 0);
+    hipLaunchKernelGGL(pack_conv_weights_kernel, dim3((unsigned)std::min<size_t>((n_out + 255) / 256, 2048)), dim3(256), 0, st, to_out_w, packed + n_qkv,
+                       C, kAttnHid, 1, hid_pad, 1, 0);
+    AttnArgs aa;
+    memset(&aa, 0, sizeof(aa));
+    aa.x = x; aa.wqkv = packed; aa.wout = packed + n_qkv; aa.bout = to_out_b; aa.g = norm_g; aa.b = norm_b;
+    int rc = launch_attention(l, aa, B, st);
+    hipError_t e = hipGetLastError();
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(packed);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail((int)e, "mpdx_attention_block: %s", hipGetErrorString(e));
+    return 0;
+}
+
 }  // extern "C"
 

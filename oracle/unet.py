@@ -2,8 +2,9 @@
 
 State-dict driven restatement of mpd/models/diffusion_models/temporal_unet.py:118-171 with the building
 blocks of mpd/models/layers/layers.py (TimeEncoder :229-240, SinusoidalPosEmb :243-255, Downsample1d :258-264,
-Upsample1d :267-273, Conv1dBlock :276-293, ResidualTemporalBlock :323-355, group_norm_n_groups :389-395) for the
-only configuration any reference script builds: conditioning_type=None, self_attention=False.
+Upsample1d :267-273, Conv1dBlock :276-293, ResidualTemporalBlock :323-355, group_norm_n_groups :389-395, and the
+Residual(PreNorm(LinearAttention)) block :174-226 of a self_attention=True network) for conditioning_type=None.  The self-attention
+blocks run wherever the state dict carries their keys (downs.i.2, mid_attn, ups.j.2); a plain state dict runs the network without them.
 """
 import math
 
@@ -62,6 +63,34 @@ def residual_temporal_block(sd: dict, p: str, x: torch.Tensor, temb: torch.Tenso
     return h + res
 
 
+def layer_norm_channels(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
+    # layers.py:201-204: over the channels of every position, biased variance, affine g / b of shape [1,C,1]
+    var = torch.var(x, dim=1, unbiased=False, keepdim=True)
+    mean = torch.mean(x, dim=1, keepdim=True)
+    return (x - mean) / (var + eps).sqrt() * g + b
+
+
+ATTN_HEADS, ATTN_DIM_HEAD = 4, 32   # LinearAttention's defaults (layers.py:208), the only values temporal_unet.py builds
+
+
+def linear_attention_block(sd: dict, p: str, x: torch.Tensor) -> torch.Tensor:
+    """x [B,C,L] -> Residual(PreNorm(C, LinearAttention(C)))(x), parameters `p`.fn.norm.{g,b}, `p`.fn.fn.{to_qkv,to_out}.  layers.py:174-226."""
+    B, _, L = x.shape
+    xn = layer_norm_channels(x, sd[p + ".fn.norm.g"], sd[p + ".fn.norm.b"])  # PreNorm :189-191
+    qkv = F.conv1d(xn, sd[p + ".fn.fn.to_qkv.weight"])  # 1x1, no bias :213,217
+    q, k, v = (a.reshape(B, ATTN_HEADS, ATTN_DIM_HEAD, L) for a in qkv.chunk(3, dim=1))  # 'b (h c) d -> b h c d' :218
+    q = q * ATTN_DIM_HEAD ** -0.5  # :219
+    k = k.softmax(dim=-1)  # over the positions :221
+    context = torch.einsum("bhdn,bhen->bhde", k, v)  # :222
+    out = torch.einsum("bhde,bhdn->bhen", context, q).reshape(B, ATTN_HEADS * ATTN_DIM_HEAD, L)  # :224-225
+    return F.conv1d(out, sd[p + ".fn.fn.to_out.weight"], sd[p + ".fn.fn.to_out.bias"]) + x  # :226, Residual :180
+
+
+def _self_attention(sd: dict, p: str, x: torch.Tensor) -> torch.Tensor:
+    # nn.Identity when the network was built with self_attention=False (temporal_unet.py:82,93,104)
+    return linear_attention_block(sd, p, x) if (p + ".fn.fn.to_qkv.weight") in sd else x
+
+
 def n_resolutions(sd: dict) -> int:
     n = 0
     while f"downs.{n}.0.blocks.0.block.0.weight" in sd:
@@ -78,23 +107,27 @@ def unet_forward(sd: dict, x: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
     for i in range(nres):  # :141-150
         h = residual_temporal_block(sd, f"downs.{i}.0", h, temb)
         h = residual_temporal_block(sd, f"downs.{i}.1", h, temb)
+        h = _self_attention(sd, f"downs.{i}.2", h)  # :146, before the skip is pushed
         skips.append(h)
         if i < nres - 1:  # Downsample1d, Identity on the last level
             h = F.conv1d(h, sd[f"downs.{i}.4.conv.weight"], sd[f"downs.{i}.4.conv.bias"], stride=2, padding=1)
     h = residual_temporal_block(sd, "mid_block1", h, temb)  # :152-156
+    h = _self_attention(sd, "mid_attn", h)  # :153
     h = residual_temporal_block(sd, "mid_block2", h, temb)
     for j in range(nres - 1):  # :158-165; every up stage upsamples, the level-0 skip is never popped
         h = torch.cat((h, skips.pop()), dim=1)
         h = residual_temporal_block(sd, f"ups.{j}.0", h, temb)
         h = residual_temporal_block(sd, f"ups.{j}.1", h, temb)
+        h = _self_attention(sd, f"ups.{j}.2", h)  # :162
         h = F.conv_transpose1d(h, sd[f"ups.{j}.4.conv.weight"], sd[f"ups.{j}.4.conv.bias"], stride=2, padding=1)
     h = conv1d_block(sd, "final_conv.0", h)  # :167
     h = F.conv1d(h, sd["final_conv.1.weight"], sd["final_conv.1.bias"])
     return h.transpose(1, 2)  # :169
 
 
-def unet_param_shapes(state_dim: int, unet_input_dim: int = 32, dim_mults=(1, 2, 4, 8), time_emb_dim: int = 32) -> dict:
-    """name -> shape of every TemporalUnet parameter (the module tree of temporal_unet.py:60-116)."""
+def unet_param_shapes(state_dim: int, unet_input_dim: int = 32, dim_mults=(1, 2, 4, 8), time_emb_dim: int = 32,
+                      self_attention: bool = False) -> dict:
+    """name -> shape of every TemporalUnet parameter (the module tree of temporal_unet.py:60-116), in state_dict() order."""
     dims = [state_dim] + [unet_input_dim * m for m in dim_mults]
     in_out = list(zip(dims[:-1], dims[1:]))
     shapes = {
@@ -117,19 +150,32 @@ def unet_param_shapes(state_dim: int, unet_input_dim: int = 32, dim_mults=(1, 2,
             shapes[p + ".residual_conv.weight"] = (co, ci, 1)
             shapes[p + ".residual_conv.bias"] = (co,)
 
+    def attn(p, c):
+        if not self_attention:
+            return
+        hid = ATTN_HEADS * ATTN_DIM_HEAD
+        shapes[p + ".fn.fn.to_qkv.weight"] = (3 * hid, c, 1)
+        shapes[p + ".fn.fn.to_out.weight"] = (c, hid, 1)
+        shapes[p + ".fn.fn.to_out.bias"] = (c,)
+        shapes[p + ".fn.norm.g"] = (1, c, 1)
+        shapes[p + ".fn.norm.b"] = (1, c, 1)
+
     nres = len(in_out)
     for i, (ci, co) in enumerate(in_out):
         rtb(f"downs.{i}.0", ci, co)
         rtb(f"downs.{i}.1", co, co)
+        attn(f"downs.{i}.2", co)
         if i < nres - 1:
             shapes[f"downs.{i}.4.conv.weight"] = (co, co, 3)
             shapes[f"downs.{i}.4.conv.bias"] = (co,)
     mid = dims[-1]
     rtb("mid_block1", mid, mid)
+    attn("mid_attn", mid)
     rtb("mid_block2", mid, mid)
     for j, (ci, co) in enumerate(reversed(in_out[1:])):
         rtb(f"ups.{j}.0", co * 2, ci)
         rtb(f"ups.{j}.1", ci, ci)
+        attn(f"ups.{j}.2", ci)
         shapes[f"ups.{j}.4.conv.weight"] = (ci, ci, 4)  # ConvTranspose1d: [C_in, C_out, k]
         shapes[f"ups.{j}.4.conv.bias"] = (ci,)
     cblock("final_conv.0", unet_input_dim, unet_input_dim)
