@@ -8,7 +8,7 @@
 // divisions by runtime widths).  The host's buffer placement for the standard networks never changes, so it is written down here;
 // every LDS address of a static program becomes `lane base + immediate`.
 //
-// Safety.  The host still COMPUTES the geometry (build_fused_segment, mpdx.hip: live-range placement, bank-conflict-searched row
+// Safety.  The host still COMPUTES the geometry (SegmentBuilder, fused_build.hpp: live-range placement, bank-conflict-searched row
 // strides) and compares every field with the table of the program it matched (fused_geom_matches); on any difference the segment
 // runs on the generic op-list kernel with runtime descriptors - slower, never wrong (tests/test_abi_cpu.py asserts that the
 // standard networks do get the static programs).  To regenerate a table: MPDX_DEBUG_FUSE=2 prints it in this initialiser form.

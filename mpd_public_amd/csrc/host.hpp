@@ -1,6 +1,7 @@
 // host.hpp - the host-side model (layer plan, parameter table, fused segments) and the launcher interface between the translation
-// units of libmpdx.so.  The library is built from one host TU (mpdx.hip: model building, the planning loop, the C ABI, the small
-// streaming kernels) and one TU per kernel family - k_conv.hip (conv_block.hpp), k_ws.hip (conv_ws.hpp), k_fused.hip /
+// units of libmpdx.so.  The library is built from one host TU (mpdx.hip: model building, tile choice and the launch units of a pass, the
+// planning loop, the C ABI, the small streaming kernels; it alone includes fused_build.hpp - the fused-segment builder and build_units - and
+// unet_measure.hpp - the timing / trace entry points and the launch-unit queries) and one TU per kernel family - k_conv.hip (conv_block.hpp), k_ws.hip (conv_ws.hpp), k_fused.hip /
 // k_fused_train.hip (fused_level.hpp), k_guide.hip (guide.hpp), k_attn.hip (attn.hpp), k_train.hip (train.hpp + train_host.hpp), k_planner.hip
 // (planner.hpp + planner_host.hpp) - so that an edit to one kernel family recompiles that family only (mpd_public_amd/build.py
 // compiles the TUs in parallel and keeps the objects).  A kernel template is instantiated in exactly ONE TU, behind a plain function
@@ -37,6 +38,7 @@ int fail(int code, const char* fmt, ...);
         if (e_ != hipSuccess) return ::mpdx::fail((int)e_, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 int raise_lds_limit(const void* kern);   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel)
+int dev_hooks_missing(const char* fn);   // 0 in a development build (-DMPDX_DEV_HOOKS); else the MPDX_E_STATE error of a trace / ablation entry point
 
 // final_conv[1] (Conv1d(32 -> D, k=1), temporal_unet.py:113-116) fused with the DDPM posterior step
 // (diffusion_model_base.py:121-155, sample_functions.py:31-62) and hard conditioning (sample_functions.py:5-8).
@@ -138,9 +140,6 @@ struct mpdx_unet {
     int pack_version = 0, streams_version = -1;
     struct Unit { int fused; int layer; bool pair; };   // fused >= 0: fused[fused]; else layers[layer] (pair: + layers[layer+1] in one launch)
     std::vector<int> owner;                  // layer -> fused segment (-1: per-layer launch)
-    // mpdx_plan's second chain (small batches run as two concurrent half-batch chains): side stream + fork / join events, created on first use
-    struct PlanSide { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
-    PlanSide side;
     // training (train_host.hpp)
     struct TrainLayer {
         int src1_l = -2, src2_l = -2, res_l = -2;   // layer that produced the tensor (-1: the network input, -2: none)

@@ -170,10 +170,7 @@ int mpdx_guide_time(const mpdx_guide_params* gp, float* x, float* grad_out, cons
 
 /* dev tool: one guide launch with s_memtime stamps (16 slots per wave, 8 waves -> 128 values) of workgroup 0 */
 int mpdx_guide_trace(const mpdx_guide_params* gp, float* x, const uint32_t* absmax_in, int B, int H, int D, void* stream, long long* stamps64) {
-#ifndef MPDX_DEV_HOOKS
-    return fail(MPDX_E_STATE, "%s needs a development build of libmpdx.so (MPDX_BUILD_DEFS=-DMPDX_DEV_HOOKS MPDX_BUILD_OUT=build_ab/libmpdx_dev.so python -m mpd_public_amd.build, then MPDX_LIB=build_ab/libmpdx_dev.so): "
-                "the production kernels carry no trace / ablation hooks", __func__);
-#endif
+    if (int rc = dev_hooks_missing(__func__)) return rc;
     if (!stamps64) return fail(MPDX_E_INVALID, "null argument");
     hipStream_t st = (hipStream_t)stream;
     long long* dev = nullptr;

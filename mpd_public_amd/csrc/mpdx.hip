@@ -1,4 +1,5 @@
-// mpdx.hip - libmpdx.so: host-side layer plan + C ABI (include/mpdx.h) + the small streaming kernels.
+// mpdx.hip - libmpdx.so: host-side layer plan, the launch units of a U-Net pass, the planning loop, the C ABI (include/mpdx.h) + the small streaming
+// kernels.  Two host headers are this file's alone: fused_build.hpp (the whole-trajectory programs' descriptors), unet_measure.hpp (timing / trace entries).
 //
 // gfx950 only.  No CUDA shims, no dual paths.  All device memory is caller-owned; nothing here synchronises.
 #include "host.hpp"
@@ -33,7 +34,6 @@ int raise_lds_limit(const void* kern) {
 }
 
 static long long* g_conv_trace = nullptr;   // dev tool (mpdx_layer_trace)
-static thread_local int g_plan_chains = 1;  // > 1 while mpdx_plan enqueues a plan as that many concurrent sub-batch chains (tile choice)
 
 // ------------------------------------------------------------------------------------------------ small kernels
 
@@ -270,13 +270,7 @@ __global__ void pack_conv_weights_kernel(const float* __restrict__ src, float* _
     }
 }
 
-
 // ------------------------------------------------------------------------------------------------ host-side model
-
-}  // namespace mpdx
-
-
-namespace mpdx {
 
 static int gn_groups(int c) {  // layers.py:389-395
     if (c < 8) return 1;
@@ -481,410 +475,11 @@ static void build_model(mpdx_unet* u) {
     if (H != Hv) u->xpad_slot = u->n_slots++;   // one more workspace slot: the padded copy of the network input
 }
 
-// ------------------------------------------------------------------------------------------------ fused segments
-// Try to turn layers [i0, i1) (an outer U-Net level: 2 residual blocks + resample [+ final_conv[0]]) into one
-// fused_level_kernel program.  Returns false (and leaves the per-layer path) if any shape constraint fails.
-// MPDX_DEBUG_FUSE: 0 not set, 1 set (the segments built and the shape constraint that rejected one), 2 a value >= 2 (their LDS geometry too)
-static int debug_fuse_level() {
-    const char* e = sw::debug_fuse();
-    return !e ? 0 : (atoi(e) >= 2 ? 2 : 1);
-}
-static bool fuse_reject(int line) {
-    if (debug_fuse_level()) fprintf(stderr, "[mpdx] fused segment rejected at mpdx.hip:%d\n", line);
-    return false;
-}
+}  // namespace mpdx
 
-struct HostBuf { int off4 = -1, rs4 = 0, rows = 0; size_t size4 = 0; int def = 1 << 30, last = -1; };
+#include "fused_build.hpp"   // build_units: which layer ranges run as whole-trajectory programs, and their descriptors
 
-static bool build_fused_segment(mpdx_unet* u, int i0, int i1, bool with_final) {
-    mpdx_unet::Fused f;
-    f.first = i0; f.count = i1 - i0; f.has_final = with_final;
-    FusedArgs& a = f.tmpl;
-    memset(&a, 0, sizeof(a));
-    const Layer& l0 = u->layers[i0];
-    f.in1 = l0.src1; f.in2 = l0.src2;
-    a.gc1 = l0.c1; a.gc2 = l0.c2; a.L0 = l0.L_in;
-    std::vector<HostBuf> bufs;
-    std::unordered_map<long, int> bufmap;  // (slot, L) -> LDS buffer
-    // LDS activation buffers are placed AFTER the op list is known, by live range [first write, last read] in op indices
-    // (-1 = staged by the prologue): buffers whose ranges do not intersect share addresses.
-    auto new_buf = [&](int cpad, int L) {
-        HostBuf hb;
-        const int rs = pick_row_stride(cpad, CONV_S1, L, L, L + 4);
-        hb.rs4 = rs / 4; hb.rows = L + 4; hb.size4 = (size_t)(L + 4) * (rs / 4);
-        bufs.push_back(hb);
-        return (int)bufs.size() - 1;
-    };
-    auto touch = [&](int id, int opi, bool write) {
-        if (id < 0) return;
-        if (write) bufs[id].def = std::min(bufs[id].def, opi);
-        bufs[id].last = std::max(bufs[id].last, opi);
-    };
-    int in_buf = -1;
-    bool in_slot_rewritten = false;   // a layer of the segment has written the workspace slot the segment's input came in
-    // the LDS buffer a layer writes its output (workspace slot `slot`, L positions) to.  A slot written again with the same shape re-uses its buffer (the
-    // blocks' HB / RB temporaries, an up level's second block writing the slot the level's input came in) - except a buffer too narrow for it (three-level
-    // network, round 6: mid_block1's 128 channels go to the slot downs.1's Downsample1d output - the segment input, 64 channels - came in): a buffer of its own
-    auto buf_for = [&](int slot, int L, int cpad) {
-        const long key = (long)(slot + 8) * 4096 + L;
-        auto it = bufmap.find(key);
-        if (it != bufmap.end()) {
-            const int rs = pick_row_stride(cpad, CONV_S1, L, L, L + 4);
-            if (it->second == in_buf) in_slot_rewritten = true;   // (src_buf: from here on that slot is a tensor of the segment, no longer its input)
-            if (bufs[it->second].rs4 >= rs / 4) return it->second;
-        }
-        const int id = new_buf(cpad, L);
-        bufmap[key] = id;
-        return id;
-    };
-    in_buf = new_buf(l0.cin_pad, l0.L_in);
-    a.in_clear = (l0.cin_pad != l0.c1 + l0.c2) ? 1 : 0;  // channel padding of the staged input
-    touch(in_buf, -1, true);
-    bufmap[(long)(l0.src1 + 8) * 4096 + l0.L_in] = in_buf;
-    int cat_buf = -1;    // buffer whose tail columns hold a skip tensor staged by the prologue (concat inside the program)
-    auto src_buf = [&](const Layer& l, int i) -> int {   // LDS buffer a layer reads (-1: not available inside the segment)
-        if (i == i0 || (!in_slot_rewritten && l.src1 == l0.src1 && l.src2 == l0.src2 && l.L_in == l0.L_in)) return in_buf;
-        const long key = (long)(l.src1 + 8) * 4096 + l.L_in;
-        if (!bufmap.count(key)) return -1;
-        if (l.src2 != SRC_NONE) {   // cat(x produced in LDS, skip from global): the producer's buffer was made wide enough (below)
-            if (bufmap[key] != cat_buf || f.in3 != l.src2) return -1;
-        }
-        return bufmap[key];
-    };
-    // a layer of the segment (not the first) that concatenates a global skip tensor behind a tensor produced inside
-    auto cat_consumer = [&](int from, int slot, int L) -> const Layer* {
-        for (int k = from; k < i1; ++k) {
-            const Layer& n = u->layers[k];
-            if (n.src1 == slot && n.L_in == L && n.src2 != SRC_NONE && !(n.src1 == l0.src1 && n.src2 == l0.src2)) return &n;
-            if (n.dst == slot) break;   // overwritten: later readers see another tensor
-        }
-        return nullptr;
-    };
-    struct HostOp { int src = -1, rsrc = -1, res = -1, dst = -1; const Layer* l = nullptr; const Layer* r = nullptr; int nblk = 0, ncr = 0, tot = 0, nstream = 0; };
-    std::vector<HostOp> hops;
-    int ng = 0;
-    int pending_res = -1;   // index of a residual 1x1 conv waiting to be folded into the block's blocks[1]
-    for (int i = i0; i < i1; ++i) {
-        const Layer& l = u->layers[i];
-        // a block's residual 1x1 conv is folded into blocks[1] (the next layer, which adds its output after Mish)
-        if (l.mode == CONV_S1 && l.ks == 1 && l.epi == EPI_BIAS && i + 1 < i1 && u->layers[i + 1].res == l.dst &&
-            u->layers[i + 1].epi == EPI_GN_MISH && u->layers[i + 1].L_out == l.L_out && u->layers[i + 1].cout == l.cout) {
-            pending_res = i;
-            continue;
-        }
-        if (a.nops >= kMaxFusedOps - (with_final ? 1 : 0)) return fuse_reject(__LINE__);
-        FusedOp& op = a.ops[a.nops];
-        memset(&op, 0, sizeof(op));
-        HostOp ho;
-        ho.l = &l;
-        const int gn = l.epi == EPI_GN_MISH ? 1 : 0;
-        if (gn && (l.gs * 8 != l.cout || l.mode != CONV_S1)) return fuse_reject(__LINE__);   // the shapes assume GroupNorm(8 groups)
-        ho.src = src_buf(l, i);
-        if (ho.src < 0) return fuse_reject(__LINE__);
-        if (pending_res >= 0) {
-            ho.r = &u->layers[pending_res];
-            ho.rsrc = src_buf(*ho.r, pending_res);
-            if (ho.rsrc < 0) return fuse_reject(__LINE__);
-            pending_res = -1;
-        } else if (l.res != SRC_NONE) {
-            const long key = (long)(l.res + 8) * 4096 + l.L_out;
-            if (!bufmap.count(key)) return fuse_reject(__LINE__);
-            ho.res = bufmap[key];
-        }
-        const int nc16 = l.cin_pad / 16, rnc16 = ho.r ? ho.r->cin_pad / 16 : 0;
-        op.shape = fused_shape_id(l.mode, l.ks, nc16, rnc16, l.cout, l.L_out, gn);
-        if (op.shape < 0) return fuse_reject(__LINE__);
-        ho.nblk = nc16 * (l.mode == CONV_UPT ? 2 : l.ks); ho.ncr = rnc16; ho.tot = ho.nblk + ho.ncr;
-        ho.nstream = (l.cout / 16) * (l.mode == CONV_UPT ? 2 : 1);
-        const int msn = l.cout / 16, msw = std::min(msn, kFusedWaves), mp = msn / msw;   // tile rows, rows in flight, M-passes (FusedShape)
-        a.msmask[a.nops] = msw - 1;
-        a.slen[a.nops] = ho.tot * (l.mode == CONV_UPT ? 2 : mp);
-        // destination: LDS if a later layer of the segment (or the final op) reads it; global if someone outside does
-        bool read_inside = with_final && i == i1 - 1;
-        for (int k = i + 1; k < i1; ++k) {
-            const Layer& n = u->layers[k];
-            if ((n.src1 == l.dst && n.L_in == l.L_out) || (n.res == l.dst && n.L_out == l.L_out)) read_inside = true;
-            if (n.dst == l.dst) break;  // overwritten
-        }
-        bool read_outside = false;
-        bool overwritten_inside = false;  // the slot is re-used by a later layer of this segment: this value never leaves
-        for (int k = i + 1; k < i1; ++k)
-            if (u->layers[k].dst == l.dst) { overwritten_inside = true; break; }
-        for (size_t k = i1; k < u->layers.size() && !overwritten_inside; ++k) {
-            const Layer& n = u->layers[k];
-            if (n.src1 == l.dst || n.src2 == l.dst || n.res == l.dst) { read_outside = true; break; }
-            if (n.dst == l.dst) break;
-        }
-        if (i == i1 - 1 && !with_final) read_outside = true;
-        if (read_inside) {
-            const Layer* cc = cat_consumer(i + 1, l.dst, l.L_out);
-            if (cc) {   // this op's output is the head of a concat: make the buffer wide enough for the skip tensor behind it
-                if (cat_buf >= 0 || cc->c1 != l.cout || (cc->c2 & 3) || (l.cout & 3) || (size_t)cc->L_in * (cc->c2 / 4) > 1024) {
-                    if (debug_fuse_level()) fprintf(stderr, "[mpdx] cat: layer %s -> %s cat_buf %d c1 %d c2 %d cout %d L %d\n", l.name.c_str(), cc->name.c_str(), cat_buf, cc->c1, cc->c2, l.cout, cc->L_in);
-                    return fuse_reject(__LINE__);
-                }
-                ho.dst = buf_for(l.dst, l.L_out, cc->c1 + cc->c2);
-                cat_buf = ho.dst;
-                f.in3 = cc->src2;
-                f.in3_consumer = (int)(cc - &u->layers[0]);
-                a.c3 = cc->c2; a.L3 = cc->L_in; a.s3_col4 = cc->c1 / 4;
-                touch(cat_buf, -1, true);   // its skip columns are written by the prologue: live from the start
-            } else ho.dst = buf_for(l.dst, l.L_out, l.cout);
-        } else ho.dst = -1;
-        if (ho.dst >= 0 && (ho.dst == ho.src || ho.dst == ho.res || ho.dst == ho.rsrc)) return fuse_reject(__LINE__);
-        op.gdst = -1;
-        if (read_outside) {
-            if (ng >= 3) return fuse_reject(__LINE__);
-            f.gout_slot[ng] = l.dst;
-            op.gdst = ng++;
-        }
-        touch(ho.src, a.nops, false); touch(ho.res, a.nops, false); touch(ho.rsrc, a.nops, false); touch(ho.dst, a.nops, true);
-        hops.push_back(ho);
-        f.op_layer.push_back(i);
-        a.nops++;
-    }
-    if (pending_res >= 0) return fuse_reject(__LINE__);
-    int final_src = -1;
-    if (with_final) {
-        const Layer& lf = u->layers[i1 - 1];
-        FusedOp& op = a.ops[a.nops++];
-        memset(&op, 0, sizeof(op));
-        op.shape = kFusedShapeFinal;
-        final_src = bufmap[(long)(lf.dst + 8) * 4096 + lf.L_out];
-        touch(final_src, a.nops - 1, false);
-        a.H = lf.L_out;
-        a.Cf = u->cfg.unet_input_dim; a.D = u->cfg.state_dim;
-        a.fw_off = (int)u->params[u->pidx.at("final_conv.1.weight")].off;
-        a.fb_off = (int)u->params[u->pidx.at("final_conv.1.bias")].off;
-    }
-    size_t off4 = 0;
-    {   // first-fit placement in order of definition; two buffers may share addresses iff one is dead strictly before the
-        // op that first writes the other
-        const int nbuf = (int)bufs.size();
-        std::vector<int> order(nbuf);
-        for (int i = 0; i < nbuf; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](int x, int y) { return bufs[x].def < bufs[y].def; });
-        for (int oi = 0; oi < nbuf; ++oi) {
-            HostBuf& bi = bufs[order[oi]];
-            if (bi.last < bi.def) bi.last = bi.def;
-            size_t cand = 0;
-            for (bool moved = true; moved;) {
-                moved = false;
-                for (int oj = 0; oj < oi; ++oj) {
-                    const HostBuf& bj = bufs[order[oj]];
-                    const bool live_overlap = !(bj.last < bi.def || bi.last < bj.def);
-                    const size_t lo = (size_t)bj.off4, hi = lo + bj.size4;
-                    if (live_overlap && cand < hi && lo < cand + bi.size4) { cand = hi; moved = true; }
-                }
-            }
-            bi.off4 = (int)cand;
-            off4 = std::max(off4, cand + bi.size4);
-        }
-    }
-    a.in_off4 = bufs[in_buf].off4; a.in_rs4 = bufs[in_buf].rs4; a.in_rows = bufs[in_buf].rows;
-    if (cat_buf >= 0) { a.s3_off4 = bufs[cat_buf].off4; a.s3_rs4 = bufs[cat_buf].rs4; }
-    // weight streams + parameter block of the segment: a dedicated area at the end of `packed`
-    size_t area = u->packed_floats;
-    int poff = 0, tt_lo = 1 << 30, tt_hi = 0;
-    for (size_t k = 0; k < hops.size(); ++k) {
-        const HostOp& ho = hops[k];
-        const Layer& l = *ho.l;
-        FusedOp& op = a.ops[k];
-        op.src_off4 = bufs[ho.src].off4; op.src_rs4 = bufs[ho.src].rs4;
-        op.rsrc_off4 = ho.rsrc >= 0 ? bufs[ho.rsrc].off4 : 0; op.rsrc_rs4 = ho.rsrc >= 0 ? bufs[ho.rsrc].rs4 : 0;
-        op.res_off4 = ho.res >= 0 ? bufs[ho.res].off4 : -1; op.res_rs4 = ho.res >= 0 ? bufs[ho.res].rs4 : 0;
-        op.dst_off4 = ho.dst >= 0 ? bufs[ho.dst].off4 : -1; op.dst_rs4 = ho.dst >= 0 ? bufs[ho.dst].rs4 : 0;
-        op.sbase = (int)area;
-        const int MSn = l.cout / 16, nc16 = l.cin_pad / 16;
-        const size_t woff = u->params[l.w].off;
-        if (l.mode == CONV_UPT) {   // streams (ms, parity): slots {2 par, 2 par + 1} of every 16-channel chunk
-            for (int par = 0; par < 2; ++par)
-                f.jobs.push_back({woff + (size_t)par * 2 * 256, area + (size_t)par * ho.tot * 256, MSn, nc16 * 4 * 256, 2 * ho.tot * 256, nc16, 4 * 256, 2 * 256, 512});
-        } else if (MSn > kFusedWaves) {   // M-passes: wave-stream s = [tile row s | tile row s + 4], each [conv blocks | folded residual blocks]
-            const int mp = MSn / kFusedWaves;
-            f.jobs.push_back({woff, area, mp, kFusedWaves * ho.nblk * 256, ho.tot * 256, kFusedWaves, ho.nblk * 256, mp * ho.tot * 256, ho.nblk * 256});
-            if (ho.r)
-                f.jobs.push_back({u->params[ho.r->w].off, area + (size_t)ho.nblk * 256, mp, kFusedWaves * ho.ncr * 256, ho.tot * 256, kFusedWaves, ho.ncr * 256,
-                                  mp * ho.tot * 256, ho.ncr * 256});
-        } else {
-            f.jobs.push_back({woff, area, MSn, ho.nblk * 256, ho.tot * 256, 1, 0, 0, ho.nblk * 256});
-            if (ho.r) f.jobs.push_back({u->params[ho.r->w].off, area + (size_t)ho.nblk * 256, MSn, ho.ncr * 256, ho.tot * 256, 1, 0, 0, ho.ncr * 256});
-        }
-        area += (size_t)ho.nstream * ho.tot * 256;
-        op.p_off = poff;
-        poff += 4 * l.cout;
-        op.tb_off = l.tb_off;   // made relative to the staged slice below
-        if (l.tb_off >= 0) { tt_lo = std::min(tt_lo, l.tb_off); tt_hi = std::max(tt_hi, l.tb_off + l.cout); }
-    }
-    if (with_final) { a.ops[a.nops - 1].src_off4 = bufs[final_src].off4; a.ops[a.nops - 1].src_rs4 = bufs[final_src].rs4; }
-    area += (size_t)kFusedRing * 256;   // the ring request of the last stream may read up to 16 blocks past its end
-    if (with_final) {   // final_conv[1]: rows padded to Cf + 4 floats (bank spread), the bias behind them
-        if (a.H * a.D > kFinalPre * kFusedThreads || (a.Cf & 3)) return fuse_reject(__LINE__);
-        a.fpar_off = poff;
-        poff += (a.D * (a.Cf + 4) + a.D + 3) / 4 * 4;
-    }
-    a.gpar_off = (int)area; a.par_floats = poff;
-    for (size_t k = 0; k < hops.size(); ++k) {
-        const HostOp& ho = hops[k];
-        const Layer& l = *ho.l;
-        const size_t pb = area + a.ops[k].p_off;
-        f.jobs.push_back({u->params[l.b].off, pb, 1, 0, 0, 1, 0, 0, l.cout});
-        if (l.gamma >= 0) f.jobs.push_back({u->params[l.gamma].off, pb + l.cout, 1, 0, 0, 1, 0, 0, l.cout});
-        if (l.beta >= 0) f.jobs.push_back({u->params[l.beta].off, pb + 2 * (size_t)l.cout, 1, 0, 0, 1, 0, 0, l.cout});
-        if (ho.r) f.jobs.push_back({u->params[ho.r->b].off, pb + 3 * (size_t)l.cout, 1, 0, 0, 1, 0, 0, l.cout});
-    }
-    if (with_final) {
-        f.jobs.push_back({(size_t)a.fw_off, area + a.fpar_off, a.D, a.Cf, a.Cf + 4, 1, 0, 0, a.Cf});
-        f.jobs.push_back({(size_t)a.fb_off, area + a.fpar_off + (size_t)a.D * (a.Cf + 4), 1, 0, 0, 1, 0, 0, a.D});
-    }
-    area += poff;
-    if (tt_hi > 0) {
-        a.tt_lo = tt_lo; a.tt_n = (tt_hi - tt_lo + 3) / 4 * 4;
-        for (int k = 0; k < (int)hops.size(); ++k)
-            if (a.ops[k].tb_off >= 0) a.ops[k].tb_off -= tt_lo;
-    }
-    // behind the activation buffers: GroupNorm exchange | time-table slice | parameter block.  The block whose size depends on the state
-    // dimension (final_conv[1]'s weights) comes LAST, so that every other LDS offset of a program is the same for every state_dim
-    // (fused_geom.hpp holds them as compile-time constants)
-    a.stat_off = (int)off4 * 4;     // GroupNorm exchange: 8 tiles x 4 rows x (mean, M2)
-    off4 += 16;
-    a.tt_off = (int)off4 * 4;
-    off4 += (size_t)a.tt_n / 4;
-    a.par_off = (int)off4 * 4;
-    off4 += (size_t)(poff + 3) / 4;
-
-    if ((size_t)(poff / 4 + a.tt_n / 4) > 2048) return fuse_reject(__LINE__);   // prologue: 2048 float4 of parameters per workgroup
-    {
-        const int c4n = (a.gc1 + a.gc2 + 3) / 4;
-        int l4 = 0;
-        while ((1 << l4) < c4n) ++l4;
-        a.lg_c4n = ((1 << l4) == c4n) ? l4 : -1;
-        if ((size_t)a.L0 * c4n > 2048) return fuse_reject(__LINE__);   // prologue holds the input window in registers (2048 float4)
-    }
-    f.lds_bytes = off4 * 16;
-    if (f.lds_bytes > 160 * 1024) return fuse_reject(__LINE__);
-    u->packed_floats = area;
-    {   // a known op sequence runs as a static program
-        auto matches = [&](const int* ids, int n) {
-            if (n != a.nops) return false;
-            for (int k = 0; k < n; ++k) if (a.ops[k].shape != ids[k]) return false;
-            return true;
-        };
-        if (sw::static_programs()) {
-            if (matches(FusedSeqDown::ids, FusedSeqDown::N)) f.program = 0;
-            else if (matches(FusedSeqUpA::ids, FusedSeqUpA::N)) f.program = 1;
-            else if (matches(FusedSeqUpB::ids, FusedSeqUpB::N)) f.program = 2;
-            else if (matches(FusedSeqUpAB::ids, FusedSeqUpAB::N)) f.program = 3;
-            else if (matches(FusedSeqMid2::ids, FusedSeqMid2::N)) f.program = 4;
-            else if (matches(FusedSeqDown3::ids, FusedSeqDown3::N)) f.program = 5;
-            else if (matches(FusedSeqMid3::ids, FusedSeqMid3::N)) f.program = 6;
-            // the static programs with a geometry table read their LDS layout as compile-time constants (fused_geom.hpp): the layout computed
-            // above must BE that table, otherwise the segment runs on the generic op-list kernel (runtime descriptors)
-            const int sdim = u->cfg.state_dim;
-            if ((f.program == 0 && !fused_geom_matches(a, GeomDown::g, sdim)) || (f.program == 3 && !fused_geom_matches(a, GeomUpAB::g, sdim)) ||
-                (f.program == 5 && !fused_geom_matches(a, GeomDown3::g, sdim)) || (f.program == 6 && !fused_geom_matches(a, GeomMid3::g, sdim))) {
-                if (debug_fuse_level()) fprintf(stderr, "[mpdx] fused segment: geometry differs from the table of program %d -> generic kernel\n", f.program);
-                f.program = -1;
-            }
-        }
-    }
-    if (debug_fuse_level() >= 2) {   // dev: the segment's LDS geometry as a fused_geom.hpp initialiser
-        fprintf(stderr, "// program %d: layers [%d,%d) %s..%s, LDS %zu B\n{ %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, {\n", f.program, i0, i1,
-                u->layers[i0].name.c_str(), u->layers[i1 - 1].name.c_str(), f.lds_bytes, a.nops, a.in_off4, a.in_rs4, a.in_rows, a.L0,
-                (a.gc1 == u->cfg.state_dim && a.gc2 == 0) ? -1 : a.gc1, a.gc2, a.c3, a.L3, a.s3_off4, a.s3_rs4, a.s3_col4, a.stat_off, a.par_off, with_final ? -1 : a.par_floats, a.tt_off,
-                a.tt_n, a.fpar_off, with_final ? a.H : 0, with_final ? a.Cf : 0);
-        for (int k = 0; k < a.nops; ++k) {
-            const FusedOp& o = a.ops[k];
-            fprintf(stderr, "    {%d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d},\n", o.shape, o.src_off4, o.src_rs4, o.rsrc_off4, o.rsrc_rs4, o.res_off4, o.res_rs4,
-                    o.dst_off4, o.dst_rs4, o.gdst, o.p_off, o.tb_off);
-        }
-        fprintf(stderr, "}},\n");
-    }
-    u->fused.push_back(f);
-    if (debug_fuse_level())
-        fprintf(stderr, "[mpdx] fused segment %zu: layers [%d,%d) %s..%s  %d ops  %zu buffers  LDS %zu B  streams+params %zu floats  program %d\n",
-                u->fused.size() - 1, i0, i1, u->layers[i0].name.c_str(), u->layers[i1 - 1].name.c_str(), a.nops, bufs.size(), f.lds_bytes,
-                area - (size_t)a.ops[0].sbase, u->fused.back().program);
-    return true;
-}
-
-static void build_units(mpdx_unet* u) {
-    const int nl = u->cfg.n_levels;
-    const int n = (int)u->layers.size();
-    auto range_of = [&](const std::string& prefix, int& i0, int& i1) {
-        i0 = -1; i1 = -1;
-        for (int i = 0; i < n; ++i)
-            if (u->layers[i].name.compare(0, prefix.size(), prefix) == 0) { if (i0 < 0) i0 = i; i1 = i + 1; }
-        return i0 >= 0;
-    };
-    std::vector<int> owner(n, -1);
-    if (u->masked()) { u->owner = owner; return; }   // a horizon in a zero-padded container: every layer as its own (masking) launch
-    // self-attention: a block sits between a level's second residual block and its resample, which the whole-trajectory programs run back to
-    // back in LDS - every layer as its own launch (the convolutions keep their pairs and weight-stationary variants)
-    if (u->cfg.self_attention) { u->owner = owner; return; }
-    const bool merge = !sw::no_merge();
-    auto try_seg = [&](const std::string& prefix, bool with_final) {
-        int i0, i1;
-        if (!range_of(prefix, i0, i1)) return;
-        if (with_final) {
-            if (i1 != n - 1 || u->layers[n - 1].name.compare(0, 12, "final_conv.0") != 0) return;
-            i1 = n;
-        }
-        for (int i = i0; i < i1; ++i) if (owner[i] >= 0) return;
-        if (build_fused_segment(u, i0, i1, with_final))
-            for (int i = i0; i < i1; ++i) owner[i] = (int)u->fused.size() - 1;
-    };
-    // the outer down levels as ONE program if it fits (every launch boundary + prologue removed is ~5 us per step): with four
-    // levels downs.0 + downs.1 + downs.2 (15 ops; measured cfg 2 23.10 -> 22.47 ms, cfg 5 shard 624 -> 617 ms against two programs;
-    // MPDX_MERGE_DOWN3=0 keeps them apart), else downs.0 + downs.1
-    bool merged_down = false;
-    if (nl >= 4 && merge && sw::merge_down3()) {
-        int a0, a1, b0, b1, c0, c1;
-        if (range_of("downs.0.", a0, a1) && range_of("downs.1.", b0, b1) && range_of("downs.2.", c0, c1) && a1 == b0 && b1 == c0 &&
-            build_fused_segment(u, a0, c1, false)) {
-            for (int i = a0; i < c1; ++i) owner[i] = (int)u->fused.size() - 1;
-            merged_down = true;
-        }
-    }
-    if (!merged_down && nl >= 3 && merge) {
-        int a0, a1, b0, b1;
-        if (range_of("downs.0.", a0, a1) && range_of("downs.1.", b0, b1) && a1 == b0 && build_fused_segment(u, a0, b1, false)) {
-            for (int i = a0; i < b1; ++i) owner[i] = (int)u->fused.size() - 1;
-            merged_down = true;
-        }
-    }
-    if (!merged_down) {
-        try_seg("downs.0.", false);
-        if (nl >= 3) try_seg("downs.1.", false);
-    }
-    // the third down level (C = 128, L = 16: two tile rows per wave) as its own program
-    if (nl >= 4 && !sw::no_mid2()) try_seg("downs.2.", false);
-    // three levels: the innermost level (no Downsample1d) and the two middle blocks - eight Conv1dBlocks of 128 channels on L / 4 positions - as ONE
-    // program (round 6; they were nine launches of ~4.8 us: a training iteration at batch 32 spent 43 us there).  MPDX_NO_MID3=1: per layer as before
-    if (nl == 3 && !sw::no_mid3()) {
-        int a0, a1, b0, b1, c0, c1;
-        bool free_ = range_of("downs.2.", a0, a1) && range_of("mid_block1.", b0, b1) && range_of("mid_block2.", c0, c1) && a1 == b0 && b1 == c0;
-        for (int i = a0; free_ && i < c1; ++i) free_ = owner[i] < 0;
-        if (free_ && build_fused_segment(u, a0, c1, false))
-            for (int i = a0; i < c1; ++i) owner[i] = (int)u->fused.size() - 1;
-    }
-    // the two outer up levels + final_conv + DDPM step as ONE program (the second level's skip tensor is staged by the prologue)
-    bool merged_up = false;
-    if (nl >= 3 && !sw::no_merge_up() && merge) {
-        int a0, a1, b0, b1;
-        if (range_of("ups." + std::to_string(nl - 3) + ".", a0, a1) && range_of("ups." + std::to_string(nl - 2) + ".", b0, b1) && a1 == b0 &&
-            b1 == n - 1 && u->layers[n - 1].name.compare(0, 12, "final_conv.0") == 0 && build_fused_segment(u, a0, n, true)) {
-            for (int i = a0; i < n; ++i) owner[i] = (int)u->fused.size() - 1;
-            merged_up = true;
-        }
-    }
-    if (!merged_up) {
-        if (nl >= 3) try_seg("ups." + std::to_string(nl - 3) + ".", false);
-        try_seg("ups." + std::to_string(nl - 2) + ".", true);
-    }
-    u->owner = owner;
-}
-
+namespace mpdx {
 
 // tile choice.  Measured on MI355X at B=100 (tools/ablate_layers.py): per-launch time is dominated by fixed costs
 // (launch boundary ~3 us, epilogue ~1.9 us), halving the tile to co-schedule two workgroups per CU does NOT pay
@@ -904,7 +499,7 @@ void choose_tile(const Layer& l, int B, int& MT, int& NT) {
         MT = (min_mt <= 16 && l.cout % 16 == 0) ? 16 : 32;
         return;
     }
-    const int target = std::max(1, sw::target_wgs() / g_plan_chains);   // concurrent sub-batch chains of a plan share the CUs
+    const int target = std::max(1, sw::target_wgs());
     auto wgs = [&](int mt, int nt) { return (long)(l.cout / mt) * ((npos + nt - 1) / nt); };
     const int pad = (l.mode == CONV_S1) ? l.ks / 2 : 1;
     auto lds = [&](int mt, int nt) {  // max(staged windows, K-partial buffer), as conv_block_lds_bytes
@@ -1233,6 +828,28 @@ static double unit_bytes(const mpdx_unet* u, const mpdx_unet::Unit& un, int B) {
     return b;
 }
 
+// One pass over the launch units, then the final kernel unless a program had it - the ONE walk of the planning path and of the timing entries
+// (unet_measure.hpp).  hook(kSkipUnit, i) != 0 leaves unit i out; hook(kBeforeLaunch / kAfterLaunch, i) runs around every launch and returns an error
+// code; the final kernel counts as launch units.size().  A skipped program that holds the final op still stands for it: no separate final kernel either.
+enum PassEvent { kSkipUnit, kBeforeLaunch, kAfterLaunch };
+template <class Hook>
+static int walk_pass(mpdx_unet* u, const std::vector<mpdx_unet::Unit>& units, const float* packed, const float* row, const float* x, float* ws,
+                     int B, FinalArgs& fa, hipStream_t st, Hook&& hook) {
+    const int n = (int)units.size();
+    bool final_done = false;
+    for (int i = 0; i < n; ++i) {
+        if (units[i].fused >= 0) final_done |= u->fused[units[i].fused].has_final;
+        if (hook(kSkipUnit, i)) continue;
+        if (int rc = hook(kBeforeLaunch, i)) return rc;
+        if (int rc = run_unit(u, units[i], packed, row, x, ws, B, &fa, st)) return rc;
+        if (int rc = hook(kAfterLaunch, i)) return rc;
+    }
+    if (final_done) return 0;
+    if (int rc = hook(kBeforeLaunch, n)) return rc;
+    if (int rc = run_final(u, packed, fa, B, ws, st)) return rc;
+    return hook(kAfterLaunch, n);
+}
+
 // one U-Net pass + the final 1x1 conv / DDPM step described by `fa` (fa.mode 0: eps only)
 static int run_unet_and_final(mpdx_unet* u, const float* packed, const float* timetab, int T, const float* x, int t, int B,
                               float* ws, FinalArgs& fa, hipStream_t st) {
@@ -1240,8 +857,6 @@ static int run_unet_and_final(mpdx_unet* u, const float* packed, const float* ti
     if (t < 0 || t >= T) return fail(MPDX_E_INVALID, "timestep %d outside [0,%d)", t, T);
     if (B <= 0) return fail(MPDX_E_INVALID, "B must be positive");
     const float* row = timetab + (size_t)t * u->tt_row;
-    const auto units = current_units(u, B, nullptr);
-    bool final_done = false;
     if (u->masked()) {   // the network reads its input from the zero-padded container copy
         float* xc = ws + u->slot_floats * (size_t)B * u->xpad_slot;
         const size_t nx = (size_t)B * u->Hc * u->cfg.state_dim;
@@ -1249,19 +864,23 @@ static int run_unet_and_final(mpdx_unet* u, const float* packed, const float* ti
                            u->cfg.state_dim);
         x = xc;
     }
-    for (const auto& un : units) {
-        if (int rc = run_unit(u, un, packed, row, x, ws, B, &fa, st)) return rc;
-        if (un.fused >= 0) final_done |= u->fused[un.fused].has_final;
-    }
-    if (!final_done)
-        if (int rc = run_final(u, packed, fa, B, ws, st)) return rc;
-    return 0;
+    return walk_pass(u, current_units(u, B, nullptr), packed, row, x, ws, B, fa, st, [](PassEvent, int) { return 0; });
 }
 
+// the trace / ablation entry points exist in a development build only: 0 there, else the error that says how to make one
+int dev_hooks_missing(const char* fn) {
+#ifdef MPDX_DEV_HOOKS
+    return (void)fn, 0;
+#endif
+    return fail(MPDX_E_STATE, "%s needs a development build of libmpdx.so (MPDX_BUILD_DEFS=-DMPDX_DEV_HOOKS MPDX_BUILD_OUT=build_ab/libmpdx_dev.so python -m mpd_public_amd.build, then MPDX_LIB=build_ab/libmpdx_dev.so): "
+                "the production kernels carry no trace / ablation hooks", fn);
+}
 
 }  // namespace mpdx
 
 using namespace mpdx;
+
+#include "unet_measure.hpp"   // mpdx_unet_profile / _time_units / _time_without, mpdx_bench_layer, the trace entries, the launch-unit queries
 
 extern "C" {
 
@@ -1320,7 +939,6 @@ void mpdx_unet_destroy(mpdx_unet* u) {
     if (u && u->pack_descs_dev) (void)hipFree(u->pack_descs_dev);
     if (u && u->pack_chunks_dev) (void)hipFree(u->pack_chunks_dev);
     if (u && u->jobs_dev) (void)hipFree(u->jobs_dev);
-    if (u && u->side.stream) { (void)hipStreamDestroy(u->side.stream); (void)hipEventDestroy(u->side.fork); (void)hipEventDestroy(u->side.join); }
     delete u;
 }
 
@@ -1460,37 +1078,6 @@ int mpdx_weighted_loss(const float* pred, const float* targ, const float* weight
     return 0;
 }
 
-
-// ---- sub-batch chains (MEASURED AND REJECTED, round 4; kept behind MPDX_PLAN_CHAINS=2 so that the measurement can be repeated).
-// Idea: a plan of a small batch (B = 100) is a chain of ~1 600 dependent launches whose kernels cannot fill 256 CUs and whose boundaries
-// (~2.3 us of every launch's rocprof duration lie outside the workgroups' own lifetimes) add up to a sixth of the step; trajectories are
-// independent, so the batch is cut into two halves that run as two independent chains on two HIP streams (side stream forked from / joined
-// into the caller's stream with events, no host synchronisation; the halves meet only at a guided step's guide iterations, whose
-// whole-tensor range test couples them).  Results are bit-identical to the single chain (tests/test_gpu_parity.py, test_gpu_guide.py pass
-// with the split on).  Measured on MI355X (profiles/r04_plan_chains.txt): cfg 2 24.8 vs 20.3 ms, cfg 3 27.3 vs 21.9, cfg 4 29.6 vs 24.1 -
-// SLOWER, and not because of the host: replayed as ONE hipGraph (tools/graph_probe_plan.py) the two-chain plan takes 25.2 ms against 20.15
-// for the single chain's graph.  Two half-batch kernels do not share the chip the way one full-batch kernel uses it: every launch pays its
-// fixed phases (staging, K-reduction, epilogue, boundary) for half the work, and the dispatcher does not interleave the two queues finely
-// enough to hide one chain's boundaries under the other's kernels.
-namespace mpdx {
-static int plan_side(mpdx_unet* u, mpdx_unet::PlanSide** out) {   // the handle's side stream + fork / join events (created on first use; one handle = one device)
-    mpdx_unet::PlanSide& s = u->side;
-    if (!s.stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&s.fork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&s.join, hipEventDisableTiming));
-    }
-    *out = &s;
-    return 0;
-}
-// trajectories of the first chain (0: one chain - the default).  MPDX_PLAN_CHAINS=2 switches the split on (development A/B).
-static int plan_split_point(int B, int npc, int n_ctx) {
-    if (sw::plan_chains() != 2 || B < 16) return 0;
-    if (n_ctx >= 2) return (n_ctx / 2) * npc;     // whole contexts per chain: the range-test flags stay per chain
-    return std::min(B - 4, ((B / 2) + 3) & ~3);   // one context: both chains publish into its one flag (atomicMax)
-}
-}  // namespace mpdx
-
 int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, const mpdx_step_coefs* coefs, int n_without_noise,
               float* x, const float* noise, const float* hard_start, const float* hard_goal, float* chain, int B, float* ws,
               const mpdx_guide_params* guide, int n_guide_steps, int t_start_guide, uint32_t* guide_flags, int n_per_ctx,
@@ -1517,22 +1104,6 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
     // x_T with hard conditioning; chain[0]
     hipLaunchKernelGGL(add_noise_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, st, x, (const float*)nullptr,
                        hard_start, hard_goal, 0.f, 0.f, chain, B, H, D);
-    // two concurrent sub-batch chains (see plan_split_point): chain c covers trajectories [b0[c], b0[c] + nb[c])
-    const int B0 = plan_split_point(B, npc, n_ctx);
-    const int nch = B0 > 0 ? 2 : 1;
-    mpdx_unet::PlanSide* side = nullptr;
-    if (nch == 2) {
-        if (int rc = plan_side(u, &side)) return rc;
-        if (int rc = ensure_fused_streams(u, packed, st)) return rc;   // (a one-off re-assembly of the weight streams stays ahead of the fork)
-        HIP_TRY(hipEventRecord(side->fork, st));
-        HIP_TRY(hipStreamWaitEvent(side->stream, side->fork, 0));
-    }
-    const int b0[2] = {0, B0}, nb[2] = {nch == 2 ? B0 : B, B - B0};
-    hipStream_t sts[2] = {st, side ? side->stream : st};
-    float* wss[2] = {ws, ws + u->slot_floats * (size_t)nb[0] * u->n_slots};   // two disjoint workspaces inside the caller's one
-    struct ChainsGuard { int* p; ~ChainsGuard() { *p = 1; } } guard{&g_plan_chains};
-    g_plan_chains = nch;
-    bool forked = nch == 2;
     int k = 0;
     for (int i = T - 1; i >= -n_without_noise; --i, ++k) {
         const int t = i < 0 ? 0 : i;
@@ -1545,35 +1116,19 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
         if (!noise && t != 0) { rng.on = 1; rng.seed = rng_seed; rng.offset = rng_offset; rng.elem0 = (unsigned long long)(k + 1) * n; }
         float* ch = chain ? chain + (size_t)(k + 1) * n : nullptr;
         uint32_t* fl = guided ? guide_flags + (size_t)k * (n_guide_steps + 1) * n_ctx : nullptr;
-        if (nch == 2 && !forked) {   // behind a guided step's joined guide iterations: fork again
-            HIP_TRY(hipEventRecord(side->fork, st));
-            HIP_TRY(hipStreamWaitEvent(side->stream, side->fork, 0));
-            forked = true;
+        FinalArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        fa.x_in = x; fa.out = x;
+        fa.k = coefs[t];
+        fa.n_per_ctx = npc;
+        if (!guided) {
+            fa.rng = rng; fa.noise = nz; fa.hs = hard_start; fa.hg = hard_goal;
+            fa.chain = ch; fa.mode = 1;
+        } else {
+            fa.mode = 2; fa.absmax = fl;  // posterior mean + its max|.| per context
         }
-        for (int c = 0; c < nch; ++c) {
-            const size_t eo = (size_t)b0[c] * H * D;   // element offset of the chain's first trajectory
-            FinalArgs fa;
-            memset(&fa, 0, sizeof(fa));
-            fa.x_in = x + eo; fa.out = x + eo;
-            fa.k = coefs[t];
-            fa.n_per_ctx = npc;
-            if (!guided) {
-                fa.rng = rng;
-                fa.rng.elem0 += eo;
-                fa.noise = nz ? nz + eo : nullptr;
-                fa.hs = hard_start ? hard_start + (size_t)b0[c] * D : nullptr; fa.hg = hard_goal ? hard_goal + (size_t)b0[c] * D : nullptr;
-                fa.chain = ch ? ch + eo : nullptr; fa.mode = 1;
-            } else {
-                fa.mode = 2; fa.absmax = fl + b0[c] / npc;  // posterior mean + its max|.| per context
-            }
-            if (int rc = run_unet_and_final(u, packed, timetab, T, x + eo, t, nb[c], wss[c], fa, sts[c])) return rc;
-        }
+        if (int rc = run_unet_and_final(u, packed, timetab, T, x, t, B, ws, fa, st)) return rc;
         if (guided) {
-            if (nch == 2) {   // the guide iterations couple the chains (whole-tensor range test of a context): joined stream, whole batch
-                HIP_TRY(hipEventRecord(side->join, side->stream));
-                HIP_TRY(hipStreamWaitEvent(st, side->join, 0));
-                forked = false;
-            }
             for (int j = 0; j < n_guide_steps; ++j) {
                 const bool last = j == n_guide_steps - 1;  // the last iteration also adds the noise term and appends to the chain
                 if (int rc = launch_guide(guide, x, nullptr, hard_start, hard_goal, fl + (size_t)j * n_ctx, fl + (size_t)(j + 1) * n_ctx, npc, B, H,
@@ -1584,312 +1139,14 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
         }
         if (dbg) {   // MPDX_DEBUG: attribute launch / execution errors to the loop iteration that caused them
             if (dbg >= 2) {
-                hipError_t e = hipStreamSynchronize(st);
-                if (e == hipSuccess && nch == 2) e = hipStreamSynchronize(side->stream);
+                const hipError_t e = hipStreamSynchronize(st);
                 if (e != hipSuccess) return fail((int)e, "mpdx_plan: loop iteration %d (t=%d%s) faulted: %s", k, t, guided ? ", guided" : "", hipGetErrorString(e));
             }
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return fail((int)e, "mpdx_plan: launch in loop iteration %d (t=%d%s) failed: %s", k, t, guided ? ", guided" : "", hipGetErrorString(e));
         }
     }
-    if (nch == 2 && forked) {   // join: the caller's stream continues behind both chains
-        HIP_TRY(hipEventRecord(side->join, side->stream));
-        HIP_TRY(hipStreamWaitEvent(st, side->join, 0));
-    }
     HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int mpdx_unet_profile(mpdx_unet* u, const float* packed, const float* timetab, int T, const float* x, int t, int B, float* ws,
-                      void* stream, int cap, float* ms_out, double* flops_out, const char** names_out, int* n_out) {
-    if (!u || !packed || !timetab || !x || !ws || !ms_out || !n_out) return fail(MPDX_E_INVALID, "null argument");
-    if (int rc = check_ready(u)) return rc;
-    if (t < 0 || t >= T) return fail(MPDX_E_INVALID, "timestep %d outside [0,%d)", t, T);
-    hipStream_t st = (hipStream_t)stream;
-    bool fin_fused = false;
-    const auto units = current_units(u, B, &fin_fused);
-    const bool need_final = !fin_fused;
-    const int nl = (int)units.size() + (need_final ? 1 : 0);
-    if (cap < nl) return fail(MPDX_E_INVALID, "need room for %d launches", nl);
-    static float* scratch = nullptr;  // eps sink owned by the library (measurement helper only)
-    static size_t scratch_n = 0;
-    const size_t need = (size_t)B * u->cfg.n_support_points * u->cfg.state_dim;
-    if (scratch_n < need) { if (scratch) (void)hipFree(scratch); HIP_TRY(hipMalloc(&scratch, need * sizeof(float))); scratch_n = need; }
-    FinalArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.out = scratch; fa.mode = 0; fa.n_per_ctx = 1;
-    std::vector<hipEvent_t> ev(2 * nl);
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-    const float* row = timetab + (size_t)t * u->tt_row;
-    static std::vector<std::string> fused_names;
-    fused_names.resize(u->fused.size());
-    int rc = 0;
-    for (int i = 0; i < (int)units.size() && !rc; ++i) {
-        HIP_TRY(hipEventRecord(ev[2 * i], st));
-        const double fl = unit_flops(u, units[i], B);
-        rc = run_unit(u, units[i], packed, row, x, ws, B, &fa, st);
-        if (units[i].fused >= 0) {
-            const auto& f = u->fused[units[i].fused];
-            fused_names[units[i].fused] = "fused[" + u->layers[f.first].name.substr(0, u->layers[f.first].name.find(".blocks")) + "..+" +
-                                          std::to_string(f.count) + (f.has_final ? " layers+final_conv.1+ddpm_step]" : " layers]");
-            if (names_out) names_out[i] = fused_names[units[i].fused].c_str();
-        } else if (names_out) names_out[i] = u->layers[units[i].layer].name.c_str();
-        HIP_TRY(hipEventRecord(ev[2 * i + 1], st));
-        if (flops_out) flops_out[i] = fl;
-    }
-    if (!rc && need_final) {
-        HIP_TRY(hipEventRecord(ev[2 * (nl - 1)], st));
-        rc = run_final(u, packed, fa, B, ws, st);
-        HIP_TRY(hipEventRecord(ev[2 * (nl - 1) + 1], st));
-        if (flops_out) flops_out[nl - 1] = 0.0;
-        if (names_out) names_out[nl - 1] = "final_conv.1+ddpm_step";
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    for (int i = 0; i < nl && !rc; ++i) HIP_TRY(hipEventElapsedTime(&ms_out[i], ev[2 * i], ev[2 * i + 1]));
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    *n_out = nl;
-    return rc;
-}
-
-/* dev tool: one launch of layer `layer` with s_memtime stamps (7 per workgroup) of the first and the last workgroup */
-int mpdx_layer_trace(mpdx_unet* u, const float* packed, const float* timetab, const float* x, int layer, int B, float* ws, void* stream,
-                     long long* stamps32) {
-#ifndef MPDX_DEV_HOOKS
-    return fail(MPDX_E_STATE, "%s needs a development build of libmpdx.so (MPDX_BUILD_DEFS=-DMPDX_DEV_HOOKS MPDX_BUILD_OUT=build_ab/libmpdx_dev.so python -m mpd_public_amd.build, then MPDX_LIB=build_ab/libmpdx_dev.so): "
-                "the production kernels carry no trace / ablation hooks", __func__);
-#endif
-    if (!u || layer < 0 || layer >= (int)u->layers.size() || !stamps32) return fail(MPDX_E_INVALID, "bad argument");
-    if (int rc = check_ready(u)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    long long* dev = nullptr;
-    HIP_TRY(hipMalloc(&dev, 32 * sizeof(long long)));
-    HIP_TRY(hipMemsetAsync(dev, 0, 32 * sizeof(long long), st));
-    g_conv_trace = dev;
-    int rc = run_layer(u, u->layers[layer], packed, timetab, x, ws, B, st);
-    g_conv_trace = nullptr;
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(stamps32, dev, 32 * sizeof(long long), hipMemcpyDeviceToHost));
-    (void)hipFree(dev);
-    return rc;
-}
-
-/* dev tool: run fused segment `seg` once with per-phase s_memtime stamps of workgroup 0 / wave 0; stamps_out[n] */
-int mpdx_fused_trace(mpdx_unet* u, const float* packed, const float* timetab, const float* x, int seg, int B, float* ws, void* stream,
-                     long long* stamps_out, int cap, int* n_out, int* nops_out) {
-#ifndef MPDX_DEV_HOOKS
-    return fail(MPDX_E_STATE, "%s needs a development build of libmpdx.so (MPDX_BUILD_DEFS=-DMPDX_DEV_HOOKS MPDX_BUILD_OUT=build_ab/libmpdx_dev.so python -m mpd_public_amd.build, then MPDX_LIB=build_ab/libmpdx_dev.so): "
-                "the production kernels carry no trace / ablation hooks", __func__);
-#endif
-    if (!u || seg < 0 || seg >= (int)u->fused.size()) return fail(MPDX_E_INVALID, "bad segment");
-    if (int rc = check_ready(u)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    long long* dev = nullptr;
-    HIP_TRY(hipMalloc(&dev, 1024 * sizeof(long long)));
-    HIP_TRY(hipMemsetAsync(dev, 0, 1024 * sizeof(long long), st));
-    static float* scratch = nullptr;
-    if (!scratch) HIP_TRY(hipMalloc(&scratch, (size_t)1 << 24));
-    FinalArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.out = scratch; fa.mode = 0; fa.n_per_ctx = 1;
-    // the traced launch runs IN CONTEXT: two untraced U-Net passes, then a third pass in which only segment `seg` stamps - same
-    // predecessors, cache and clock state as in production, no host synchronisation in between
-    int rc = 0;
-    for (int pass = 0; pass < 3 && !rc; ++pass) {
-        if (pass == 2) { g_fused_trace = dev; g_fused_trace_seg = seg; }
-        rc = run_unet_and_final(u, packed, timetab, 1 << 30, x, 0, B, ws, fa, st);
-    }
-    g_fused_trace_seg = -1;
-    g_fused_trace = nullptr;
-    HIP_TRY(hipStreamSynchronize(st));
-    const int n = std::min(cap, 1024);   // 8 waves x 128 slots
-    HIP_TRY(hipMemcpy(stamps_out, dev, n * sizeof(long long), hipMemcpyDeviceToHost));
-    (void)hipFree(dev);
-    if (n_out) *n_out = n;
-    if (nops_out) *nops_out = u->fused[seg].tmpl.nops;
-    return rc;
-}
-
-/* in-situ timing: `reps` full U-Net passes; ONE event pair brackets launch units [unit_first, unit_last] of each pass
- * (so the bracketed kernels run in their real context - cold weights, real predecessor - and the event cost is
- * amortised over the run).  *ms_avg = average bracketed time per pass.  Synchronises. */
-int mpdx_unet_time_units(mpdx_unet* u, const float* packed, const float* timetab, int T, const float* x, int t, int B, float* ws,
-                         void* stream, int unit_first, int unit_last, int reps, float* ms_avg) {
-    if (!u || !packed || !timetab || !x || !ws || !ms_avg || reps < 1) return fail(MPDX_E_INVALID, "bad argument");
-    if (int rc = check_ready(u)) return rc;
-    if (t < 0 || t >= T) return fail(MPDX_E_INVALID, "timestep %d outside [0,%d)", t, T);
-    hipStream_t st = (hipStream_t)stream;
-    const auto units = current_units(u, B, nullptr);
-    if (unit_first < 0 || unit_last >= (int)units.size() || unit_first > unit_last) return fail(MPDX_E_INVALID, "bad unit range");
-    static float* scratch = nullptr;
-    static size_t scratch_n = 0;
-    const size_t need = (size_t)B * u->cfg.n_support_points * u->cfg.state_dim;
-    if (scratch_n < need) { if (scratch) (void)hipFree(scratch); HIP_TRY(hipMalloc(&scratch, need * sizeof(float))); scratch_n = need; }
-    FinalArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.out = scratch; fa.mode = 0; fa.n_per_ctx = 1;
-    const float* row = timetab + (size_t)t * u->tt_row;
-    std::vector<hipEvent_t> ev(2 * reps);
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-    int rc = 0;
-    for (int r = 0; r < reps && !rc; ++r) {
-        bool final_done = false;
-        for (int i = 0; i < (int)units.size() && !rc; ++i) {
-            if (i == unit_first) HIP_TRY(hipEventRecord(ev[2 * r], st));
-            rc = run_unit(u, units[i], packed, row, x, ws, B, &fa, st);
-            if (units[i].fused >= 0) final_done |= u->fused[units[i].fused].has_final;
-            if (i == unit_last) HIP_TRY(hipEventRecord(ev[2 * r + 1], st));
-        }
-        if (!rc && !final_done) rc = run_final(u, packed, fa, B, ws, st);
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    double tot = 0.0;
-    for (int r = 0; r < reps && !rc; ++r) { float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, ev[2 * r], ev[2 * r + 1])); tot += ms; }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    *ms_avg = (float)(tot / reps);
-    return rc;
-}
-
-/* measurement helper (bench.py roofline leg, the DIFFERENTIAL form): `reps` back-to-back U-Net passes WITHOUT the launch units whose bit is set in skip_mask
- * (0: nothing skipped) between ONE HIP-event pair on the launch stream -> average ms per pass.  The cost of a launch class inside
- * the pass = (pass with everything) - (pass without the class): no event pair sits next to the measured launches (an event pair around a single
- * 35-us launch adds ~5 us of marker processing + dispatch gap that the un-instrumented stream does not have).  The skipped units' consumers read
- * whatever the workspace holds: timing only, the output is not meaningful. */
-int mpdx_unet_time_without(mpdx_unet* u, const float* packed, const float* timetab, int T, const float* x, int t, int B, float* ws,
-                           void* stream, unsigned long long skip_mask, int reps, float* ms_avg) {
-    if (!u || !packed || !timetab || !x || !ws || !ms_avg || reps < 1) return fail(MPDX_E_INVALID, "bad argument");
-    if (int rc = check_ready(u)) return rc;
-    if (t < 0 || t >= T) return fail(MPDX_E_INVALID, "timestep %d outside [0,%d)", t, T);
-    hipStream_t st = (hipStream_t)stream;
-    const auto units = current_units(u, B, nullptr);
-    if (units.size() > 64) return fail(MPDX_E_INVALID, "more than 64 launch units");
-    static float* scratch = nullptr;
-    static size_t scratch_n = 0;
-    const size_t need = (size_t)B * u->cfg.n_support_points * u->cfg.state_dim;
-    if (scratch_n < need) { if (scratch) (void)hipFree(scratch); HIP_TRY(hipMalloc(&scratch, need * sizeof(float))); scratch_n = need; }
-    FinalArgs fa;
-    memset(&fa, 0, sizeof(fa));
-    fa.out = scratch; fa.mode = 0; fa.n_per_ctx = 1;
-    const float* row = timetab + (size_t)t * u->tt_row;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    int rc = 0;
-    auto one_pass = [&]() {
-        bool final_done = false;
-        for (int i = 0; i < (int)units.size() && !rc; ++i) {
-            if (units[i].fused >= 0) final_done |= u->fused[units[i].fused].has_final;   // (a skipped program with the final op: no separate final kernel either)
-            if ((skip_mask >> i) & 1ull) continue;
-            rc = run_unit(u, units[i], packed, row, x, ws, B, &fa, st);
-        }
-        if (!rc && !final_done) rc = run_final(u, packed, fa, B, ws, st);
-    };
-    for (int r = 0; r < 3 && !rc; ++r) one_pass();   // warm-up (code objects, clocks)
-    HIP_TRY(hipEventRecord(e0, st));
-    for (int r = 0; r < reps && !rc; ++r) one_pass();
-    HIP_TRY(hipEventRecord(e1, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *ms_avg = ms / (float)reps;
-    return rc;
-}
-
-/* layer index of launch unit i (-1 for a fused unit / the final kernel): lets bench.py query the tile of a unit */
-int mpdx_unet_unit_layer(const mpdx_unet* u, int B, int i) {
-    if (!u) return -1;
-    const auto units = current_units(u, B, nullptr);
-    if (i < 0 || i >= (int)units.size()) return -1;
-    return units[i].fused >= 0 ? -1 : units[i].layer;
-}
-
-/* which kernel runs fused segment `seg`: 0..5 = a static program (fused_program_kernel<FusedSeq...>; 0, 3, 5 read their LDS geometry from the
- * compile-time tables of fused_geom.hpp), -1 = the generic op-list kernel (runtime descriptors), -2 = no such segment */
-int mpdx_unet_fused_program(const mpdx_unet* u, int seg) {
-    if (!u || seg < 0 || seg >= (int)u->fused.size()) return -2;
-    return u->fused[seg].program;
-}
-
-/* algorithmic bytes of launch unit i at batch B (weights once + boundary activations once); 0 for a bad index */
-double mpdx_unet_unit_bytes(const mpdx_unet* u, int B, int i) {
-    if (!u) return 0.0;
-    const auto units = current_units(u, B, nullptr);
-    if (i < 0 || i >= (int)units.size()) return 0.0;
-    return unit_bytes(u, units[i], B);
-}
-
-/* 1 when launch unit i is a paired launch (blocks[0] + the block's residual 1x1 conv in one conv_pair_kernel) */
-int mpdx_unet_unit_is_pair(const mpdx_unet* u, int B, int i) {
-    if (!u) return 0;
-    const auto units = current_units(u, B, nullptr);
-    return (i >= 0 && i < (int)units.size() && units[i].fused < 0 && units[i].pair) ? 1 : 0;
-}
-
-int mpdx_bench_layer(mpdx_unet* u, const float* packed, const float* timetab, const float* x, int layer, int B, float* ws,
-                     void* stream, int reps, int dbg, float* ms_per_launch) {
-    if (!u || !packed || !timetab || !x || !ws || !ms_per_launch) return fail(MPDX_E_INVALID, "null argument");
-    if (int rc = check_ready(u)) return rc;
-    if (layer < 0 || layer >= (int)u->layers.size()) return fail(MPDX_E_INVALID, "bad layer index");
-#ifndef MPDX_DEV_HOOKS
-    if (dbg & 15) return fail(MPDX_E_STATE, "phase-ablation masks need a development build of libmpdx.so (MPDX_BUILD_DEFS=-DMPDX_DEV_HOOKS)");
-#endif
-    hipStream_t st = (hipStream_t)stream;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    for (int i = 0; i < 5; ++i)
-        if (int rc = run_layer(u, u->layers[layer], packed, timetab, x, ws, B, st, dbg & 15)) return rc;
-    if (dbg & 16) {  // replay the same launches from a hipGraph (device-side launch cadence, no host in the loop)
-        hipGraph_t graph;
-        hipGraphExec_t exec;
-        HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        for (int i = 0; i < reps; ++i)
-            if (int rc = run_layer(u, u->layers[layer], packed, timetab, x, ws, B, st, dbg & 15)) return rc;
-        HIP_TRY(hipStreamEndCapture(st, &graph));
-        HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        HIP_TRY(hipGraphLaunch(exec, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipEventRecord(e0, st));
-        HIP_TRY(hipGraphLaunch(exec, st));
-        HIP_TRY(hipEventRecord(e1, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        float msg = 0.f;
-        HIP_TRY(hipEventElapsedTime(&msg, e0, e1));
-        *ms_per_launch = msg / reps;
-        (void)hipGraphExecDestroy(exec); (void)hipGraphDestroy(graph);
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        return 0;
-    }
-    HIP_TRY(hipEventRecord(e0, st));
-    for (int i = 0; i < reps; ++i)
-        if (int rc = run_layer(u, u->layers[layer], packed, timetab, x, ws, B, st, dbg)) return rc;
-    HIP_TRY(hipEventRecord(e1, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    *ms_per_launch = ms / reps;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return 0;
-}
-
-int mpdx_unet_layer_tile(const mpdx_unet* u, int i, int B, char* buf, size_t buflen) {
-    if (!u || !buf || i < 0 || i >= (int)u->layers.size()) return fail(MPDX_E_INVALID, "bad layer index");
-    const Layer& l = u->layers[i];
-    if (l.attn) { snprintf(buf, buflen, "attn %dx%d", attn_cols(l.cout, l.L_out) / l.L_out, l.L_out); return 0; }   // trajectories x positions per workgroup
-    int MT, NT;
-    ConvArgs dummy;
-    memset(&dummy, 0, sizeof(dummy));
-    const Layer* l2 = (i + 1 < (int)u->layers.size() && pair_tile(l, u->layers[i + 1], B, MT, NT)) ? &u->layers[i + 1] : nullptr;
-    if (const int v = weight_stationary_variant(l, l2, dummy, B, 0)) {   // "ws": the weight-stationary persistent kernel (conv_ws.hpp)
-        if (v == 6) snprintf(buf, buflen, "wsp 32x16/2x1+1x1");   // conv_wsp_kernel: a pair of waves per tile, whole K per wave
-        else if (v >= 4) snprintf(buf, buflen, "wsn 16x16/8x1");   // conv_wsn_kernel: 8 waves = 8 position tiles, whole K per wave
-        else snprintf(buf, buflen, "ws %dx16/1x8%s", v == 1 ? 32 : 16, v == 3 ? "+1x1" : "");
-        return 0;
-    }
-    choose_tile(l, B, MT, NT);
-    if (l.cout % MT) MT = 16;
-    const bool ks = layer_ksplit(l);
-    snprintf(buf, buflen, "%dx%d/%dx%d", MT, NT, ks ? 1 : NT / 16, ks ? 8 : 8 / (NT / 16));
     return 0;
 }
 

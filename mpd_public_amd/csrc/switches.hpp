@@ -43,7 +43,6 @@ constexpr int kUnset = INT_MIN;   // default of an INT switch that has to tell "
     X(no_mid3,             "MPDX_NO_MID3",              PRESENT, false,   LIVE, "three levels: the innermost level + the two middle blocks per layer, not as one program (nine launches of ~4.8 us: 43 us of a batch-32 training iteration)") \
     X(static_programs,     "MPDX_STATIC_PROGRAMS",      ON,      true,    ONCE, "0: every fused segment on the generic op-list kernel (runtime descriptors), none as a static program") \
     X(pair,                "MPDX_PAIR",                 ON,      true,    ONCE, "0: blocks[0] and the residual 1x1 convolution of a ResidualTemporalBlock as two launches (conv_pair_kernel off)") \
-    X(plan_chains,         "MPDX_PLAN_CHAINS",          INT,     0,       ONCE, "2: mpdx_plan enqueues a plan as two concurrent sub-batch chains") \
     X(guide_dense,         "MPDX_GUIDE_DENSE",          INT,     -1,      ONCE, "Panda guide, dense variant (no FK table, 128 VGPRs: two workgroups per CU): 0 / 1 force it off / on, -1 from batch 512 on") \
     /* ---- tile and launch-shape overrides (development) */ \
     X(tile,                "MPDX_TILE",                 STR,     nullptr, ONCE, "MTxNT: the per-layer kernels' tile wherever it is legal for the layer") \

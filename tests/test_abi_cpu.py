@@ -199,6 +199,53 @@ def test_standard_networks_run_the_static_programs_with_compile_time_geometry(li
     lib.mpdx_unet_destroy(h)
 
 
+# (switches, kwargs of _create, programs of the segments in order, mpdx_unet_packed_floats).  H = 64, width 32 unless said otherwise.
+SEGMENT_LAYOUTS = [
+    ({}, dict(state_dim=4), [5, 3], 4648152),
+    ({}, dict(state_dim=14), [5, 3], 4648856),
+    ({}, dict(state_dim=4, n_levels=3, dim_mults=(1, 2, 4)), [0, 6, 3], 1975384),
+    ({}, dict(state_dim=14, n_levels=3, dim_mults=(1, 2, 4)), [0, 6, 3], 1976088),
+    ({}, dict(state_dim=4, n_levels=2, dim_mults=(1, 2)), [-1, 2], 330520),
+    ({}, dict(state_dim=33), [-1, 4, 1], 4590212),
+    ({}, dict(state_dim=64, n_levels=3, dim_mults=(1, 2, 4)), [-1, 6, 1], 1914368),
+    ({}, dict(state_dim=4, unet_input_dim=64, n_levels=3, dim_mults=(1, 2, 4)), [], 3895204),
+    ({}, dict(state_dim=4, n_support_points=128), [], 3956420),
+    ({"MPDX_NO_MERGE": "1"}, dict(state_dim=4), [-1, -1, 4, 1, 2], 4660440),
+    ({"MPDX_NO_MERGE": "1"}, dict(state_dim=4, n_levels=3, dim_mults=(1, 2, 4)), [-1, -1, 6, 1, 2], 1983576),
+    ({"MPDX_NO_MERGE_UP": "1"}, dict(state_dim=4), [5, 1, 2], 4652248),
+    ({"MPDX_MERGE_DOWN3": "0"}, dict(state_dim=4), [0, 4, 3], 4652248),
+    ({"MPDX_NO_MID2": "1"}, dict(state_dim=33), [-1, 1], 4239492),
+    ({"MPDX_NO_MID3": "1"}, dict(state_dim=4, n_levels=3, dim_mults=(1, 2, 4)), [0, 3], 1344600),
+]
+
+
+@pytest.mark.parametrize("env,kw,programs,packed_floats", SEGMENT_LAYOUTS)
+def test_segment_layout_totals_are_pinned(lib, env, kw, programs, packed_floats):
+    """Which layer ranges become programs, in which order, on which kernel, and how many floats their weight streams and parameter blocks add to
+    `packed` - for the standard networks, the odd ones (two levels, state dims that pad the input to 48 / 64 channels, width 64 and H = 128, which
+    build no segment) and every switch of build_units.  Programs 0, 3, 5 and 6 appear only when the computed LDS placement equals the table of
+    csrc/fused_geom.hpp byte for byte, so these few integers pin the placement too.  The numbers are the library's before the segment builder was
+    split into stages (csrc/fused_build.hpp); the switches are read per call."""
+    import os
+    saved = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        rc, h = _create(lib, **kw)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    assert rc == 0, (kw, lib.mpdx_last_error())
+    got = []
+    while lib.mpdx_unet_fused_program(h, len(got)) != -2:
+        got.append(lib.mpdx_unet_fused_program(h, len(got)))
+    floats = lib.mpdx_unet_packed_floats(h)
+    lib.mpdx_unet_destroy(h)
+    assert (got, floats) == (programs, packed_floats), (env, kw, got, floats)
+
+
 def test_elementwise_helpers_of_the_diffusion_class_match_the_oracle():
     """predict_start_from_noise / predict_noise_from_start / q_posterior (diffusion_model_base.py:109-141): kept on the class for callers that use them
     directly; plain tensor arithmetic on the schedule buffers (the planning loop runs the same formulas inside its fused kernels) - against the oracle."""

@@ -154,3 +154,79 @@ def test_measurement_helpers_guide_time_and_unit_bytes():
     n_conv = sum(v.numel() for k, v in net.state_dict().items() if k.endswith("weight") and v.dim() == 3 and not k.startswith("final_conv.1"))
     assert i == 15 and tot > 4.0 * n_conv   # two programs + thirteen per-layer / paired launches; at least every conv weight once
     assert lib.mpdx_unet_unit_bytes(hdl, B, i) == 0.0
+
+
+def _timing_entries_leave_the_handle_usable(H, fused_path):
+    """eps0 = forward; profile, time_units, time_without (nothing skipped / the last unit skipped), bench_layer; forward again: the same bits."""
+    import ctypes as C
+    import mpd_public_amd as m
+    from mpd_public_amd import _lib, synthetic as syn
+    lib = _lib.load()
+    B, D, T, t = 4, 4, 100, 50
+    net = m.TemporalUnet(n_support_points=H, state_dim=D, unet_input_dim=32, dim_mults=(1, 2, 4, 8))
+    net.load_state_dict(syn.synth_state_dict({k: tuple(v.shape) for k, v in net.state_dict().items()}), strict=True)
+    net = net.cuda()
+    hdl, packed, tab, ws = net.engine(T, B)
+    st = _lib.current_stream()
+    Hc = 1 << (H - 1).bit_length()   # the timing entries hand x to the layers as it is: backed by a whole container of rows for a padded horizon
+    g = torch.Generator().manual_seed(3)
+    xbuf = torch.zeros(B * Hc * D, device="cuda")
+    xbuf[:B * H * D] = torch.randn(B * H * D, generator=g).cuda()
+    x = xbuf[:B * H * D].view(B, H, D)
+    args = (hdl, packed.data_ptr(), tab.data_ptr(), net._timetab_T, x.data_ptr())
+
+    def forward():
+        eps = torch.empty(B, H, D, device="cuda")
+        _lib.check(lib.mpdx_unet_forward(*args, t, eps.data_ptr(), B, ws.data_ptr(), st), "mpdx_unet_forward")
+        torch.cuda.synchronize()
+        return eps
+    eps0 = forward()
+    assert bool(torch.isfinite(eps0).all()) and float(eps0.abs().max()) > 0
+    n_units = 0
+    while lib.mpdx_unet_unit_layer(hdl, B, n_units) >= 0 or lib.mpdx_unet_unit_bytes(hdl, B, n_units) > 0:
+        n_units += 1
+    cap = 128
+    ms, fl, names, n = (C.c_float * cap)(), (C.c_double * cap)(), (C.c_char_p * cap)(), C.c_int()
+    _lib.check(lib.mpdx_unet_profile(*args, t, B, ws.data_ptr(), st, cap, ms, fl, names, C.byref(n)), "mpdx_unet_profile")
+    got = [names[i].decode() for i in range(n.value)]
+    if fused_path:   # the last unit is the program that holds the final op: no separate final kernel
+        assert n.value == n_units and got[-1].startswith("fused[") and got[-1].endswith("+final_conv.1+ddpm_step]"), got
+    else:            # one launch per layer or pair, the final kernel behind them
+        assert n.value == n_units + 1 and got[-1] == "final_conv.1+ddpm_step" and not any(s.startswith("fused[") for s in got), got
+    assert all(got) and all(ms[i] > 0 for i in range(n.value)), (got, list(ms[:n.value]))
+    out = C.c_float()
+    _lib.check(lib.mpdx_unet_time_units(*args, t, B, ws.data_ptr(), st, 0, n_units - 1, 2, C.byref(out)), "mpdx_unet_time_units")
+    assert out.value > 0
+    for mask in (0, 1 << (n_units - 1)):
+        out = C.c_float()
+        _lib.check(lib.mpdx_unet_time_without(*args, t, B, ws.data_ptr(), st, C.c_uint64(mask), 2, C.byref(out)), "mpdx_unet_time_without")
+        assert out.value > 0, mask
+    out = C.c_float()
+    _lib.check(lib.mpdx_bench_layer(hdl, packed.data_ptr(), tab.data_ptr(), x.data_ptr(), 0, B, ws.data_ptr(), st, 2, 0, C.byref(out)), "mpdx_bench_layer")
+    assert out.value > 0
+    assert torch.equal(forward(), eps0)
+    # the trace entries exist in a development build only and say so
+    stamps = (C.c_longlong * 128)()
+    assert lib.mpdx_layer_trace(hdl, packed.data_ptr(), tab.data_ptr(), x.data_ptr(), 0, B, ws.data_ptr(), st, stamps) == -3
+    assert b"development build" in lib.mpdx_last_error() and b"mpdx_layer_trace" in lib.mpdx_last_error()
+    assert lib.mpdx_guide_trace(None, x.data_ptr(), None, B, H, D, st, stamps) == -3
+    assert b"development build" in lib.mpdx_last_error() and b"mpdx_guide_trace" in lib.mpdx_last_error()
+    assert torch.equal(forward(), eps0)
+
+
+@pytest.mark.parametrize("H,fused", [(64, True), (64, False), (48, True)], ids=["programs", "per_layer", "masked_H48"])
+def test_timing_entries_run_and_leave_the_handle_usable(H, fused):
+    """mpdx_unet_profile / _time_units / _time_without / mpdx_bench_layer on one handle each: on the fused programs (the last unit holds the final op),
+    with MPDX_FUSED=0 (read per call: per-layer launches with pairs and a separate final kernel) and on a horizon in a padded container (per layer by
+    construction).  Every entry returns 0 with a positive time, and the forward pass behind them gives the bits it gave before them."""
+    import os
+    saved = os.environ.get("MPDX_FUSED")
+    if not fused:
+        os.environ["MPDX_FUSED"] = "0"
+    try:
+        _timing_entries_leave_the_handle_usable(H, fused_path=fused and H == 64)
+    finally:
+        if saved is None:
+            os.environ.pop("MPDX_FUSED", None)
+        else:
+            os.environ["MPDX_FUSED"] = saved

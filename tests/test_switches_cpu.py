@@ -14,7 +14,7 @@ ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "mpd_public_amd" / "csrc"
 
 NAMES = """BWD_DBG DEBUG DEBUG_FUSE DEBUG_TRAIN FUSED FUSED_MASK GEO GUIDE_DENSE KSPLIT
-   LDS_CAP_KB MERGE_DOWN3 NO_MERGE NO_MERGE_UP NO_MID2 NO_MID3 PAIR PLAN_CHAINS
+   LDS_CAP_KB MERGE_DOWN3 NO_MERGE NO_MERGE_UP NO_MID2 NO_MID3 PAIR
    STATIC_PROGRAMS TARGET_WGS TILE TIME_TAIL_SPLIT TRAIN_BIAS_FOLD TRAIN_BWD_MID
    TRAIN_BWD_PROG TRAIN_BWD_PROG_MAX_B TRAIN_DEFERRED
    TRAIN_FUSED_FWD TRAIN_GN_FUSE TRAIN_GN_INPLACE TRAIN_PAIR TRAIN_PAIR_FWD
@@ -50,7 +50,7 @@ def test_getenv_only_in_switches_hpp():
 
 def test_table_is_the_known_set():
     t = table()
-    assert sorted(t) == sorted("MPDX_" + n for n in NAMES) and len(t) == 46
+    assert sorted(t) == sorted("MPDX_" + n for n in NAMES) and len(t) == 45
     for name, (fn, kind, dflt, timing, doc) in t.items():
         assert fn == name[len("MPDX_"):].lower(), (name, fn)
         assert kind in ("PRESENT", "ON", "INT", "UINT", "STR") and timing in ("ONCE", "LIVE") and doc.strip(), name

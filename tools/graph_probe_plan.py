@@ -1,5 +1,5 @@
-"""dev probe: a whole plan replayed as a hipGraph (torch.cuda.CUDAGraph capture of dm.plan), one chain vs two concurrent sub-batch chains
-(MPDX_PLAN_CHAINS is read once per process: run it once per setting).  Timing only - the captured noise is frozen."""
+"""dev probe: a whole plan replayed as a hipGraph (torch.cuda.CUDAGraph capture of dm.plan) against the same plan enqueued eagerly.
+Timing only - the captured noise is frozen."""
 import sys, time, os
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -40,4 +40,4 @@ t0 = time.perf_counter()
 for _ in range(10): g.replay()
 torch.cuda.synchronize()
 graph = (time.perf_counter() - t0) / 10 * 1e3
-print(f"{cfg} chains_env={os.environ.get('MPDX_PLAN_CHAINS', 'default')}  eager {eager:.3f} ms  graph replay {graph:.3f} ms  (capture+instantiate {cap:.1f} ms)  finite={bool(torch.isfinite(out[0]).all())}")
+print(f"{cfg}  eager {eager:.3f} ms  graph replay {graph:.3f} ms  (capture+instantiate {cap:.1f} ms)  finite={bool(torch.isfinite(out[0]).all())}")
