@@ -65,6 +65,14 @@ int mpdx_version(void);
 /* ---- model construction: replaces TemporalUnet(**unet_configs) + load_state_dict (inference.py:132-148) ---- */
 int    mpdx_unet_create(const mpdx_unet_cfg* cfg, mpdx_unet** out);
 void   mpdx_unet_destroy(mpdx_unet* u);
+/* Handle option of mpdx_plan (default on).  The reference's reverse loop (p_sample_loop, diffusion_model_base.py:157-182) feeds the x_{t-1} of one
+ * ddpm_sample_fn call (sample_functions.py:17-62) straight into the next call's model(x, t): on an unguided iteration that has a successor, mpdx_plan
+ * runs the step's last program (up levels + final_conv + DDPM update) and the next step's first program (down levels) as ONE launch, one workgroup
+ * per trajectory, where the standard four-level network on H = 64 runs and the batch is at most one workgroup per compute unit.  The results
+ * are bit-identical with the option off; every other entry point runs the separate kernels.  mpdx_unet_plan_joined: how many joined launches the last
+ * mpdx_plan call on this handle issued (0: the option is off or the network / batch does not admit it). */
+int    mpdx_unet_set_plan_join(mpdx_unet* u, int on);
+int    mpdx_unet_plan_joined(const mpdx_unet* u);
 /* number of state-dict tensors the model expects; their names/shapes (identical to the reference's keys) */
 int    mpdx_unet_num_params(const mpdx_unet* u);
 int    mpdx_unet_param_info(const mpdx_unet* u, int idx, const char** name, int32_t shape[3], int32_t* ndim);

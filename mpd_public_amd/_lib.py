@@ -75,6 +75,8 @@ SIGNATURES = {
     "mpdx_version": (_i, []),
     "mpdx_unet_create": (_i, [C.POINTER(UnetCfg), C.POINTER(_vp)]),
     "mpdx_unet_destroy": (None, [_vp]),
+    "mpdx_unet_set_plan_join": (_i, [_vp, _i]),
+    "mpdx_unet_plan_joined": (_i, [_vp]),
     "mpdx_unet_num_params": (_i, [_vp]),
     "mpdx_unet_param_info": (_i, [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_int32 * 3), C.POINTER(C.c_int32)]),
     "mpdx_unet_packed_floats": (_sz, [_vp]),

@@ -153,6 +153,22 @@ struct FusedArgs {
     long long* trace;    // dev tool: s_memtime stamps of workgroup 0, 128 slots per wave (null in production)
 };
 
+// fused_join_kernel (end of this file): what the DOWN part of a joined launch needs at run time.  Everything else of the down program is its compile-time
+// geometry table; the up part carries a whole FusedArgs.  (Two FusedArgs by value would be 2.9 KB of kernel arguments; this block adds 120 bytes.)
+struct FusedJoinDown {
+    const float* packed;
+    const float* tt_row;         // conditioning row of the NEXT timestep (the down part belongs to the pass after the up part's)
+    float* gout[3];
+    int gpar_off, tt_lo;
+    int sbase[kMaxFusedOps];     // FusedOp::sbase of the down program's ops
+};
+struct FusedJoinArgs { FusedArgs up; FusedJoinDown dn; };
+__device__ __forceinline__ FusedOp fused_runtime_desc(const FusedJoinDown& a, int i) {
+    FusedOp op = {};
+    op.sbase = a.sbase[i]; op.save_out = op.save_pre = -1;
+    return op;
+}
+
 // The LDS layout scalars of a program as the kernels read them: compile-time constants for a static program with a geometry table
 // (fused_geom.hpp; everything folds into immediates), the argument block's fields otherwise.
 struct FusedLay {
@@ -237,8 +253,9 @@ __device__ __forceinline__ float row_sum16(float v) {
 //   to it; after the last conv op both describe any valid block)
 // SAVE: the training forward's variant (every op also stores its output and its GroupNorm input through FusedArgs::save); the planning
 // kernels are instantiated without it (measured on one box: 22.54 vs 22.62 ms per cfg-2 plan with the stores merely compiled in)
-template <class S, bool SAVE = false>
-__device__ __forceinline__ void fused_conv_op(const FusedArgs& a, const FusedLay& lay, const FusedOp& op, f32x4 (&ring)[kFusedRing], float* smem, int wave, int lane, int b,
+// A: the argument block the op reads `packed`, `gout` (and, SAVE, `save`) from: FusedArgs, or FusedJoinDown for the down part of fused_join_kernel
+template <class S, bool SAVE = false, class A = FusedArgs>
+__device__ __forceinline__ void fused_conv_op(const A& a, const FusedLay& lay, const FusedOp& op, f32x4 (&ring)[kFusedRing], float* smem, int wave, int lane, int b,
                                               int nbase, int nmax, long long* tr_base, int& tr) {
     constexpr int P = kFusedRing, DB = MPDX_FUSED_DB, NTW = S::NTW, NJ = S::NJ;
     f32x4* const sm4 = (f32x4*)smem;
@@ -369,7 +386,7 @@ __device__ __forceinline__ void fused_conv_op(const FusedArgs& a, const FusedLay
                 have_add = true;
             }
             v[t] = (acc[t][0] + acc[t][1]) + bi;
-            if (SAVE && op.save_pre >= 0) *(f32x4*)(a.save + op.save_pre + ((size_t)b * S::LOUT + npos[t]) * S::COUT + c0) = v[t];
+            if constexpr (SAVE) if (op.save_pre >= 0) *(f32x4*)(a.save + op.save_pre + ((size_t)b * S::LOUT + npos[t]) * S::COUT + c0) = v[t];
         }
         // sum over the rows of a lane's group that live in other DPP rows of this wave (LOCAL only)
         auto rows_sum = [&](float x) -> float {
@@ -442,7 +459,7 @@ __device__ __forceinline__ void fused_conv_op(const FusedArgs& a, const FusedLay
         if (!col_ok) continue;
         if (op.dst_off4 >= 0) sm4[op.dst_off4 + (npos[t] + 2) * op.dst_rs4 + (c0t[t] >> 2)] = y[t];
         if (op.gdst >= 0) *(f32x4*)(a.gout[op.gdst] + ((size_t)b * S::LOUT + npos[t]) * S::COUT + c0t[t]) = y[t];
-        if (SAVE && op.save_out >= 0) *(f32x4*)(a.save + op.save_out + ((size_t)b * S::LOUT + npos[t]) * S::COUT + c0t[t]) = y[t];
+        if constexpr (SAVE) if (op.save_out >= 0) *(f32x4*)(a.save + op.save_out + ((size_t)b * S::LOUT + npos[t]) * S::COUT + c0t[t]) = y[t];
     }
     if (op.dst_off4 >= 0) {   // halo rows of the buffer this op defines (2 above, 2 below its L_out interior rows)
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
@@ -614,7 +631,9 @@ __device__ __forceinline__ void fused_final_prefetch(const FusedArgs& a, const F
 
 // CF: the channel count of final_conv[0] when the program fixes it (static programs: the dot product unrolls, its 2 * CF / 4 LDS
 // reads are issued together), 0 = read it from the argument block.
-template <int CF = 0>
+// JOIN_OFF4 >= 0 (fused_join_kernel): x_{t-1} also goes into the interior rows of the NEXT pass's staged input buffer at JOIN_OFF4 (row stride JOIN_RS4
+// float4) - after hard conditioning, the bits that go to `out`.
+template <int CF = 0, int JOIN_OFF4 = -1, int JOIN_RS4 = 0>
 __device__ __forceinline__ void fused_final_op(const FusedArgs& a, const FusedLay& lay, const FusedOp& op, const FinalPre& fp, float* smem, int tid, int lane, int b) {
     f32x4* const sm4 = (f32x4*)smem;
     constexpr int NT_ = kFusedThreads;
@@ -685,6 +704,7 @@ __device__ __forceinline__ void fused_final_op(const FusedArgs& a, const FusedLa
         }
         a.out[o] = r;
         if (a.chain) a.chain[o] = r;
+        if constexpr (JOIN_OFF4 >= 0) smem[(JOIN_OFF4 + (p + 2) * JOIN_RS4) * 4 + d] = r;
         vmax = fmaxf(vmax, fabsf(r));
     }
     if (a.absmax) {
@@ -749,9 +769,10 @@ MPDX_FUSED_SHAPES(X)
 
 // op I of a static program: the runtime descriptor (weight-stream base, training offsets) with every LDS geometry field replaced by the
 // program's compile-time table entry, when it has one
-template <class GEOM, int I, bool SAVE>
-__device__ __forceinline__ FusedOp fused_static_desc(const FusedArgs& a) {
-    FusedOp op = a.ops[I];
+__device__ __forceinline__ FusedOp fused_runtime_desc(const FusedArgs& a, int i) { return a.ops[i]; }
+template <class GEOM, int I, bool SAVE, class A = FusedArgs>
+__device__ __forceinline__ FusedOp fused_static_desc(const A& a) {
+    FusedOp op = fused_runtime_desc(a, I);
     if constexpr (GEOM::has) {
         constexpr FusedGeomOp g = GEOM::g.ops[I];
         op.shape = g.shape;
@@ -832,5 +853,161 @@ using FusedSeqUpAB = FusedSeq<GeomUpAB, 8, 9, 10, 10, 11, 12, 13, 14, 14, 15, 2,
 using FusedSeqDown3 = FusedSeq<GeomDown3, 0, 1, 2, 2, 3, 4, 5, 6, 6, 7, 16, 17, 18, 18, 19>;   // downs.0 + downs.1 + downs.2 in one launch
 using FusedSeqMid2 = FusedSeq<GeomNone, 16, 17, 18, 18, 19>;                                 // downs.2 (C = 128, L = 16): two tile rows per wave
 using FusedSeqMid3 = FusedSeq<GeomMid3, 16, 17, 18, 18, 18, 18, 18, 18>;                     // three-level network: downs.2 (no Downsample1d) + mid_block1 + mid_block2
+
+
+// ---- JOINED launch of the planning loop: the up program of step k, then - in the same workgroup - the down program of step k + 1.
+// The up program ends in the DDPM update of trajectory b and the next pass's down program starts from exactly that trajectory, one workgroup per
+// trajectory both: no workgroup waits for another.  The junction replaces a launch boundary and the down program's prologue (cold kernarg fetch, cold
+// first touch of input / parameters / conditioning row, first weight blocks): x_{t-1} goes from the final op's registers into the down program's
+// staged-input buffer, the down program's parameter block and conditioning slice are requested at kernel entry into an LDS region of their own,
+// and the weight ring of the last up conv op runs on into the down program's op 0 as it runs across any two ops.  The arithmetic of every op is
+// the separate kernels' (same functions, same order): the chain is bit-identical.
+//
+// LDS: [0, kJoinTail) is the up program's layout as it stands; the down program's ACTIVATION buffers overlay it from 0 (all of the up program's
+// buffers are dead after the final op - the one still read while x_{t-1} is written is the final op's source, which the staged-input buffer
+// does not touch: static_assert below); the down program's tail (GroupNorm exchange | conditioning slice | parameters) is live from the prologue
+// on and sits behind the up program's, at kJoinTail.  84 KB in all: the host selects the joined kernel only where one workgroup per CU runs anyway.
+constexpr int kJoinTail = 16512;   // floats; >= the up program's end at state_dim 16 (par_off 13312 + fpar_off 2048 + 16 * (Cf 32 + 4) + 16 = 15 952), with room for Cf = 64
+
+template <class SU, class SD>
+struct FusedJoinLay {
+    static constexpr FusedGeom gu = SU::GEOM::g, gd = SD::GEOM::g;
+    static constexpr int shift = kJoinTail - gd.stat_off;                     // the down program's tail moves up by this many floats
+    static constexpr int stat_off = gd.stat_off + shift, tt_off = gd.tt_off + shift, par_off = gd.par_off + shift;
+    static constexpr int lds_floats = par_off + gd.par_floats;
+    static constexpr int npar4 = gd.par_floats / 4, ntt4 = gd.tt_n / 4;
+    static constexpr int JK = (npar4 + ntt4 + kFusedThreads - 1) / kFusedThreads;   // float4 per thread of the early parameter request
+    static constexpr int fsrc_off4 = gu.ops[SU::N - 1].src_off4, fsrc_rs4 = gu.ops[SU::N - 1].src_rs4;   // the final op's source buffer
+    static_assert(SU::GEOM::has && SD::GEOM::has, "joined programs need geometry tables");
+    static_assert(SU::ids[SU::N - 1] == kFusedShapeFinal && SU::ids[SU::N - 2] != kFusedShapeFinal, "the up program ends in conv op + final op");
+    static_assert(gd.gc1 < 0 && gd.c3 == 0 && gd.L0 == gu.H, "the down program starts from the network input");
+    static_assert(gd.par_floats >= 0 && gd.par_floats % 4 == 0 && gd.tt_n % 4 == 0, "down parameters: whole float4");
+    static_assert(gu.par_off + gu.fpar_off + 16 * (gu.Cf + 4) + 16 <= kJoinTail && gd.stat_off <= kJoinTail, "down tail behind both programs' other areas");
+    static_assert(gd.in_off4 + gd.in_rows * gd.in_rs4 <= fsrc_off4 || fsrc_off4 + (gu.H + 4) * fsrc_rs4 <= gd.in_off4, "staged input overlaps the final op's source");
+    static_assert((gd.in_off4 + gd.in_rows * gd.in_rs4) * 4 <= gu.stat_off, "staged input overlaps the up program's tail");
+    static_assert(2 * gd.in_rs4 <= kFusedThreads, "the junction zeroes the halo rows in one pass of the workgroup");
+};
+
+template <class SU, class SD, int I>
+__device__ __forceinline__ void fused_join_up_from(const FusedArgs& a, const FusedJoinDown& dn, const FusedLay& lay, f32x4 (&ring)[kFusedRing], FinalPre& fp, float* smem,
+                                                   int tid, int wave, int lane, int b, long long* tr_base, int& tr) {
+    using GU = typename SU::GEOM;
+    if constexpr (I < SU::N) {
+        constexpr int SH = SU::ids[I], NEXT = I + 1 < SU::N ? SU::ids[I + 1 < SU::N ? I + 1 : I] : -1;
+        if constexpr (SH == kFusedShapeFinal) {
+            const FusedOp op = fused_static_desc<GU, I, false>(a);
+            fused_final_op<SU::template prev_cout<I>(), SD::GEOM::g.in_off4, SD::GEOM::g.in_rs4>(a, lay, op, fp, smem, tid, lane, b);
+            if (tr_base) tr_base[tr] = (long long)__builtin_readcyclecounter();
+            ++tr;
+        } else if constexpr (NEXT == kFusedShapeFinal) {
+            // the last conv op: as fused_static_op, but the ring's cross-over requests are the down program's first blocks
+            fused_final_prefetch(a, lay, fp, tid, b);
+            const FusedOp op = fused_static_desc<GU, I, false>(a);
+            using N0 = typename FusedShapeOf<SD::ids[0]>::type;
+            const int nbase = (dn.sbase[0] + (wave & (N0::MSn < kFusedWaves ? N0::MSn - 1 : kFusedWaves - 1)) * (N0::SLEN * 256)) * 4;
+            fused_conv_op<typename FusedShapeOf<SH>::type, false>(a, lay, op, ring, smem, wave, lane, b, nbase, N0::SLEN - 1, tr_base, tr);
+        } else {
+            fused_static_op<GU, SH, I, NEXT, SU::template prev_cout<I>(), false>(a, lay, ring, fp, smem, tid, wave, lane, b, tr_base, tr);
+        }
+        fused_join_up_from<SU, SD, I + 1>(a, dn, lay, ring, fp, smem, tid, wave, lane, b, tr_base, tr);
+    }
+}
+
+template <class SD, int I>
+__device__ __forceinline__ void fused_join_down_from(const FusedJoinDown& dn, const FusedLay& lay, f32x4 (&ring)[kFusedRing], float* smem, int wave, int lane, int b,
+                                                     long long* tr_base, int& tr) {
+    if constexpr (I < SD::N) {
+        const FusedOp op = fused_static_desc<typename SD::GEOM, I, false>(dn);
+        int nbase = dn.sbase[I] * 4;
+        int nmax = 0;
+        if constexpr (I + 1 < SD::N) {
+            using N = typename FusedShapeOf<SD::ids[I + 1 < SD::N ? I + 1 : I]>::type;
+            nbase = (dn.sbase[I + 1] + (wave & (N::MSn < kFusedWaves ? N::MSn - 1 : kFusedWaves - 1)) * (N::SLEN * 256)) * 4;
+            nmax = N::SLEN - 1;
+        }
+        // (a wave's 128 trace slots end inside the down part: its later ops go unstamped)
+        fused_conv_op<typename FusedShapeOf<SD::ids[I]>::type, false>(dn, lay, op, ring, smem, wave, lane, b, nbase, nmax, tr + 5 <= 128 ? tr_base : nullptr, tr);
+        fused_join_down_from<SD, I + 1>(dn, lay, ring, smem, wave, lane, b, tr_base, tr);
+    }
+}
+
+template <class SU, class SD>
+__global__ __launch_bounds__(kFusedThreads) void fused_join_kernel(const FusedJoinArgs ja) {
+#ifndef MPDX_NO_WARM_KERNARG
+    warm_kernarg<(int)sizeof(FusedJoinArgs)>();
+#endif
+    using JL = FusedJoinLay<SU, SD>;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    f32x4* const sm4 = (f32x4*)smem;
+    const FusedArgs& a = ja.up;
+    const FusedJoinDown& dn = ja.dn;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x;
+    int tr = 0;
+    long long* const tr_base = (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wave * 128 : nullptr;
+    if (tr_base) tr_base[tr] = (long long)__builtin_readcyclecounter();
+    ++tr;
+    // the down part's parameter block and its slice of the next timestep's conditioning row: requested with the up prologue's loads, so
+    // that their cold first touch (~1.4 us) is one round trip with everything else the launch touches first
+    f32x4 jv[JL::JK];
+#pragma unroll
+    for (int k = 0; k < JL::JK; ++k) {
+        const int idx = tid + k * kFusedThreads;
+        const int it = idx - JL::npar4 < JL::ntt4 ? idx - JL::npar4 : 0;   // (clamped: the last pass is partial)
+        const float* src = idx < JL::npar4 ? dn.packed + dn.gpar_off + (size_t)idx * 4 : dn.tt_row + dn.tt_lo + (size_t)it * 4;
+        jv[k] = *(const f32x4*)src;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    f32x4 ring[kFusedRing];
+    FinalPre fp;
+    const FusedLay lay = fused_lay<typename SU::GEOM>(a);
+    fused_prologue<typename SU::GEOM>(a, lay, smem, ring, tid, lane, wave, b, tr_base, tr);
+    // (region [kJoinTail, ...) belongs to nobody else; first read after the junction's barrier)
+#pragma unroll
+    for (int k = 0; k < JL::JK; ++k) {
+        const int idx = tid + k * kFusedThreads;
+        if (idx < JL::npar4) sm4[(JL::par_off >> 2) + idx] = jv[k];
+        else if (idx - JL::npar4 < JL::ntt4) sm4[(JL::tt_off >> 2) + idx - JL::npar4] = jv[k];
+    }
+    fused_join_up_from<SU, SD, 0>(a, dn, lay, ring, fp, smem, tid, wave, lane, b, tr_base, tr);
+
+    // ---- junction.  The final op has written x_{t-1} to `out` (the next up part's final op reads x_in there; the chain row likewise) and into the
+    // interior rows of the down program's staged-input buffer; here the rest of what fused_prologue produces: zero halo rows, zero channel padding.
+    //
+    // Global memory: the down part below overwrites workspace slots (its gout[0..2]: the two skip tensors and the L = 8 output) that the up part
+    // of THIS launch has read as gsrc2 / gsrc3 (and possibly gsrc1, when slots are re-used).  That is safe because (1) the up part reads its three
+    // global inputs in fused_prologue only - they are in LDS before the prologue's barrier - and its ops have no global source or destination
+    // (GeomUpAB: every gdst is -1; the final op reads x_in / noise / hard conditions and writes out / chain, none of them a workspace slot), and (2) every
+    // global address of either part is indexed by this workgroup's trajectory b: no workgroup reads or writes another trajectory's rows.
+    {
+        constexpr FusedGeom gd = SD::GEOM::g;
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        if (tid < 2 * gd.in_rs4) {
+            sm4[gd.in_off4 + tid] = z;
+            sm4[gd.in_off4 + (gd.in_rows - 2) * gd.in_rs4 + tid] = z;
+        }
+        const int D = a.D;
+#pragma unroll
+        for (int k = 0; k < (gd.L0 * gd.in_rs4 + kFusedThreads - 1) / kFusedThreads; ++k) {
+            const int i = tid + k * kFusedThreads;
+            if (i >= gd.L0 * gd.in_rs4) continue;
+            const int l = i / gd.in_rs4, c = (i - l * gd.in_rs4) * 4;      // row, first channel of this float4 column
+            const int at = gd.in_off4 + (l + 2) * gd.in_rs4 + (c >> 2);
+            if (c >= D) sm4[at] = z;
+            else if (c + 4 > D) {
+#pragma unroll
+                for (int e = 1; e < 4; ++e)
+                    if (c + e >= D) smem[at * 4 + e] = 0.f;
+            }
+        }
+    }
+    lds_barrier();
+    if (tr_base) tr_base[tr] = (long long)__builtin_readcyclecounter();
+    ++tr;
+    FusedLay dlay = {};
+    dlay.stat_off = JL::stat_off; dlay.par_off = JL::par_off; dlay.tt_off = JL::tt_off;
+    fused_join_down_from<SD, 0>(dn, dlay, ring, smem, wave, lane, b, tr_base, tr);
+}
 
 }  // namespace mpdx

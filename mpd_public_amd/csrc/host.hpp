@@ -118,6 +118,8 @@ struct mpdx_unet {
     // the network input is copied into workspace slot `xpad_slot` ([B][Hc][D], zero rows behind the H real ones) at the head of a pass
     int Hc = 0, xpad_slot = -1;
     bool masked() const { return Hc != cfg.n_support_points; }
+    int plan_joined = 0;      // joined launches of the last mpdx_plan call (mpdx_unet_plan_joined)
+    int plan_join = 1;        // mpdx_unet_set_plan_join: mpdx_plan may run a step's up program and the next step's down program as one launch
     // launch units: fused whole-trajectory segments (fused_level.hpp) or single layers
     struct CopyJob { size_t src, dst; int n0, ss0, ds0, n1, ss1, ds1, n_inner; };   // strided copy inside `packed` (float units)
     struct Fused {
@@ -181,6 +183,8 @@ int launch_weight_stationary(int variant, const Layer& l, ConvArgs& a, const Con
 // ---- k_fused.hip (planning programs) / k_fused_train.hip (the variants that keep activations for the backward pass)
 int launch_fused_args(const mpdx_unet::Fused& f, const FusedArgs& a, int B, hipStream_t st, bool save = false);
 int launch_fused_train(const mpdx_unet::Fused& f, const FusedArgs& a, int B, hipStream_t st);
+int launch_fused_join(const FusedJoinArgs& ja, int B, hipStream_t st);   // fused_join_kernel<FusedSeqUpAB, FusedSeqDown3> (programs 3 and 5)
+size_t fused_join_lds_bytes();
 // ---- k_guide.hip
 struct NoiseRng;
 int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const float* hs, const float* hg, const uint32_t* amax_in,

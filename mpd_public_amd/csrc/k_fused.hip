@@ -41,4 +41,12 @@ int launch_fused_args(const mpdx_unet::Fused& f, const FusedArgs& a, int B, hipS
     return 0;
 }
 
+// the joined launch of the planning loop: up program (both up levels + final op) of one step, down program (three down levels) of the next
+size_t fused_join_lds_bytes() { return (size_t)FusedJoinLay<FusedSeqUpAB, FusedSeqDown3>::lds_floats * sizeof(float); }
+int launch_fused_join(const FusedJoinArgs& ja, int B, hipStream_t st) {
+    if (int rc = raise_lds_limit((const void*)fused_join_kernel<FusedSeqUpAB, FusedSeqDown3>)) return rc;
+    hipLaunchKernelGGL((fused_join_kernel<FusedSeqUpAB, FusedSeqDown3>), dim3(B), dim3(kFusedThreads), fused_join_lds_bytes(), st, ja);
+    return 0;
+}
+
 }  // namespace mpdx

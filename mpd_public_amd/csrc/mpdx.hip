@@ -755,12 +755,12 @@ int claim_fused_stream_jobs(mpdx_unet* u, const float* packed, const void** jobs
 
 // programs that exist in the training-forward variant (the two of the standard 4-level network, and the generic op-list kernel)
 bool fused_save_variant(const mpdx_unet::Fused& f) { return f.program == 0 || f.program == 3 || f.program == 5 || f.program == 6 || f.program < 0; }
-static int run_fused(mpdx_unet* u, const mpdx_unet::Fused& f, const float* packed, const float* tt_row, const float* x, float* ws,
-                     int B, const FinalArgs* fa, hipStream_t st) {
+// the argument block of one launch of segment f
+static int fill_fused_args(mpdx_unet* u, const mpdx_unet::Fused& f, const float* packed, const float* tt_row, const float* x, float* ws,
+                           int B, const FinalArgs* fa, FusedArgs& a) {
     const size_t slot = u->slot_floats * (size_t)B;
     auto src = [&](int s) -> const float* { return s == SRC_X ? x : (s == SRC_NONE ? nullptr : ws + slot * s); };
-    if (int rc = ensure_fused_streams(u, packed, st)) return rc;
-    FusedArgs a = f.tmpl;
+    a = f.tmpl;
     a.packed = packed; a.tt_row = tt_row;
     a.gsrc1 = src(f.in1); a.gsrc2 = src(f.in2);
     a.gsrc3 = f.in3 != SRC_NONE ? src(f.in3) : a.gsrc1;
@@ -773,7 +773,30 @@ static int run_fused(mpdx_unet* u, const mpdx_unet::Fused& f, const float* packe
         a.absmax = fa->absmax; a.fmode = fa->mode; a.n_per_ctx = fa->n_per_ctx > 0 ? fa->n_per_ctx : B; a.k = fa->k;
         a.rng = fa->rng;
     }
+    return 0;
+}
+static int run_fused(mpdx_unet* u, const mpdx_unet::Fused& f, const float* packed, const float* tt_row, const float* x, float* ws,
+                     int B, const FinalArgs* fa, hipStream_t st) {
+    if (int rc = ensure_fused_streams(u, packed, st)) return rc;
+    FusedArgs a;
+    if (int rc = fill_fused_args(u, f, packed, tt_row, x, ws, B, fa, a)) return rc;
     return launch_fused_args(f, a, B, st);
+}
+// mpdx_plan only: the up program `up` of a pass (row `tt_row`, step `fa`) and the down program `dn` of the NEXT pass (row `tt_next`) as one launch
+// (fused_join_kernel).  The down part starts from the x_{t-1} the up part has just computed, so its global input pointer is not used.
+static int run_fused_join(mpdx_unet* u, const mpdx_unet::Fused& up, const mpdx_unet::Fused& dn, const float* packed, const float* tt_row, const float* tt_next,
+                          const float* x, float* ws, int B, const FinalArgs* fa, hipStream_t st, long long* trace = nullptr) {
+    if (int rc = ensure_fused_streams(u, packed, st)) return rc;
+    FusedJoinArgs ja;
+    FusedArgs d;
+    if (int rc = fill_fused_args(u, up, packed, tt_row, x, ws, B, fa, ja.up)) return rc;
+    if (int rc = fill_fused_args(u, dn, packed, tt_next, x, ws, B, nullptr, d)) return rc;
+    ja.up.trace = trace;   // dev tool (mpdx_fused_trace with seg == number of segments); null in the plan
+    ja.dn.packed = d.packed; ja.dn.tt_row = d.tt_row;
+    for (int k = 0; k < 3; ++k) ja.dn.gout[k] = d.gout[k];
+    ja.dn.gpar_off = d.gpar_off; ja.dn.tt_lo = d.tt_lo;
+    for (int k = 0; k < kMaxFusedOps; ++k) ja.dn.sbase[k] = k < d.nops ? d.ops[k].sbase : 0;
+    return launch_fused_join(ja, B, st);
 }
 
 
@@ -867,6 +890,34 @@ static int run_unet_and_final(mpdx_unet* u, const float* packed, const float* ti
     return walk_pass(u, current_units(u, B, nullptr), packed, row, x, ws, B, fa, st, [](PassEvent, int) { return 0; });
 }
 
+// One pass of mpdx_plan's loop.  skip_down: the pass's first unit - the down program - has already run as the tail of the pass before; tt_next != null:
+// the pass's last unit - the up program - runs joined with the next pass's down program (can_join_passes holds).  Neither: run_unet_and_final.
+static int run_plan_pass(mpdx_unet* u, const float* packed, const float* timetab, int T, const float* x, int t, int B, float* ws, FinalArgs& fa,
+                         hipStream_t st, bool skip_down, const float* tt_next) {
+    if (!skip_down && !tt_next) return run_unet_and_final(u, packed, timetab, T, x, t, B, ws, fa, st);
+    const float* row = timetab + (size_t)t * u->tt_row;
+    const auto units = current_units(u, B, nullptr);
+    const int n = (int)units.size();
+    for (int i = skip_down ? 1 : 0; i < n - (tt_next ? 1 : 0); ++i)
+        if (int rc = run_unit(u, units[i], packed, row, x, ws, B, &fa, st)) return rc;
+    if (tt_next) return run_fused_join(u, u->fused[units[n - 1].fused], u->fused[units[0].fused], packed, row, tt_next, x, ws, B, &fa, st);
+    return 0;
+}
+// Can mpdx_plan join passes at batch B?  The pass starts with the three-level down program from the network input and ends with the two-level up
+// program that holds the final op (the standard four-level network on a power-of-two horizon of 64), and one workgroup per CU runs anyway: the
+// joined kernel's 84 KB of LDS admit one workgroup per CU where the separate programs (59.1 / 63.5 KB) admit two.
+static bool can_join_passes(const mpdx_unet* u, int B) {
+    if (!u->plan_join || u->masked()) return false;
+    const auto units = current_units(u, B, nullptr);
+    if (units.size() < 2 || units.front().fused < 0 || units.back().fused < 0 || units.front().fused == units.back().fused) return false;
+    const mpdx_unet::Fused& dn = u->fused[units.front().fused];
+    const mpdx_unet::Fused& up = u->fused[units.back().fused];
+    if (dn.program != 5 || dn.in1 != SRC_X || dn.in2 != SRC_NONE || dn.has_final || up.program != 3 || !up.has_final) return false;
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
+    return B <= cus;
+}
+
 // the trace / ablation entry points exist in a development build only: 0 there, else the error that says how to make one
 int dev_hooks_missing(const char* fn) {
 #ifdef MPDX_DEV_HOOKS
@@ -934,6 +985,13 @@ int mpdx_unet_create(const mpdx_unet_cfg* cfg, mpdx_unet** out) {
     *out = u;
     return 0;
 }
+
+int mpdx_unet_set_plan_join(mpdx_unet* u, int on) {
+    if (!u) return fail(MPDX_E_INVALID, "null argument");
+    u->plan_join = on ? 1 : 0;
+    return 0;
+}
+int mpdx_unet_plan_joined(const mpdx_unet* u) { return u ? u->plan_joined : 0; }
 
 void mpdx_unet_destroy(mpdx_unet* u) {
     if (u && u->pack_descs_dev) (void)hipFree(u->pack_descs_dev);
@@ -1104,10 +1162,17 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
     // x_T with hard conditioning; chain[0]
     hipLaunchKernelGGL(add_noise_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, st, x, (const float*)nullptr,
                        hard_start, hard_goal, 0.f, 0.f, chain, B, H, D);
+    // An unguided iteration that has a successor runs its up program and the successor's down program as ONE launch (nothing modifies x between the
+    // two); the successor then starts at its second unit.  Whether the successor is guided does not matter.
+    const bool join_ok = can_join_passes(u, B);
+    bool down_done = false;   // this iteration's down program ran as the tail of the iteration before
+    u->plan_joined = 0;
     int k = 0;
     for (int i = T - 1; i >= -n_without_noise; --i, ++k) {
         const int t = i < 0 ? 0 : i;
         const bool guided = guide && i < t_start_guide;  // sample_functions.py:39 compares the un-clamped index
+        const bool join = join_ok && !guided && i > -n_without_noise;
+        const float* tt_next = join ? timetab + (size_t)(i - 1 < 0 ? 0 : i - 1) * u->tt_row : nullptr;
         const float* nz = (t == 0 || !noise) ? nullptr : noise + (size_t)k * n;  // noise[t == 0] = 0  (sample_functions.py:52)
         // noise == NULL: the step's draw is generated in place; iteration k uses elements [(k+1) n, (k+2) n) of the stream whose
         // first n elements are x_T (what mpdx_randn(x, n, seed, offset) wrote): the same bits a pre-generated tensor would hold
@@ -1127,7 +1192,9 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
         } else {
             fa.mode = 2; fa.absmax = fl;  // posterior mean + its max|.| per context
         }
-        if (int rc = run_unet_and_final(u, packed, timetab, T, x, t, B, ws, fa, st)) return rc;
+        if (int rc = run_plan_pass(u, packed, timetab, T, x, t, B, ws, fa, st, down_done, tt_next)) return rc;
+        down_done = join;
+        u->plan_joined += join ? 1 : 0;
         if (guided) {
             for (int j = 0; j < n_guide_steps; ++j) {
                 const bool last = j == n_guide_steps - 1;  // the last iteration also adds the noise term and appends to the chain

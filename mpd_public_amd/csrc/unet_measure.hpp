@@ -121,11 +121,15 @@ int mpdx_layer_trace(mpdx_unet* u, const float* packed, const float* timetab, co
     return 0;
 }
 
-/* dev tool: run fused segment `seg` once with per-phase s_memtime stamps of workgroup 0 / wave 0; stamps_out[n] */
+/* dev tool: run fused segment `seg` once with per-phase s_memtime stamps of workgroup 0 / wave 0; stamps_out[n].
+ * seg == number of segments: the JOINED launch of mpdx_plan (up program of a pass + down program of the next, fused_join_kernel), in the same context;
+ * its stamps are the up program's, one after the junction's barrier, then five per down op as far as a wave's 128 slots reach; *nops_out = both programs' ops */
 int mpdx_fused_trace(mpdx_unet* u, const float* packed, const float* timetab, const float* x, int seg, int B, float* ws, void* stream,
                      long long* stamps_out, int cap, int* n_out, int* nops_out) {
     if (int rc = dev_hooks_missing(__func__)) return rc;
-    if (!u || seg < 0 || seg >= (int)u->fused.size()) return fail(MPDX_E_INVALID, "bad segment");
+    if (!u || seg < 0 || seg > (int)u->fused.size()) return fail(MPDX_E_INVALID, "bad segment");
+    const bool joined = seg == (int)u->fused.size();
+    if (joined && !can_join_passes(u, B)) return fail(MPDX_E_INVALID, "bad segment (this network / batch has no joined launch)");
     if (int rc = check_ready(u)) return rc;
     hipStream_t st = (hipStream_t)stream;
     DevStamps dev;
@@ -137,6 +141,14 @@ int mpdx_fused_trace(mpdx_unet* u, const float* packed, const float* timetab, co
     ResetOnExit<long long*> untrace{g_fused_trace, nullptr};
     ResetOnExit<int> unselect{g_fused_trace_seg, -1};
     for (int pass = 0; pass < 3; ++pass) {
+        if (pass == 2 && joined) {   // the pass as mpdx_plan runs it when the next one follows unguided: its last unit is the joined launch
+            const auto units = current_units(u, B, nullptr);
+            const int nu = (int)units.size();
+            for (int i = 0; i + 1 < nu; ++i)
+                if (int rc = run_unit(u, units[i], packed, timetab, x, ws, B, &fa, st)) return rc;
+            if (int rc = run_fused_join(u, u->fused[units[nu - 1].fused], u->fused[units[0].fused], packed, timetab, timetab, x, ws, B, &fa, st, dev.p)) return rc;
+            break;
+        }
         if (pass == 2) { g_fused_trace = dev.p; g_fused_trace_seg = seg; }
         if (int rc = run_unet_and_final(u, packed, timetab, 1 << 30, x, 0, B, ws, fa, st)) return rc;
     }
@@ -144,7 +156,10 @@ int mpdx_fused_trace(mpdx_unet* u, const float* packed, const float* timetab, co
     const int n = std::min(cap, 1024);   // 8 waves x 128 slots
     HIP_TRY(hipMemcpy(stamps_out, dev.p, n * sizeof(long long), hipMemcpyDeviceToHost));
     if (n_out) *n_out = n;
-    if (nops_out) *nops_out = u->fused[seg].tmpl.nops;
+    if (nops_out) {
+        if (joined) { const auto units = current_units(u, B, nullptr); *nops_out = u->fused[units.back().fused].tmpl.nops + u->fused[units.front().fused].tmpl.nops; }
+        else *nops_out = u->fused[seg].tmpl.nops;
+    }
     return 0;
 }
 

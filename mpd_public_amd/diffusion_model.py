@@ -180,6 +180,9 @@ class GaussianDiffusionModel(nn.Module):
             n_gs = int(n_guide_steps)
             t_sg = int(min(t_start_guide, T + 1)) if t_start_guide != float("inf") else T + 1
             flags = torch.empty(steps * (n_gs + 1) * ((B + npc - 1) // npc), dtype=torch.int32, device=dev)
+        # diagnostic hook (tests compare it between two plans): mpdx_plan's guide_flags of the LAST plan, [steps][n_guide_steps + 1][contexts] int32 on the
+        # device, None after an unguided plan.  Not part of the reference's interface; it keeps steps * (n_guide_steps + 1) * contexts * 4 bytes alive.
+        self.last_guide_flags = flags
         # T here is the LOOP length / coefficient-table length (not the time-table capacity)
         _lib.check(_lib.load().mpdx_plan(hdl, packed.data_ptr(), tab.data_ptr(), T, coefs, n0,
                                          x.data_ptr(), noise_ptr, _lib.ptr(hs), _lib.ptr(hg), _lib.ptr(chain), B,

@@ -177,6 +177,15 @@ class TemporalUnet(nn.Module):
             self._h = h
         return self._h
 
+    def set_plan_join(self, on: bool):
+        """mpdx_unet_set_plan_join: may the fused planning loop run a step's up program and the next step's down program as one launch (default: yes)?
+        Results are bit-identical either way.  A handle option: a copy of the module (deepcopy, pickle) starts from the default again."""
+        _lib.check(_lib.load().mpdx_unet_set_plan_join(self._handle(), int(bool(on))), "mpdx_unet_set_plan_join")
+
+    def plan_joined(self) -> int:
+        """Joined launches of the last fused plan on this model (mpdx_unet_plan_joined)."""
+        return int(_lib.load().mpdx_unet_plan_joined(self._handle()))
+
     def _param_stamp(self):
         """(address, version counter) of every parameter: load_state_dict, an optimiser step, .to() and in-place edits all change it.  The parameter LIST is
         cached - walking the module tree costs 0.15 ms, which the step-by-step protocol loop paid per denoising step (round 6: 65.7 -> 21 ms per plan together

@@ -15,7 +15,8 @@ hdl, packed, tab, ws = dm.model.engine(100, B)
 x = torch.randn(B, 64, 4, device="cuda")
 dm.model(x, torch.full((B,), 50, device="cuda", dtype=torch.long))
 st = torch.cuda.current_stream().cuda_stream
-for seg in range(4):
+# the index behind the last segment is the joined launch of mpdx_plan (up program + the next pass's down program), where the network has it
+for seg in range(5):
     stamps = (C.c_longlong * 1024)(); n = C.c_int(); nops = C.c_int()
     if lib.mpdx_fused_trace(hdl, packed.data_ptr(), tab.data_ptr(), x.data_ptr(), seg, B, ws.data_ptr(), st, stamps, 1024, C.byref(n), C.byref(nops)):
         break   # no such segment
@@ -24,8 +25,14 @@ for seg in range(4):
     t0 = min(w[0] for w in W if w)
     print(f"segment {seg}: {nops.value} ops; wave 0 total {W[0][-1] - W[0][0]} ticks; stamps relative to the first wave's entry, per wave")
     names = ["entry", "loads issued", "zeros", "prologue barrier"]
-    for oi in range(nops.value):
+    joined = nops.value > 16   # two programs' ops: only the joined launch has more than 16
+    n_up = 11 if joined else nops.value
+    for oi in range(n_up):
         names += [f"op{oi} entered", f"op{oi} k-loop", f"op{oi} barrier A", f"op{oi} epilogue", f"op{oi} barrier B"]
+    if joined:
+        names += ["final op done", "junction barrier"]
+        for oi in range(nops.value - 12):
+            names += [f"down op{oi} entered", f"down op{oi} k-loop", f"down op{oi} barrier A", f"down op{oi} epilogue", f"down op{oi} barrier B"]
     nst = max(len(w) for w in W)
     for i in range(nst):
         row = [(w[i] - t0) if i < len(w) else -1 for w in W]
