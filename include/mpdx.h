@@ -198,6 +198,7 @@ int mpdx_randn(float* out, size_t n, uint64_t seed, uint64_t offset, void* strea
 #define MPDX_FIELD_GRID      3 /* precomputed signed-distance grid in global memory (guide and metrics kernels only; see below) */
 #define MPDX_ROBOT_POINTMASS 0
 #define MPDX_ROBOT_PANDA     1
+#define MPDX_ROBOT_CHAIN     2 /* a serial kinematic chain given at run time as a table (mpdx_guide_params.chain, layout below); guide, metrics, mpdx_plan */
 
 typedef struct mpdx_field {
     int32_t kind;                       /* MPDX_FIELD_* */
@@ -232,7 +233,7 @@ typedef struct mpdx_field {
 
 typedef struct mpdx_guide_params {
     int32_t robot;                      /* MPDX_ROBOT_* */
-    int32_t q_dim;                      /* 2, 3 (point mass) or 7 (Panda); state dim D = 2*q_dim (pos + vel) */
+    int32_t q_dim;                      /* 2, 3 (point mass), 7 (Panda) or the chain's n_joints (1 ... 8); state dim D = 2*q_dim (pos + vel) */
     int32_t ws_dim;                     /* workspace dimension 2 or 3 */
     int32_t interpolate;                /* interpolate_trajectories_for_collision (guides.py:152) */
     int32_t n_interp;                   /* num_interpolated_points_for_collision; effective reference value 128 */
@@ -283,7 +284,43 @@ typedef struct mpdx_guide_params {
     int32_t scene_stride;               /* floats per scene block: a multiple of 4, >= 2*MPDX_MAX_FIELDS + the per-scene tables */
     const int32_t* scene_of_ctx;        /* device array: scene index per group of scene_n_per_ctx consecutive trajectories */
     int32_t scene_n_per_ctx;            /* trajectories per entry of scene_of_ctx (a member: the metrics entry points have no n_per_ctx argument) */
+    /* --- MPDX_ROBOT_CHAIN: a serial kinematic chain described by a table (an extension: the reference builds one of its own robots by name).
+     * Both members zero: the block behaves exactly as before they existed (they are looked at for robot == MPDX_ROBOT_CHAIN only).
+     * The table is fp32 words; integer entries are int32 bit patterns (as the scene header); sizes in floats:
+     *   header   4 floats                       n_joints (1 ... MPDX_ROBOT_CHAIN_MAX_JOINTS), n_spheres (1 ... MPDX_ROBOT_CHAIN_MAX_SPHERES),
+     *                                           n_pairs (0 ... MPDX_ROBOT_CHAIN_MAX_PAIRS), 0                                          [int32]
+     *   joint j  MPDX_ROBOT_CHAIN_JOINT_FLOATS  R[9] row-major rotation, parent frame from joint frame at q = 0 | t[3] translation |
+     *                                           type [int32]: MPDX_ROBOT_CHAIN_REVOLUTE about the joint frame's z, MPDX_ROBOT_CHAIN_PRISMATIC
+     *                                           along it | 3 pad floats
+     *   sphere s MPDX_ROBOT_CHAIN_SPHERE_FLOATS frame [int32]: 0 = the fixed base, k = moves with joint k (1-based) | offset[3] in that frame |
+     *                                           radius | 3 pad floats
+     *   pair     2 floats                       sphere indices (a, b) of a self-collision pair                                          [int32]
+     * Forward kinematics:  T_0 = I;  T_j = T_{j-1} [R_j | t_j] M_j(q_j),  M = Rot_z(q) (revolute) or Trans_z(q) (prismatic);  z_j = third column
+     * of T_j's rotation, O_j its origin;  sphere centre P_s = O_f + Rot_f offset_s  (f = frame of s; frame 0: P_s = offset_s).  An arbitrary joint
+     * axis or a base pose is folded into R and t by the caller.  The Panda's modified-DH frame [Rot_x(alpha) Trans_x(a) Trans_z(d)] Rot_z(theta) is
+     * of this form (Rot_z and Trans_z commute).  Joint gradients of a force F_s on sphere s:  revolute g_j = z_j . sum_s (P_s - O_j) x F_s,
+     * prismatic g_j = z_j . sum_s F_s, over the spheres with frame(s) >= j; a base-frame sphere feels forces and gives no gradient.
+     * Hinges: objects / workspace relu(r_s + cutoff_margin - sdf), self relu(r_a + r_b - |P_a - P_b|); link_margin is not used.
+     * A chain robot takes MPDX_FIELD_OBJECTS, MPDX_FIELD_WORKSPACE and MPDX_FIELD_SELF fields (scene batches included); a MPDX_FIELD_GRID field
+     * is refused, and so is ws_dim != 3 (a planar arm is a chain whose axes are all z, among 3-D primitives).
+     * Checked on the host before any launch (MPDX_E_INVALID, message naming the member at fault): counts inside the caps, n_chain_floats covers
+     * the table, q_dim == n_joints, ws_dim == 3, every frame <= n_joints, pair indices < n_spheres, radii > 0, every R orthonormal to 1e-4, type
+     * 0 or 1, a MPDX_FIELD_SELF field only with n_pairs > 0, no MPDX_FIELD_GRID field.  The table is read for this check (a device table is
+     * copied to the host once per (pointer, size) and the verdict remembered; the kernels clamp every index they take from the table, so a
+     * table rewritten in place afterwards reads other entries, never memory outside it).
+     * Entry points that take a chain: mpdx_guide_step, mpdx_guide_step_scaled, mpdx_guide_time, mpdx_traj_metrics, mpdx_traj_metrics_mask,
+     * mpdx_plan; mpdx_gpmp_step, mpdx_rrt_connect, mpdx_rrt_paths and mpdx_sdf_grid_bake know the built-in robots only. */
+    const float* chain;                 /* device pointer: the chain table (NULL unless robot == MPDX_ROBOT_CHAIN) */
+    int32_t n_chain_floats;             /* floats in chain: >= 4 + 16 n_joints + 8 n_spheres + 2 n_pairs */
 } mpdx_guide_params;
+#define MPDX_ROBOT_CHAIN_MAX_JOINTS    8
+#define MPDX_ROBOT_CHAIN_MAX_SPHERES   16
+#define MPDX_ROBOT_CHAIN_MAX_PAIRS     24
+#define MPDX_ROBOT_CHAIN_HEADER_FLOATS 4
+#define MPDX_ROBOT_CHAIN_JOINT_FLOATS  16
+#define MPDX_ROBOT_CHAIN_SPHERE_FLOATS 8
+#define MPDX_ROBOT_CHAIN_REVOLUTE      0
+#define MPDX_ROBOT_CHAIN_PRISMATIC     1
 #define MPDX_SCENE_HEADER_WORDS 8            /* 2 * MPDX_MAX_FIELDS */
 #define MPDX_SCENE_MAX_STAGED_FLOATS 12288   /* scene_stride + shared tail: the kernels' LDS budget for one staged table */
 

@@ -35,7 +35,11 @@ SCENE_HEADER_WORDS = 2 * MAX_FIELDS      # MPDX_SCENE_HEADER_WORDS
 SCENE_MAX_STAGED_FLOATS = 12 * 1024      # MPDX_SCENE_MAX_STAGED_FLOATS
 FIELD_OBJECTS, FIELD_WORKSPACE, FIELD_SELF, FIELD_GRID = 0, 1, 2, 3
 GRID_LINEAR, GRID_NEAREST = 0, 1
-ROBOT_POINTMASS, ROBOT_PANDA = 0, 1
+ROBOT_POINTMASS, ROBOT_PANDA, ROBOT_CHAIN = 0, 1, 2
+# MPDX_ROBOT_CHAIN_*: caps and record sizes (floats) of the chain table (layout in include/mpdx.h)
+ROBOT_CHAIN_MAX_JOINTS, ROBOT_CHAIN_MAX_SPHERES, ROBOT_CHAIN_MAX_PAIRS = 8, 16, 24
+ROBOT_CHAIN_HEADER_FLOATS, ROBOT_CHAIN_JOINT_FLOATS, ROBOT_CHAIN_SPHERE_FLOATS = 4, 16, 8
+ROBOT_CHAIN_REVOLUTE, ROBOT_CHAIN_PRISMATIC = 0, 1
 
 
 class Field(C.Structure):
@@ -55,7 +59,9 @@ class GuideParams(C.Structure):
                 ("clip_rule", C.c_int32), ("max_grad_value", C.c_float), ("gp_half_factor", C.c_int32),
                 ("identity_normalizer", C.c_int32), ("grids", C.c_void_p), ("n_grid_floats", C.c_int32),
                 # several obstacle scenes in one batch (layout of the scene blocks in include/mpdx.h); all zero: one scene
-                ("n_scenes", C.c_int32), ("scene_stride", C.c_int32), ("scene_of_ctx", C.c_void_p), ("scene_n_per_ctx", C.c_int32)]
+                ("n_scenes", C.c_int32), ("scene_stride", C.c_int32), ("scene_of_ctx", C.c_void_p), ("scene_n_per_ctx", C.c_int32),
+                # MPDX_ROBOT_CHAIN: the kinematic table (device pointer) and its size in floats; both zero for the built-in robots
+                ("chain", C.c_void_p), ("n_chain_floats", C.c_int32)]
 
 
 class GpmpOpts(C.Structure):

@@ -1,0 +1,470 @@
+// chain.hpp - the guide update and the trajectory metrics for a serial kinematic chain given at run time as a table (MPDX_ROBOT_CHAIN,
+// include/mpdx.h: header | joints [R | t | type] | link spheres [frame | offset | radius] | self-collision pairs).
+//
+// Replaces nothing in the reference: it builds one of its own robots by name (scripts/inference/inference.py:107-123); a robot described by a
+// table is this package's extension.  The arithmetic is that of the Panda kernel (guide.hpp) with the kinematics read
+// from the table: forces on the link spheres from the same device functions (objects_force, workspace_force, the pair force of the self
+// field), folded onto the joints (revolute g_j = z_j . sum (P_s - O_j) x F_s, prismatic g_j = z_j . sum F_s over the spheres joint j moves),
+// then the Panda kernel's later phases as they are: the fixed-order gather to the supports with the clip and the weight, and guide_gp_apply.
+//
+// Mapping.  One 512-thread workgroup per trajectory.  The number of joints QD is a template parameter (1 ... 8: the state layout [H][2 QD]
+// of guide_gp_apply is compile-time); the numbers of spheres and pairs are run-time values read from the staged table, clamped to the caps, and
+// every index taken from the table (frame, pair member) is clamped before use.  Register arrays are indexed by unrolled loop counters only:
+// per-sphere data live in LDS, the per-joint accumulators are predicated on the sphere's (wave-uniform) frame.  No scratch.
+//   phase 1  FK once per interpolated point: O_k, z_k, P_s -> LDS (odd stride per point)
+//   phase 2  wave = (point half, field): forces on every link sphere (or pair), folded to joint gradients -> LDS
+//   phase 3  wave f gathers field f to the supports, clips, weights          phase 4  sum over fields, GP prior, apply (guide_gp_apply)
+#pragma once
+#include "guide.hpp"
+
+namespace mpdx {
+
+constexpr int kChainHdr = MPDX_ROBOT_CHAIN_HEADER_FLOATS, kChainJF = MPDX_ROBOT_CHAIN_JOINT_FLOATS, kChainSF = MPDX_ROBOT_CHAIN_SPHERE_FLOATS;
+constexpr int kChainMaxS = MPDX_ROBOT_CHAIN_MAX_SPHERES, kChainMaxP = MPDX_ROBOT_CHAIN_MAX_PAIRS;
+
+struct ChainGuideArgs {
+    GuideArgs g;            // as the other guide kernels take it
+    const float* table;     // the chain table (device)
+    int n_table_floats;     // floats a workgroup stages: header + joints + spheres + pairs of the validated table
+};
+
+// sphere / pair counts of the staged table: the header's, clamped to the caps and to what the staged floats hold (scalar registers)
+struct ChainCounts { int ns, np; };
+template <int QD>
+__device__ __forceinline__ ChainCounts chain_counts(const float* __restrict__ table, int n_floats) {
+    const int32_t* h = reinterpret_cast<const int32_t*>(table);
+    const int room_s = (n_floats - kChainHdr - QD * kChainJF) / kChainSF;
+    ChainCounts c;
+    c.ns = __builtin_amdgcn_readfirstlane(min(max(h[1], 0), min(kChainMaxS, max(room_s, 0))));
+    const int room_p = (n_floats - kChainHdr - QD * kChainJF - c.ns * kChainSF) / 2;
+    c.np = __builtin_amdgcn_readfirstlane(c.ns > 0 ? min(max(h[2], 0), min(kChainMaxP, max(room_p, 0))) : 0);
+    return c;
+}
+
+// Forward kinematics of one configuration from the staged table: T_j = T_{j-1} [R_j | t_j] M_j(q_j).  The configuration is the interpolation
+// l0 * qa + l1 * qb of two rows of the LDS-staged state, read joint by joint (the joint loop is a real loop: its index addresses LDS only).
+// oz (or null): O_k at oz[3 k + r], z_k at oz[3 QD + 3 k + r]; pp: sphere centre s at pp[3 s + r].  The spheres of a frame are placed while that
+// frame's transform is in registers (the frame of a sphere is wave-uniform: a scalar branch per (frame, sphere)).
+template <int QD, bool WRITE_OZ>
+__device__ __forceinline__ void chain_fk(const float* __restrict__ stab, int ns, const float* __restrict__ qa, const float* __restrict__ qb, float l0, float l1,
+                                         float* __restrict__ oz, float* __restrict__ pp) {
+    const int32_t* tabi = reinterpret_cast<const int32_t*>(stab);
+    const float* sph = stab + kChainHdr + QD * kChainJF;
+    float R[3][3] = {{1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, {0.f, 0.f, 1.f}}, T[3] = {0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int k = -1; k < QD; ++k) {
+        if (k >= 0) {
+            const float* J = stab + kChainHdr + k * kChainJF;
+            const bool prismatic = __builtin_amdgcn_readfirstlane(tabi[kChainHdr + k * kChainJF + 12]) != 0;
+            const float qk = l0 * qa[k] + l1 * qb[k];
+            float A[3][3], Tn[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) A[r][c] = R[r][0] * J[c] + R[r][1] * J[3 + c] + R[r][2] * J[6 + c];
+                Tn[r] = R[r][0] * J[9] + R[r][1] * J[10] + R[r][2] * J[11] + T[r];
+            }
+            float st = 0.f, ct = 1.f, dz = 0.f;
+            if (prismatic) dz = qk;
+            else { st = sinf(qk); ct = cosf(qk); }   // (joint limits are the caller's: the range-reduced forms, not the hardware approximations)
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                R[r][0] = A[r][0] * ct + A[r][1] * st;
+                R[r][1] = A[r][1] * ct - A[r][0] * st;
+                R[r][2] = A[r][2];
+                T[r] = Tn[r] + dz * A[r][2];
+                if constexpr (WRITE_OZ) { oz[k * 3 + r] = T[r]; oz[QD * 3 + k * 3 + r] = R[r][2]; }
+            }
+        }
+#pragma unroll 1
+        for (int s = 0; s < ns; ++s) {   // the spheres of frame k + 1 (frame 0: the fixed base, before the first joint)
+            const int fr = __builtin_amdgcn_readfirstlane(min(max(tabi[kChainHdr + QD * kChainJF + s * kChainSF], 0), QD));
+            if (fr != k + 1) continue;
+            const float ox = sph[s * kChainSF + 1], oy = sph[s * kChainSF + 2], oz_ = sph[s * kChainSF + 3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) pp[s * 3 + r] = T[r] + R[r][0] * ox + R[r][1] * oy + R[r][2] * oz_;
+        }
+    }
+}
+
+// phase 2 for one interpolated point and one field: the forces on the link spheres (or pairs), accumulated per joint k as the total force Ft[k]
+// and moment about the world origin Mt[k] of the spheres joint k moves (frame > k, frames 1-based), then
+//     revolute  g_k = z_k . (Mt[k] - O_k x Ft[k])        prismatic  g_k = z_k . Ft[k]
+// fk: the point's FK record in LDS (O | Z | P); g_out: QD floats in LDS
+template <int QD>
+__device__ __forceinline__ void chain_point_field(const dev_guide_params& gp, const dev_field& fld, const float* __restrict__ sprim, const float* __restrict__ stab,
+                                                  const ChainCounts& cn, const float* __restrict__ fk, float* __restrict__ g_out) {
+    const int32_t* tabi = reinterpret_cast<const int32_t*>(stab);
+    constexpr int SPH = kChainHdr + QD * kChainJF;
+    const float* P = fk + 6 * QD;
+    float Ft[QD][3], Mt[QD][3];
+#pragma unroll
+    for (int k = 0; k < QD; ++k) { Ft[k][0] = Ft[k][1] = Ft[k][2] = 0.f; Mt[k][0] = Mt[k][1] = Mt[k][2] = 0.f; }
+    // a force f on the sphere at p of frame fr (sign sg): every joint below the frame feels it
+    auto push = [&](int fr, const float (&p)[3], const float (&f)[3], float sg) {
+        const float m[3] = {p[1] * f[2] - p[2] * f[1], p[2] * f[0] - p[0] * f[2], p[0] * f[1] - p[1] * f[0]};
+#pragma unroll
+        for (int k = 0; k < QD; ++k) {
+            if (fr > k) {   // (wave-uniform)
+#pragma unroll
+                for (int r = 0; r < 3; ++r) { Ft[k][r] += sg * f[r]; Mt[k][r] += sg * m[r]; }
+            }
+        }
+    };
+    if (fld.kind == MPDX_FIELD_SELF) {
+        const int pr0 = SPH + cn.ns * kChainSF;
+        for (int pr = 0; pr < cn.np; ++pr) {
+            const int sa = __builtin_amdgcn_readfirstlane(min(max(tabi[pr0 + 2 * pr], 0), cn.ns - 1));
+            const int sb = __builtin_amdgcn_readfirstlane(min(max(tabi[pr0 + 2 * pr + 1], 0), cn.ns - 1));
+            const int fa = __builtin_amdgcn_readfirstlane(min(max(tabi[SPH + sa * kChainSF], 0), QD));
+            const int fb = __builtin_amdgcn_readfirstlane(min(max(tabi[SPH + sb * kChainSF], 0), QD));
+            const float ra = stab[SPH + sa * kChainSF + 4], rb = stab[SPH + sb * kChainSF + 4];
+            const float pa[3] = {P[sa * 3], P[sa * 3 + 1], P[sa * 3 + 2]}, pb[3] = {P[sb * 3], P[sb * 3 + 1], P[sb * 3 + 2]};
+            const float dx = pa[0] - pb[0], dy = pa[1] - pb[1], dz = pa[2] - pb[2];
+            const float d2 = dx * dx + dy * dy + dz * dz;
+            const float dist = __builtin_amdgcn_sqrtf(d2);
+            const float inv = (ra + rb - dist > 0.f && dist > 0.f) ? __builtin_amdgcn_rsqf(d2) : 0.f;
+            const float f[3] = {dx * inv, dy * inv, dz * inv};   // d cost / d P_b = +f,  d cost / d P_a = -f
+            push(fa, pa, f, -1.f);
+            push(fb, pb, f, 1.f);
+        }
+    } else {
+        for (int s = 0; s < cn.ns; ++s) {
+            const int fr = __builtin_amdgcn_readfirstlane(min(max(tabi[SPH + s * kChainSF], 0), QD));
+            const float margin = stab[SPH + s * kChainSF + 4] + gp.cutoff_margin;
+            const float p[3] = {P[s * 3], P[s * 3 + 1], P[s * 3 + 2]};
+            float f[3];
+            if (fld.kind == MPDX_FIELD_OBJECTS) objects_force<3>(sprim, fld, p, margin, f);
+            else if (fld.kind == MPDX_FIELD_WORKSPACE) workspace_force<3>(fld, p, margin, f);
+            else { f[0] = f[1] = f[2] = 0.f; }
+            push(fr, p, f, 1.f);   // (a base-frame sphere, fr = 0: felt, no joint moves it)
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < QD; ++k) {
+        const bool prismatic = __builtin_amdgcn_readfirstlane(tabi[kChainHdr + k * kChainJF + 12]) != 0;
+        const float O[3] = {fk[k * 3], fk[k * 3 + 1], fk[k * 3 + 2]}, Z[3] = {fk[3 * QD + k * 3], fk[3 * QD + k * 3 + 1], fk[3 * QD + k * 3 + 2]};
+        const float cx = O[1] * Ft[k][2] - O[2] * Ft[k][1], cy = O[2] * Ft[k][0] - O[0] * Ft[k][2], cz = O[0] * Ft[k][1] - O[1] * Ft[k][0];
+        const float rev = Z[0] * (Mt[k][0] - cx) + Z[1] * (Mt[k][1] - cy) + Z[2] * (Mt[k][2] - cz);
+        const float pri = Z[0] * Ft[k][0] + Z[1] * Ft[k][1] + Z[2] * Ft[k][2];
+        g_out[k] = prismatic ? pri : rev;
+    }
+}
+
+template <int QD, bool MULTI_SCENE>
+__global__ __launch_bounds__(512, 2) void guide_step_chain_kernel(const ChainGuideArgs ca) {
+    constexpr int D = 2 * QD, MAXF = MPDX_MAX_FIELDS, WPT = 8, FKS = chain_fk_stride(QD);
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const GuideArgs& a = ca.g;
+    const dev_guide_params& gp = a.gp;
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int b = blockIdx.x;
+    const int H = a.H;
+    const int N = gp.interpolate ? gp.n_interp : H;
+    const int nsw = (H + 63) >> 6;   // support waves (H <= 128)
+    const int hs_ = (wv < nsw ? wv : 0) * 64 + lane;
+    const bool live = hs_ < H;
+    int tr_i = 0;
+#define G_STAMP() do { if (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) a.trace[wv * 16 + tr_i] = (long long)__builtin_readcyclecounter(); ++tr_i; } while (0)
+    G_STAMP();  // 0 entry
+    const int ntab = ca.n_table_floats;
+    float* sx = sm;                              // [H][D]  unnormalised state
+    float* stab = sx + H * D;                    // the chain table
+    float* sfk = stab + ((ntab + 3) & ~3);       // [N][FKS]  O | Z | P per interpolated point
+    float* sG = sfk + N * FKS;                   // [MAXF][N][QD]  joint gradients per (field, point)
+    float* sC = sG + MAXF * N * QD;              // [MAXF][H][QD]  clipped, weighted per-field support-point gradients
+    float* snz = sC + ((MAXF * H * QD + (int)((sC - sm) & 3) + 3) & ~3) - (int)((sC - sm) & 3);   // 16-byte aligned: [H * D + 8] the step's noise, drawn
+    float* snz_x = snz + H * D + 8;              // in whole groups of four (H * D need not be a multiple of 4 here) | [H * D] the normalised state
+    float* sprim = snz_x + H * D;
+    SceneCounts sc_n;
+    if constexpr (MULTI_SCENE) {
+        const int s = scene_of_traj(a.scene, b);
+        sc_n = scene_counts(gp, gp.prims + (size_t)s * a.scene.stride);
+        stage_scene_table(gp, a.scene, s, sprim, threadIdx.x, 64 * WPT);
+    } else {
+        for (int i = threadIdx.x; i < gp.n_prim_floats; i += 64 * WPT) sprim[i] = gp.prims[i];
+    }
+    for (int i = threadIdx.x; i < ntab; i += 64 * WPT) stab[i] = ca.table[i];
+    const ChainCounts cn = chain_counts<QD>(ca.table, ntab);
+    float* shc = sprim + ((gp.n_prim_floats + 3) & ~3);   // [2][D] this trajectory's hard conditions (apply mode)
+    if (!a.grad_out && (int)threadIdx.x < 2 * D) {
+        const int which = (int)threadIdx.x >= D ? 1 : 0, d = (int)threadIdx.x - which * D;
+        const float* p = which ? a.hg : a.hs;
+        if (p) shc[which * D + d] = p[(size_t)b * D + d];
+    }
+
+    // ---- load + unnormalise (normalization.py:156-167) by the whole workgroup (the trajectory's H * D floats are contiguous)
+    const int ctx = b / a.n_per_ctx;
+    {
+        const int n = H * D;
+        const float* const xb = a.x + (size_t)b * n;
+        for (int i = threadIdx.x; i < n; i += 64 * WPT) snz_x[i] = xb[i];
+        float mn = 0.f, mx = 0.f;   // the limits, one per lane, fetched per element through the crossbar below
+#pragma unroll
+        for (int d = 0; d < D; ++d) { mn = lane == d ? gp.mins[d] : mn; mx = lane == d ? gp.maxs[d] : mx; }
+        const bool clipall = __uint_as_float(a.amax_in[ctx]) > 1.0001f;
+        __syncthreads();
+        for (int i = threadIdx.x; i < ((n + 64 * WPT - 1) / (64 * WPT)) * (64 * WPT); i += 64 * WPT) {   // (whole waves take part in the shuffles)
+            const int ic = i < n ? i : 0, d = ic % D;
+            const float lo = __shfl(mn, d, 64), hi = __shfl(mx, d, 64);
+            const float xnd = snz_x[ic];
+            const float c = clipall ? fminf(fmaxf(xnd, -1.f), 1.f) : xnd;
+            const float u01 = __fadd_rn(c, 1.0f) * 0.5f;
+            const float xud = gp.identity_normalizer == 1 ? xnd : gp.identity_normalizer == 2 ? __fadd_rn(__fmul_rn(xnd, hi), lo)
+                                                            : __fadd_rn(__fmul_rn(u01, __fsub_rn(hi, lo)), lo);
+            if (i < n) sx[i] = xud;
+        }
+    }
+    __syncthreads();
+    G_STAMP();  // 1 state unnormalised + staged, tables in LDS
+
+    // ---- phase 1: interpolate + FK, once per point
+    const float scale = (N > 1) ? (float)(H - 1) / (float)(N - 1) : 0.f;  // align_corners=True
+    for (int i = wv * 64 + lane; i < N; i += 64 * WPT) {
+        int i0 = i, i1 = i;
+        float l0 = 1.f, l1 = 0.f;
+        if (gp.interpolate) {
+            const float u = scale * (float)i;
+            i0 = (int)u;
+            if (i0 > H - 1) i0 = H - 1;
+            i1 = i0 + 1 < H ? i0 + 1 : H - 1;
+            l1 = u - (float)i0;
+            l0 = 1.0f - l1;
+        }
+        float* fk = sfk + i * FKS;
+        chain_fk<QD, true>(stab, cn.ns, sx + i0 * D, sx + i1 * D, l0, l1, fk, fk + 6 * QD);
+    }
+    __syncthreads();
+    G_STAMP();  // 2 FK in LDS
+
+    // ---- phase 2: wave = (point half, field slot): every link sphere / pair of the field, folded to joint gradients
+    {
+        const int half = wv & 1, slot = wv >> 1;
+        for (int f = slot; f < gp.n_fields; f += WPT / 2) {
+            dev_field fld;
+            if constexpr (MULTI_SCENE) fld = scene_field(gp, sc_n, f); else fld = gp.fields[f];
+            for (int i = half * 64 + lane; i < N; i += 128) chain_point_field<QD>(gp, fld, sprim, stab, cn, sfk + i * FKS, sG + (f * N + i) * QD);
+        }
+    }
+    G_STAMP();  // 3 this wave's forces done
+    __syncthreads();
+    G_STAMP();  // 4 all waves done
+
+    // the step's noise (last guide iteration, drawn in place): by the waves that do not gather, under the gather
+    const unsigned long long ne0 = a.rng.elem0 + (unsigned long long)b * H * D;
+    if (a.rng.on && !a.grad_out && wv >= MAXF) guide_draw_noise(a.rng, ne0, H * D, snz, threadIdx.x - 64 * MAXF, 64 * (WPT - MAXF));
+
+    // ---- phase 3: wave f gathers field f to the support points (transpose of the interpolation, fixed order), clips, weights
+    if (wv < gp.n_fields) {
+        const int f = wv;
+        for (int sb = 0; sb < nsw; ++sb) {
+            const int hg_ = sb * 64 + lane;
+            if (hg_ >= H) continue;
+            int ilo = hg_, ihi = hg_;
+            if (gp.interpolate && scale > 0.f) {
+                ilo = (int)((float)(hg_ - 1) / scale) - 1;   // points of the segments (hg-1, hg) and (hg, hg+1): any number per segment
+                ihi = (int)((float)(hg_ + 1) / scale) + 1;
+                if (ilo < 0) ilo = 0;
+                if (ihi > N - 1) ihi = N - 1;
+            }
+            float g[QD];
+#pragma unroll
+            for (int j = 0; j < QD; ++j) g[j] = 0.f;
+            for (int i = ilo; i <= ihi; ++i) {
+                int i0 = i, i1 = i;
+                float l0 = 1.f, l1 = 0.f;
+                if (gp.interpolate) {
+                    const float u = scale * (float)i;
+                    i0 = (int)u;
+                    if (i0 > H - 1) i0 = H - 1;
+                    i1 = i0 + 1 < H ? i0 + 1 : H - 1;
+                    l1 = u - (float)i0;
+                    l0 = 1.0f - l1;
+                }
+                const bool m0 = i0 == hg_, m1 = i1 == hg_ && gp.interpolate;
+                if (m0 || m1) {
+#pragma unroll
+                    for (int j = 0; j < QD; ++j) {
+                        const float v = sG[(f * N + i) * QD + j];
+                        if (m0) g[j] += l0 * v;
+                        if (m1) g[j] += l1 * v;
+                    }
+                }
+            }
+            // clip over ALL D dims of (g + 1e-6): the velocity dims of a collision gradient are 0
+            clip_waypoint_grad<QD>(gp, g, QD);
+            const bool interior = hg_ > 0 && hg_ < H - 1;
+#pragma unroll
+            for (int j = 0; j < QD; ++j) sC[(f * H + hg_) * QD + j] = interior ? gp.fields[f].weight * g[j] : 0.f;
+        }
+    }
+    __syncthreads();
+    G_STAMP();  // 5 gathered + clipped
+    if (wv >= nsw) return;
+
+    // ---- phase 4 (the support wave(s)): sum over fields, GP prior, apply
+    float total[D], xu[D], xn[D];
+    const size_t base = ((size_t)b * H + (live ? hs_ : 0)) * D;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+        total[d] = 0.f;
+        xu[d] = live ? sx[hs_ * D + d] : 0.f;
+        xn[d] = live ? snz_x[hs_ * D + d] : 0.f;
+    }
+    if (live) {
+        for (int f = 0; f < gp.n_fields; ++f) {
+#pragma unroll
+            for (int j = 0; j < QD; ++j) total[j] += sC[(f * H + hs_) * QD + j];
+        }
+    }
+    guide_gp_apply<QD>(a, b, ctx, lane, hs_, H, live, xn, xu, sx, total, base, (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 6 : nullptr,
+                       snz + (int)(ne0 & 3ull), shc);
+#undef G_STAMP
+}
+
+// traj_metrics_kernel (guide.hpp) for a chain: the same out4 and mask; collision flags with the link radii, no margin, over the objects,
+// workspace and self fields; path length and smoothness are joint-space figures, computed as there.  One wave per trajectory, lane = interpolated
+// waypoint; the waypoint's sphere centres live in LDS (sP, odd stride per lane).
+constexpr int kChainPS = 3 * kChainMaxS + 1;
+template <int QD, bool MULTI_SCENE>
+__global__ __launch_bounds__(64) void traj_metrics_chain_kernel(const dev_guide_params gp, const float* __restrict__ x, float* __restrict__ out, int B, int H, int n_check,
+                                                                uint8_t* __restrict__ mask, const dev_scenes scene, const float* __restrict__ table, int ntab) {
+    constexpr int D = 2 * QD;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int lane = threadIdx.x, b = blockIdx.x;
+    float* sx = sm;
+    float* stab = sx + H * D;
+    float* sP = stab + ((ntab + 3) & ~3);
+    float* sprim = sP + 64 * kChainPS;
+    SceneCounts sc_n;
+    if constexpr (MULTI_SCENE) {
+        const int s = scene_of_traj(scene, b);
+        sc_n = scene_counts(gp, gp.prims + (size_t)s * scene.stride);
+        stage_scene_table(gp, scene, s, sprim, lane, 64);
+    } else {
+        for (int i = lane; i < gp.n_prim_floats; i += 64) sprim[i] = gp.prims[i];
+    }
+    for (int i = lane; i < ntab; i += 64) stab[i] = table[i];
+    const ChainCounts cn = chain_counts<QD>(table, ntab);
+    for (int i = lane; i < H * D; i += 64) sx[i] = x[(size_t)b * H * D + i];
+    __syncthreads();
+    float plen = 0.f, smooth = 0.f;
+    for (int h = lane; h < H - 1; h += 64) {
+        float a2 = 0.f, v2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < QD; ++j) {
+            const float dq = sx[(h + 1) * D + j] - sx[h * D + j], dv = sx[(h + 1) * D + QD + j] - sx[h * D + QD + j];
+            a2 += dq * dq; v2 += dv * dv;
+        }
+        plen += sqrtf(a2); smooth += sqrtf(v2);
+    }
+    const int N = n_check;
+    const float scale = (N > 1) ? (float)(H - 1) / (float)(N - 1) : 0.f;
+    const int32_t* tabi = reinterpret_cast<const int32_t*>(stab);
+    constexpr int SPH = kChainHdr + QD * kChainJF;
+    float* P = sP + lane * kChainPS;
+    float ncoll = 0.f;
+    for (int i = lane; i < N; i += 64) {
+        const float u = scale * (float)i;
+        int i0 = (int)u;
+        if (i0 > H - 1) i0 = H - 1;
+        const int i1 = i0 + 1 < H ? i0 + 1 : H - 1;
+        const float l1 = u - (float)i0, l0 = 1.0f - l1;
+        chain_fk<QD, false>(stab, cn.ns, sx + i0 * D, sx + i1 * D, l0, l1, nullptr, P);
+        bool hit = false;
+        for (int f = 0; f < gp.n_fields; ++f) {
+            const int kind = gp.fields[f].kind;
+            if (kind == MPDX_FIELD_SELF) {
+                const int pr0 = SPH + cn.ns * kChainSF;
+                for (int pr = 0; pr < cn.np; ++pr) {
+                    const int sa = __builtin_amdgcn_readfirstlane(min(max(tabi[pr0 + 2 * pr], 0), cn.ns - 1));
+                    const int sb = __builtin_amdgcn_readfirstlane(min(max(tabi[pr0 + 2 * pr + 1], 0), cn.ns - 1));
+                    const float dx = P[sa * 3] - P[sb * 3], dy = P[sa * 3 + 1] - P[sb * 3 + 1], dz = P[sa * 3 + 2] - P[sb * 3 + 2];
+                    hit |= sqrtf(dx * dx + dy * dy + dz * dz) < stab[SPH + sa * kChainSF + 4] + stab[SPH + sb * kChainSF + 4];
+                }
+            } else if (kind == MPDX_FIELD_OBJECTS || kind == MPDX_FIELD_WORKSPACE) {
+                dev_field fld;
+                if constexpr (MULTI_SCENE) fld = scene_field(gp, sc_n, f); else fld = gp.fields[f];
+                for (int s = 0; s < cn.ns; ++s) {
+                    const float rad = stab[SPH + s * kChainSF + 4];
+                    const float p3[3] = {P[s * 3], P[s * 3 + 1], P[s * 3 + 2]};
+                    if (kind == MPDX_FIELD_OBJECTS) hit |= objects_sdf<3>(sprim, fld, p3) < rad;
+                    else {
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) hit |= (p3[j] - fld.ws_min[j] < rad) || (fld.ws_max[j] - p3[j] < rad);
+                    }
+                }
+            }
+        }
+        ncoll += hit ? 1.f : 0.f;
+        if (mask) mask[(size_t)b * N + i] = hit ? 1 : 0;
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        ncoll += __shfl_xor(ncoll, s, 64);
+        plen += __shfl_xor(plen, s, 64);
+        smooth += __shfl_xor(smooth, s, 64);
+    }
+    if (lane == 0) {
+        out[(size_t)b * 4 + 0] = ncoll; out[(size_t)b * 4 + 1] = plen; out[(size_t)b * 4 + 2] = smooth; out[(size_t)b * 4 + 3] = (float)N;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+// what the launchers know of a validated chain table
+struct ChainInfo { int n_joints, n_spheres, n_pairs, n_floats; };
+
+inline int chain_table_floats(int nj, int ns, int np) { return kChainHdr + nj * kChainJF + ns * kChainSF + 2 * np; }
+
+// The checks of a chain table held in HOST memory (t: gp.n_chain_floats floats) against its parameter block: nullptr = fine (*info filled), else
+// what is wrong, naming the member at fault.  After them every offset the kernels form lies inside the table.
+inline const char* chain_table_problem(const mpdx_guide_params& gp, const float* t, ChainInfo* info) {
+    static thread_local char msg[200];
+    const int32_t* ti = reinterpret_cast<const int32_t*>(t);
+    const int nj = ti[0], ns = ti[1], np = ti[2];
+    if (nj < 1 || nj > MPDX_ROBOT_CHAIN_MAX_JOINTS) { snprintf(msg, sizeof(msg), "chain: n_joints %d outside 1 ... %d (MPDX_ROBOT_CHAIN_MAX_JOINTS)", nj, MPDX_ROBOT_CHAIN_MAX_JOINTS); return msg; }
+    if (ns < 1 || ns > kChainMaxS) { snprintf(msg, sizeof(msg), "chain: n_spheres %d outside 1 ... %d (MPDX_ROBOT_CHAIN_MAX_SPHERES)", ns, kChainMaxS); return msg; }
+    if (np < 0 || np > kChainMaxP) { snprintf(msg, sizeof(msg), "chain: n_pairs %d outside 0 ... %d (MPDX_ROBOT_CHAIN_MAX_PAIRS)", np, kChainMaxP); return msg; }
+    const int need = chain_table_floats(nj, ns, np);
+    if (gp.n_chain_floats < need) { snprintf(msg, sizeof(msg), "chain: n_chain_floats %d does not cover the table (%d floats for %d joints, %d spheres, %d pairs)", gp.n_chain_floats, need, nj, ns, np); return msg; }
+    if (gp.q_dim != nj) { snprintf(msg, sizeof(msg), "chain: q_dim %d != n_joints %d of the chain table", gp.q_dim, nj); return msg; }
+    for (int j = 0; j < nj; ++j) {
+        const float* J = t + kChainHdr + j * kChainJF;
+        const int type = ti[kChainHdr + j * kChainJF + 12];
+        if (type != MPDX_ROBOT_CHAIN_REVOLUTE && type != MPDX_ROBOT_CHAIN_PRISMATIC) { snprintf(msg, sizeof(msg), "chain: joint %d type %d (0 = revolute, 1 = prismatic)", j, type); return msg; }
+        for (int r = 0; r < 3; ++r)
+            for (int c = r; c < 3; ++c) {
+                float d = 0.f;
+                for (int k = 0; k < 3; ++k) d += J[r * 3 + k] * J[c * 3 + k];
+                if (!(fabsf(d - (r == c ? 1.f : 0.f)) <= 1e-4f)) { snprintf(msg, sizeof(msg), "chain: joint %d R is not orthonormal to 1e-4 (rows %d . %d = %g)", j, r, c, (double)d); return msg; }
+            }
+        for (int k = 9; k < 12; ++k)
+            if (!(fabsf(J[k]) < 3.0e38f)) { snprintf(msg, sizeof(msg), "chain: joint %d t is not finite", j); return msg; }
+    }
+    for (int s = 0; s < ns; ++s) {
+        const float* S = t + kChainHdr + nj * kChainJF + s * kChainSF;
+        const int fr = ti[kChainHdr + nj * kChainJF + s * kChainSF];
+        if (fr < 0 || fr > nj) { snprintf(msg, sizeof(msg), "chain: sphere %d frame %d outside 0 ... n_joints (%d)", s, fr, nj); return msg; }
+        if (!(S[4] > 0.f) || !(S[4] < 3.0e38f)) { snprintf(msg, sizeof(msg), "chain: sphere %d radius must be positive and finite", s); return msg; }
+        for (int k = 1; k < 4; ++k)
+            if (!(fabsf(S[k]) < 3.0e38f)) { snprintf(msg, sizeof(msg), "chain: sphere %d offset is not finite", s); return msg; }
+    }
+    for (int p = 0; p < np; ++p) {
+        const int a = ti[kChainHdr + nj * kChainJF + ns * kChainSF + 2 * p], b = ti[kChainHdr + nj * kChainJF + ns * kChainSF + 2 * p + 1];
+        if (a < 0 || a >= ns || b < 0 || b >= ns) { snprintf(msg, sizeof(msg), "chain: pair %d indices (%d, %d) outside n_spheres (%d)", p, a, b, ns); return msg; }
+    }
+    for (int f = 0; f < gp.n_fields && f < MPDX_MAX_FIELDS; ++f)
+        if (gp.fields[f].kind == MPDX_FIELD_SELF && np == 0) return "chain: a MPDX_FIELD_SELF field needs n_pairs > 0 in the chain table";
+    info->n_joints = nj; info->n_spheres = ns; info->n_pairs = np; info->n_floats = need;
+    return nullptr;
+}
+
+// ---- k_guide.hip: the checks of a MPDX_ROBOT_CHAIN block, the table read where it lies (a device table: copied to the host once per (pointer, size))
+const char* chain_params_check(const mpdx_guide_params& gp, ChainInfo* info);
+// ---- k_chain.hip: every guide_step_chain_kernel / traj_metrics_chain_kernel instantiation
+int launch_chain_guide(const GuideArgs& a, const float* table, const ChainInfo& ci, bool multi, size_t lds, int B, hipStream_t st);
+int launch_chain_metrics(const dev_guide_params& g, const float* x, float* out4, uint8_t* mask, int n_check, int B, int H, const dev_scenes& sc, const float* table,
+                         const ChainInfo& ci, bool multi, hipStream_t st);
+
+}  // namespace mpdx

@@ -1077,8 +1077,14 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(co
 }
 
 
+// MPDX_ROBOT_CHAIN (chain.hpp): floats per interpolated point of the FK table in LDS, O[QD][3] | Z[QD][3] | P[MPDX_ROBOT_CHAIN_MAX_SPHERES][3]  (odd stride)
+constexpr int chain_fk_stride(int qd) { return 6 * qd + 3 * MPDX_ROBOT_CHAIN_MAX_SPHERES + 1; }
+
 inline size_t guide_lds_bytes(const mpdx_guide_params& gp, int H, int D, bool dense = false) {
     const int N = gp.interpolate ? gp.n_interp : H;
+    if (gp.robot == MPDX_ROBOT_CHAIN)   // state | chain table | FK table | joint gradients | per-field support gradients | noise + normalised state | primitives | hard conditions
+        return ((size_t)H * D + (size_t)(gp.n_chain_floats + 3) + (size_t)N * chain_fk_stride(D / 2) + (size_t)MPDX_MAX_FIELDS * N * (D / 2) + (size_t)MPDX_MAX_FIELDS * H * (D / 2) +
+                (size_t)(2 * H * D + 8 + 3) + (size_t)gp.n_prim_floats + 3 + 2 * D) * sizeof(float);
     if (gp.robot == MPDX_ROBOT_PANDA)
         return (size_t)(H * D + (dense ? 0 : N * kPandaFKS) + MPDX_MAX_FIELDS * kPandaParts * N * 7 + MPDX_MAX_FIELDS * H * 7 + (2 * H * D + 4 + 3) + gp.n_prim_floats + 3 + 2 * D) * sizeof(float);
     return (size_t)(H * D + 2 * MPDX_MAX_FIELDS * N * (D / 2) + gp.n_prim_floats) * sizeof(float);

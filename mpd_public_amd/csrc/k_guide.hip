@@ -1,10 +1,59 @@
 // k_guide.hip - the cost-guidance and trajectory-metrics kernels (guide.hpp) and their C-ABI entry points.
 #include "host.hpp"
 #include "guide.hpp"
+#include "chain.hpp"   // the chain robot's block checks and the launchers of its kernels (instantiated in k_chain.hip)
 
 namespace mpdx {
 
 static long long* g_guide_trace = nullptr;  // dev tool (mpdx_guide_trace)
+
+// The checks of a MPDX_ROBOT_CHAIN block, in the order: members of the block (nothing is dereferenced), then the table.  A table in host (or
+// managed) memory is read where it lies; a device table is copied to the host ONCE per (pointer, size) and the verdict kept - launches inside
+// the planning loop neither copy nor synchronise (the kernels clamp every index they take from the table).
+const char* chain_params_check(const mpdx_guide_params& gp, ChainInfo* info) {
+    if (!gp.chain) return "chain robot without a chain table (chain == NULL)";
+    if (gp.n_chain_floats < chain_table_floats(1, 1, 0)) return "chain: n_chain_floats does not cover the table header, one joint and one sphere";
+    if (gp.q_dim < 1 || gp.q_dim > MPDX_ROBOT_CHAIN_MAX_JOINTS) return "chain: q_dim outside 1 ... MPDX_ROBOT_CHAIN_MAX_JOINTS";
+    if (gp.ws_dim != 3) return "chain: ws_dim must be 3 (a planar arm is a chain whose axes are all z, among 3-D primitives)";
+    if (has_grid_field(gp)) return "chain: a MPDX_FIELD_GRID field is not supported with a chain robot (primitive, workspace and self fields)";
+    if ((uintptr_t)gp.chain & 3) return "chain table must be 4-byte aligned";
+    struct Seen { const float* p; int n; ChainInfo ci; };
+    static std::mutex mu;
+    static std::vector<Seen> seen;
+    const int n = std::min(gp.n_chain_floats, chain_table_floats(MPDX_ROBOT_CHAIN_MAX_JOINTS, MPDX_ROBOT_CHAIN_MAX_SPHERES, MPDX_ROBOT_CHAIN_MAX_PAIRS));
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    const hipError_t e = hipPointerGetAttributes(&at, gp.chain);
+    if (e != hipSuccess) (void)hipGetLastError();   // (an ordinary host pointer, or no device at all: not an error of this call)
+    const bool on_device = e == hipSuccess && at.type == hipMemoryTypeDevice;
+    if (!on_device) return chain_table_problem(gp, gp.chain, info);
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        for (const Seen& s : seen)
+            if (s.p == gp.chain && s.n == gp.n_chain_floats && s.ci.n_joints == gp.q_dim) {
+                *info = s.ci;
+                for (int f = 0; f < gp.n_fields && f < MPDX_MAX_FIELDS; ++f)
+                    if (gp.fields[f].kind == MPDX_FIELD_SELF && s.ci.n_pairs == 0) return "chain: a MPDX_FIELD_SELF field needs n_pairs > 0 in the chain table";
+                return nullptr;
+            }
+    }
+    std::vector<float> host((size_t)n);
+    if (hipMemcpy(host.data(), gp.chain, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        return "chain: the chain table could not be read from the device";
+    }
+    if (const char* why = chain_table_problem(gp, host.data(), info)) return why;
+    std::lock_guard<std::mutex> lock(mu);
+    if (seen.size() >= 64) seen.clear();
+    seen.push_back({gp.chain, gp.n_chain_floats, *info});
+    return nullptr;
+}
+
+const char* chain_params_problem(const mpdx_guide_params& gp) {
+    if (gp.robot != MPDX_ROBOT_CHAIN) return nullptr;
+    ChainInfo ci;
+    return chain_params_check(gp, &ci);
+}
 
 // per-context max|x| (the range test of LimitsNormalizer.unnormalize) for the API path
 __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x, uint32_t* out, size_t per_ctx, int n_ctx) {
@@ -26,6 +75,10 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
     if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS) return fail(MPDX_E_INVALID, "n_fields %d", gp->n_fields);
     if (gp->interpolate && (gp->n_interp < H || gp->n_interp > 8 * H)) return fail(MPDX_E_INVALID, "n_interp %d unsupported", gp->n_interp);
     if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
+    ChainInfo chain_info;   // (a chain robot's own refusals first: it takes no grid field at all)
+    memset(&chain_info, 0, sizeof(chain_info));
+    if (gp->robot == MPDX_ROBOT_CHAIN)
+        if (const char* why = chain_params_check(*gp, &chain_info)) return fail(MPDX_E_INVALID, "%s", why);
     if (const char* why = grid_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
     if (const char* why = scene_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
     if (gp->robot == MPDX_ROBOT_PANDA && (((uintptr_t)x & 15) || ((size_t)H * D) % 4))
@@ -48,6 +101,7 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
     a.scene = dev_scenes_of(*gp);
     mpdx_guide_params staged = *gp;   // (the LDS carve is sized by what a workgroup stages)
     staged.n_prim_floats = staged_prim_floats(*gp);
+    if (gp->robot == MPDX_ROBOT_CHAIN) staged.n_chain_floats = chain_info.n_floats;
     // Panda at large batch: the dense variant (no FK table, 128 VGPRs: two workgroups per CU); MPDX_GUIDE_DENSE=0/1 forces it off / on
     const int dense_env = sw::guide_dense();
     const bool dense = gp->robot == MPDX_ROBOT_PANDA && (dense_env >= 0 ? dense_env != 0 : B >= 512) && guide_lds_bytes(staged, H, D, true) <= 80 * 1024;
@@ -81,6 +135,9 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
     }
 #undef MPDX_GUIDE_PM
 #undef MPDX_GUIDE_PANDA
+    else if (gp->robot == MPDX_ROBOT_CHAIN) {   // (q_dim == n_joints, ws_dim == 3: checked above)
+        if (int rc = launch_chain_guide(a, gp->chain, chain_info, multi, lds, B, st)) return rc;
+    }
     else
         return fail(MPDX_E_INVALID, "unsupported robot %d / q_dim %d / ws_dim %d", gp->robot, gp->q_dim, gp->ws_dim);
     return 0;
@@ -120,11 +177,20 @@ int mpdx_traj_metrics_mask(const mpdx_guide_params* gp, const float* x_unnormali
     if (n_check < 2) n_check = H;
     if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS) return fail(MPDX_E_INVALID, "n_fields %d", gp->n_fields);
     if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
+    ChainInfo chain_info;
+    memset(&chain_info, 0, sizeof(chain_info));
+    if (gp->robot == MPDX_ROBOT_CHAIN)
+        if (const char* why = chain_params_check(*gp, &chain_info)) return fail(MPDX_E_INVALID, "%s", why);
     if (const char* why = grid_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
     if (const char* why = scene_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
     hipStream_t st = (hipStream_t)stream;
     const bool grid = has_grid_field(*gp), multi = has_scenes(*gp);
     const dev_guide_params g = dev_params_staged(*gp);   // (n_prim_floats = what a workgroup stages: the table, or one scene block + the shared tail)
+    if (gp->robot == MPDX_ROBOT_CHAIN) {
+        if (int rc = launch_chain_metrics(g, x_unnormalised, out4, mask, n_check, B, H, dev_scenes_of(*gp), gp->chain, chain_info, multi, st)) return rc;
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     const size_t lds = (size_t)(H * D + g.n_prim_floats) * sizeof(float);
     dev_grids gr;
     memset(&gr, 0, sizeof(gr));
@@ -151,6 +217,7 @@ int mpdx_guide_time(const mpdx_guide_params* gp, float* x, float* grad_out, cons
                     int reps, void* stream, float* ms_avg) {
     if (!gp || !x || !grad_out || !absmax_in || !ms_avg || reps < 1) return fail(MPDX_E_INVALID, "bad argument");
     if (const char* why = scene_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);   // (before the events: nothing is created for a refused block)
+    if (const char* why = chain_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
     hipStream_t st = (hipStream_t)stream;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));

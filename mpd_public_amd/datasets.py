@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 
 from . import synthetic as syn
-from .planning import PlanningTask, make_env, make_robot
+from .planning import PlanningTask, RobotChain, make_env, make_robot
 
 
 class LimitsNormalizer:
@@ -139,7 +139,9 @@ class TrajectoryDataset:
                  obstacle_cutoff_margin=0.05, use_extra_objects=True, tensor_args=None, base_dir=None, normalizer="LimitsNormalizer",
                  sdf_grid=None, **kw):
         self.tensor_args = tensor_args or {"device": "cpu", "dtype": torch.float32}
-        self.env, self.robot = make_env(env_id), make_robot(robot_id)
+        # robot_id: one of the reference's names, or (extension) a planning.RobotChain - a serial chain described by a table
+        chain = isinstance(robot_id, RobotChain)
+        self.env, self.robot = make_env(env_id), (robot_id if chain else make_robot(robot_id))
         # sdf_grid (extension, default None: primitive tables): the task's fixed objects as a baked signed-distance grid (planning.PlanningTask)
         self.task = PlanningTask(self.env, self.robot, obstacle_cutoff_margin=obstacle_cutoff_margin,
                                  use_extra_objects=use_extra_objects, tensor_args=self.tensor_args, sdf_grid=sdf_grid)
@@ -150,7 +152,7 @@ class TrajectoryDataset:
         self.normalizer_name = normalizer if isinstance(normalizer, str) else normalizer.__name__
         if self.normalizer_name not in NORMALIZERS:
             raise NameError(f"name {self.normalizer_name!r} is not defined")
-        mins, maxs = syn.limits_for(robot_id)
+        mins, maxs = self.robot.limits() if chain else syn.limits_for(robot_id)
         mins, maxs = mins[: self.state_dim], maxs[: self.state_dim]
         if self.normalizer_name == "GaussianNormalizer":
             if base_dir is None:

@@ -112,6 +112,12 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
         grid_t = planes[0] if len(planes) == 1 else torch.cat(planes)   # (a single plane is used in place: no second copy of a 7.8-MB grid)
         gp.grids, gp.n_grid_floats = grid_t.data_ptr(), goff
     gp.grids_tensor = grid_t   # a Python attribute of the ctypes object: the buffer lives as long as the params that point into it
+    gp.chain_tensor = None
+    if robot.robot_id == _lib.ROBOT_CHAIN:   # the kinematic table of a planning.RobotChain (layout in include/mpdx.h), kept alive the same way
+        if planes:
+            raise ValueError("a RobotChain takes primitive, workspace and self fields: no FIELD_GRID field")
+        gp.chain_tensor = torch.from_numpy(robot.table()).to(device)
+        gp.chain, gp.n_chain_floats = gp.chain_tensor.data_ptr(), gp.chain_tensor.numel()
     return gp, prim_t
 
 

@@ -38,8 +38,9 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
                weight_grad_cost_smoothness: float = 1e-7, factor_num_interpolated_points_for_collision: float = 1.5,
                trajectory_duration: float = 5.0, device: str = "cuda", debug: bool = True, render: bool = False, seed: int = 30,
                results_dir: str = "logs", model_dir: str = None, model_args: dict = None, sdf_grid_cell_size: float = None,
-               sdf_grid_mode: str = "linear", **kwargs):
-    """sdf_grid_cell_size / sdf_grid_mode (extension): None (default) keeps the primitive tables; a cell size makes the task's FIXED objects a
+               sdf_grid_mode: str = "linear", robot=None, **kwargs):
+    """robot (extension): a planning.RobotChain that replaces the robot named in `model_id` (the environment is still taken from it).
+    sdf_grid_cell_size / sdf_grid_mode (extension): None (default) keeps the primitive tables; a cell size makes the task's FIXED objects a
     signed-distance grid baked on the device ('linear' interpolation or 'nearest' node, planning.PlanningTask(sdf_grid=...))."""
     torch.manual_seed(seed)
     if not torch.cuda.is_available():
@@ -62,7 +63,7 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
     env_id, robot_id = model_id.split("-")
 
     sdf_grid = None if sdf_grid_cell_size is None else dict(cell_size=float(sdf_grid_cell_size), mode=sdf_grid_mode)
-    dataset = TrajectoryDataset(env_id=env_id, robot_id=robot_id, use_extra_objects=True, obstacle_cutoff_margin=0.05,
+    dataset = TrajectoryDataset(env_id=env_id, robot_id=robot if robot is not None else robot_id, use_extra_objects=True, obstacle_cutoff_margin=0.05,
                                 include_velocity=args["include_velocity"], tensor_args=tensor_args, sdf_grid=sdf_grid)
     n_support_points, robot, task = dataset.n_support_points, dataset.robot, dataset.task
     dt = trajectory_duration / n_support_points

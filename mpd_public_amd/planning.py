@@ -123,6 +123,131 @@ class RobotPanda:
     get_velocity = RobotPointMass.get_velocity
 
 
+# the package's Panda geometry (csrc/guide.hpp kPanda*): modified-DH rows (alpha_{i-1}, a_{i-1}, d_i), link spheres (frame 1..7, offset along the
+# frame's z, radius) and self-collision pairs
+PANDA_MDH_ALPHA = (0.0, -math.pi / 2, math.pi / 2, math.pi / 2, -math.pi / 2, math.pi / 2, math.pi / 2)
+PANDA_MDH_A = (0.0, 0.0, 0.0, 0.0825, -0.0825, 0.0, 0.088)
+PANDA_MDH_D = (0.333, 0.0, 0.316, 0.0, 0.384, 0.0, 0.0)
+PANDA_LINK_SPHERES = ((1, -0.15, 0.10), (1, 0.0, 0.10), (3, -0.15, 0.09), (3, 0.0, 0.09), (4, 0.0, 0.09), (5, -0.25, 0.08),
+                      (5, -0.12, 0.08), (5, 0.0, 0.08), (7, 0.0, 0.07), (7, 0.107, 0.06), (7, 0.17, 0.06))
+PANDA_SELF_PAIRS = ((8, 0), (8, 1), (8, 2), (9, 0), (9, 1), (9, 2), (9, 3), (10, 0), (10, 1), (10, 2), (10, 3), (10, 4))
+
+
+class RobotChain:
+    """A serial kinematic chain described by a table (an extension: the reference builds one of its own robots by name); the guide and metrics
+    kernels of csrc/chain.hpp run on it (robot id MPDX_ROBOT_CHAIN, table layout and forward kinematics in include/mpdx.h).
+
+    joints      one (R, t, type) per joint, base to tip: R [3, 3] rotation and t [3] translation of the joint frame in its parent frame at
+                q = 0; type 'revolute' (0: about the joint frame's z) or 'prismatic' (1: along it).  T_j = T_{j-1} [R | t] M(q_j).
+    spheres     one (frame, offset [3], radius) per link collision sphere: frame 0 = the fixed base, k = moves with joint k (1-based)
+    self_pairs  (a, b) sphere index pairs of the self-collision field (none: the task has no self field)
+    q_limits    (lo [n], hi [n]) joint limits, default (-pi, pi); v_limit: the velocity limit of the synthetic normaliser
+    At most 8 joints, 16 spheres and 24 pairs; 3-D workspaces, primitive / workspace / self fields (no signed-distance grid)."""
+
+    def __init__(self, joints, spheres, self_pairs=(), q_limits=None, v_limit=2.5, name="RobotChain"):
+        joints, spheres, self_pairs = list(joints), list(spheres), [tuple(p) for p in self_pairs]
+        nj, ns, npair = len(joints), len(spheres), len(self_pairs)
+        if not 1 <= nj <= _lib.ROBOT_CHAIN_MAX_JOINTS:
+            raise ValueError(f"joints: {nj} joints, 1 ... {_lib.ROBOT_CHAIN_MAX_JOINTS} are supported")
+        if not 1 <= ns <= _lib.ROBOT_CHAIN_MAX_SPHERES:
+            raise ValueError(f"spheres: {ns} spheres, 1 ... {_lib.ROBOT_CHAIN_MAX_SPHERES} are supported")
+        if npair > _lib.ROBOT_CHAIN_MAX_PAIRS:
+            raise ValueError(f"self_pairs: {npair} pairs, at most {_lib.ROBOT_CHAIN_MAX_PAIRS} are supported")
+        types = {"revolute": _lib.ROBOT_CHAIN_REVOLUTE, "prismatic": _lib.ROBOT_CHAIN_PRISMATIC, 0: 0, 1: 1}
+        self.joint_R, self.joint_t, self.joint_type = np.zeros((nj, 3, 3)), np.zeros((nj, 3)), np.zeros(nj, np.int32)
+        for j, jt in enumerate(joints):
+            if len(jt) != 3:
+                raise ValueError(f"joints[{j}]: (R [3, 3], t [3], type) is expected")
+            R, t = np.asarray(jt[0], np.float64), np.asarray(jt[1], np.float64)
+            if R.shape != (3, 3) or t.shape != (3,) or not (np.isfinite(R).all() and np.isfinite(t).all()):
+                raise ValueError(f"joints[{j}]: R must be a finite [3, 3] matrix and t a finite 3-vector")
+            if np.abs(R.astype(np.float32) @ R.astype(np.float32).T - np.eye(3, dtype=np.float32)).max() > 1e-4:
+                raise ValueError(f"joints[{j}]: R is not orthonormal to 1e-4")
+            if isinstance(jt[2], (bool, float)) or jt[2] not in types:
+                raise ValueError(f"joints[{j}]: type {jt[2]!r} ('revolute' / 0 or 'prismatic' / 1)")
+            self.joint_R[j], self.joint_t[j], self.joint_type[j] = R, t, types[jt[2]]
+        self.sphere_frame, self.sphere_offset, self.sphere_radius = np.zeros(ns, np.int32), np.zeros((ns, 3)), np.zeros(ns)
+        for k, sp in enumerate(spheres):
+            if len(sp) != 3:
+                raise ValueError(f"spheres[{k}]: (frame, offset [3], radius) is expected")
+            fr, off, rad = int(sp[0]), np.asarray(sp[1], np.float64), float(sp[2])
+            if fr != sp[0] or not 0 <= fr <= nj:
+                raise ValueError(f"spheres[{k}]: frame {sp[0]!r} outside 0 ... n_joints ({nj})")
+            if off.shape != (3,) or not np.isfinite(off).all():
+                raise ValueError(f"spheres[{k}]: offset must be a finite 3-vector")
+            if not (rad > 0 and math.isfinite(rad)):
+                raise ValueError(f"spheres[{k}]: radius must be positive and finite")
+            self.sphere_frame[k], self.sphere_offset[k], self.sphere_radius[k] = fr, off, rad
+        for k, pr in enumerate(self_pairs):
+            if len(pr) != 2 or any(int(v) != v or not 0 <= int(v) < ns for v in pr):
+                raise ValueError(f"self_pairs[{k}]: indices {pr!r} outside the {ns} spheres")
+        self.self_pairs = np.asarray(self_pairs, np.int32).reshape(-1, 2)
+        if q_limits is None:
+            q_limits = (np.full(nj, -math.pi), np.full(nj, math.pi))
+        lo, hi = (np.asarray(v, np.float32).reshape(-1) for v in q_limits)
+        if lo.shape != (nj,) or hi.shape != (nj,) or not (np.isfinite(lo).all() and np.isfinite(hi).all()) or (hi <= lo).any():
+            raise ValueError(f"q_limits: (lo [{nj}], hi [{nj}]) with lo < hi is expected")
+        if not (float(v_limit) > 0 and math.isfinite(float(v_limit))):
+            raise ValueError("v_limit must be positive and finite")
+        self.q_limits, self.v_limit = (lo, hi), float(v_limit)
+        self.name, self.q_dim, self.link_margin, self.dt = name, nj, 0.0, None
+        self.robot_id = _lib.ROBOT_CHAIN
+
+    get_position = RobotPointMass.get_position
+    get_velocity = RobotPointMass.get_velocity
+
+    @property
+    def n_spheres(self) -> int:
+        return len(self.sphere_radius)
+
+    @property
+    def n_pairs(self) -> int:
+        return len(self.self_pairs)
+
+    def limits(self):
+        """(mins [D], maxs [D]) of the synthetic trajectory normaliser: the joint limits, then +-v_limit."""
+        vv = np.full(self.q_dim, self.v_limit, np.float32)
+        return np.concatenate([self.q_limits[0], -vv]), np.concatenate([self.q_limits[1], vv])
+
+    def table(self) -> np.ndarray:
+        """The float32 chain table of include/mpdx.h (integer entries as int32 bit patterns)."""
+        nj, ns, npair = self.q_dim, self.n_spheres, self.n_pairs
+        H, JF, SF = _lib.ROBOT_CHAIN_HEADER_FLOATS, _lib.ROBOT_CHAIN_JOINT_FLOATS, _lib.ROBOT_CHAIN_SPHERE_FLOATS
+        tab = np.zeros(H + JF * nj + SF * ns + 2 * npair, np.float32)
+        ti = tab.view(np.int32)
+        ti[0], ti[1], ti[2] = nj, ns, npair
+        for j in range(nj):
+            o = H + JF * j
+            tab[o: o + 9], tab[o + 9: o + 12], ti[o + 12] = self.joint_R[j].reshape(-1), self.joint_t[j], self.joint_type[j]
+        for k in range(ns):
+            o = H + JF * nj + SF * k
+            ti[o], tab[o + 1: o + 4], tab[o + 4] = self.sphere_frame[k], self.sphere_offset[k], self.sphere_radius[k]
+        o = H + JF * nj + SF * ns
+        ti[o: o + 2 * npair] = self.self_pairs.reshape(-1)
+        return tab
+
+    @classmethod
+    def from_mdh(cls, alpha, a, d, spheres, self_pairs=(), **kw):
+        """A chain of revolute joints from modified-DH rows (Craig): T_i = Rot_x(alpha_{i-1}) Trans_x(a_{i-1}) Rot_z(theta_i) Trans_z(d_i), i.e.
+        [R | t] = Rot_x(alpha) Trans_x(a) Trans_z(d) followed by the joint rotation (Rot_z and Trans_z commute)."""
+        joints = []
+        for al, aa, dd in zip(alpha, a, d):
+            ca, sa = math.cos(al), math.sin(al)
+            joints.append((np.array([[1.0, 0.0, 0.0], [0.0, ca, -sa], [0.0, sa, ca]]), np.array([aa, -sa * dd, ca * dd]), "revolute"))
+        return cls(joints, spheres, self_pairs, **kw)
+
+    @classmethod
+    def panda(cls, name="RobotPandaChain"):
+        """The package's own Panda (geometry, link spheres, self-collision pairs and joint limits of RobotPanda) expressed as a chain.  RobotPanda
+        stays the robot to plan a Panda with: its kernels are specialised (profiles/chain_guide_probe.md)."""
+        joints = []
+        for al, aa, dd in zip(PANDA_MDH_ALPHA, PANDA_MDH_A, PANDA_MDH_D):
+            ca, sa = float(round(math.cos(al))), float(round(math.sin(al)))   # alpha is a multiple of pi / 2: exact entries, as the kernel's tables
+            joints.append((np.array([[1.0, 0.0, 0.0], [0.0, ca, -sa], [0.0, sa, ca]]), np.array([aa, -sa * dd, ca * dd]), "revolute"))
+        spheres = [(fr, (0.0, 0.0, off), rad) for fr, off, rad in PANDA_LINK_SPHERES]
+        return cls(joints, spheres, PANDA_SELF_PAIRS, q_limits=(syn.PANDA_Q_MIN, syn.PANDA_Q_MAX), v_limit=2.5, name=name)
+
+
 def make_robot(robot_id: str):
     if robot_id == "RobotPointMass":
         return RobotPointMass(2)
@@ -269,6 +394,11 @@ class PlanningTask:
         torch_robotics does, as recalled: the precomputed grid is for the fixed objects only).  An environment that already carries a grid
         (env.grid_fixed, set by task_from_torch_robotics) uses it as it is."""
         self.env, self.robot, self.obstacle_cutoff_margin = env, robot, obstacle_cutoff_margin
+        if isinstance(robot, RobotChain):
+            if env.dim != 3:
+                raise ValueError("a RobotChain lives in a 3-D workspace (a planar arm is a chain whose axes are all z, among 3-D primitives)")
+            if sdf_grid is not None or getattr(env, "grid_fixed", None) is not None:
+                raise ValueError("a RobotChain takes primitive, workspace and self fields: no signed-distance grid")
         self.tensor_args = tensor_args or {"device": "cpu", "dtype": torch.float32}
         self.ws_min, self.ws_max = env.limits
         self.sdf_grid = dict(sdf_grid) if sdf_grid is not None else None
@@ -285,7 +415,8 @@ class PlanningTask:
             self.df_collision_objects = CollisionField(_lib.FIELD_OBJECTS, objects=env.obj_fixed, name="objects")
         self.df_collision_extra_objects = CollisionField(_lib.FIELD_OBJECTS, objects=env.obj_extra, name="extra_objects") if use_extra_objects else None
         self.df_collision_ws_boundaries = CollisionField(_lib.FIELD_WORKSPACE, ws_min=self.ws_min, ws_max=self.ws_max, name="workspace")
-        self.df_collision_self = CollisionField(_lib.FIELD_SELF, name="self") if robot.name == "RobotPanda" else None
+        has_self = robot.name == "RobotPanda" or (isinstance(robot, RobotChain) and robot.n_pairs > 0)
+        self.df_collision_self = CollisionField(_lib.FIELD_SELF, name="self") if has_self else None
 
     def get_collision_fields(self) -> List[CollisionField]:
         out = [self.df_collision_self, self.df_collision_objects, self.df_collision_ws_boundaries, self.df_collision_extra_objects]
@@ -355,6 +486,8 @@ class PlanningTask:
         raise ValueError("No collision free configuration was found")
 
     def q_limits(self, device="cpu"):
+        if isinstance(self.robot, RobotChain):
+            return torch.tensor(self.robot.q_limits[0], device=device), torch.tensor(self.robot.q_limits[1], device=device)
         lo, hi = syn.limits_for(self.robot.name if self.robot.q_dim != 3 else "RobotPointMass3D")
         qd = self.robot.q_dim
         if self.robot.name == "RobotPointMass":
