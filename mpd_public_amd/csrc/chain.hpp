@@ -166,74 +166,35 @@ __global__ __launch_bounds__(512, 2) void guide_step_chain_kernel(const ChainGui
     const int hs_ = (wv < nsw ? wv : 0) * 64 + lane;
     const bool live = hs_ < H;
     int tr_i = 0;
-#define G_STAMP() do { if (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) a.trace[wv * 16 + tr_i] = (long long)__builtin_readcyclecounter(); ++tr_i; } while (0)
     G_STAMP();  // 0 entry
     const int ntab = ca.n_table_floats;
-    float* sx = sm;                              // [H][D]  unnormalised state
-    float* stab = sx + H * D;                    // the chain table
-    float* sfk = stab + ((ntab + 3) & ~3);       // [N][FKS]  O | Z | P per interpolated point
-    float* sG = sfk + N * FKS;                   // [MAXF][N][QD]  joint gradients per (field, point)
-    float* sC = sG + MAXF * N * QD;              // [MAXF][H][QD]  clipped, weighted per-field support-point gradients
-    float* snz = sC + ((MAXF * H * QD + (int)((sC - sm) & 3) + 3) & ~3) - (int)((sC - sm) & 3);   // 16-byte aligned: [H * D + 8] the step's noise, drawn
-    float* snz_x = snz + H * D + 8;              // in whole groups of four (H * D need not be a multiple of 4 here) | [H * D] the normalised state
-    float* sprim = snz_x + H * D;
-    SceneCounts sc_n;
-    if constexpr (MULTI_SCENE) {
-        const int s = scene_of_traj(a.scene, b);
-        sc_n = scene_counts(gp, gp.prims + (size_t)s * a.scene.stride);
-        stage_scene_table(gp, a.scene, s, sprim, threadIdx.x, 64 * WPT);
-    } else {
-        for (int i = threadIdx.x; i < gp.n_prim_floats; i += 64 * WPT) sprim[i] = gp.prims[i];
-    }
+    const GuideLds L = guide_lds_layout(kGuideChain, H, D, N, gp.n_prim_floats, ntab);
+    float* sx = sm + L.sx;        // [H][D]  unnormalised state
+    float* stab = sm + L.stab;    // the chain table
+    float* sfk = sm + L.sfk;      // [N][FKS]  O | Z | P per interpolated point
+    float* sG = sm + L.sG;        // [MAXF][N][QD]  joint gradients per (field, point)
+    float* sC = sm + L.sC;        // [MAXF][H][QD]  clipped, weighted per-field support-point gradients
+    float* snz = sm + L.snz;      // 16-byte aligned: [H * D + 8] the step's noise, drawn in whole groups of four (H * D need not be a multiple of 4 here)
+    float* snz_x = sm + L.snz_x;  // [H * D] the normalised state
+    float* sprim = sm + L.sprim;
+    float* shc = sm + L.shc;      // [2][D] this trajectory's hard conditions (apply mode)
+    const SceneCounts sc_n = stage_prims<MULTI_SCENE>(gp, a.scene, b, sprim, threadIdx.x, 64 * WPT);
     for (int i = threadIdx.x; i < ntab; i += 64 * WPT) stab[i] = ca.table[i];
     const ChainCounts cn = chain_counts<QD>(ca.table, ntab);
-    float* shc = sprim + ((gp.n_prim_floats + 3) & ~3);   // [2][D] this trajectory's hard conditions (apply mode)
-    if (!a.grad_out && (int)threadIdx.x < 2 * D) {
-        const int which = (int)threadIdx.x >= D ? 1 : 0, d = (int)threadIdx.x - which * D;
-        const float* p = which ? a.hg : a.hs;
-        if (p) shc[which * D + d] = p[(size_t)b * D + d];
-    }
+    stage_hard_conds(a.hs, a.hg, !a.grad_out, b, D, shc);
 
-    // ---- load + unnormalise (normalization.py:156-167) by the whole workgroup (the trajectory's H * D floats are contiguous)
+    // ---- load + unnormalise (normalization.py:156-167) by the whole workgroup, dword loads (H * D need not be a multiple of 4)
     const int ctx = b / a.n_per_ctx;
-    {
-        const int n = H * D;
-        const float* const xb = a.x + (size_t)b * n;
-        for (int i = threadIdx.x; i < n; i += 64 * WPT) snz_x[i] = xb[i];
-        float mn = 0.f, mx = 0.f;   // the limits, one per lane, fetched per element through the crossbar below
-#pragma unroll
-        for (int d = 0; d < D; ++d) { mn = lane == d ? gp.mins[d] : mn; mx = lane == d ? gp.maxs[d] : mx; }
-        const bool clipall = __uint_as_float(a.amax_in[ctx]) > 1.0001f;
-        __syncthreads();
-        for (int i = threadIdx.x; i < ((n + 64 * WPT - 1) / (64 * WPT)) * (64 * WPT); i += 64 * WPT) {   // (whole waves take part in the shuffles)
-            const int ic = i < n ? i : 0, d = ic % D;
-            const float lo = __shfl(mn, d, 64), hi = __shfl(mx, d, 64);
-            const float xnd = snz_x[ic];
-            const float c = clipall ? fminf(fmaxf(xnd, -1.f), 1.f) : xnd;
-            const float u01 = __fadd_rn(c, 1.0f) * 0.5f;
-            const float xud = gp.identity_normalizer == 1 ? xnd : gp.identity_normalizer == 2 ? __fadd_rn(__fmul_rn(xnd, hi), lo)
-                                                            : __fadd_rn(__fmul_rn(u01, __fsub_rn(hi, lo)), lo);
-            if (i < n) sx[i] = xud;
-        }
-    }
+    stage_state_unnormalised<D, 64 * WPT>(gp, a.x + (size_t)b * H * D, H * D, __uint_as_float(a.amax_in[ctx]) > 1.0001f, sx, snz_x, lane);
     __syncthreads();
     G_STAMP();  // 1 state unnormalised + staged, tables in LDS
 
     // ---- phase 1: interpolate + FK, once per point
-    const float scale = (N > 1) ? (float)(H - 1) / (float)(N - 1) : 0.f;  // align_corners=True
+    const float scale = interp_scale(H, N);
     for (int i = wv * 64 + lane; i < N; i += 64 * WPT) {
-        int i0 = i, i1 = i;
-        float l0 = 1.f, l1 = 0.f;
-        if (gp.interpolate) {
-            const float u = scale * (float)i;
-            i0 = (int)u;
-            if (i0 > H - 1) i0 = H - 1;
-            i1 = i0 + 1 < H ? i0 + 1 : H - 1;
-            l1 = u - (float)i0;
-            l0 = 1.0f - l1;
-        }
+        const InterpPair ip = interp_pair(gp.interpolate, scale, i, H);
         float* fk = sfk + i * FKS;
-        chain_fk<QD, true>(stab, cn.ns, sx + i0 * D, sx + i1 * D, l0, l1, fk, fk + 6 * QD);
+        chain_fk<QD, true>(stab, cn.ns, sx + ip.i0 * D, sx + ip.i1 * D, ip.l0, ip.l1, fk, fk + 6 * QD);
     }
     __syncthreads();
     G_STAMP();  // 2 FK in LDS
@@ -258,93 +219,29 @@ __global__ __launch_bounds__(512, 2) void guide_step_chain_kernel(const ChainGui
     // ---- phase 3: wave f gathers field f to the support points (transpose of the interpolation, fixed order), clips, weights
     if (wv < gp.n_fields) {
         const int f = wv;
-        for (int sb = 0; sb < nsw; ++sb) {
-            const int hg_ = sb * 64 + lane;
-            if (hg_ >= H) continue;
-            int ilo = hg_, ihi = hg_;
-            if (gp.interpolate && scale > 0.f) {
-                ilo = (int)((float)(hg_ - 1) / scale) - 1;   // points of the segments (hg-1, hg) and (hg, hg+1): any number per segment
-                ihi = (int)((float)(hg_ + 1) / scale) + 1;
-                if (ilo < 0) ilo = 0;
-                if (ihi > N - 1) ihi = N - 1;
-            }
-            float g[QD];
-#pragma unroll
-            for (int j = 0; j < QD; ++j) g[j] = 0.f;
-            for (int i = ilo; i <= ihi; ++i) {
-                int i0 = i, i1 = i;
-                float l0 = 1.f, l1 = 0.f;
-                if (gp.interpolate) {
-                    const float u = scale * (float)i;
-                    i0 = (int)u;
-                    if (i0 > H - 1) i0 = H - 1;
-                    i1 = i0 + 1 < H ? i0 + 1 : H - 1;
-                    l1 = u - (float)i0;
-                    l0 = 1.0f - l1;
-                }
-                const bool m0 = i0 == hg_, m1 = i1 == hg_ && gp.interpolate;
-                if (m0 || m1) {
-#pragma unroll
-                    for (int j = 0; j < QD; ++j) {
-                        const float v = sG[(f * N + i) * QD + j];
-                        if (m0) g[j] += l0 * v;
-                        if (m1) g[j] += l1 * v;
-                    }
-                }
-            }
-            // clip over ALL D dims of (g + 1e-6): the velocity dims of a collision gradient are 0
-            clip_waypoint_grad<QD>(gp, g, QD);
-            const bool interior = hg_ > 0 && hg_ < H - 1;
-#pragma unroll
-            for (int j = 0; j < QD; ++j) sC[(f * H + hg_) * QD + j] = interior ? gp.fields[f].weight * g[j] : 0.f;
-        }
+        gather_clip_weight<QD>(gp, f, nsw, lane, H, N, scale, sC, [&](int i, int j) { return sG[(f * N + i) * QD + j]; });
     }
     __syncthreads();
     G_STAMP();  // 5 gathered + clipped
     if (wv >= nsw) return;
-
-    // ---- phase 4 (the support wave(s)): sum over fields, GP prior, apply
-    float total[D], xu[D], xn[D];
-    const size_t base = ((size_t)b * H + (live ? hs_ : 0)) * D;
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        total[d] = 0.f;
-        xu[d] = live ? sx[hs_ * D + d] : 0.f;
-        xn[d] = live ? snz_x[hs_ * D + d] : 0.f;
-    }
-    if (live) {
-        for (int f = 0; f < gp.n_fields; ++f) {
-#pragma unroll
-            for (int j = 0; j < QD; ++j) total[j] += sC[(f * H + hs_) * QD + j];
-        }
-    }
-    guide_gp_apply<QD>(a, b, ctx, lane, hs_, H, live, xn, xu, sx, total, base, (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 6 : nullptr,
-                       snz + (int)(ne0 & 3ull), shc);
-#undef G_STAMP
+    sum_fields_and_apply<QD>(a, b, ctx, lane, wv, hs_, H, live, sx, snz_x, sC, snz + (int)(ne0 & 3ull), shc);
 }
 
 // traj_metrics_kernel (guide.hpp) for a chain: the same out4 and mask; collision flags with the link radii, no margin, over the objects,
 // workspace and self fields; path length and smoothness are joint-space figures, computed as there.  One wave per trajectory, lane = interpolated
 // waypoint; the waypoint's sphere centres live in LDS (sP, odd stride per lane).
-constexpr int kChainPS = 3 * kChainMaxS + 1;
 template <int QD, bool MULTI_SCENE>
 __global__ __launch_bounds__(64) void traj_metrics_chain_kernel(const dev_guide_params gp, const float* __restrict__ x, float* __restrict__ out, int B, int H, int n_check,
                                                                 uint8_t* __restrict__ mask, const dev_scenes scene, const float* __restrict__ table, int ntab) {
     constexpr int D = 2 * QD;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int lane = threadIdx.x, b = blockIdx.x;
-    float* sx = sm;
-    float* stab = sx + H * D;
-    float* sP = stab + ((ntab + 3) & ~3);
-    float* sprim = sP + 64 * kChainPS;
-    SceneCounts sc_n;
-    if constexpr (MULTI_SCENE) {
-        const int s = scene_of_traj(scene, b);
-        sc_n = scene_counts(gp, gp.prims + (size_t)s * scene.stride);
-        stage_scene_table(gp, scene, s, sprim, lane, 64);
-    } else {
-        for (int i = lane; i < gp.n_prim_floats; i += 64) sprim[i] = gp.prims[i];
-    }
+    const MetricsLds L = metrics_lds_layout(true, H, D, gp.n_prim_floats, ntab);
+    float* sx = sm + L.sx;
+    float* stab = sm + L.stab;
+    float* sP = sm + L.sP;
+    float* sprim = sm + L.sprim;
+    const SceneCounts sc_n = stage_prims<MULTI_SCENE>(gp, scene, b, sprim, lane, 64);
     for (int i = lane; i < ntab; i += 64) stab[i] = table[i];
     const ChainCounts cn = chain_counts<QD>(table, ntab);
     for (int i = lane; i < H * D; i += 64) sx[i] = x[(size_t)b * H * D + i];
@@ -360,18 +257,14 @@ __global__ __launch_bounds__(64) void traj_metrics_chain_kernel(const dev_guide_
         plen += sqrtf(a2); smooth += sqrtf(v2);
     }
     const int N = n_check;
-    const float scale = (N > 1) ? (float)(H - 1) / (float)(N - 1) : 0.f;
+    const float scale = interp_scale(H, N);
     const int32_t* tabi = reinterpret_cast<const int32_t*>(stab);
     constexpr int SPH = kChainHdr + QD * kChainJF;
     float* P = sP + lane * kChainPS;
     float ncoll = 0.f;
     for (int i = lane; i < N; i += 64) {
-        const float u = scale * (float)i;
-        int i0 = (int)u;
-        if (i0 > H - 1) i0 = H - 1;
-        const int i1 = i0 + 1 < H ? i0 + 1 : H - 1;
-        const float l1 = u - (float)i0, l0 = 1.0f - l1;
-        chain_fk<QD, false>(stab, cn.ns, sx + i0 * D, sx + i1 * D, l0, l1, nullptr, P);
+        const InterpPair ip = interp_pair(true, scale, i, H);
+        chain_fk<QD, false>(stab, cn.ns, sx + ip.i0 * D, sx + ip.i1 * D, ip.l0, ip.l1, nullptr, P);
         bool hit = false;
         for (int f = 0; f < gp.n_fields; ++f) {
             const int kind = gp.fields[f].kind;

@@ -24,6 +24,7 @@
 #include "../../include/mpdx.h"
 #include "conv_block.hpp"
 #include "grid_field.hpp"
+#include "guide_common.hpp"
 #include "scene_table.hpp"
 
 namespace mpdx {
@@ -335,16 +336,10 @@ __global__ __launch_bounds__(64) void traj_metrics_kernel(const dev_guide_params
     constexpr int D = 2 * QD;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int lane = threadIdx.x, b = blockIdx.x;
-    float* sx = sm;
-    float* sprim = sx + H * D;
-    SceneCounts sc_n;
-    if constexpr (MULTI_SCENE) {
-        const int s = scene_of_traj(scene, b);
-        sc_n = scene_counts(gp, gp.prims + (size_t)s * scene.stride);
-        stage_scene_table(gp, scene, s, sprim, lane, 64);
-    } else {
-        for (int i = lane; i < gp.n_prim_floats; i += 64) sprim[i] = gp.prims[i];
-    }
+    const MetricsLds L = metrics_lds_layout(false, H, D, gp.n_prim_floats);
+    float* sx = sm + L.sx;
+    float* sprim = sm + L.sprim;
+    const SceneCounts sc_n = stage_prims<MULTI_SCENE>(gp, scene, b, sprim, lane, 64);
     for (int i = lane; i < H * D; i += 64) sx[i] = x[(size_t)b * H * D + i];
     __syncthreads();
     float plen = 0.f, smooth = 0.f;
@@ -358,17 +353,13 @@ __global__ __launch_bounds__(64) void traj_metrics_kernel(const dev_guide_params
         plen += sqrtf(a2); smooth += sqrtf(v2);
     }
     const int N = n_check;
-    const float scale = (N > 1) ? (float)(H - 1) / (float)(N - 1) : 0.f;
+    const float scale = interp_scale(H, N);
     float ncoll = 0.f;
     for (int i = lane; i < N; i += 64) {
-        const float u = scale * (float)i;
-        int i0 = (int)u;
-        if (i0 > H - 1) i0 = H - 1;
-        const int i1 = i0 + 1 < H ? i0 + 1 : H - 1;
-        const float l1 = u - (float)i0, l0 = 1.0f - l1;
+        const InterpPair ip = interp_pair(true, scale, i, H);
         float q[QD];
 #pragma unroll
-        for (int j = 0; j < QD; ++j) q[j] = l0 * sx[i0 * D + j] + l1 * sx[i1 * D + j];
+        for (int j = 0; j < QD; ++j) q[j] = ip.l0 * sx[ip.i0 * D + j] + ip.l1 * sx[ip.i1 * D + j];
         bool hit = false;
         if (ROBOT == MPDX_ROBOT_POINTMASS) {
             float p[DIM];
@@ -547,6 +538,61 @@ __device__ __forceinline__ void guide_draw_noise(const NoiseRng& rng, unsigned l
     }
 }
 
+// Phase 3 of the Panda and chain kernels: the wave of field f gathers the field's point gradients to the support points (transpose of the
+// interpolation, fixed order; one or two blocks of 64 supports), clips over ALL D dims of (g + 1e-6) (the velocity dims of a collision gradient
+// are 0), zeroes the endpoints, weights -> sC[f][H][QD].  point_grad(i, j): joint gradient j of interpolated point i, summed over what holds it.
+template <int QD, class PointGrad>
+__device__ __forceinline__ void gather_clip_weight(const dev_guide_params& gp, int f, int nsw, int lane, int H, int N, float scale, float* sC, PointGrad point_grad) {
+    for (int sb = 0; sb < nsw; ++sb) {
+        const int hg_ = sb * 64 + lane;
+        if (hg_ >= H) continue;
+        const SupportWindow w = support_window(hg_, scale, N, gp.interpolate);
+        float g[QD];
+#pragma unroll
+        for (int j = 0; j < QD; ++j) g[j] = 0.f;
+        for (int i = w.ilo; i <= w.ihi; ++i) {
+            const InterpPair ip = interp_pair(gp.interpolate, scale, i, H);
+            const bool m0 = ip.i0 == hg_, m1 = ip.i1 == hg_ && gp.interpolate;
+            if (m0 || m1) {
+#pragma unroll
+                for (int j = 0; j < QD; ++j) {
+                    const float v = point_grad(i, j);
+                    if (m0) g[j] += ip.l0 * v;
+                    if (m1) g[j] += ip.l1 * v;
+                }
+            }
+        }
+        clip_waypoint_grad<QD>(gp, g, QD);
+        const bool interior = hg_ > 0 && hg_ < H - 1;
+#pragma unroll
+        for (int j = 0; j < QD; ++j) sC[(f * H + hg_) * QD + j] = interior ? gp.fields[f].weight * g[j] : 0.f;
+    }
+}
+
+// Phase 4 of the chain kernel (the support wave(s); the Panda kernel keeps its own copy, see there): sum over fields, GP prior, apply.  sx = the unnormalised state the prologue staged,
+// sxn = the normalised state as loaded (nothing has written x since); snoise, shc: see guide_gp_apply.
+template <int QD>
+__device__ __forceinline__ void sum_fields_and_apply(const GuideArgs& a, int b, int ctx, int lane, int wv, int hs_, int H, bool live, const float* sx, const float* sxn,
+                                                     const float* sC, const float* snoise, const float* shc) {
+    constexpr int D = 2 * QD;
+    __builtin_assume(shc != nullptr);   // (both callers stage the hard conditions: guide_gp_apply's global-memory fallback, 2 D loads on the kernel's tail, drops out)
+    float total[D], xu[D], xn[D];
+    const size_t base = ((size_t)b * H + (live ? hs_ : 0)) * D;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+        total[d] = 0.f;
+        xu[d] = live ? sx[hs_ * D + d] : 0.f;
+        xn[d] = live ? sxn[hs_ * D + d] : 0.f;
+    }
+    if (live) {
+        for (int f = 0; f < a.gp.n_fields; ++f) {
+#pragma unroll
+            for (int j = 0; j < QD; ++j) total[j] += sC[(f * H + hs_) * QD + j];
+        }
+    }
+    guide_gp_apply<QD>(a, b, ctx, lane, hs_, H, live, xn, xu, sx, total, base, (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 6 : nullptr, snoise, shc);
+}
+
 // Point-mass robots (QD = DIM = 2 or 3).  WPT = waves per trajectory.  The collision part (SDF force per interpolated point
 // and per field) is split over WPT waves as (point slice) x (field): PW = min(WPT,2) point slices, WPT/PW field slots;
 // wave 0 then gathers, clips, adds the GP term and applies the update.  WPT = 8 (2 point halves x up to 4 fields): the
@@ -570,21 +616,14 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
     const int hs_ = (wv < nsw ? wv : 0) * 64 + lane;   // this thread's support index (waves >= nsw shadow block 0: their copy is unused)
     const bool live = hs_ < H;
     int tr_i = 0;
-#define G_STAMP() do { if (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) a.trace[wv * 16 + tr_i] = (long long)__builtin_readcyclecounter(); ++tr_i; } while (0)
     G_STAMP();  // 0 entry
     // LDS carve: unnormalised state [H][D] | point forces A,B [MAXF][N][QD] each | primitive table
-    float* sx = sm;
-    float* sA = sx + H * D;
-    float* sB = sA + MAXF * N * QD;
-    float* sprim = sB + MAXF * N * QD;
-    SceneCounts sc_n;
-    if constexpr (MULTI_SCENE) {
-        const int s = scene_of_traj(a.scene, b);
-        sc_n = scene_counts(gp, gp.prims + (size_t)s * a.scene.stride);
-        stage_scene_table(gp, a.scene, s, sprim, threadIdx.x, 64 * WPT);
-    } else {
-        for (int i = threadIdx.x; i < gp.n_prim_floats; i += 64 * WPT) sprim[i] = gp.prims[i];
-    }
+    const GuideLds L = guide_lds_layout(kGuidePointMass, H, D, N, gp.n_prim_floats);
+    float* sx = sm + L.sx;
+    float* sA = sm + L.sA;
+    float* sB = sm + L.sB;
+    float* sprim = sm + L.sprim;
+    const SceneCounts sc_n = stage_prims<MULTI_SCENE>(gp, a.scene, b, sprim, threadIdx.x, 64 * WPT);
 
     // ---- load + unnormalise (normalization.py:156-167)
     const int ctx = b / a.n_per_ctx;
@@ -594,33 +633,20 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
 #pragma unroll
     for (int d = 0; d < D; ++d) {
         xn[d] = live ? a.x[base + d] : 0.f;
-        const float c = clipall ? fminf(fmaxf(xn[d], -1.f), 1.f) : xn[d];
-        const float u01 = __fadd_rn(c, 1.0f) * 0.5f;
-        // identity_normalizer: 0 limits (normalization.py:156-167), 1 Identity (:111-116), 2 GaussianNormalizer (:140-141: x * stds + means - the
-        // host passes means in `mins`, stds in `maxs`; no range test)
-        xu[d] = gp.identity_normalizer == 1 ? xn[d] : gp.identity_normalizer == 2 ? __fadd_rn(__fmul_rn(xn[d], gp.maxs[d]), gp.mins[d])
-                                                    : __fadd_rn(__fmul_rn(u01, __fsub_rn(gp.maxs[d], gp.mins[d])), gp.mins[d]);
+        xu[d] = unnormalise_one(gp.identity_normalizer, xn[d], gp.mins[d], gp.maxs[d], clipall);
         if (live && wv < nsw) sx[hs_ * D + d] = xu[d];
     }
     __syncthreads();
     G_STAMP();  // 1 state unnormalised + staged
 
     // ---- collision terms on the interpolated positions
-    const float scale = (N > 1) ? (float)(H - 1) / (float)(N - 1) : 0.f;  // align_corners=True
+    const float scale = interp_scale(H, N);
     for (int i = (wv % PW) * 64 + lane; i < N; i += 64 * PW) {
-        int i0 = i, i1 = i;
-        float l0 = 1.f, l1 = 0.f;
-        if (gp.interpolate) {
-            const float u = scale * (float)i;
-            i0 = (int)u;
-            if (i0 > H - 1) i0 = H - 1;
-            i1 = i0 + 1 < H ? i0 + 1 : H - 1;
-            l1 = u - (float)i0;
-            l0 = 1.0f - l1;
-        }
+        const InterpPair ip = interp_pair(gp.interpolate, scale, i, H);
+        const float l0 = ip.l0, l1 = ip.l1;
         float q[QD];
 #pragma unroll
-        for (int j = 0; j < QD; ++j) q[j] = l0 * sx[i0 * D + j] + l1 * sx[i1 * D + j];
+        for (int j = 0; j < QD; ++j) q[j] = l0 * sx[ip.i0 * D + j] + l1 * sx[ip.i1 * D + j];
 
         if (ROBOT == MPDX_ROBOT_POINTMASS) {
             float p[DIM];
@@ -654,7 +680,7 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
     // ---- gather to support points (transpose of the interpolation), clip, zero ends, weight: wave f handles field f and
     //      leaves its clipped, weighted gradient in LDS; wave 0 then adds the fields in order (same additions as one wave
     //      looping over the fields)
-    float* sC = sB;   // [MAXF][H][QD]: overlays sB after the barrier below (every gatherer has its sums in registers by then)
+    float* sC = sm + L.sC;   // [MAXF][H][QD]: overlays sB after the barrier below (every gatherer has its sums in registers by then)
     constexpr int NSB = 2;   // support blocks of 64 (H <= 128)
     float cg[NSB][QD];
 #pragma unroll
@@ -668,29 +694,17 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
         for (int sb = 0; sb < NSB; ++sb) {
             const int hg_ = sb * 64 + lane;   // the support this lane gathers in block sb
             if (sb >= nsw || hg_ >= H) continue;
-            int ilo = hg_, ihi = hg_;
-            if (gp.interpolate && scale > 0.f) {
-                ilo = (int)((float)(hg_ - 1) / scale) - 1;   // points of the segments (hg-1, hg) and (hg, hg+1): any number per segment
-                ihi = (int)((float)(hg_ + 1) / scale) + 1;
-                if (ilo < 0) ilo = 0;
-                if (ihi > N - 1) ihi = N - 1;
-            }
+            const SupportWindow w = support_window(hg_, scale, N, gp.interpolate);
             float g[QD];
 #pragma unroll
             for (int j = 0; j < QD; ++j) g[j] = 0.f;
-            for (int i = ilo; i <= ihi; ++i) {
-                int i0 = i, i1 = i;
-                if (gp.interpolate) {
-                    const float u = scale * (float)i;
-                    i0 = (int)u;
-                    if (i0 > H - 1) i0 = H - 1;
-                    i1 = i0 + 1 < H ? i0 + 1 : H - 1;
-                }
-                if (i0 == hg_) {
+            for (int i = w.ilo; i <= w.ihi; ++i) {   // (its own gather: the products l0 * force, l1 * force were rounded when stored - the shared one would fuse them)
+                const InterpPair ip = interp_pair(gp.interpolate, scale, i, H);
+                if (ip.i0 == hg_) {
 #pragma unroll
                     for (int j = 0; j < QD; ++j) g[j] += sA[(f * N + i) * QD + j];
                 }
-                if (i1 == hg_ && gp.interpolate) {
+                if (ip.i1 == hg_ && gp.interpolate) {
 #pragma unroll
                     for (int j = 0; j < QD; ++j) g[j] += sB[(f * N + i) * QD + j];
                 }
@@ -727,7 +741,6 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
     }
     G_STAMP();  // 4 gathered + clipped
     guide_gp_apply<QD>(a, b, ctx, lane, hs_, H, live, xn, xu, sx, total, base, (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 5 : nullptr);
-#undef G_STAMP
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -742,7 +755,7 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
 //   phase 3  wave f gathers field f to the support points (transpose of the interpolation, summing the groups in a fixed
 //            order), clips by norm, weights
 //   phase 4  wave 0: sum over fields, GP prior, apply (guide_gp_apply)
-constexpr int kPandaFKS = 75;   // floats per interpolated point in LDS: O[7][3] | Z[7][3] | P[11][3]  (odd stride: no bank conflicts)
+// (kPandaFKS floats per interpolated point in LDS: O[7][3] | Z[7][3] | P[11][3], guide_common.hpp)
 // Sphere groups (round 5).  The kernel is VALU-issue bound once two workgroups share a CU (stamps + ISA census, profiles/r05_guide_*):
 // what counts is the number of instructions, so the split follows the kinematic chain - a group's joint gradients and (in the dense
 // variant) its forward kinematics stop at the highest frame its spheres sit on:
@@ -750,7 +763,6 @@ constexpr int kPandaFKS = 75;   // floats per interpolated point in LDS: O[7][3]
 //     group 1: spheres 4-6  (frames 4,5,5)   -> joints 0-4      group 3: sphere 10 (frame 7) + ALL 12 self-collision pairs
 // (round 4: {0-2, 3-5, 6-8, 9-10} with 3 pairs each: every group touched frame 7 through its pairs, i.e. 4 x the full FK and 4 x a
 // 7-joint fold for the self field).  Entries of sG that are zero by construction are neither written nor read.
-constexpr int kPandaParts = 4;
 constexpr int panda_group_first(int part) { return part == 0 ? 0 : part == 1 ? 4 : part == 2 ? 7 : part == 3 ? 10 : 11; }
 constexpr int panda_group_joints(int part) { return part == 0 ? 3 : part == 1 ? 5 : 7; }      // joints that move the group's spheres
 // (the self field lives in part 3 alone, with all 7 joints)
@@ -769,19 +781,10 @@ __device__ __forceinline__ void panda_group_forces(const dev_guide_params& gp, c
     for (int i = half * 64 + lane; i < N; i += 128) {
         float O[7][3], Z[7][3], P[kPandaNS][3];
         if constexpr (FKREG) {
-            int i0 = i, i1 = i;
-            float l0 = 1.f, l1 = 0.f;
-            if (gp.interpolate) {
-                const float u = scale * (float)i;
-                i0 = (int)u;
-                if (i0 > H - 1) i0 = H - 1;
-                i1 = i0 + 1 < H ? i0 + 1 : H - 1;
-                l1 = u - (float)i0;
-                l0 = 1.0f - l1;
-            }
+            const InterpPair ip = interp_pair(gp.interpolate, scale, i, H);
             float q[QD];
 #pragma unroll
-            for (int j = 0; j < QD; ++j) q[j] = l0 * sx[i0 * D + j] + l1 * sx[i1 * D + j];
+            for (int j = 0; j < QD; ++j) q[j] = ip.l0 * sx[ip.i0 * D + j] + ip.l1 * sx[ip.i1 * D + j];
             panda_fk<QD, NJ>(q, O, Z);
 #pragma unroll
             for (int s = 0; s < kPandaNS; ++s) {
@@ -891,8 +894,10 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(co
     const int hs_ = (wv < nsw ? wv : 0) * 64 + lane;
     const bool live = hs_ < H;
     int tr_i = 0;
-#define G_STAMP() do { if (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) a.trace[wv * 16 + tr_i] = (long long)__builtin_readcyclecounter(); ++tr_i; } while (0)
     G_STAMP();  // 0 entry
+    // This kernel keeps its own prologue, carve and last phase: with the shared helpers of the chain kernel (stage_hard_conds,
+    // stage_state_unnormalised, sum_fields_and_apply) and a carve from guide_lds_layout it ran 1.9 % slower at B = 100 and at B = 6400, same
+    // bits (profiles/guide_shared_phases_ab.md).  guide_lds_layout states the same offsets (the launcher sizes the launch by it).
     float* sx = sm;                           // [H][D]  unnormalised state
     float* sfk = sx + H * D;                  // [N][kPandaFKS]   (not in the DENSE variant)
     float* sG = sfk + (DENSE ? 0 : N * kPandaFKS);   // [MAXF][NP][N][QD]  partial joint gradients
@@ -948,21 +953,12 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(co
     G_STAMP();  // 1 state unnormalised + staged
 
     // ---- phase 1: interpolate + FK, once per point
-    const float scale = (N > 1) ? (float)(H - 1) / (float)(N - 1) : 0.f;  // align_corners=True
+    const float scale = interp_scale(H, N);
     for (int i = wv * 64 + lane; i < N && !DENSE; i += 64 * WPT) {
-        int i0 = i, i1 = i;
-        float l0 = 1.f, l1 = 0.f;
-        if (gp.interpolate) {
-            const float u = scale * (float)i;
-            i0 = (int)u;
-            if (i0 > H - 1) i0 = H - 1;
-            i1 = i0 + 1 < H ? i0 + 1 : H - 1;
-            l1 = u - (float)i0;
-            l0 = 1.0f - l1;
-        }
+        const InterpPair ip = interp_pair(gp.interpolate, scale, i, H);
         float q[QD];
 #pragma unroll
-        for (int j = 0; j < QD; ++j) q[j] = l0 * sx[i0 * D + j] + l1 * sx[i1 * D + j];
+        for (int j = 0; j < QD; ++j) q[j] = ip.l0 * sx[ip.i0 * D + j] + ip.l1 * sx[ip.i1 * D + j];
         float O[7][3], Z[7][3];
         panda_fk(q, O, Z);
         float* fk = sfk + i * kPandaFKS;
@@ -1002,53 +998,17 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(co
     // ---- phase 3: wave f gathers field f to the support points (one or two blocks of 64), clips, weights
     if (wv < gp.n_fields) {
         const int f = wv;
-        // the parts of sG[(f, .)] that hold data are known per field kind (panda_part_joints): two straight-line variants of the gather,
+        // the parts of sG[(f, .)] that hold data are known per field kind (panda_group_joints): two straight-line variants of the gather,
         // chosen once per wave (a per-element test inside the loop doubled this phase: 6.3 k -> 12 k cycles, tools/guide_trace.py)
         auto gather = [&](auto self_c) {
             constexpr bool SELFK = decltype(self_c)::value;
-            for (int sb = 0; sb < nsw; ++sb) {
-                const int hg_ = sb * 64 + lane;
-                if (hg_ >= H) continue;
-                int ilo = hg_, ihi = hg_;
-                if (gp.interpolate && scale > 0.f) {
-                    ilo = (int)((float)(hg_ - 1) / scale) - 1;   // points of the segments (hg-1, hg) and (hg, hg+1): any number per segment
-                    ihi = (int)((float)(hg_ + 1) / scale) + 1;
-                    if (ilo < 0) ilo = 0;
-                    if (ihi > N - 1) ihi = N - 1;
-                }
-                float g[QD];
+            gather_clip_weight<QD>(gp, f, nsw, lane, H, N, scale, sC, [&](int i, int j) {
+                float v = 0.f;
 #pragma unroll
-                for (int j = 0; j < QD; ++j) g[j] = 0.f;
-                for (int i = ilo; i <= ihi; ++i) {
-                    int i0 = i, i1 = i;
-                    float l0 = 1.f, l1 = 0.f;
-                    if (gp.interpolate) {
-                        const float u = scale * (float)i;
-                        i0 = (int)u;
-                        if (i0 > H - 1) i0 = H - 1;
-                        i1 = i0 + 1 < H ? i0 + 1 : H - 1;
-                        l1 = u - (float)i0;
-                        l0 = 1.0f - l1;
-                    }
-                    const bool m0 = i0 == hg_, m1 = i1 == hg_ && gp.interpolate;
-                    if (m0 || m1) {
-#pragma unroll
-                        for (int j = 0; j < QD; ++j) {
-                            float v = 0.f;
-#pragma unroll
-                            for (int pt = 0; pt < NP; ++pt)
-                                if (SELFK ? pt == NP - 1 : j < panda_group_joints(pt)) v += sG[((f * NP + pt) * N + i) * QD + j];   // (compile time)
-                            if (m0) g[j] += l0 * v;
-                            if (m1) g[j] += l1 * v;
-                        }
-                    }
-                }
-                // clip over ALL D dims of (g + 1e-6): the velocity dims of a collision gradient are 0
-                clip_waypoint_grad<QD>(gp, g, QD);
-                const bool interior = hg_ > 0 && hg_ < H - 1;
-#pragma unroll
-                for (int j = 0; j < QD; ++j) sC[(f * H + hg_) * QD + j] = interior ? gp.fields[f].weight * g[j] : 0.f;
-            }
+                for (int pt = 0; pt < NP; ++pt)
+                    if (SELFK ? pt == NP - 1 : j < panda_group_joints(pt)) v += sG[((f * NP + pt) * N + i) * QD + j];   // (compile time)
+                return v;
+            });
         };
         if (gp.fields[f].kind == MPDX_FIELD_SELF) gather(std::true_type{}); else gather(std::false_type{});
     }
@@ -1073,21 +1033,12 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(co
     }
     guide_gp_apply<QD>(a, b, ctx, lane, hs_, H, live, xn, xu, sx, total, base, (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 6 : nullptr,
                        snz + (int)(ne0 & 3ull), shc);
-#undef G_STAMP
 }
 
-
-// MPDX_ROBOT_CHAIN (chain.hpp): floats per interpolated point of the FK table in LDS, O[QD][3] | Z[QD][3] | P[MPDX_ROBOT_CHAIN_MAX_SPHERES][3]  (odd stride)
-constexpr int chain_fk_stride(int qd) { return 6 * qd + 3 * MPDX_ROBOT_CHAIN_MAX_SPHERES + 1; }
-
+// bytes of dynamic LDS of a guide launch (n_prim_floats / n_chain_floats of gp: what a workgroup stages)
 inline size_t guide_lds_bytes(const mpdx_guide_params& gp, int H, int D, bool dense = false) {
-    const int N = gp.interpolate ? gp.n_interp : H;
-    if (gp.robot == MPDX_ROBOT_CHAIN)   // state | chain table | FK table | joint gradients | per-field support gradients | noise + normalised state | primitives | hard conditions
-        return ((size_t)H * D + (size_t)(gp.n_chain_floats + 3) + (size_t)N * chain_fk_stride(D / 2) + (size_t)MPDX_MAX_FIELDS * N * (D / 2) + (size_t)MPDX_MAX_FIELDS * H * (D / 2) +
-                (size_t)(2 * H * D + 8 + 3) + (size_t)gp.n_prim_floats + 3 + 2 * D) * sizeof(float);
-    if (gp.robot == MPDX_ROBOT_PANDA)
-        return (size_t)(H * D + (dense ? 0 : N * kPandaFKS) + MPDX_MAX_FIELDS * kPandaParts * N * 7 + MPDX_MAX_FIELDS * H * 7 + (2 * H * D + 4 + 3) + gp.n_prim_floats + 3 + 2 * D) * sizeof(float);
-    return (size_t)(H * D + 2 * MPDX_MAX_FIELDS * N * (D / 2) + gp.n_prim_floats) * sizeof(float);
+    const GuideKind kind = gp.robot == MPDX_ROBOT_CHAIN ? kGuideChain : gp.robot != MPDX_ROBOT_PANDA ? kGuidePointMass : dense ? kGuidePandaDense : kGuidePandaSparse;
+    return guide_lds_layout(kind, H, D, gp.interpolate ? gp.n_interp : H, gp.n_prim_floats, gp.n_chain_floats).total * sizeof(float);
 }
 
 }  // namespace mpdx

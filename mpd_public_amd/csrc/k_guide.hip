@@ -66,21 +66,27 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
     if ((threadIdx.x & 63) == 0) atomicMax(out + ctx, __float_as_uint(m));
 }
 
+int guide_block_problem(const mpdx_guide_params* gp, int D, ChainInfo* chain_info) {
+    if (D != 2 * gp->q_dim || D > 16) return fail(MPDX_E_INVALID, "state dim %d != 2*q_dim (%d)", D, gp->q_dim);
+    if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS) return fail(MPDX_E_INVALID, "n_fields %d", gp->n_fields);
+    if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
+    if (!chain_info) return 0;   // (the baseline planners: built-in robots, one scene, no grid - refusals of their own)
+    memset(chain_info, 0, sizeof(*chain_info));
+    if (gp->robot == MPDX_ROBOT_CHAIN)   // (a chain robot's own refusals first: it takes no grid field at all)
+        if (const char* why = chain_params_check(*gp, chain_info)) return fail(MPDX_E_INVALID, "%s", why);
+    if (const char* why = grid_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
+    if (const char* why = scene_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
+    return 0;
+}
+
 int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const float* hs, const float* hg,
                         const uint32_t* amax_in, uint32_t* amax_out, int n_per_ctx, int B, int H, int D, hipStream_t st,
                         const float* noise, float noise_scale, float noise_extra, float* chain, float guide_scale, const NoiseRng* rng) {
     if (!gp || !x || !amax_in) return fail(MPDX_E_INVALID, "null argument");
     if (H > 128 || H < 2) return fail(MPDX_E_INVALID, "guide kernel: one support point per lane of one or two waves: H=%d unsupported (max 128)", H);
-    if (D != 2 * gp->q_dim || D > 16) return fail(MPDX_E_INVALID, "state dim %d != 2*q_dim (%d)", D, gp->q_dim);
-    if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS) return fail(MPDX_E_INVALID, "n_fields %d", gp->n_fields);
+    ChainInfo chain_info;
+    if (int rc = guide_block_problem(gp, D, &chain_info)) return rc;
     if (gp->interpolate && (gp->n_interp < H || gp->n_interp > 8 * H)) return fail(MPDX_E_INVALID, "n_interp %d unsupported", gp->n_interp);
-    if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
-    ChainInfo chain_info;   // (a chain robot's own refusals first: it takes no grid field at all)
-    memset(&chain_info, 0, sizeof(chain_info));
-    if (gp->robot == MPDX_ROBOT_CHAIN)
-        if (const char* why = chain_params_check(*gp, &chain_info)) return fail(MPDX_E_INVALID, "%s", why);
-    if (const char* why = grid_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
-    if (const char* why = scene_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
     if (gp->robot == MPDX_ROBOT_PANDA && (((uintptr_t)x & 15) || ((size_t)H * D) % 4))
         return fail(MPDX_E_INVALID, "Panda guide: x must be 16-byte aligned with H * D a multiple of 4 (the trajectory is staged with 16-byte loads)");
     GuideArgs a;
@@ -107,40 +113,24 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
     const bool dense = gp->robot == MPDX_ROBOT_PANDA && (dense_env >= 0 ? dense_env != 0 : B >= 512) && guide_lds_bytes(staged, H, D, true) <= 80 * 1024;
     const size_t lds = guide_lds_bytes(staged, H, D, dense);
     if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "guide needs %zu B of LDS (n_interp %d too large)", lds, gp->n_interp);
-#define MPDX_GUIDE_PM(QD_)                                                                                                                      \
-    {                                                                                                                                           \
-        if (multi && grid) hipLaunchKernelGGL((guide_step_kernel<QD_, QD_, MPDX_ROBOT_POINTMASS, 8, true, true>), dim3(B), dim3(512), lds, st, a);   \
-        else if (multi) hipLaunchKernelGGL((guide_step_kernel<QD_, QD_, MPDX_ROBOT_POINTMASS, 8, false, true>), dim3(B), dim3(512), lds, st, a); \
-        else if (grid) hipLaunchKernelGGL((guide_step_kernel<QD_, QD_, MPDX_ROBOT_POINTMASS, 8, true>), dim3(B), dim3(512), lds, st, a);         \
-        else hipLaunchKernelGGL((guide_step_kernel<QD_, QD_, MPDX_ROBOT_POINTMASS, 8>), dim3(B), dim3(512), lds, st, a);                         \
-    }
-#define MPDX_GUIDE_PANDA(...)                                                                          \
-    {                                                                                                  \
-        if (int rc = raise_lds_limit((const void*)guide_step_panda_kernel<__VA_ARGS__>)) return rc;    \
-        hipLaunchKernelGGL((guide_step_panda_kernel<__VA_ARGS__>), dim3(B), dim3(512), lds, st, a);    \
-    }
-    if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 2 && gp->ws_dim == 2) MPDX_GUIDE_PM(2)
-    else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 3 && gp->ws_dim == 3) MPDX_GUIDE_PM(3)
-    else if (gp->robot == MPDX_ROBOT_PANDA && gp->q_dim == 7 && gp->ws_dim == 3) {
-        if (multi) {
-            if (dense && grid) MPDX_GUIDE_PANDA(true, true, true)
-            else if (dense) MPDX_GUIDE_PANDA(true, false, true)
-            else if (grid) MPDX_GUIDE_PANDA(false, true, true)
-            else MPDX_GUIDE_PANDA(false, false, true)
-        }
-        else if (dense && grid) MPDX_GUIDE_PANDA(true, true)
-        else if (dense) MPDX_GUIDE_PANDA(true)
-        else if (grid) MPDX_GUIDE_PANDA(false, true)
-        else MPDX_GUIDE_PANDA(false)
-    }
-#undef MPDX_GUIDE_PM
-#undef MPDX_GUIDE_PANDA
-    else if (gp->robot == MPDX_ROBOT_CHAIN) {   // (q_dim == n_joints, ws_dim == 3: checked above)
-        if (int rc = launch_chain_guide(a, gp->chain, chain_info, multi, lds, B, st)) return rc;
-    }
-    else
-        return fail(MPDX_E_INVALID, "unsupported robot %d / q_dim %d / ws_dim %d", gp->robot, gp->q_dim, gp->ws_dim);
-    return 0;
+    if (gp->robot == MPDX_ROBOT_CHAIN) return launch_chain_guide(a, gp->chain, chain_info, multi, lds, B, st);   // (q_dim == n_joints, ws_dim == 3: checked above)
+    int rc = 0;
+    const bool known = with_builtin_robot(*gp, [&](auto qd, auto, auto robot) {
+        if constexpr (decltype(robot)::value == MPDX_ROBOT_PANDA)
+            rc = with_bools([&](auto dense_c, auto grid_c, auto multi_c) {
+                auto kern = guide_step_panda_kernel<decltype(dense_c)::value, decltype(grid_c)::value, decltype(multi_c)::value>;
+                if (int r = raise_lds_limit((const void*)kern)) return r;
+                hipLaunchKernelGGL(kern, dim3(B), dim3(512), lds, st, a);
+                return 0;
+            }, dense, grid, multi);
+        else   // (the point mass has no dense variant and stays under the default LDS limit's refusal: no raise_lds_limit)
+            with_bools([&](auto grid_c, auto multi_c) {
+                constexpr int QD = decltype(qd)::value;
+                hipLaunchKernelGGL((guide_step_kernel<QD, QD, MPDX_ROBOT_POINTMASS, 8, decltype(grid_c)::value, decltype(multi_c)::value>), dim3(B), dim3(512), lds, st, a);
+            }, grid, multi);
+    });
+    if (!known) return fail(MPDX_E_INVALID, "unsupported robot %d / q_dim %d / ws_dim %d", gp->robot, gp->q_dim, gp->ws_dim);
+    return rc;
 }
 
 }  // namespace mpdx
@@ -173,42 +163,29 @@ int mpdx_traj_metrics_mask(const mpdx_guide_params* gp, const float* x_unnormali
                            void* stream) {
     if (!gp || !x_unnormalised || !out4 || B <= 0) return fail(MPDX_E_INVALID, "bad argument");
     if (H > 128 || H < 2) return fail(MPDX_E_INVALID, "H=%d unsupported (max 128)", H);
-    if (D != 2 * gp->q_dim || D > 16) return fail(MPDX_E_INVALID, "state dim %d != 2*q_dim (%d)", D, gp->q_dim);
-    if (n_check < 2) n_check = H;
-    if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS) return fail(MPDX_E_INVALID, "n_fields %d", gp->n_fields);
-    if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
     ChainInfo chain_info;
-    memset(&chain_info, 0, sizeof(chain_info));
-    if (gp->robot == MPDX_ROBOT_CHAIN)
-        if (const char* why = chain_params_check(*gp, &chain_info)) return fail(MPDX_E_INVALID, "%s", why);
-    if (const char* why = grid_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
-    if (const char* why = scene_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
+    if (int rc = guide_block_problem(gp, D, &chain_info)) return rc;
+    if (n_check < 2) n_check = H;
     hipStream_t st = (hipStream_t)stream;
     const bool grid = has_grid_field(*gp), multi = has_scenes(*gp);
     const dev_guide_params g = dev_params_staged(*gp);   // (n_prim_floats = what a workgroup stages: the table, or one scene block + the shared tail)
+    const dev_scenes sc = dev_scenes_of(*gp);
     if (gp->robot == MPDX_ROBOT_CHAIN) {
-        if (int rc = launch_chain_metrics(g, x_unnormalised, out4, mask, n_check, B, H, dev_scenes_of(*gp), gp->chain, chain_info, multi, st)) return rc;
+        if (int rc = launch_chain_metrics(g, x_unnormalised, out4, mask, n_check, B, H, sc, gp->chain, chain_info, multi, st)) return rc;
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    const size_t lds = (size_t)(H * D + g.n_prim_floats) * sizeof(float);
+    const size_t lds = metrics_lds_layout(false, H, D, g.n_prim_floats).total * sizeof(float);
     dev_grids gr;
     memset(&gr, 0, sizeof(gr));
     if (grid) gr = dev_grids_of(*gp);
-    const dev_scenes sc = dev_scenes_of(*gp);
-#define MPDX_METRICS(QD_, DIM_, ROBOT_)                                                                                                                                          \
-    {                                                                                                                                                                            \
-        if (multi && grid) hipLaunchKernelGGL((traj_metrics_kernel<QD_, DIM_, ROBOT_, true, true>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr, sc);    \
-        else if (multi) hipLaunchKernelGGL((traj_metrics_kernel<QD_, DIM_, ROBOT_, false, true>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr, sc);  \
-        else if (grid) hipLaunchKernelGGL((traj_metrics_kernel<QD_, DIM_, ROBOT_, true>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr, sc);          \
-        else hipLaunchKernelGGL((traj_metrics_kernel<QD_, DIM_, ROBOT_>), dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr, sc);                          \
-    }
-    if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 2 && gp->ws_dim == 2) MPDX_METRICS(2, 2, MPDX_ROBOT_POINTMASS)
-    else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 3 && gp->ws_dim == 3) MPDX_METRICS(3, 3, MPDX_ROBOT_POINTMASS)
-    else if (gp->robot == MPDX_ROBOT_PANDA && gp->q_dim == 7 && gp->ws_dim == 3) MPDX_METRICS(7, 3, MPDX_ROBOT_PANDA)
-#undef MPDX_METRICS
-    else
-        return fail(MPDX_E_INVALID, "unsupported robot %d / q_dim %d / ws_dim %d", gp->robot, gp->q_dim, gp->ws_dim);
+    const bool known = with_builtin_robot(*gp, [&](auto qd, auto dim, auto robot) {
+        with_bools([&](auto grid_c, auto multi_c) {
+            hipLaunchKernelGGL((traj_metrics_kernel<decltype(qd)::value, decltype(dim)::value, decltype(robot)::value, decltype(grid_c)::value, decltype(multi_c)::value>),
+                               dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr, sc);
+        }, grid, multi);
+    });
+    if (!known) return fail(MPDX_E_INVALID, "unsupported robot %d / q_dim %d / ws_dim %d", gp->robot, gp->q_dim, gp->ws_dim);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -216,8 +193,8 @@ int mpdx_traj_metrics_mask(const mpdx_guide_params* gp, const float* x_unnormali
 int mpdx_guide_time(const mpdx_guide_params* gp, float* x, float* grad_out, const uint32_t* absmax_in, int n_per_ctx, int B, int H, int D,
                     int reps, void* stream, float* ms_avg) {
     if (!gp || !x || !grad_out || !absmax_in || !ms_avg || reps < 1) return fail(MPDX_E_INVALID, "bad argument");
-    if (const char* why = scene_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);   // (before the events: nothing is created for a refused block)
-    if (const char* why = chain_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
+    ChainInfo chain_info;
+    if (int rc = guide_block_problem(gp, D, &chain_info)) return rc;   // (before the events: nothing is created for a refused block)
     hipStream_t st = (hipStream_t)stream;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));

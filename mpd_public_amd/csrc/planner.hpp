@@ -453,7 +453,7 @@ __global__ __launch_bounds__(kGpmpThreads, 1) void gpmp_lm_kernel(const GpmpArgs
     float* red = rhs + NR;                           // [64] reduction scratch
     int* ps = (int*)(red + 64);                      // [H + 1] first interpolation point of every support segment
     float* sprim = (float*)(ps + H + 2);
-    for (int i = tid; i < gp.n_prim_floats; i += NTHR) sprim[i] = gp.prims[i];
+    stage_prims(gp, sprim, tid, NTHR);
     const size_t base = (size_t)b * H * D;
     for (int i = tid; i < H * D; i += NTHR) {
         const float xv = a.x[base + i];
@@ -472,7 +472,7 @@ __global__ __launch_bounds__(kGpmpThreads, 1) void gpmp_lm_kernel(const GpmpArgs
     if (lam < 0.f) return;   // converged earlier (marked by a negative lambda): x is final, delta is zero - nothing left to do
     __syncthreads();
 
-    const float scale = (N > 1) ? (float)(H - 1) / (float)(N - 1) : 0.f;
+    const float scale = interp_scale(H, N);
     const float s_gp = 1.0f / (gp.sigma_gp * gp.sigma_gp), s_ob = 1.0f / (a.sigma_obs * a.sigma_obs);
     const float dt = gp.dt;
     const float qa = 12.0f / (dt * dt * dt), qb = -6.0f / (dt * dt), qc = 4.0f / dt;   // Q^-1 = [[qa, qb], [qb, qc]] (x) I
@@ -480,18 +480,9 @@ __global__ __launch_bounds__(kGpmpThreads, 1) void gpmp_lm_kernel(const GpmpArgs
     // linearise the collision factors at `src` and return F(src) (uniform over the workgroup)
     auto linearise = [&](const float* src) -> float {
         auto point_q = [&](int i, float (&q)[QD]) {
-            int i0 = i, i1 = i;
-            float l0 = 1.f, l1 = 0.f;
-            if (gp.interpolate) {
-                const float u = scale * (float)i;
-                i0 = (int)u;
-                if (i0 > H - 1) i0 = H - 1;
-                i1 = i0 + 1 < H ? i0 + 1 : H - 1;
-                l1 = u - (float)i0;
-                l0 = 1.0f - l1;
-            }
+            const InterpPair ip = interp_pair(gp.interpolate, scale, i, H);
 #pragma unroll
-            for (int j = 0; j < QD; ++j) q[j] = l0 * src[i0 * D + j] + l1 * src[i1 * D + j];
+            for (int j = 0; j < QD; ++j) q[j] = ip.l0 * src[ip.i0 * D + j] + ip.l1 * src[ip.i1 * D + j];
         };
         if (4 * N <= NTHR && (size_t)2 * N * MSZ <= (size_t)2 * n * DD) {   // (one task per thread: 4 N of them)
             // FOUR threads per point (round 5; N is a multiple of 64 in practice: the part is wave-uniform): parts 0 / 1 write the two [N][MSZ] term
@@ -594,7 +585,7 @@ __global__ __launch_bounds__(kGpmpThreads, 1) void gpmp_lm_kernel(const GpmpArgs
         if (gp.interpolate && scale > 0.f) {
             i = (int)((float)h / scale);
             if (i > N) i = N;
-            auto lo = [&](int k) { int v = (int)(scale * (float)k); return v > H - 1 ? H - 1 : v; };
+            auto lo = [&](int k) { return interp_pair(true, scale, k, H).i0; };
             while (i > 0 && lo(i - 1) >= h) --i;
             while (i < N && lo(i) < h) ++i;
         }
@@ -608,15 +599,8 @@ __global__ __launch_bounds__(kGpmpThreads, 1) void gpmp_lm_kernel(const GpmpArgs
         // points that touch support h: those whose lower support is h - 1 or h
         const int plo = ps[h - 1], phi = ps[h + 1] - 1;
         auto point_w = [&](int i, int& i0, int& i1, float& l0, float& l1) {
-            i0 = i; i1 = i; l0 = 1.f; l1 = 0.f;
-            if (gp.interpolate) {
-                const float u = scale * (float)i;
-                i0 = (int)u;
-                if (i0 > H - 1) i0 = H - 1;
-                i1 = i0 + 1 < H ? i0 + 1 : H - 1;
-                l1 = u - (float)i0;
-                l0 = 1.0f - l1;
-            }
+            const InterpPair ip = interp_pair(gp.interpolate, scale, i, H);
+            i0 = ip.i0; i1 = ip.i1; l0 = ip.l0; l1 = ip.l1;
         };
         auto msum = [&](int i, int off) { return sM[(size_t)i * MSZ + off] + sM[((size_t)N + i) * MSZ + off]; };
         if (e < T0) {            // pos-pos lower triangle of the diagonal block
@@ -797,7 +781,7 @@ __global__ __launch_bounds__(kRrtThreads) void rrt_connect_kernel(const RrtArgs 
     float* sred = sq + 3 * 8;                  // [4][2] per-wave arg-min
     int* sint = (int*)(sred + 8);              // [0] nearest index
     float* sprim = (float*)(sint + 8);
-    for (int i = tid; i < gp.n_prim_floats; i += kRrtThreads) sprim[i] = gp.prims[i];
+    stage_prims(gp, sprim, tid, kRrtThreads);
     float* gnodes = a.nodes + (size_t)b * 2 * M * QD;
     int* gpar = a.parent + (size_t)b * 2 * M;
     if (tid < QD) {
@@ -979,7 +963,7 @@ __global__ __launch_bounds__(kRrtThreads) void rrt_path_kernel(const RrtPathArgs
     int* spar = sidx + kPathMax;                  // [2][M] parent links
     int* sint = spar + 2 * M;                     // [16] scalars: 0 m, 1 n0, 4..7 per-wave hit flags
     float* sprim = (float*)(sint + 16);
-    for (int i = tid; i < gp.n_prim_floats; i += kRrtThreads) sprim[i] = gp.prims[i];
+    stage_prims(gp, sprim, tid, kRrtThreads);
     const int* gpar = a.parent + (size_t)b * 2 * M;
     for (int i = tid; i < 2 * M; i += kRrtThreads) spar[i] = gpar[i];
     const int l0 = a.link[(size_t)b * 2], l1 = a.link[(size_t)b * 2 + 1];

@@ -1,4 +1,4 @@
-// planner_host.hpp - C-ABI entry points of the baseline planners (csrc/planner.hpp); included at the end of mpdx.hip.
+// planner_host.hpp - C-ABI entry points of the baseline planners (csrc/planner.hpp); included by k_planner.hip.
 #pragma once
 #include "planner.hpp"
 
@@ -6,14 +6,21 @@ namespace mpdx {
 // the argument checks launch_guide applies to a guide parameter block, for the planners that copy it into their kernel arguments
 // (gn_point / config_hit index gp.fields; the GPMP2 kernel's support-window arithmetic assumes n_interp >= H).  H == 0: no horizon (RRT).
 static int check_planner_params(const mpdx_guide_params* gp, int H, int D) {
-    if (D != 2 * gp->q_dim || D > 16) return fail(MPDX_E_INVALID, "state dim %d != 2*q_dim (%d)", D, gp->q_dim);
-    if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS) return fail(MPDX_E_INVALID, "n_fields %d", gp->n_fields);
-    if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
+    if (int rc = guide_block_problem(gp, D, nullptr)) return rc;
     if (gp->n_scenes > 1) return fail(MPDX_E_INVALID, "the baseline planners take one scene (n_scenes = %d): scene batches are for the guide and metrics kernels", gp->n_scenes);
     for (int f = 0; f < gp->n_fields; ++f)   // gn_point / config_hit scan primitive tables: a grid field would be skipped silently
         if (gp->fields[f].kind == MPDX_FIELD_GRID) return fail(MPDX_E_INVALID, "grid fields: guide and metrics only (field %d is a MPDX_FIELD_GRID)", f);
     if (H > 0 && gp->interpolate && (gp->n_interp < 2 || gp->n_interp < H || gp->n_interp > 8 * H))
         return fail(MPDX_E_INVALID, "n_interp %d unsupported for H=%d", gp->n_interp, H);
+    return 0;
+}
+
+// a planner kernel's launch: the LDS limit is raised above 64 KB only
+template <class K, class A>
+static int launch_planner(K kern, int blocks, int threads, size_t lds, hipStream_t st, const A& a) {
+    if (lds > 64 * 1024)
+        if (int rc = raise_lds_limit((const void*)kern)) return rc;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, st, a);
     return 0;
 }
 }  // namespace mpdx
@@ -35,20 +42,14 @@ int mpdx_gpmp_step(const mpdx_guide_params* gp, const mpdx_gpmp_opts* o, float* 
     a.step = o->step; a.adaptive = o->adaptive; a.solve = solve;
     const int N = gp->interpolate ? gp->n_interp : H;
     hipStream_t st = (hipStream_t)stream;
-#define MPDX_GPMP(QD_, DIM_, ROBOT_)                                                                                     \
-    {                                                                                                                    \
-        const size_t lds = gpmp_lds_bytes<QD_>(H, N, gp->n_prim_floats);                                                 \
-        if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "GPMP2 step needs %zu B of LDS (H=%d, %d points)", lds, H, N);  \
-        auto kern = gpmp_lm_kernel<QD_, DIM_, ROBOT_>;                                                                   \
-        if (lds > 64 * 1024)                                                                                             \
-            if (int rc = raise_lds_limit((const void*)kern)) return rc;                                                  \
-        hipLaunchKernelGGL(kern, dim3(B), dim3(kGpmpThreads), lds, st, a);                                               \
-    }
-    if (gp->robot == MPDX_ROBOT_PANDA && gp->q_dim == 7) MPDX_GPMP(7, 3, MPDX_ROBOT_PANDA)
-    else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 2) MPDX_GPMP(2, 2, MPDX_ROBOT_POINTMASS)
-    else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 3) MPDX_GPMP(3, 3, MPDX_ROBOT_POINTMASS)
-    else return fail(MPDX_E_INVALID, "GPMP2 step: unsupported robot %d / q_dim %d", gp->robot, gp->q_dim);
-#undef MPDX_GPMP
+    int rc = 0;
+    const bool known = with_builtin_robot(*gp, [&](auto qd, auto dim, auto robot) {
+        const size_t lds = gpmp_lds_bytes<decltype(qd)::value>(H, N, gp->n_prim_floats);
+        if (lds > 160 * 1024) rc = fail(MPDX_E_INVALID, "GPMP2 step needs %zu B of LDS (H=%d, %d points)", lds, H, N);
+        else rc = launch_planner(gpmp_lm_kernel<decltype(qd)::value, decltype(dim)::value, decltype(robot)::value>, B, kGpmpThreads, lds, st, a);
+    }, false);
+    if (!known) return fail(MPDX_E_INVALID, "GPMP2 step: unsupported robot %d / q_dim %d", gp->robot, gp->q_dim);
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -69,20 +70,15 @@ int mpdx_rrt_connect(const mpdx_guide_params* gp, const mpdx_rrt_opts* o, const 
     a.step = o->step; a.max_nodes = o->max_nodes; a.max_iters = o->max_iters; a.max_connect = o->max_connect_steps; a.n_checks = o->n_edge_checks;
     a.seed = o->seed;
     hipStream_t st = (hipStream_t)stream;
-#define MPDX_RRT(QD_, DIM_, ROBOT_)                                                                                      \
-    {                                                                                                                    \
-        const size_t lds = rrt_lds_bytes<QD_>(o->max_nodes, gp->n_prim_floats);                                          \
-        if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "RRT-Connect: %d nodes x %d dims need %zu B of LDS", o->max_nodes, QD_, lds); \
-        auto kern = rrt_connect_kernel<QD_, DIM_, ROBOT_>;                                                               \
-        if (lds > 64 * 1024)                                                                                             \
-            if (int rc = raise_lds_limit((const void*)kern)) return rc;                                                  \
-        hipLaunchKernelGGL(kern, dim3(n), dim3(kRrtThreads), lds, st, a);                                                \
-    }
-    if (gp->robot == MPDX_ROBOT_PANDA && gp->q_dim == 7) MPDX_RRT(7, 3, MPDX_ROBOT_PANDA)
-    else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 2) MPDX_RRT(2, 2, MPDX_ROBOT_POINTMASS)
-    else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 3) MPDX_RRT(3, 3, MPDX_ROBOT_POINTMASS)
-    else return fail(MPDX_E_INVALID, "RRT-Connect: unsupported robot %d / q_dim %d", gp->robot, gp->q_dim);
-#undef MPDX_RRT
+    int rc = 0;
+    const bool known = with_builtin_robot(*gp, [&](auto qd, auto dim, auto robot) {
+        constexpr int QD = decltype(qd)::value;
+        const size_t lds = rrt_lds_bytes<QD>(o->max_nodes, gp->n_prim_floats);
+        if (lds > 160 * 1024) rc = fail(MPDX_E_INVALID, "RRT-Connect: %d nodes x %d dims need %zu B of LDS", o->max_nodes, QD, lds);
+        else rc = launch_planner(rrt_connect_kernel<QD, decltype(dim)::value, decltype(robot)::value>, n, kRrtThreads, lds, st, a);
+    }, false);
+    if (!known) return fail(MPDX_E_INVALID, "RRT-Connect: unsupported robot %d / q_dim %d", gp->robot, gp->q_dim);
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -99,20 +95,15 @@ int mpdx_rrt_paths(const mpdx_guide_params* gp, const float* start, const float*
     a.gp = dev_params_of(*gp); a.start = start; a.goal = goal; a.nodes = nodes; a.parent = parent; a.link = link; a.out = trajs_out; a.path_len = path_len;
     a.max_nodes = max_nodes; a.H = H; a.n_checks = n_edge_checks; a.rounds = rounds; a.dt = dt;
     hipStream_t st = (hipStream_t)stream;
-#define MPDX_RRTP(QD_, DIM_, ROBOT_)                                                                                     \
-    {                                                                                                                    \
-        const size_t lds = rrt_path_lds_bytes<QD_>(max_nodes, H, gp->n_prim_floats);                                     \
-        if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "RRT paths: %d nodes x %d dims need %zu B of LDS", max_nodes, QD_, lds); \
-        auto kern = rrt_path_kernel<QD_, DIM_, ROBOT_>;                                                                  \
-        if (lds > 64 * 1024)                                                                                             \
-            if (int rc = raise_lds_limit((const void*)kern)) return rc;                                                  \
-        hipLaunchKernelGGL(kern, dim3(n), dim3(kRrtThreads), lds, st, a);                                                \
-    }
-    if (gp->robot == MPDX_ROBOT_PANDA && gp->q_dim == 7) MPDX_RRTP(7, 3, MPDX_ROBOT_PANDA)
-    else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 2) MPDX_RRTP(2, 2, MPDX_ROBOT_POINTMASS)
-    else if (gp->robot == MPDX_ROBOT_POINTMASS && gp->q_dim == 3) MPDX_RRTP(3, 3, MPDX_ROBOT_POINTMASS)
-    else return fail(MPDX_E_INVALID, "RRT paths: unsupported robot %d / q_dim %d", gp->robot, gp->q_dim);
-#undef MPDX_RRTP
+    int rc = 0;
+    const bool known = with_builtin_robot(*gp, [&](auto qd, auto dim, auto robot) {
+        constexpr int QD = decltype(qd)::value;
+        const size_t lds = rrt_path_lds_bytes<QD>(max_nodes, H, gp->n_prim_floats);
+        if (lds > 160 * 1024) rc = fail(MPDX_E_INVALID, "RRT paths: %d nodes x %d dims need %zu B of LDS", max_nodes, QD, lds);
+        else rc = launch_planner(rrt_path_kernel<QD, decltype(dim)::value, decltype(robot)::value>, n, kRrtThreads, lds, st, a);
+    }, false);
+    if (!known) return fail(MPDX_E_INVALID, "RRT paths: unsupported robot %d / q_dim %d", gp->robot, gp->q_dim);
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
 }
