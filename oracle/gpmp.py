@@ -45,9 +45,10 @@ def objective(theta, robot, collision_costs, dt, sigma_gp, sigma_obs, n_interp) 
     return 0.5 * (r * r).sum()
 
 
-def lm_step(theta: torch.Tensor, robot, collision_costs, dt: float, sigma_gp: float, sigma_obs: float, n_interp: int, lam: float):
-    """One damped Gauss-Newton step for ONE trajectory theta [H, 2q] (float64 recommended).  Returns (delta [H, 2q] with zero rows at
-    the fixed start / goal states, F(theta))."""
+def normal_equations(theta: torch.Tensor, robot, collision_costs, dt: float, sigma_gp: float, sigma_obs: float, n_interp: int, lam: float):
+    """The damped Gauss-Newton system of ONE trajectory theta [H, 2q] over its free states (rows 1 .. H-2, flattened):
+    (A, g, F) with A = J^T J + lam diag(J^T J) [(H-2) 2q, (H-2) 2q], g = J^T r and F = 1/2 r.r; the step solves A delta = -g.
+    n_interp = 0: collision factors on the supports."""
     H, D = theta.shape
     free0 = theta[1:-1].reshape(-1).detach().clone()
 
@@ -59,7 +60,15 @@ def lm_step(theta: torch.Tensor, robot, collision_costs, dt: float, sigma_gp: fl
     A = J.T @ J
     g = J.T @ r
     A = A + lam * torch.diag(torch.diagonal(A))
+    return A, g, 0.5 * (r * r).sum()
+
+
+def lm_step(theta: torch.Tensor, robot, collision_costs, dt: float, sigma_gp: float, sigma_obs: float, n_interp: int, lam: float):
+    """One damped Gauss-Newton step for ONE trajectory theta [H, 2q] (float64 recommended).  Returns (delta [H, 2q] with zero rows at
+    the fixed start / goal states, F(theta))."""
+    H, D = theta.shape
+    A, g, F = normal_equations(theta, robot, collision_costs, dt, sigma_gp, sigma_obs, n_interp, lam)
     delta = -torch.linalg.solve(A, g)
     out = torch.zeros_like(theta)
     out[1:-1] = delta.reshape(H - 2, D)
-    return out, 0.5 * (r * r).sum()
+    return out, F

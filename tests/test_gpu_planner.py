@@ -182,9 +182,16 @@ def test_gpmp2_lm_step_vs_oracle(env_id, robot_id, H, n_interp):
                                           ds.state_dim, 1, _lib.current_stream()), "mpdx_gpmp_step")
     torch.cuda.synchronize()
     assert torch.equal(x.cpu(), xu)                      # the first call accepts the (zero) proposal: the point is unchanged
+    import gpmp_ref
     for b in range(B):
         want, F = ogpmp.lm_step(xu[b].double(), robot, coll, dt, sigma_gp, sigma_obs, n_interp, lam)
         got = delta[b].cpu().double()
+        # the step as a solution of the oracle's float64 system (tests/gpmp_ref.py): normwise backward error within 32 x the all-fp32
+        # oracle's and never above 2e-6, on every trajectory whose factors an fp32 evaluation can decide
+        rec = gpmp_ref.oracle_record(ds, xu[b], n_interp, lam)
+        eta = gpmp_ref.backward_error(rec["A"], rec["g"], got[1:-1])
+        print(f"GPMP_STEP {robot_id} H={H} N={n_interp} b={b} eta_gpu={eta:.2e} eta_ref32={rec['eta_ref32']:.2e} ambiguous={int(rec['ambiguous'])}")
+        assert rec["ambiguous"] or eta <= min(gpmp_ref.ETA_FACTOR * rec["eta_ref32"], gpmp_ref.ETA_CEIL), (b, eta, rec["eta_ref32"])
         assert float(F) > 0 and abs(float(state[b, 0]) - float(F)) <= 2e-4 * float(F), (b, float(state[b, 0]), float(F))
         assert not got[0].any() and not got[-1].any()
         scale = float(want.abs().max())

@@ -253,6 +253,29 @@ def test_planners_and_bake_refuse_scenes():
     assert "one scene only" in lib.mpdx_last_error().decode()
 
 
+def test_gpmp_step_refuses_unsupported_horizons_without_launching():
+    """mpdx_gpmp_step's shape limits, each refused on the host (-1) with the offending value in mpdx_last_error: fewer than two free supports,
+    fewer interpolated points than supports or more than 8 per support (the support-window arithmetic), and a Panda horizon whose
+    block-tridiagonal system does not fit 160 KB of LDS."""
+    from mpd_public_amd import _lib
+    lib = _lib_or_skip()
+    buf = (C.c_float * (128 * 14))()
+    a = lambda b: C.cast(b, C.c_void_p)
+    o = _lib.GpmpOpts(2e-2, 10.0, 0.2, 1e-7, 1e7, 1.0, 1)
+
+    def block(n_interp, panda=False):
+        gp = _valid_block()
+        gp.n_scenes, gp.n_interp = 1, n_interp
+        gp.use_gp, gp.dt, gp.sigma_gp = 1, 5.0 / 64, 1.0
+        if panda:
+            gp.robot, gp.q_dim, gp.ws_dim = _lib.ROBOT_PANDA, 7, 3
+        return gp
+    for gp, H, D, want in ((block(8), 3, 4, "H=3"), (block(23), 24, 4, "n_interp 23 unsupported for H=24"), (block(193), 24, 4, "n_interp 193 unsupported for H=24"),
+                           (block(128, panda=True), 80, 14, "LDS (H=80, 128 points)")):
+        assert lib.mpdx_gpmp_step(C.byref(gp), C.byref(o), a(buf), a(buf), a(buf), 1, H, D, 1, None) == -1, want
+        assert want in lib.mpdx_last_error().decode(), (want, lib.mpdx_last_error().decode())
+
+
 # ---------------------------------------------------------------------------------------------------------------- PlanningScenes / guide / plan_contexts
 def test_planning_scenes_validation():
     import mpd_public_amd as m
