@@ -187,6 +187,15 @@ __device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_
     const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
     c0 = n0; c1 = n1; c2 = n2; c3 = n3;
 }
+// Box-Muller radius sqrt(-2 ln u) of the uniform u = (k + 0.5) / 2^24, k a 24-bit integer.  From k = 2^23 on k + 0.5 has 25 significant bits and rounds (to even) in
+// float32: u is off by up to 2^-25 - harmless for an angle, but the radius ~ sqrt(2 (1 - u)) magnifies it by 1 / r as u -> 1: |dz| 2.6e-5 measured, up to 2.4e-4 at
+// k = 2^24 - 1 (u rounded to 1, both normals of the pair exactly 0).  The last 1024 values of k therefore take the series -2 ln(1 - v) = 2 v + v^2 + O(v^3) with
+// v = (2^24 - k - 0.5) / 2^24 <= 6.1e-5, which float32 holds exactly (the dropped term is 1.2e-9 relative); every other k keeps the logf form bit for bit.
+__device__ __forceinline__ float philox_radius(uint32_t k) {
+    const float u = ((float)k + 0.5f) * (1.0f / 16777216.0f);
+    const float v = ((float)(16777216u - k) - 0.5f) * (1.0f / 16777216.0f);
+    return sqrtf(k >= 16777216u - 1024u ? 2.0f * v + v * v : -2.0f * logf(u));
+}
 __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t ctr, float (&z)[4]) {
     uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0x243F6A88u, c3 = 0x85A308D3u;
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
@@ -195,9 +204,8 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t ctr, floa
         philox_round(c0, c1, c2, c3, k0, k1);
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
-    const float u0 = ((float)(c0 >> 8) + 0.5f) * (1.0f / 16777216.0f), u1 = ((float)(c1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(c2 >> 8) + 0.5f) * (1.0f / 16777216.0f), u3 = ((float)(c3 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
+    const float u1 = ((float)(c1 >> 8) + 0.5f) * (1.0f / 16777216.0f), u3 = ((float)(c3 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float r0 = philox_radius(c0 >> 8), r1 = philox_radius(c2 >> 8);
     float s0, cs0, s1, cs1;
     sincosf(6.28318530717958647692f * u1, &s0, &cs0);
     sincosf(6.28318530717958647692f * u3, &s1, &cs1);

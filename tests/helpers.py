@@ -194,21 +194,23 @@ def kernel_path(fused: bool):
 
 
 # ---------------------------------------------------------------------------------------------- decidable plan figures (guided plans)
-def oracle_hinge_slack(dataset, xu, n_check=256, dtype=torch.float64):
-    """Per interpolated waypoint of the UNNORMALISED trajectories xu [B,H,D] (CPU): slack[b,i] = max over EVERY collision hinge of the
-    waypoint (link sphere x field: objects / workspace faces / self-collision pairs) of (margin - signed distance), margin = link
-    radius (no cutoff margin) - the quantity whose sign IS the collision flag of inference.py:288-297 (a waypoint collides iff
-    slack > 0), evaluated in `dtype`.  |slack| < eps marks a waypoint whose flag no fp32 evaluation can decide."""
+def oracle_collision_terms(dataset, dtype=torch.float64):
+    """The oracle's collision cost terms (one per field) of a product dataset, in `dtype`."""
     from oracle import costs as oc
-    from oracle.guide import interpolate_points_v1
     _, comp = oracle_guide(dataset, dtype=dtype)
-    xi = interpolate_points_v1(xu.to(dtype), n_check)
-    slack = torch.full(xi.shape[:2], -float("inf"), dtype=dtype)
-    for term in comp.cost_l:
-        if not isinstance(term, oc.CostCollision):
-            continue
+    return [term for term in comp.cost_l if isinstance(term, oc.CostCollision)]
+
+
+def oracle_config_slack(dataset, q, dtype=torch.float64, terms=None):
+    """slack[...] of the configurations q [..., q_dim] (CPU): max over EVERY collision hinge of the configuration (link sphere x field:
+    objects / workspace faces / self-collision pairs) of (margin - signed distance), margin = link radius (no cutoff margin).  A
+    configuration collides iff slack > 0.  `terms`: oracle_collision_terms(dataset, dtype) built once by a caller that asks often."""
+    terms = oracle_collision_terms(dataset, dtype) if terms is None else terms
+    q = torch.as_tensor(q).to(dtype)
+    slack = torch.full(q.shape[:-1], -float("inf"), dtype=dtype)
+    for term in terms:
         rob, f = term.robot, term.field
-        pts = rob.link_points(xi[..., : rob.q_dim])          # [B, N, K, dim]
+        pts = rob.link_points(q[..., : rob.q_dim])          # [..., K, dim]
         radii = rob.radii.to(dtype)
         if f.kind == "objects":
             s = radii - f.sdf(pts)
@@ -220,6 +222,16 @@ def oracle_hinge_slack(dataset, xu, n_check=256, dtype=torch.float64):
             s = radii[f.pairs[:, 0]] + radii[f.pairs[:, 1]] - torch.linalg.norm(a - b, dim=-1)
         slack = torch.maximum(slack, s.amax(-1))
     return slack
+
+
+def oracle_hinge_slack(dataset, xu, n_check=256, dtype=torch.float64):
+    """Per interpolated waypoint of the UNNORMALISED trajectories xu [B,H,D] (CPU): slack[b,i] = max over EVERY collision hinge of the
+    waypoint (link sphere x field: objects / workspace faces / self-collision pairs) of (margin - signed distance), margin = link
+    radius (no cutoff margin) - the quantity whose sign IS the collision flag of inference.py:288-297 (a waypoint collides iff
+    slack > 0), evaluated in `dtype`.  |slack| < eps marks a waypoint whose flag no fp32 evaluation can decide."""
+    from oracle.guide import interpolate_points_v1
+    xi = interpolate_points_v1(xu.to(dtype), n_check)
+    return oracle_config_slack(dataset, xi, dtype)
 
 
 def guided_parity_record(dm, sd, guide, gk, hc, T, n0, nb, n_check=256, eps=1e-5, seed=31, threads=16, weights=(1e-2, 1e-7)):
@@ -326,3 +338,29 @@ def guided_parity_record(dm, sd, guide, gk, hc, T, n0, nb, n_check=256, eps=1e-5
                                      "note": "different chains: the third figure of a count over nb x n_check waypoints moves between ANY two fp32 evaluations "
                                              "(second row: the CPU oracle against itself in fp64) - decided by chain_class instead"},
         "oracle_cpu_plan_s": {"fp32": round(s32, 2), "fp64": round(s64, 2)}, "weights": "synthetic (random-init): the figures are those of un-trained plans"}
+
+
+# ---------------------------------------------------------------------------------------------- RRT-Connect replay (tests/rrt_ref.py)
+def rrt_problem(dataset, case, terms=None):
+    """rrt_ref.Problem of one of rrt_ref.CASES for a product dataset: limits from the task (or the case's own sampling box), collisions
+    from the oracle's float64 hinge slack."""
+    import rrt_ref
+    terms = oracle_collision_terms(dataset) if terms is None else terms
+    lo, hi = (v.cpu().numpy() for v in dataset.task.q_limits("cpu"))
+    if "box" in case:
+        lo, hi = np.asarray(case["box"][0], dtype=np.float32), np.asarray(case["box"][1], dtype=np.float32)
+    n = case["n"]
+    start, goal = (np.tile(np.asarray(case[k], dtype=np.float32), (n, 1)) for k in ("start", "goal"))
+    return rrt_ref.Problem(start, goal, lo, hi, case["step"], case["max_nodes"], case["max_iters"], case["max_connect_steps"], case["n_edge_checks"],
+                           rrt_ref.case_seed(case), lambda q: oracle_config_slack(dataset, q, terms=terms).numpy())
+
+
+@contextlib.contextmanager
+def single_thread():
+    """ATen with one thread: the replay issues thousands of reductions over a few dozen numbers, which a thread pool only slows down"""
+    old = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(old)

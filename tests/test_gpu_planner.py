@@ -1,7 +1,7 @@
 """GPU tests of the baseline planners behind generate_collision_free_trajectories: batched RRT-Connect with
 the HIP collision checker, the GPMP-objective optimiser (HIP guide kernel in raw units) against the oracle's costs, and the entry.
 The reference's planners are un-vendored (mp_baselines): PARITY UNPINNED - the checks are the algorithm's own invariants plus the
-oracle's restatement of the objective."""
+oracle's restatement of the objective (RRT-Connect is also replayed insertion by insertion by its float64 restatement: tests/test_gpu_rrt_replay.py)."""
 import pickle
 
 import numpy as np

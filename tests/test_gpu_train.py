@@ -499,7 +499,8 @@ def test_graph_replayed_steps_equal_eager_steps():
         ts_e.loss_backward(x0, hc, t=TTS[k % 2].cuda(), noise=noise); ts_e.adam_step(1e-3, max_norm=1.0)
         ts_g.step(x0, hc, 1e-3, max_norm=1.0, t=TTS[k % 2].cuda(), noise=noise, use_graph=True)
     assert float((ts_g.fp.flat - ts_e.fp.flat).abs().max().cpu()) <= 1e-6 * float(ts_e.fp.flat.abs().max().cpu())
-    # without t / noise the graph draws them itself (torch's graph-safe generator): the loss differs from replay to replay
+    # without t / noise the pass's first launch draws them on the device (mpdx_train_draw: Philox keyed by the model's seed, positioned by the device-resident
+    # step count - the values themselves are pinned in tests/test_gpu_rng.py): the loss differs from replay to replay
     dm_r = _model(4, 1)
     ts_r = TrainStep(dm_r)
     ls, tts, nzs = [], [], []
