@@ -410,7 +410,19 @@ int mpdx_rrt_connect(const mpdx_guide_params* gp, const mpdx_rrt_opts* opts, con
  * greedily (`rounds` passes, edges checked on n_edge_checks interpolated configurations) and resampled uniformly in arc length to H support
  * points with central-difference velocities -> trajs_out[n][H][2 q_dim]; path_len[n] (or NULL) = nodes of the shortcut path.  An unsolved problem
  * becomes the straight line.  Replaces the path extraction / smoothing that MultiSampleBasedPlanner + HybridPlanner do between RRTConnect and GPMP2
- * (scripts/generate_data/generate_trajectories.py:68-105; un-vendored: the published algorithms, parity unpinned). */
+ * (scripts/generate_data/generate_trajectories.py:68-105; un-vendored: the published algorithms, parity unpinned).
+ *   path        start ... link[b][0] along tree 0's parents (root first), then link[b][1] ... goal along tree 1's parents.  A NEGATIVE entry in
+ *               either link means unsolved.  A path of more than 1024 nodes is treated as unsolved too: both give the straight line
+ *               [start[b], goal[b]] and path_len 2 (start / goal are read for these problems only; the roots of the trees otherwise).
+ *   shortcut    per round, from node i to the LAST later node whose edge is free, else to the next node; it ends when a round removes nothing
+ *               (one round of this rule already leaves a fixed point) or 2 nodes are left; rounds = 0: none.  An edge is checked on the
+ *               configurations (1 - w) qa + w qb, w = c / (n_edge_checks - 1), end points included, link radius only.
+ *   resample    u_h = total arc length * h / (H - 1); segment = first node with cumulative length > u_h, clamped to [1, m - 1]; linear
+ *               interpolation (segment length clamped to 1e-12: start == goal gives H copies of it); supports 0 and H - 1 are exactly the
+ *               first and the last node; velocities (x[h + 1] - x[h - 1]) / (2 dt), zero at both ends.
+ *   refused with MPDX_E_INVALID before any launch: a null pointer (path_len may be null), n < 1, max_nodes < 2, H outside [2, 1024], dt <= 0,
+ *               n_edge_checks outside [2, 256], rounds < 0, and a max_nodes whose LDS need
+ *               4 (1024 q_dim + H q_dim + 2048 + 2 max_nodes + 16 + n_prim_floats) bytes exceeds 160 KB. */
 int mpdx_rrt_paths(const mpdx_guide_params* gp, const float* start, const float* goal, const float* nodes, const int32_t* parent, const int32_t* link,
                    float* trajs_out, int32_t* path_len, int n, int max_nodes, int H, float dt, int n_edge_checks, int rounds, void* stream);
 

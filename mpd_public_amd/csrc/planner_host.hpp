@@ -86,7 +86,8 @@ int mpdx_rrt_connect(const mpdx_guide_params* gp, const mpdx_rrt_opts* o, const 
 int mpdx_rrt_paths(const mpdx_guide_params* gp, const float* start, const float* goal, const float* nodes, const int32_t* parent, const int32_t* link,
                    float* trajs_out, int32_t* path_len, int n, int max_nodes, int H, float dt, int n_edge_checks, int rounds, void* stream) {
     using namespace mpdx;
-    if (!gp || !start || !goal || !nodes || !parent || !link || !trajs_out || n <= 0) return fail(MPDX_E_INVALID, "null argument");
+    if (!gp || !start || !goal || !nodes || !parent || !link || !trajs_out) return fail(MPDX_E_INVALID, "RRT paths: null argument");
+    if (n <= 0) return fail(MPDX_E_INVALID, "RRT paths: n %d", n);
     if (max_nodes < 2 || H < 2 || H > 1024 || !(dt > 0.f) || n_edge_checks < 2 || n_edge_checks > kRrtThreads || rounds < 0)
         return fail(MPDX_E_INVALID, "RRT paths: max_nodes %d, H %d, dt %g, n_edge_checks %d, rounds %d", max_nodes, H, (double)dt, n_edge_checks, rounds);
     if (int rc = check_planner_params(gp, 0, 2 * gp->q_dim)) return rc;

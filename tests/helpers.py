@@ -364,3 +364,40 @@ def single_thread():
         yield
     finally:
         torch.set_num_threads(old)
+
+
+# ---------------------------------------------------------------------------------------------- mpdx_rrt_paths (tests/paths_ref.py)
+def paths_case(name, terms_cache={}):
+    """(dataset on the CPU, paths_ref.Problem with the oracle's float64 slack) of paths_ref.CASES[name]"""
+    import mpd_public_amd as m
+    import paths_ref
+    env, robot, p = paths_ref.CASES[name]()
+    if (env, robot) not in terms_cache:
+        ds = m.TrajectoryDataset(env, robot, tensor_args={"device": "cpu", "dtype": torch.float32})
+        terms_cache[env, robot] = (ds, oracle_collision_terms(ds))
+    ds, terms = terms_cache[env, robot]
+    p.slack_fn = lambda q: oracle_config_slack(ds, q, terms=terms).numpy()
+    return ds, p
+
+
+def oracle_deciding_hinge(dataset, q, terms=None):
+    """Of the configurations q [N, q_dim]: (largest slack, "objects" | "workspace" | "self", index of the link sphere - or of the
+    self-collision pair - whose hinge it is) of the ONE configuration with the largest slack: the hinge that decides an edge's check."""
+    terms = oracle_collision_terms(dataset) if terms is None else terms
+    q = torch.as_tensor(q).to(torch.float64)
+    best = (-float("inf"), None, -1)
+    for term in terms:
+        rob, f = term.robot, term.field
+        pts, radii = rob.link_points(q[..., : rob.q_dim]), rob.radii.to(torch.float64)
+        if f.kind == "objects":
+            s = radii - f.sdf(pts)
+        elif f.kind == "workspace":
+            m_ = radii.unsqueeze(-1)
+            s = torch.cat([m_ - (pts - f.ws_min.to(torch.float64)), m_ - (f.ws_max.to(torch.float64) - pts)], dim=-1).amax(-1)
+        else:
+            a, b = pts[..., f.pairs[:, 0], :], pts[..., f.pairs[:, 1], :]
+            s = radii[f.pairs[:, 0]] + radii[f.pairs[:, 1]] - torch.linalg.norm(a - b, dim=-1)
+        v, i = s.amax(0).max(-1)
+        if float(v) > best[0]:
+            best = (float(v), f.kind, int(i))
+    return best
