@@ -309,7 +309,7 @@ typedef struct mpdx_guide_params {
      * copied to the host once per (pointer, size) and the verdict remembered; the kernels clamp every index they take from the table, so a
      * table rewritten in place afterwards reads other entries, never memory outside it).
      * Entry points that take a chain: mpdx_guide_step, mpdx_guide_step_scaled, mpdx_guide_time, mpdx_traj_metrics, mpdx_traj_metrics_mask,
-     * mpdx_plan; mpdx_gpmp_step, mpdx_rrt_connect, mpdx_rrt_paths and mpdx_sdf_grid_bake know the built-in robots only. */
+     * mpdx_plan, and mpdx_ik_solve (a chain only); mpdx_gpmp_step, mpdx_rrt_connect, mpdx_rrt_paths and mpdx_sdf_grid_bake know the built-in robots only. */
     const float* chain;                 /* device pointer: the chain table (NULL unless robot == MPDX_ROBOT_CHAIN) */
     int32_t n_chain_floats;             /* floats in chain: >= 4 + 16 n_joints + 8 n_spheres + 2 n_pairs */
 } mpdx_guide_params;
@@ -425,6 +425,52 @@ int mpdx_rrt_connect(const mpdx_guide_params* gp, const mpdx_rrt_opts* opts, con
  *               4 (1024 q_dim + H q_dim + 2048 + 2 max_nodes + 16 + n_prim_floats) bytes exceeds 160 KB. */
 int mpdx_rrt_paths(const mpdx_guide_params* gp, const float* start, const float* goal, const float* nodes, const int32_t* parent, const int32_t* link,
                    float* trajs_out, int32_t* path_len, int n, int max_nodes, int H, float dt, int n_edge_checks, int rounds, void* stream);
+
+/* ---- inverse kinematics of a chain robot: n end-effector targets x `restarts` seeds in one launch.  Replaces nothing in the reference: it takes
+ * every goal as a joint configuration (inference.py:161 draws one with task.random_coll_free_q); a task-space goal for a table-driven robot is
+ * this package's extension.  A redundant arm has a set of configurations for one pose: the restarts that converge are
+ * samples of it (collision filtering stays with mpdx_traj_metrics).
+ *
+ * Damped least squares (Levenberg-Marquardt), all in fp32, one independent problem per (target, restart).  Per iteration, in this order:
+ *   FK         of frame f = opts->frame (1 ... n_joints; frame 0 is the fixed base and is refused) by the recurrence of the chain table above,
+ *              T_j = T_{j-1} [R_j | t_j] M_j(q_j) with sinf / cosf, keeping O_j and z_j for j <= f; tool point p = O_f + Rot_f offset.
+ *   residual   e = [p - p*; w_r e_R],  e_R = 1/2 sum_i Rot_f[:, i] x R*[:, i]  (it points from the current to the target orientation);
+ *              w_r = rot_weight; w_r = 0: position only, the rotation rows are skipped (R* is not read into the result; err_out[..][1] = 0).
+ *   Jacobian   joint j <= f contributes one column: revolute Jv = z_j x (p - O_j), Jw = z_j; prismatic Jv = z_j, Jw = 0; joints j > f: zero columns.
+ *              The residual's Jacobian is J = [Jv; -w_r Jw]: the rotation block is the usual geometric-Jacobian Gauss-Newton approximation
+ *              (d e_R / dq = -Jw to first order in e_R, exact at e_R = 0).
+ *   solve      (J^T J + lambda I) dq = -J^T e  by a Cholesky factorisation of the n_joints x n_joints system; a zero column gives dq_j = 0 exactly.
+ *              Every squared pivot is >= lambda in exact arithmetic and is floored there (max(d, lambda)): rounding cannot make dq non-finite.
+ *   candidate  q_c = min(max(q + dq, q_lo), q_hi),  F = 1/2 |e(q)|^2,  F_c = 1/2 |e(q_c)|^2.
+ *              adaptive = 1: accept (q <- q_c) iff F_c < F, then lambda <- max(lambda * lambda_down, lambda_min); else lambda <- min(lambda * lambda_up,
+ *              lambda_max).  adaptive = 0: every candidate is accepted and lambda stays lambda_init (the semantics of mpdx_gpmp_opts.adaptive).
+ *   stop       before every iteration (and once behind the last): converged when |p - p*| <= pos_tol and, with w_r > 0, |e_R| <= rot_tol and
+ *              trace(Rot_f^T R*) > 1 (e_R also vanishes at a rotation error of 180 degrees: the trace rules that zero out); a restart also
+ *              stops after max_iters iterations.  A converged restart is left as it is.
+ * Seeds: q_init [n][restarts][n_joints], clamped into [q_lo, q_hi] (a seed inside the limits is used bit for bit); or NULL: restart r of target i draws
+ *   u = philox_uniform4(seed, (i << 32) | (2 r + k)), k = 0 for joints 0 ... 3 and k = 1 for joints 4 ... 7 (the uniforms of mpdx_rrt_connect: Philox4x32-10,
+ *   u = ((word >> 8) + 0.5) / 2^24) and starts at fmaf(q_hi - q_lo, u, q_lo), clamped into [q_lo, q_hi].
+ * Outputs per restart: q_out [n][restarts][n_joints], always inside the limits; err_out [n][restarts][2] = |p - p*| and |e_R| at
+ *   q_out; status [n][restarts]: bit 0 = converged, bits 8 ... = iterations used.  max_iters = 0 returns the (clamped) seeds with their errors.
+ * Of gp only the chain members count: robot (MPDX_ROBOT_CHAIN), q_dim, chain, n_chain_floats, checked as for the guide; the fields, the primitive
+ * table and the scene members are ignored.  target [n][12]: p*, then R* row-major (an orthonormal matrix; the identity will do with w_r = 0).
+ * Refused with MPDX_E_INVALID before any launch, the message naming the argument: a null pointer (q_init may be null), n outside 1 ... 65535,
+ *   restarts outside 1 ... 4096, a built-in robot id, a bad chain table, frame outside 1 ... n_joints, a non-finite offset, q_lo > q_hi or
+ *   non-finite limits, rot_weight < 0, non-positive pos_tol / rot_tol / lambda_init, max_iters < 0, and with adaptive = 1 lambda_up < 1,
+ *   lambda_down outside (0, 1], lambda_min <= 0 or lambda_max < lambda_min. */
+typedef struct mpdx_ik_opts {
+    int32_t  frame;                     /* 1 ... n_joints: the frame whose tool point is placed */
+    float    offset[3];                 /* tool point in that frame */
+    float    q_lo[8], q_hi[8];          /* joint limits (entries past n_joints are not read) */
+    float    rot_weight;                /* w_r (metres per radian); 0: position only */
+    float    pos_tol, rot_tol;
+    float    lambda_init, lambda_up, lambda_down, lambda_min, lambda_max;
+    int32_t  adaptive;
+    int32_t  max_iters;
+    uint64_t seed;
+} mpdx_ik_opts;
+int mpdx_ik_solve(const mpdx_guide_params* gp, const mpdx_ik_opts* opts, const float* target, const float* q_init, float* q_out, float* err_out,
+                  int32_t* status, int n, int restarts, void* stream);
 
 /* ---- the whole planning loop: replaces GaussianDiffusionModel.p_sample_loop driven by run_inference
  * (diffusion_model_base.py:157-182,285-316) with sample_fn=ddpm_sample_fn.  Everything is enqueued on `stream`

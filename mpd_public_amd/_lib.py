@@ -74,6 +74,12 @@ class RrtOpts(C.Structure):
                 ("max_connect_steps", C.c_int32), ("n_edge_checks", C.c_int32), ("seed", C.c_uint64)]
 
 
+class IkOpts(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("offset", C.c_float * 3), ("q_lo", C.c_float * 8), ("q_hi", C.c_float * 8), ("rot_weight", C.c_float),
+                ("pos_tol", C.c_float), ("rot_tol", C.c_float), ("lambda_init", C.c_float), ("lambda_up", C.c_float), ("lambda_down", C.c_float),
+                ("lambda_min", C.c_float), ("lambda_max", C.c_float), ("adaptive", C.c_int32), ("max_iters", C.c_int32), ("seed", C.c_uint64)]
+
+
 # every symbol include/mpdx.h declares: name -> (restype, argtypes)
 _vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
 SIGNATURES = {
@@ -132,6 +138,7 @@ SIGNATURES = {
     "mpdx_gpmp_step": (_i, [C.POINTER(GuideParams), C.POINTER(GpmpOpts), _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mpdx_rrt_paths": (_i, [C.POINTER(GuideParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp]),
     "mpdx_rrt_connect": (_i, [C.POINTER(GuideParams), C.POINTER(RrtOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mpdx_ik_solve": (_i, [C.POINTER(GuideParams), C.POINTER(IkOpts), _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
 }
 
 

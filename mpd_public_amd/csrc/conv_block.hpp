@@ -211,6 +211,18 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t ctr, floa
     sincosf(6.28318530717958647692f * u3, &s1, &cs1);
     z[0] = r0 * cs0; z[1] = r0 * s0; z[2] = r1 * cs1; z[3] = r1 * s1;
 }
+// the four uniforms u = ((word >> 8) + 0.5) / 2^24 of one counter (RRT-Connect's samples, planner.hpp; the IK solver's seeds, ik.hpp)
+__device__ __forceinline__ void philox_uniform4(uint64_t seed, uint64_t ctr, float (&u)[4]) {
+    uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0x243F6A88u, c3 = 0x85A308D3u;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c0, c1, c2, c3, k0, k1);
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    u[0] = ((float)(c0 >> 8) + 0.5f) * (1.0f / 16777216.0f); u[1] = ((float)(c1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    u[2] = ((float)(c2 >> 8) + 0.5f) * (1.0f / 16777216.0f); u[3] = ((float)(c3 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+}
 // the value mpdx_randn(out, n, seed, offset) writes to out[i]
 __device__ __forceinline__ float philox_normal_at(uint64_t seed, uint64_t offset, uint64_t i) {
     float z[4];

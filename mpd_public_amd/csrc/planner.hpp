@@ -705,18 +705,6 @@ struct RrtArgs {
     unsigned long long seed;
 };
 
-__device__ __forceinline__ void philox_uniform4(uint64_t seed, uint64_t ctr, float (&u)[4]) {
-    uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0x243F6A88u, c3 = 0x85A308D3u;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c0, c1, c2, c3, k0, k1);
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    u[0] = ((float)(c0 >> 8) + 0.5f) * (1.0f / 16777216.0f); u[1] = ((float)(c1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    u[2] = ((float)(c2 >> 8) + 0.5f) * (1.0f / 16777216.0f); u[3] = ((float)(c3 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-}
-
 // does configuration q collide?  `part` / `nparts` split the Panda's link spheres and self-collision pairs over threads
 template <int QD, int DIM, int ROBOT>
 __device__ __forceinline__ bool config_hit(const dev_guide_params& gp, const float* sprim, const float (&q)[QD], int part, int nparts) {

@@ -38,8 +38,12 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
                weight_grad_cost_smoothness: float = 1e-7, factor_num_interpolated_points_for_collision: float = 1.5,
                trajectory_duration: float = 5.0, device: str = "cuda", debug: bool = True, render: bool = False, seed: int = 30,
                results_dir: str = "logs", model_dir: str = None, model_args: dict = None, sdf_grid_cell_size: float = None,
-               sdf_grid_mode: str = "linear", robot=None, **kwargs):
-    """robot (extension): a planning.RobotChain that replaces the robot named in `model_id` (the environment is still taken from it).
+               sdf_grid_mode: str = "linear", robot=None, goal_ee_pos=None, goal_ee_rot=None, goal_ee_frame=None, **kwargs):
+    """goal_ee_pos / goal_ee_rot / goal_ee_frame (extension; None = a random goal configuration, as before): the goal as an end-effector target -
+    the point [x, y, z] (and the [3, 3] orientation) the frame `goal_ee_frame` (default: the last) is to reach.  The goal configuration is then the
+    task.ik_coll_free_q solution nearest to the start in joint space among those farther than the dataset's threshold_start_goal_pos; the results
+    gain `goal_ee_pos` and `goal_ee_error` (|FK(goal) - target| in float64).  A chain robot or the Panda.
+    robot (extension): a planning.RobotChain that replaces the robot named in `model_id` (the environment is still taken from it).
     sdf_grid_cell_size / sdf_grid_mode (extension): None (default) keeps the primitive tables; a cell size makes the task's FIXED objects a
     signed-distance grid baked on the device ('linear' interpolation or 'nearest' node, planning.PlanningTask(sdf_grid=...))."""
     torch.manual_seed(seed)
@@ -120,6 +124,18 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
             break
     if start_state_pos is None or goal_state_pos is None:
         raise ValueError("No collision free configuration was found")
+    goal_ee_error = None
+    if goal_ee_pos is not None:
+        from .ik import chain_of
+        ik_kw = {} if goal_ee_frame is None else dict(frame=int(goal_ee_frame))
+        q_ik = task.ik_coll_free_q(goal_ee_pos, goal_ee_rot, n_samples=32, device=tensor_args["device"], seed=seed, **ik_kw)
+        dist = torch.linalg.norm(q_ik - start_state_pos, dim=-1)
+        far = dist > dataset.threshold_start_goal_pos
+        if not bool(far.any()):
+            raise ValueError("No collision free configuration reaches the target farther than threshold_start_goal_pos from the start")
+        goal_state_pos = q_ik[far][torch.argmin(dist[far])]
+        p_goal, _ = chain_of(robot).fk(goal_state_pos.cpu(), frame=goal_ee_frame)
+        goal_ee_error = float(torch.linalg.norm(p_goal - torch.as_tensor(goal_ee_pos, dtype=torch.float64).reshape(3)))
 
     hard_conds = dataset.get_hard_conditions(torch.vstack((start_state_pos, goal_state_pos)), normalize=True)
     collision_fields = task.get_collision_fields_extra_objects() if use_guide_on_extra_objects_only else task.get_collision_fields()
@@ -209,6 +225,9 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
     }
     if t_cold is not None:   # warm_plan=True: `t_total` above timed a warmed plan; the first plan of the process (what the reference's t_total covers) took this
         results_data_dict["t_total_cold"] = t_cold
+    if goal_ee_pos is not None:
+        results_data_dict["goal_ee_pos"] = torch.as_tensor(goal_ee_pos, dtype=torch.float32).reshape(3)
+        results_data_dict["goal_ee_error"] = goal_ee_error
     if results_dir:
         out_dir = os.path.join(results_dir, model_id, "results_inference", str(seed))
         os.makedirs(out_dir, exist_ok=True)
@@ -231,5 +250,7 @@ if __name__ == "__main__":
     ap.add_argument("--n_diffusion_steps_without_noise", type=int, default=5)
     ap.add_argument("--sdf_grid_cell_size", type=float, default=None, help="fixed objects as a signed-distance grid of this cell size (default: primitive tables)")
     ap.add_argument("--sdf_grid_mode", default="linear", choices=["linear", "nearest"])
+    ap.add_argument("--goal_ee_pos", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
+                    help="plan to this end-effector position (inverse kinematics) instead of a random goal configuration")
     a = ap.parse_args()
     experiment(**vars(a))

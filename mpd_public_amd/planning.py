@@ -226,6 +226,32 @@ class RobotChain:
         ti[o: o + 2 * npair] = self.self_pairs.reshape(-1)
         return tab
 
+    def fk(self, q, frame=None, offset=(0.0, 0.0, 0.0)):
+        """Host-side forward kinematics in float64, from the joints the table is built from: q [..., n_joints] (numpy or a torch CPU tensor) ->
+        (pos [..., 3], rot [..., 3, 3]) of `frame` (0 = the fixed base ... n_joints, the default) in the world; pos is the point `offset` of
+        that frame.  T_j = T_{j-1} [R_j | t_j] M_j(q_j) as in include/mpdx.h."""
+        is_torch = torch.is_tensor(q)
+        qa = np.asarray(q.detach().cpu().numpy() if is_torch else q, np.float64)
+        if qa.shape[-1] != self.q_dim:
+            raise ValueError(f"q: last axis {qa.shape[-1]}, the chain has {self.q_dim} joints")
+        frame = self.q_dim if frame is None else int(frame)
+        if not 0 <= frame <= self.q_dim:
+            raise ValueError(f"frame {frame} outside 0 ... n_joints ({self.q_dim})")
+        lead = qa.shape[:-1]
+        R = np.broadcast_to(np.eye(3), lead + (3, 3)).copy()
+        T = np.zeros(lead + (3,))
+        for j in range(frame):
+            A = R @ self.joint_R[j]
+            T = T + R @ self.joint_t[j]
+            qj = qa[..., j]
+            if self.joint_type[j] == _lib.ROBOT_CHAIN_PRISMATIC:
+                R, T = A, T + qj[..., None] * A[..., :, 2]
+            else:
+                c, s = np.cos(qj)[..., None], np.sin(qj)[..., None]
+                R = np.stack([A[..., :, 0] * c + A[..., :, 1] * s, A[..., :, 1] * c - A[..., :, 0] * s, A[..., :, 2]], axis=-1)
+        pos = T + R @ np.asarray(offset, np.float64).reshape(3)
+        return (torch.from_numpy(pos), torch.from_numpy(R)) if is_torch else (pos, R)
+
     @classmethod
     def from_mdh(cls, alpha, a, d, spheres, self_pairs=(), **kw):
         """A chain of revolute joints from modified-DH rows (Craig): T_i = Rot_x(alpha_{i-1}) Trans_x(a_{i-1}) Rot_z(theta_i) Trans_z(d_i), i.e.
@@ -484,6 +510,32 @@ class PlanningTask:
             if sum(g.shape[0] for g in got) >= n_samples:
                 return torch.cat(got)[:n_samples]
         raise ValueError("No collision free configuration was found")
+
+    def ik_coll_free_q(self, target_pos, target_rot=None, n_samples=1, dedup_distance=0.05, device="cuda", **ik_kwargs):
+        """Collision-free configurations that place the robot's frame at an end-effector target (an extension; ik.solve_ik, whose keyword
+        arguments pass through: frame, offset, n_restarts, seed, ...).  The converged restarts are filtered as random_coll_free_q filters
+        (metrics kernel, n_check=2), sorted by position error and thinned so that no two returned configurations lie within `dedup_distance`
+        (joint-space L2); at most n_samples rows [k, q_dim] come back.  target_pos [3], target_rot None or [3, 3]."""
+        from .ik import solve_ik
+        if torch.as_tensor(target_pos).numel() != 3:
+            raise ValueError("ik_coll_free_q takes one target: target_pos [3]")
+        res = solve_ik(self.robot, torch.as_tensor(target_pos).reshape(3), None if target_rot is None else torch.as_tensor(target_rot).reshape(3, 3),
+                       device=device, **ik_kwargs)
+        q, perr = res.q[res.converged], res.pos_err[res.converged]
+        if q.shape[0]:
+            traj = torch.cat([q, torch.zeros_like(q)], -1)[:, None, :].expand(-1, 2, -1).contiguous()
+            free = self.trajectory_metrics(traj, n_check=2)[:, 0] == 0
+            q, perr = q[free], perr[free]
+        if not q.shape[0]:
+            raise ValueError("No collision free configuration reaches the target")
+        q = q[torch.argsort(perr)]
+        qc, keep = q.cpu(), []
+        for i in range(qc.shape[0]):
+            if all(float(torch.linalg.norm(qc[i] - qc[k])) > dedup_distance for k in keep):
+                keep.append(i)
+                if len(keep) >= n_samples:
+                    break
+        return q[torch.tensor(keep, device=q.device)]
 
     def q_limits(self, device="cpu"):
         if isinstance(self.robot, RobotChain):

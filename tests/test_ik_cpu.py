@@ -1,0 +1,215 @@
+"""CPU checks of the chain-robot inverse kinematics (mpdx_ik_solve, solve_ik, RobotChain.fk): the reference of tests/ik_ref.py pinned against
+autograd before any kernel is involved, the host FK against the reference FK, the C ABI's refusals (no launch, host buffers: the method of
+tests/test_chain_cpu.py), the Python refusals, and the fixture check of the GPU convergence test - the reference alone solves every target of
+every case from at least 8 of its 64 seeds, in fp64 and in fp32."""
+import ctypes as C
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+import ik_ref
+from chain_ref import RobotChainRef, description, product_robot
+
+ROBOTS = ("R1", "R3", "R8", "Panda")
+
+
+# ---------------------------------------------------------------------------------------------------------------- the reference itself
+@pytest.mark.parametrize("name", ROBOTS)
+def test_reference_jacobian_equals_autograd(name):
+    """position rows of IKRef.jacobian == d p / d q by autograd through RobotChainRef.frames (fp64), last and an intermediate frame; the columns
+    of the joints above the frame are exactly zero"""
+    rng = np.random.default_rng(11)
+    n = len(description(name)["joints"])
+    for frame in sorted({n, max(1, n // 2)}):
+        ref = ik_ref.IKRef(name, torch.float64, frame=frame, offset=(0.05, -0.02, 0.11), rot_weight=0.3)
+        for q in ik_ref.random_q(name, (5,), rng).double():
+            want = torch.autograd.functional.jacobian(lambda v: ref.pose(v)[0], q)
+            J = ref.jacobian(q)
+            assert J.shape == (6, n)
+            assert float((J[:3] - want).abs().max()) <= 1e-12, (name, frame)
+            assert not J[:, frame:].any()
+            # rotation rows: -w_r times the angular velocity Jacobian, i.e. d Rot / d q_j = [w_j]x Rot with w_j = -J[3:, j] / w_r
+            dR = torch.autograd.functional.jacobian(lambda v: ref.pose(v)[1], q)       # [3, 3, n]
+            Rot = ref.pose(q)[1]
+            for j in range(frame):
+                w = -J[3:, j] / 0.3
+                W = torch.tensor([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]], dtype=torch.float64)
+                assert float((dR[..., j] - W @ Rot).abs().max()) <= 1e-12, (name, frame, j)
+
+
+def test_reference_step_lowers_the_cost_and_pose_sign_is_right():
+    """one undamped-ish step from next to a solution lands on it: position and orientation errors both drop by orders of magnitude (a wrong sign
+    of the rotation block would double the orientation error instead)"""
+    rng = np.random.default_rng(3)
+    q_star = ik_ref.random_q("Panda", (6,), rng, margin=0.3).double()
+    tpos, trot = ik_ref.target_of("Panda", q_star)
+    ref = ik_ref.IKRef("Panda", torch.float64, rot_weight=0.3)
+    q0 = q_star + 1e-3 * torch.tensor(rng.standard_normal(q_star.shape))
+    _dq, qc, F, Fc = ref.step(q0, 1e-9, tpos, trot)
+    assert bool((Fc < 1e-4 * F).all())
+    _ep, eR0, _ = ref.errors(q0, tpos, trot)
+    _ep, eR1, _ = ref.errors(qc, tpos, trot)
+    assert float(eR1.norm(dim=-1).max()) < 1e-2 * float(eR0.norm(dim=-1).min())
+
+
+# ---------------------------------------------------------------------------------------------------------------- RobotChain.fk
+@pytest.mark.parametrize("name", ROBOTS)
+def test_robotchain_fk_equals_the_reference_frames(name):
+    rob = product_robot(name)
+    ref = RobotChainRef(description(name), torch.float64)
+    q = ik_ref.random_q(name, (64,), np.random.default_rng(5)).double()
+    fr = ref.frames(q)
+    off = (0.03, 0.07, -0.05)
+    for frame in range(rob.q_dim + 1):
+        pos, rot = rob.fk(q.numpy(), frame=frame, offset=off)
+        assert pos.shape == (64, 3) and rot.shape == (64, 3, 3) and pos.dtype == np.float64
+        want_p = (fr[frame] @ torch.tensor(list(off) + [1.0], dtype=torch.float64))[..., :3]
+        assert np.abs(pos - want_p.numpy()).max() <= 1e-12 and np.abs(rot - fr[frame][..., :3, :3].numpy()).max() <= 1e-12, (name, frame)
+    pos_t, rot_t = rob.fk(q)                      # torch in, torch out; the default frame is the last, the default point its origin
+    assert torch.is_tensor(pos_t) and float((pos_t - fr[-1][..., :3, 3]).abs().max()) <= 1e-12 and float((rot_t - fr[-1][..., :3, :3]).abs().max()) <= 1e-12
+    p1, _ = rob.fk(q[0].float())                  # a single float32 configuration
+    assert p1.shape == (3,) and p1.dtype == torch.float64
+    with pytest.raises(ValueError, match="frame"):
+        rob.fk(q, frame=rob.q_dim + 1)
+    with pytest.raises(ValueError, match="joints"):
+        rob.fk(np.zeros(rob.q_dim + 1))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the C ABI, no launch
+def _lib_or_skip():
+    from mpd_public_amd import build, _lib
+    try:
+        build.build(verbose=False)
+        return _lib.load()
+    except _lib.LibraryUnavailable as e:   # pragma: no cover
+        pytest.skip(f"libmpdx.so does not load on this host: {e}")
+
+
+def test_symbol_is_declared_exported_and_bound():
+    import subprocess
+    from mpd_public_amd import _lib
+    lib = _lib_or_skip()
+    text = (Path(__file__).resolve().parent.parent / "include" / "mpdx.h").read_text()
+    assert re.search(r"int mpdx_ik_solve\(const mpdx_guide_params\* gp, const mpdx_ik_opts\* opts,", text)
+    assert "replaces nothing in the reference" in text[text.index("inverse kinematics of a chain robot"):text.index("typedef struct mpdx_ik_opts")].lower()
+    out = subprocess.run(["nm", "-D", "--defined-only", str(_lib.lib_path())], capture_output=True, text=True, check=True).stdout
+    assert " T mpdx_ik_solve" in out
+    assert "mpdx_ik_solve" in _lib.SIGNATURES and lib.mpdx_ik_solve.argtypes is not None
+    # the struct as the header lays it out: 4 + 12 + 32 + 32 + 3 * 4 + 5 * 4 + 2 * 4 = 120 bytes, then the 8-byte seed
+    assert _lib.IkOpts.seed.offset == 120 and C.sizeof(_lib.IkOpts) == 128 and _lib.IkOpts.q_hi.offset == 48
+
+
+def _valid_call(name="R3"):
+    """a well-formed call over HOST memory: (gp, opts, dict of buffers); nothing is launched before the checks have passed"""
+    from mpd_public_amd import _lib
+    rob = product_robot(name)
+    tab = np.ascontiguousarray(rob.table())
+    gp = _lib.GuideParams()
+    gp.robot, gp.q_dim = _lib.ROBOT_CHAIN, rob.q_dim
+    gp.ws_dim, gp.n_fields = 2, 4          # of the block only the chain members count: neither the workspace dimension ...
+    gp.fields[0].kind = _lib.FIELD_GRID    # ... nor a field a chain's guide would refuse is looked at
+    gp.chain, gp.n_chain_floats = tab.ctypes.data, tab.size
+    o = _lib.IkOpts()
+    o.frame = rob.q_dim
+    for j in range(rob.q_dim):
+        o.q_lo[j], o.q_hi[j] = float(rob.q_limits[0][j]), float(rob.q_limits[1][j])
+    o.rot_weight, o.pos_tol, o.rot_tol = 0.3, 1e-4, 1e-3
+    o.lambda_init, o.lambda_up, o.lambda_down, o.lambda_min, o.lambda_max, o.adaptive, o.max_iters = 1e-2, 10.0, 0.1, 1e-6, 1e4, 1, 10
+    bufs = dict(target=(C.c_float * 24)(), q_init=(C.c_float * 64)(), q_out=(C.c_float * 64)(), err=(C.c_float * 16)(), status=(C.c_int32 * 8)(), tab=tab)
+    return gp, o, bufs
+
+
+def _solve(lib, gp, o, b, n=2, restarts=4, null=None):
+    a = lambda k: None if null == k else C.cast(b[k], C.c_void_p)
+    rc = lib.mpdx_ik_solve(None if null == "gp" else C.byref(gp), None if null == "opts" else C.byref(o), a("target"), a("q_init"), a("q_out"), a("err"),
+                           a("status"), n, restarts, None)
+    return rc, (lib.mpdx_last_error() or b"").decode()
+
+
+def test_refusals_through_the_c_abi_name_the_argument():
+    from mpd_public_amd import _lib
+    lib = _lib_or_skip()
+    nan, inf = float("nan"), float("inf")
+    cases = []
+
+    def case(what, needle, change=None, **kw):
+        cases.append((what, needle, change, kw))
+    for k, needle in (("gp", "gp"), ("opts", "opts"), ("target", "target"), ("q_out", "q_out"), ("err", "err_out"), ("status", "status")):
+        case(f"null {k}", needle, None, null=k)
+    case("n 0", "n 0", None, n=0)
+    case("n negative", "n -1", None, n=-1)
+    case("restarts 0", "restarts 0", None, restarts=0)
+    case("restarts 4097", "restarts 4097", None, restarts=4097)
+    case("frame 0", "frame 0", lambda gp, o, b: setattr(o, "frame", 0))
+    case("frame n_joints + 1", "frame 4", lambda gp, o, b: setattr(o, "frame", 4))
+    case("point-mass id", "robot 0", lambda gp, o, b: setattr(gp, "robot", _lib.ROBOT_POINTMASS))
+    case("Panda id", "robot 1", lambda gp, o, b: setattr(gp, "robot", _lib.ROBOT_PANDA))
+    case("q_lo > q_hi", "q_lo > q_hi at joint 1", lambda gp, o, b: o.q_lo.__setitem__(1, 0.6))
+    case("NaN limit", "joint 2", lambda gp, o, b: o.q_hi.__setitem__(2, nan))
+    case("infinite limit", "joint 0", lambda gp, o, b: o.q_lo.__setitem__(0, -inf))
+    case("pos_tol 0", "pos_tol", lambda gp, o, b: setattr(o, "pos_tol", 0.0))
+    case("pos_tol NaN", "pos_tol", lambda gp, o, b: setattr(o, "pos_tol", nan))
+    case("rot_tol negative", "rot_tol", lambda gp, o, b: setattr(o, "rot_tol", -1e-3))
+    case("lambda_init 0", "lambda_init", lambda gp, o, b: setattr(o, "lambda_init", 0.0))
+    case("rot_weight negative", "rot_weight", lambda gp, o, b: setattr(o, "rot_weight", -0.1))
+    case("max_iters negative", "max_iters -1", lambda gp, o, b: setattr(o, "max_iters", -1))
+    case("adaptive with lambda_up < 1", "lambda_up", lambda gp, o, b: setattr(o, "lambda_up", 0.5))
+    case("offset NaN", "offset", lambda gp, o, b: o.offset.__setitem__(1, nan))
+    case("null table", "chain == NULL", lambda gp, o, b: setattr(gp, "chain", None))
+    case("short table", "n_chain_floats", lambda gp, o, b: setattr(gp, "n_chain_floats", 60))
+    case("q_dim != n_joints", "q_dim", lambda gp, o, b: setattr(gp, "q_dim", 2))
+    case("joint type 2", "joint 0 type", lambda gp, o, b: b["tab"].view(np.int32).__setitem__(4 + 12, 2))
+    case("non-orthonormal R", "joint 1 R", lambda gp, o, b: b["tab"].__setitem__(4 + 16 + 4, 0.5))
+    case("n_joints over the cap", "n_joints", lambda gp, o, b: b["tab"].view(np.int32).__setitem__(0, 9))
+    for what, needle, change, kw in cases:
+        gp, o, b = _valid_call()
+        if change:
+            change(gp, o, b)
+        status_before = bytes(b["status"]), bytes(b["q_out"])
+        rc, msg = _solve(lib, gp, o, b, **kw)
+        assert rc == -1 and msg.startswith("ik:") and needle in msg, (what, rc, msg)
+        assert (bytes(b["status"]), bytes(b["q_out"])) == status_before, what     # nothing ran
+
+
+def test_solve_ik_refusals():
+    import mpd_public_amd as m
+    assert m.solve_ik is m.ik.solve_ik and "solve_ik" in m.__all__
+    with pytest.raises(ValueError, match="RobotPointMass"):
+        m.solve_ik(m.make_robot("RobotPointMass"), [0.1, 0.2, 0.3])
+    for rob in (product_robot("R3"), m.make_robot("RobotPanda")):
+        with pytest.raises(RuntimeError, match="GPU"):
+            m.solve_ik(rob, [0.1, 0.2, 0.3], device="cpu")
+    assert m.ik.chain_of(m.make_robot("RobotPanda")).q_dim == 7
+    assert np.array_equal(m.ik.chain_of(m.make_robot("RobotPanda")).table(), m.RobotChain.panda().table())
+    task = m.TrajectoryDataset("EnvSpheres3D", product_robot("R3")).task
+    with pytest.raises(ValueError, match="one target"):
+        task.ik_coll_free_q(np.zeros((2, 3)))
+    import inspect
+    from mpd_public_amd import inference
+    sig = inspect.signature(inference.experiment)
+    assert all(sig.parameters[k].default is None for k in ("goal_ee_pos", "goal_ee_rot", "goal_ee_frame"))
+
+
+# ---------------------------------------------------------------------------------------------------------------- fixture check
+@pytest.mark.parametrize("pose", [False, True], ids=["position", "pose"])
+@pytest.mark.parametrize("name", ik_ref.CONV_ROBOTS)
+def test_reference_solves_every_convergence_case(name, pose):
+    """the GPU convergence test asks for at least one converged restart per target and half the fp32 reference's total: the reference in fp64
+    and in fp32 solves each of the 4 targets from at least 8 of the 64 seeds, inside the limits, to the tolerances (checked in fp64)"""
+    c = ik_ref.convergence_case(name, pose)
+    check = ik_ref.IKRef(name, torch.float64, **c["kw"])
+    for dtype in (torch.float64, torch.float32):
+        s = ik_ref.reference_solution(name, pose, dtype)
+        per_target = s["converged"].sum(1).tolist()
+        print(name, "pose" if pose else "position", dtype, "converged per target", per_target)
+        assert min(per_target) >= 8, (name, pose, dtype, per_target)
+        q = s["q"].double()
+        assert bool((q >= check.lo).all() and (q <= check.hi).all())
+        ep, eR, _tr = check.errors(q, c["tpos"][:, None, :], c["trot"][:, None, :, :])
+        ok = s["converged"]
+        assert float(ep.norm(dim=-1)[ok].max()) <= 1e-4 + 1e-5
+        if pose:
+            assert float(eR.norm(dim=-1)[ok].max()) <= 1e-3 + 1e-5
