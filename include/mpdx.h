@@ -28,6 +28,7 @@ extern "C" {
 #define MPDX_E_INVALID   (-1) /* bad argument / unsupported configuration */
 #define MPDX_E_NOTFOUND  (-2) /* unknown parameter name */
 #define MPDX_E_STATE     (-3) /* call order violated (e.g. forward before all parameters were packed) */
+#define MPDX_E_DEVICE    (-4) /* a kernel gave up a bounded wait on the device; sticky on the handle (mpdx_unet_status) */
 
 #define MPDX_MAX_LEVELS 8
 
@@ -73,6 +74,25 @@ void   mpdx_unet_destroy(mpdx_unet* u);
  * mpdx_plan call on this handle issued (0: the option is off or the network / batch does not admit it). */
 int    mpdx_unet_set_plan_join(mpdx_unet* u, int on);
 int    mpdx_unet_plan_joined(const mpdx_unet* u);
+/* Inner-level run, a handle option, default on.  mpdx_plan runs the seven consecutive 256 -> 256 Conv1dBlocks of the innermost level
+ * (downs.3.0.blocks.1, downs.3.1, mid_block1, mid_block2) as ONE persistent launch where the standard four-level network on H = 64 runs without
+ * self-attention and every workgroup of that launch is resident at once (8 x ceil(B / 4) workgroups, one per compute unit: B <= 128 on 256 CUs);
+ * guided plans included.  The 8 workgroups of a position tile hand their output tiles to each other inside the launch; the arithmetic is the
+ * per-layer kernels', the results are bit-identical with the option off, and every other entry point runs the separate kernels.
+ * mpdx_unet_inner_runs: run launches of the last mpdx_plan call on this handle (0: option off, or network / batch do not admit it).
+ * The device state of the run (arrival counters, status word) belongs to the handle: one mpdx_plan of a handle at a time.
+ *
+ * Every wait inside the run is bounded (4 ms of shader clock; a layer takes under 10 us).  A workgroup whose wait runs out sets a sticky status
+ * word on the handle, makes the workgroups of its position tile leave as well, and writes NaN into its tile of the run's output, so the plan's
+ * trajectories are NaN.  mpdx_unet_status returns MPDX_E_DEVICE while the word is set (0 otherwise) and mpdx_plan refuses to start; both read
+ * host memory and never synchronise.  The window: the word is written while the plan's launches EXECUTE, so mpdx_plan's own return value only
+ * covers launches that have already run when it returns; ask mpdx_unet_status after synchronising the stream to cover the whole plan.
+ * mpdx_unet_set_status(u, 0) clears the word (the counters are re-zeroed before the next run); a non-zero word marks the handle failed as
+ * a give-up would (bit 0 set, bits 8.. the layer of the run that waited). */
+int    mpdx_unet_set_inner_run(mpdx_unet* u, int on);
+int    mpdx_unet_inner_runs(const mpdx_unet* u);
+int    mpdx_unet_status(const mpdx_unet* u);
+int    mpdx_unet_set_status(mpdx_unet* u, unsigned word);
 /* number of state-dict tensors the model expects; their names/shapes (identical to the reference's keys) */
 int    mpdx_unet_num_params(const mpdx_unet* u);
 int    mpdx_unet_param_info(const mpdx_unet* u, int idx, const char** name, int32_t shape[3], int32_t* ndim);

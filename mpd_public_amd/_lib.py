@@ -89,6 +89,10 @@ SIGNATURES = {
     "mpdx_unet_destroy": (None, [_vp]),
     "mpdx_unet_set_plan_join": (_i, [_vp, _i]),
     "mpdx_unet_plan_joined": (_i, [_vp]),
+    "mpdx_unet_set_inner_run": (_i, [_vp, _i]),
+    "mpdx_unet_inner_runs": (_i, [_vp]),
+    "mpdx_unet_status": (_i, [_vp]),
+    "mpdx_unet_set_status": (_i, [_vp, C.c_uint]),
     "mpdx_unet_num_params": (_i, [_vp]),
     "mpdx_unet_param_info": (_i, [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_int32 * 3), C.POINTER(C.c_int32)]),
     "mpdx_unet_packed_floats": (_sz, [_vp]),

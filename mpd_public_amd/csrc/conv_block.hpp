@@ -257,9 +257,30 @@ template <int NC16_> struct GeoL8 { static constexpr int L = 8, NC16 = NC16_, RS
 template <int NC16_> struct GeoUp8 { static constexpr int L = 8, NC16 = NC16_, RSPAD = 4; };
 constexpr int geo_ilog2(int v) { return v <= 1 ? 0 : 1 + geo_ilog2(v >> 1); }
 
+// One layer of a RUN of layers inside one launch (inner_run.hpp): the workgroups of a position tile hand their output tiles to each other through
+// memory, without a kernel boundary.  `counter` is the position tile's arrival counter (one add per workgroup and layer), `target` the value it holds
+// once every workgroup of the tile has published the layer before this one.
+struct RunCtx {
+    unsigned* counter = nullptr;
+    unsigned target = 0;
+    int wait = 0;            // 0: the run's first layer (its inputs come from earlier launches)
+    long long budget = 0;    // s_memtime ticks a poll may take before the workgroup gives up
+};
+constexpr unsigned kRunPoison = 0x10000000u;        // a workgroup that gave up stores target + this into the counter: its peers leave their polls at once
+constexpr unsigned kRunPoisonSeen = 0x08000000u;    // a counter this far PAST its target is poisoned (an honest one is at most 8 x layers past it)
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
 // TBRES: what a GroupNorm epilogue adds behind Mish, when known at compile time (-1: read the pointers; 0 nothing, 1 time bias, 2 residual)
-template <int MODE, int KS, int EPI, int MT, int NT, int WN, int WK, class GEO = GeoAny, int TBRES = -1>
-__device__ __forceinline__ void conv_block_body(const ConvArgs& a, const int block_id) {
+// RUN (inner_run.hpp; EPI_GN_MISH on GeoL8 with one GroupNorm group per channel tile, TBRES -1, exactly one of time bias / residual): the layer is one of
+// a run.  The arithmetic and every summation order are the ones of RUN = false; what changes is how bytes move between workgroups (recipe R1 of
+// write-through stores + counter, sc1 loads in place of an acquire):
+//   - every load of bytes another workgroup may have written in this launch (the staged window, the residual tile) is a buffer load with sc1;
+//   - the weight ring's first blocks and the epilogue's read-only operands are requested BEFORE the poll for the layer before, the halo rows zeroed there;
+//   - the output is stored write-through (sc1), every wave drains its stores, the workgroup meets at a barrier, one lane adds 1 to the tile's counter.
+// Returns false when the poll ran out of its budget or found the counter poisoned (uniform over the workgroup; nothing of the layer is stored then).
+template <int MODE, int KS, int EPI, int MT, int NT, int WN, int WK, class GEO = GeoAny, int TBRES = -1, bool RUN = false>
+__device__ __forceinline__ bool conv_block_body(const ConvArgs& a, const int block_id, const RunCtx rc = RunCtx()) {
     using G = ConvGeom<MODE, KS>;
     constexpr bool GK = GEO::L > 0;   // geometry known at compile time
     static_assert(!GK || MODE == CONV_S1 || MODE == CONV_UPT, "compile-time geometry: stride-1 and transposed convolutions on 8 input positions");
@@ -343,6 +364,51 @@ __device__ __forceinline__ void conv_block_body(const ConvArgs& a, const int blo
 #ifdef MPDX_RING_FIRST
     ring_init();
 #endif
+    // RUN: what does not depend on the layer before - requested / done while its last workgroups are still publishing
+    f32x4 run_bi = {0.f, 0.f, 0.f, 0.f}, run_ga = run_bi, run_be = run_bi, run_tb = run_bi;
+    if constexpr (RUN) {
+        static_assert(GK && MODE == CONV_S1 && EPI == EPI_GN_MISH && TBRES < 0 && WN == 1, "a run layer: stride-1 GroupNorm block with compile-time geometry");
+#ifndef MPDX_RING_FIRST
+        ring_init();
+#endif
+        // (one GroupNorm group per channel tile - gs == MT, checked on the host: the epilogue's channel of a lane does not depend on the region)
+        const int co = mt * MT + ((lane * 4) & (MT - 1));
+        run_bi = *(const f32x4*)(a.bias + co);
+        run_ga = *(const f32x4*)(a.gamma + co); run_be = *(const f32x4*)(a.beta + co);
+        run_tb = *(const f32x4*)((a.tbias ? a.tbias : a.bias) + co);   // (unconditional load: a load in a branch costs a vmcnt(0))
+        {   // zero halo rows (the staging phase's loop, below)
+            constexpr int P2 = 2 * PAD;
+            const int htot = (spt * P2) << lg_c4n;
+            for (int idx = tid; idx < htot; idx += NTHR) {
+                const int hr = idx >> lg_c4n, c4 = idx & (c4n - 1);
+                const int s = hr / P2, k = hr - s * P2;
+                const int lp = (k < PAD) ? k : (L_in + k);
+                smem4[(s * LP + lp) * RS4 + c4] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
+        }   // (the barrier that ended the layer before: every wave is done with the reduction buffer)
+        CB_STAMP();  // RUN 1: requests issued
+        if (rc.wait) {
+            // ONE wave polls the tile's counter (relaxed, agent scope: global_load_dword sc1), then the workgroup barrier, then every wave's sc1 loads.
+            // `>= target` as a signed difference, not `== target`: a peer that has seen the target may add its NEXT arrival before a slow poller
+            // looks again, and the counters are never reset (base wraps around).
+            int* const flag = (int*)(smem + (GEO::NC16 * 16 + GEO::RSPAD) * (NT / GEO::L) * (GEO::L + 2 * PAD));   // behind the staged window
+            if (wave == 0) {
+                const long long t0 = (long long)__builtin_amdgcn_s_memtime();
+                int ok;
+                for (;;) {
+                    const unsigned v = __hip_atomic_load(rc.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const int d = (int)(v - rc.target);
+                    if (d >= 0) { ok = (unsigned)d < kRunPoisonSeen; break; }
+                    if ((long long)__builtin_amdgcn_s_memtime() - t0 > rc.budget) { ok = 0; break; }
+                    __builtin_amdgcn_s_sleep(1);
+                }
+                if (lane == 0) *flag = ok;
+            }
+            __syncthreads();
+            if (!*flag) return false;
+        }
+        CB_STAMP();  // RUN 2: the layer before is published
+    }
 
     // ------------------------------------------------------------------ stage the horizon windows (+halo) into LDS
     if (!MPDX_DBG(a, 1)) {
@@ -381,7 +447,10 @@ __device__ __forceinline__ void conv_block_body(const ConvArgs& a, const int blo
             }
 #pragma unroll
             for (int u = 0; u < SB; ++u) {
-                if constexpr (VEC) {
+                if constexpr (RUN) {   // one source of C_in channels (checked on the host), read past this CU's L1
+                    const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc((void*)a.src1, 0, 0x7fffffff, 0x00020000);
+                    v[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srs, (int)(pos[u] * (GEO::NC16 * 16) + cc[u]) * 4, 0, 16));
+                } else if constexpr (VEC) {
                     const float* src = (cc[u] < a.c1) ? a.src1 + pos[u] * a.c1 + cc[u] : a.src2 + pos[u] * a.c2 + (cc[u] - a.c1);
                     v[u] = *(const f32x4*)src;
                 } else {
@@ -394,7 +463,7 @@ __device__ __forceinline__ void conv_block_body(const ConvArgs& a, const int blo
                 }
             }
 #ifndef MPDX_RING_FIRST
-            if constexpr (FIRST) ring_init();
+            if constexpr (FIRST && !RUN) ring_init();
 #endif
 #pragma unroll
             for (int u = 0; u < SB; ++u) {
@@ -413,7 +482,7 @@ __device__ __forceinline__ void conv_block_body(const ConvArgs& a, const int blo
             for (int base = tid + NTHR * SB; base < total; base += NTHR * SB) stage_pass(base, std::false_type{}, std::false_type{});
         }
         // zero halo rows (conv padding): 2*PAD rows per trajectory
-        if (PAD > 0) {
+        if (PAD > 0 && !RUN) {
             constexpr int P2 = PAD > 0 ? 2 * PAD : 1;
             const int htot = (spt * P2) << lg_c4n;
             for (int idx = tid; idx < htot; idx += NTHR) {
@@ -425,7 +494,7 @@ __device__ __forceinline__ void conv_block_body(const ConvArgs& a, const int blo
         }
     }
 #ifndef MPDX_RING_FIRST
-    if (MPDX_DBG(a, 1)) ring_init();
+    if (!RUN && MPDX_DBG(a, 1)) ring_init();
 #endif
     CB_STAMP();  // 1: own staging loads issued/written
     __syncthreads();
@@ -524,7 +593,7 @@ __device__ __forceinline__ void conv_block_body(const ConvArgs& a, const int blo
     // ------------------------------------------------------------------ epilogue
     if (MPDX_DBG(a, 4)) {
         if (tid == 0 && red[0] == 123.456f) a.dst[0] = red[1];
-        return;
+        return true;
     }
     if constexpr (EPI == EPI_GN_MISH_GEN) {
         // GroupNorm regions (group x horizon) of 64, 512, 1024 or 2048 elements - horizons other than the shipped 64 (n_support_points
@@ -704,6 +773,34 @@ __device__ __forceinline__ void conv_block_body(const ConvArgs& a, const int blo
         for (int r = wave; r < nreg; r += NWAVE) {
             const int s = r >> lg_gpt, gl = r & (gpt - 1);
             const int b = s0 + s;
+            if constexpr (RUN) {
+                // the re == 256 arithmetic below, operand for operand; bias / gamma / beta / time bias were requested before the poll, the residual
+                // tile (written in this launch) is read with sc1, the output stored write-through
+                const int e0 = lane * 4;
+                const int l = e0 >> a.lg_gs, c = gl * gs + (e0 & (gs - 1));
+                const int n = s * L_out + l, co = mt * MT + c;
+                const size_t o = ((size_t)(b < a.B ? b : 0) * L_out + l) * a.C_out + co;
+                const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.res ? a.res : a.src1), 0, 0x7fffffff, 0x00020000);
+                const f32x4 rs4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rrs, (int)o * 4, 0, 16));
+                const f32x4 ex = has_tb ? run_tb : rs4;
+                const int ri = n * MTP4 + (c >> 2);
+                f32x4 v = smem4[ri];
+#pragma unroll
+                for (int k = 1; k < WK; ++k) v += smem4[ri + k * NT * MTP4];
+                v += run_bi;
+                const float mean = wave_sum((v[0] + v[1]) + (v[2] + v[3])) * inv_re;
+                const f32x4 d = v - mean;
+                const float var = wave_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3])) * inv_re;
+                const float rstd = gn_rstd(var);
+                f32x4 y;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) y[e] = mish_nosel(d[e] * rstd * run_ga[e] + run_be[e]);
+                y += ex;
+                if (b < a.B) {
+                    const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc((void*)a.dst, 0, 0x7fffffff, 0x00020000);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), drs, (int)o * 4, 0, 16);
+                }
+            } else
             if (re == 256) {
                 const int e0 = lane * 4;
                 const int l = e0 >> a.lg_gs, c = gl * gs + (e0 & (gs - 1));
@@ -785,7 +882,16 @@ __device__ __forceinline__ void conv_block_body(const ConvArgs& a, const int blo
         }
     }
     CB_STAMP();  // 6: epilogue done (wave 0)
+    if constexpr (RUN) {
+        // publish: EVERY wave drains its write-through stores, the workgroup meets, ONE lane signals.  The barrier also ends the layer for the LDS:
+        // the next layer's halo zeroing and staging overwrite the reduction buffer.
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0) __hip_atomic_fetch_add(rc.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        CB_STAMP();  // RUN: published
+    }
 #undef CB_STAMP
+    return true;
 }
 
 template <int MODE, int KS, int EPI, int MT, int NT, int WN, int WK, class GEO = GeoAny, int TBRES = -1>

@@ -2,7 +2,7 @@
 // units of libmpdx.so.  The library is built from one host TU (mpdx.hip: model building, tile choice and the launch units of a pass, the
 // planning loop, the C ABI, the small streaming kernels; it alone includes fused_build.hpp - the fused-segment builder and build_units - and
 // unet_measure.hpp - the timing / trace entry points and the launch-unit queries) and one TU per kernel family - k_conv.hip (conv_block.hpp), k_ws.hip (conv_ws.hpp), k_fused.hip /
-// k_fused_train.hip (fused_level.hpp), k_guide.hip (guide.hpp), k_chain.hip (chain.hpp), k_ik.hip (ik.hpp), k_attn.hip (attn.hpp), k_train.hip (train.hpp + train_host.hpp), k_planner.hip
+// k_fused_train.hip (fused_level.hpp), k_guide.hip (guide.hpp), k_chain.hip (chain.hpp), k_ik.hip (ik.hpp), k_attn.hip (attn.hpp), k_inner_run.hip (inner_run.hpp), k_train.hip (train.hpp + train_host.hpp), k_planner.hip
 // (planner.hpp + planner_host.hpp) - so that an edit to one kernel family recompiles that family only (mpd_public_amd/build.py
 // compiles the TUs in parallel and keeps the objects).  A kernel template is instantiated in exactly ONE TU, behind a plain function
 // declared here; no device code crosses a TU (no -fgpu-rdc).
@@ -120,6 +120,19 @@ struct mpdx_unet {
     bool masked() const { return Hc != cfg.n_support_points; }
     int plan_joined = 0;      // joined launches of the last mpdx_plan call (mpdx_unet_plan_joined)
     int plan_join = 1;        // mpdx_unet_set_plan_join: mpdx_plan may run a step's up program and the next step's down program as one launch
+    // mpdx_plan: the seven 256 -> 256 layers of the innermost level as one persistent launch (inner_run.hpp)
+    int inner_run = 1;        // mpdx_unet_set_inner_run
+    int inner_runs = 0;       // run launches of the last mpdx_plan call (mpdx_unet_inner_runs)
+    int run_capacity = -1;    // workgroups of the run kernel resident at once on this device (-1: not asked yet; 0: none - no run)
+    long long run_budget = 0; // s_memtime ticks of 4 ms
+    unsigned* run_counters = nullptr;   // device: one arrival counter per cluster (not reset between launches: run_base advances by 8 x layers per launch)
+    unsigned run_base = 0;
+    int run_live = 1 << 30;             // clusters whose counters hold run_base (all of them while every counter is zero)
+    bool run_rezero = false;            // the counters hold a give-up's poison: zero them (and run_base) before the next launch
+    unsigned* run_status = nullptr;     // host-mapped pinned sticky word a workgroup that gives up sets; run_status_dev: the device's address of it
+    unsigned* run_status_dev = nullptr;
+    unsigned status_host = 0;           // stands in for *run_status until the device state exists
+    unsigned status_word() const { return run_status ? __atomic_load_n(run_status, __ATOMIC_RELAXED) : status_host; }
     // launch units: fused whole-trajectory segments (fused_level.hpp) or single layers
     struct CopyJob { size_t src, dst; int n0, ss0, ds0, n1, ss1, ds1, n_inner; };   // strided copy inside `packed` (float units)
     struct Fused {
@@ -174,6 +187,11 @@ int launch_final_step(const FinalArgs& fa, hipStream_t st);   // final_step_kern
 int launch_conv_layer(const Layer& l, ConvArgs& a, int B, hipStream_t st);
 bool pair_tile(const Layer& l1, const Layer& l2, int B, int& MT, int& NT);   // (mpdx.hip) do blocks[0] + the block's residual 1x1 conv run as one launch, on which tile?
 int launch_conv_pair(int MT, int NT, const ConvArgs& a1, const ConvArgs& a2, const Layer& l1, const Layer& l2, hipStream_t st);   // 1 launched, 0 does not fit, -1 error
+// ---- k_inner_run.hip: the persistent run of the innermost level's 256 -> 256 layers (inner_run.hpp)
+struct InnerRunArgs;
+int inner_run_grid(int B);                 // workgroups of a launch for batch B (the placement's surplus ones included)
+int inner_run_workgroups_per_cu();         // one occupancy query; 0: failed
+int launch_inner_run(const InnerRunArgs& ra, int B, hipStream_t st);
 // ---- k_attn.hip: the linear self-attention block (attn.hpp); a.x and the five parameter pointers set by the caller
 struct AttnArgs;
 const char* attn_unsupported(int C, int L);   // null, or why attn_kernel cannot run a level of C channels on L positions

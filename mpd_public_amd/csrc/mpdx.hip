@@ -4,6 +4,7 @@
 // gfx950 only.  No CUDA shims, no dual paths.  All device memory is caller-owned; nothing here synchronises.
 #include "host.hpp"
 #include "attn.hpp"
+#include "inner_run.hpp"
 #include "loss.hpp"
 #include "scene_table.hpp"
 
@@ -890,17 +891,108 @@ static int run_unet_and_final(mpdx_unet* u, const float* packed, const float* ti
     return walk_pass(u, current_units(u, B, nullptr), packed, row, x, ws, B, fa, st, [](PassEvent, int) { return 0; });
 }
 
+// ---- mpdx_plan only: the seven consecutive 256 -> 256 Conv1dBlocks of the innermost level as ONE persistent launch (inner_run.hpp).
+// First launch unit of that run among `units`, or -1: the standard four-level network on H = 64 without self-attention, unmasked, every layer of the run
+// a K-split 256 -> 256 block with compile-time geometry, and at most one workgroup of the launch per compute unit - all resident at once (u->run_capacity: B <= 128 on 256 CUs).
+static int inner_run_first(const mpdx_unet* u, const std::vector<mpdx_unet::Unit>& units, int B) {
+    if (!u->inner_run || u->masked() || u->cfg.self_attention || u->cfg.n_levels != 4 || u->cfg.n_support_points != 64) return -1;
+    if (u->run_capacity <= 0 || inner_run_grid(B) > u->run_capacity || !sw::geo() || sw::debug()) return -1;
+    auto fits = [&](const mpdx_unet::Unit& un) {
+        if (un.fused >= 0 || un.pair) return false;
+        const Layer& l = u->layers[un.layer];
+        if (l.attn || !(l.mode == CONV_S1 && l.ks == 5 && l.epi == EPI_GN_MISH) || l.Lv_out) return false;
+        if (!(l.c1 == 256 && l.c2 == 0 && l.src2 == SRC_NONE && l.cout == 256 && l.L_in == 8 && l.L_out == 8 && l.gs == 32 && l.cin_pad == 256 && l.rs == 264)) return false;
+        if ((l.tb_off >= 0) == (l.res != SRC_NONE)) return false;   // exactly one of time bias / residual
+        // (the per-layer launch may pick a narrower position tile at small batch: the 8-wave K split and the GroupNorm regions - the arithmetic - do
+        //  not depend on the tile's width)
+        return layer_ksplit(l);
+    };
+    const int n = (int)units.size();
+    for (int i = 0; i + kInnerRunLayers <= n; ++i) {
+        int k = 0;
+        while (k < kInnerRunLayers && fits(units[i + k])) ++k;
+        if (k == kInnerRunLayers) return i;
+    }
+    return -1;
+}
+// The handle's device state of the run, made at the first mpdx_plan call (a handle is created without a device): one occupancy query x the CU count,
+// the cluster counters, the host-mapped status word.
+static int ensure_inner_run_state(mpdx_unet* u) {
+    if (u->run_capacity >= 0) return 0;
+    u->run_capacity = 0;
+    int dev = 0, cus = 0, khz = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipDeviceGetAttribute(&khz, hipDeviceAttributeClockRate, dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    const int per_cu = inner_run_workgroups_per_cu();
+    if (per_cu <= 0 || cus <= 0) return 0;
+    const int cap = cus;   // one workgroup per compute unit (the occupancy answer says that one fits): the batches the per-layer tiles were measured at
+    const size_t words = (size_t)((cap + 7) / 8 + 8) * kInnerRunCounterStride;
+    HIP_TRY(hipMalloc((void**)&u->run_counters, words * sizeof(unsigned)));
+    HIP_TRY(hipMemset(u->run_counters, 0, words * sizeof(unsigned)));
+    HIP_TRY(hipHostMalloc((void**)&u->run_status, 64, hipHostMallocMapped));
+    *u->run_status = u->status_host;
+    HIP_TRY(hipHostGetDevicePointer((void**)&u->run_status_dev, u->run_status, 0));
+    u->run_budget = 4LL * (khz > 0 ? khz : 2400000);   // 4 ms of shader-clock ticks (s_memtime); a lower actual clock only lengthens it
+    u->run_capacity = cap;
+    return 0;
+}
+static int handle_status_error(const mpdx_unet* u, const char* fn) {
+    const unsigned w = u->status_word();
+    if (!w) return 0;
+    return fail(MPDX_E_DEVICE, "%s: a workgroup of the inner-level run gave up its wait (status 0x%x: layer %u of the run); the outputs of that plan hold NaN. "
+                "mpdx_unet_set_status(u, 0) clears the word", fn, w, w >> 8);
+}
+static int run_inner_run(mpdx_unet* u, const std::vector<mpdx_unet::Unit>& units, int first, const float* packed, const float* row, const float* x,
+                         float* ws, int B, hipStream_t st) {
+    InnerRunArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    for (int k = 0; k < kInnerRunLayers; ++k) {
+        if (int rc = make_conv_args(u, u->layers[units[first + k].layer], packed, row, x, ws, B, 0, ra.layer[k])) return rc;
+        ra.layer[k].n_tiles_n = (B + 3) / 4;
+        ra.layer[k].trace = nullptr;
+    }
+    // Every counter of a launch must hold run_base when it starts.  A launch advances the counters of ITS clusters only, so a batch with more clusters
+    // than the launch before (or a give-up's poison) zeroes them all, stream-ordered, and starts from base 0 again: at most once per plan.
+    const int nc = (B + 3) / 4;
+    if (u->run_rezero || nc > u->run_live) {
+        HIP_TRY(hipMemsetAsync(u->run_counters, 0, (size_t)((u->run_capacity + 7) / 8 + 8) * kInnerRunCounterStride * sizeof(unsigned), st));
+        u->run_base = 0; u->run_rezero = false;
+    }
+    u->run_live = nc;
+    ra.counters = u->run_counters; ra.status = u->run_status_dev; ra.budget = u->run_budget;
+    ra.base = u->run_base;   // every counter holds this when the launch starts; layer i > 0 waits for base + 8 i, the 8 arrivals of each layer before it
+    ra.n_layers = kInnerRunLayers; ra.nc = (B + 3) / 4;
+    u->run_base += 8u * kInnerRunLayers;
+    u->inner_runs++;
+    return launch_inner_run(ra, B, st);
+}
+
 // One pass of mpdx_plan's loop.  skip_down: the pass's first unit - the down program - has already run as the tail of the pass before; tt_next != null:
-// the pass's last unit - the up program - runs joined with the next pass's down program (can_join_passes holds).  Neither: run_unet_and_final.
+// the pass's last unit - the up program - runs joined with the next pass's down program (can_join_passes holds); use_run: the inner-level run replaces
+// its seven units.  None of them: run_unet_and_final.
 static int run_plan_pass(mpdx_unet* u, const float* packed, const float* timetab, int T, const float* x, int t, int B, float* ws, FinalArgs& fa,
-                         hipStream_t st, bool skip_down, const float* tt_next) {
-    if (!skip_down && !tt_next) return run_unet_and_final(u, packed, timetab, T, x, t, B, ws, fa, st);
+                         hipStream_t st, bool skip_down, const float* tt_next, bool use_run) {
+    if (!skip_down && !tt_next && !use_run) return run_unet_and_final(u, packed, timetab, T, x, t, B, ws, fa, st);
+    if (t < 0 || t >= T) return fail(MPDX_E_INVALID, "timestep %d outside [0,%d)", t, T);
     const float* row = timetab + (size_t)t * u->tt_row;
     const auto units = current_units(u, B, nullptr);
     const int n = (int)units.size();
-    for (int i = skip_down ? 1 : 0; i < n - (tt_next ? 1 : 0); ++i)
+    const int rf = use_run ? inner_run_first(u, units, B) : -1;
+    bool final_done = false;
+    for (int i = skip_down ? 1 : 0; i < n - (tt_next ? 1 : 0); ++i) {
+        if (i == rf) {
+            if (int rc = run_inner_run(u, units, rf, packed, row, x, ws, B, st)) return rc;
+            i += kInnerRunLayers - 1;
+            continue;
+        }
+        if (units[i].fused >= 0) final_done |= u->fused[units[i].fused].has_final;
         if (int rc = run_unit(u, units[i], packed, row, x, ws, B, &fa, st)) return rc;
+    }
     if (tt_next) return run_fused_join(u, u->fused[units[n - 1].fused], u->fused[units[0].fused], packed, row, tt_next, x, ws, B, &fa, st);
+    if (!final_done) return run_final(u, packed, fa, B, ws, st);
     return 0;
 }
 // Can mpdx_plan join passes at batch B?  The pass starts with the three-level down program from the network input and ends with the two-level up
@@ -993,10 +1085,30 @@ int mpdx_unet_set_plan_join(mpdx_unet* u, int on) {
 }
 int mpdx_unet_plan_joined(const mpdx_unet* u) { return u ? u->plan_joined : 0; }
 
+int mpdx_unet_set_inner_run(mpdx_unet* u, int on) {
+    if (!u) return fail(MPDX_E_INVALID, "null argument");
+    u->inner_run = on ? 1 : 0;
+    return 0;
+}
+int mpdx_unet_inner_runs(const mpdx_unet* u) { return u ? u->inner_runs : 0; }
+int mpdx_unet_status(const mpdx_unet* u) {
+    if (!u) return fail(MPDX_E_INVALID, "null argument");
+    return handle_status_error(u, "mpdx_unet_status");
+}
+int mpdx_unet_set_status(mpdx_unet* u, unsigned word) {
+    if (!u) return fail(MPDX_E_INVALID, "null argument");
+    if (u->run_status) __atomic_store_n(u->run_status, word, __ATOMIC_RELAXED);
+    u->status_host = word;
+    if (!word && u->run_counters) u->run_rezero = true;   // whatever a give-up left in the counters goes before the next run
+    return 0;
+}
+
 void mpdx_unet_destroy(mpdx_unet* u) {
     if (u && u->pack_descs_dev) (void)hipFree(u->pack_descs_dev);
     if (u && u->pack_chunks_dev) (void)hipFree(u->pack_chunks_dev);
     if (u && u->jobs_dev) (void)hipFree(u->jobs_dev);
+    if (u && u->run_counters) (void)hipFree(u->run_counters);
+    if (u && u->run_status) (void)hipHostFree(u->run_status);
     delete u;
 }
 
@@ -1142,6 +1254,7 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
               uint64_t rng_seed, uint64_t rng_offset, void* stream) {
     if (!u || !packed || !timetab || !coefs || !x || !ws || T <= 0 || n_without_noise < 0 || B <= 0)
         return fail(MPDX_E_INVALID, "bad argument");
+    if (int rc = handle_status_error(u, "mpdx_plan")) return rc;   // sticky: a run of an earlier plan on this handle gave up (no synchronisation: a host read)
     if (guide)   // the scene members are checked here, before the first launch of the loop (launch_guide checks them again per launch)
         if (const char* why = scene_params_problem(*guide)) return fail(MPDX_E_INVALID, "%s", why);
     if (guide)   // ... and so is a chain robot's table (a device table is read here, once, outside the loop)
@@ -1167,6 +1280,13 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
     // An unguided iteration that has a successor runs its up program and the successor's down program as ONE launch (nothing modifies x between the
     // two); the successor then starts at its second unit.  Whether the successor is guided does not matter.
     const bool join_ok = can_join_passes(u, B);
+    // The seven 256 -> 256 layers of the innermost level as one persistent launch (guided iterations too: the inner levels do not see the guide)
+    u->inner_runs = 0;
+    bool use_run = false;
+    if (u->inner_run && !u->masked() && !u->cfg.self_attention && u->cfg.n_levels == 4 && H == 64) {
+        if (int rc = ensure_inner_run_state(u)) return rc;
+        use_run = inner_run_first(u, current_units(u, B, nullptr), B) >= 0;
+    }
     bool down_done = false;   // this iteration's down program ran as the tail of the iteration before
     u->plan_joined = 0;
     int k = 0;
@@ -1194,7 +1314,7 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
         } else {
             fa.mode = 2; fa.absmax = fl;  // posterior mean + its max|.| per context
         }
-        if (int rc = run_plan_pass(u, packed, timetab, T, x, t, B, ws, fa, st, down_done, tt_next)) return rc;
+        if (int rc = run_plan_pass(u, packed, timetab, T, x, t, B, ws, fa, st, down_done, tt_next, use_run)) return rc;
         down_done = join;
         u->plan_joined += join ? 1 : 0;
         if (guided) {
@@ -1216,7 +1336,7 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
         }
     }
     HIP_TRY(hipGetLastError());
-    return 0;
+    return use_run ? handle_status_error(u, "mpdx_plan") : 0;   // (what has already given up by now; the rest shows at the next call or in mpdx_unet_status)
 }
 
 int mpdx_randn(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream) {

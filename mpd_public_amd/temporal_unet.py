@@ -186,6 +186,19 @@ class TemporalUnet(nn.Module):
         """Joined launches of the last fused plan on this model (mpdx_unet_plan_joined)."""
         return int(_lib.load().mpdx_unet_plan_joined(self._handle()))
 
+    def set_inner_run(self, on: bool):
+        """mpdx_unet_set_inner_run: may the fused planning loop run the seven 256 -> 256 layers of the innermost level as one persistent launch
+        (default: yes, where the network and the batch admit it)?  Results are bit-identical either way.  A handle option, like set_plan_join."""
+        _lib.check(_lib.load().mpdx_unet_set_inner_run(self._handle(), int(bool(on))), "mpdx_unet_set_inner_run")
+
+    def inner_runs(self) -> int:
+        """Inner-level run launches of the last fused plan on this model (mpdx_unet_inner_runs)."""
+        return int(_lib.load().mpdx_unet_inner_runs(self._handle()))
+
+    def status(self) -> int:
+        """mpdx_unet_status: 0, or MPDX_E_DEVICE (-4) when a kernel of this handle gave up a bounded wait (sticky; no synchronisation)."""
+        return int(_lib.load().mpdx_unet_status(self._handle()))
+
     def _param_stamp(self):
         """(address, version counter) of every parameter: load_state_dict, an optimiser step, .to() and in-place edits all change it.  The parameter LIST is
         cached - walking the module tree costs 0.15 ms, which the step-by-step protocol loop paid per denoising step (round 6: 65.7 -> 21 ms per plan together
