@@ -332,6 +332,30 @@ typedef struct mpdx_guide_params {
      * mpdx_plan, and mpdx_ik_solve (a chain only); mpdx_gpmp_step, mpdx_rrt_connect, mpdx_rrt_paths and mpdx_sdf_grid_bake know the built-in robots only. */
     const float* chain;                 /* device pointer: the chain table (NULL unless robot == MPDX_ROBOT_CHAIN) */
     int32_t n_chain_floats;             /* floats in chain: >= 4 + 16 n_joints + 8 n_spheres + 2 n_pairs */
+    /* --- tool-axis constraint of a chain robot ("carry it upright"; an extension: the reference has no task-space cost).  All members zero
+     * (tool_frame == 0): no tool term - the block behaves exactly as before these members existed.
+     * Fixed per guide: a frame f = tool_frame (1 ... n_joints), a unit axis a = tool_axis in that frame, a unit axis u = tool_world in the world and
+     * c* = tool_cos_min = cos(max_tilt).  On every interpolated point i of a trajectory (the points the collision terms use), all in fp32:
+     *   1. Rot_f(q_i) by the forward-kinematics recurrence of the chain table above (sinf / cosf);  w_i = Rot_f(q_i) a
+     *   2. d_i = u . w_i;   c_i = relu(c* - d_i);   cost = sum_i c_i
+     *   3. d c_i / d q_j = -[c_i > 0] z_j . (w_i x u)   for a revolute joint j <= f (1-based; z_j as above: the geometric Jacobian's angular part);
+     *      0 for a prismatic joint and for every joint j > f; the velocity dims get 0
+     *   4. the term is a cost of its own in the composite, handled as each collision cost is (guides.py:192-207): its point gradients are gathered to
+     *      the supports by the transpose of the interpolation (fixed order), clipped by the guide's clip rule over all D dims, the endpoints
+     *      zeroed, multiplied by tool_weight and summed with the collision terms (behind them) before the GP prior is added.
+     * At d_i = -1 (the tool axis exactly opposite) w_i x u = 0 and the gradient vanishes although the hinge is active: a saddle of the cost, as
+     * it is in exact arithmetic.  It is not worked around.
+     * Checked on the host before any launch (MPDX_E_INVALID, message naming the member): robot != MPDX_ROBOT_CHAIN (the Panda takes the term as
+     * RobotChain.panda()), tool_frame outside 1 ... n_joints, an axis that is not finite or not unit to 1e-4, tool_cos_min outside [-1, 1], a
+     * tool_weight that is not finite.
+     * Entry points that take the term: mpdx_guide_step, mpdx_guide_step_scaled, mpdx_guide_time, mpdx_plan (scene batches included) and
+     * mpdx_traj_tool_metrics; mpdx_traj_metrics / mpdx_traj_metrics_mask check the members and report collisions as before; mpdx_gpmp_step,
+     * mpdx_rrt_connect, mpdx_rrt_paths and mpdx_sdf_grid_bake refuse tool_frame != 0 (the baseline planners do not honour the constraint). */
+    int32_t tool_frame;                 /* 0: no tool term; 1 ... n_joints: the frame that carries the axis */
+    float   tool_axis[3];               /* a: unit axis in that frame */
+    float   tool_world[3];              /* u: unit axis in the world */
+    float   tool_cos_min;               /* cos(max_tilt), in [-1, 1] */
+    float   tool_weight;                /* weight of the term (the weight_grad_cost_* of the collision terms) */
 } mpdx_guide_params;
 #define MPDX_ROBOT_CHAIN_MAX_JOINTS    8
 #define MPDX_ROBOT_CHAIN_MAX_SPHERES   16
@@ -378,6 +402,13 @@ int mpdx_traj_metrics(const mpdx_guide_params* gp, const float* x_unnormalised, 
  * compare the kernel's decisions with an fp64 evaluation waypoint by waypoint. */
 int mpdx_traj_metrics_mask(const mpdx_guide_params* gp, const float* x_unnormalised, float* out4, uint8_t* mask, int n_check, int B,
                            int H, int D, void* stream);
+
+/* ---- tool-axis metrics of a chain robot (the tool members of mpdx_guide_params, which must be set: tool_frame != 0; tool_weight is not used).
+ * x_unnormalised [B,H,D]; over n_check interpolated points per trajectory (n_check < 2: H), d_i = tool_world . Rot_f(q_i) tool_axis:
+ * out2 [B,2] = {min_i d_i, number of checked points with d_i < tool_cos_min}; mask [B, n_check] bytes (1 = d_i < tool_cos_min) or NULL.
+ * The largest tilt of a trajectory is acos(min_i d_i).  mpdx_traj_metrics* and their out4 are unchanged.  Replaces nothing in the reference. */
+int mpdx_traj_tool_metrics(const mpdx_guide_params* gp, const float* x_unnormalised, float* out2, uint8_t* mask, int n_check, int B, int H, int D,
+                           void* stream);
 
 /* ---- bake a signed-distance grid from primitives: replaces GridMapSDF.__init__ (torch_robotics, un-vendored: restated, PARITY UNPINNED), which
  * samples the fixed objects' SDF (and its gradient) on a regular grid once per environment.  One thread per node: node (ix, iy, iz) sits at

@@ -61,7 +61,10 @@ class GuideParams(C.Structure):
                 # several obstacle scenes in one batch (layout of the scene blocks in include/mpdx.h); all zero: one scene
                 ("n_scenes", C.c_int32), ("scene_stride", C.c_int32), ("scene_of_ctx", C.c_void_p), ("scene_n_per_ctx", C.c_int32),
                 # MPDX_ROBOT_CHAIN: the kinematic table (device pointer) and its size in floats; both zero for the built-in robots
-                ("chain", C.c_void_p), ("n_chain_floats", C.c_int32)]
+                ("chain", C.c_void_p), ("n_chain_floats", C.c_int32),
+                # tool-axis constraint of a chain robot (arithmetic in include/mpdx.h); all zero (tool_frame == 0): no tool term
+                ("tool_frame", C.c_int32), ("tool_axis", C.c_float * 3), ("tool_world", C.c_float * 3), ("tool_cos_min", C.c_float),
+                ("tool_weight", C.c_float)]
 
 
 class GpmpOpts(C.Structure):
@@ -113,6 +116,7 @@ SIGNATURES = {
     "mpdx_guide_time": (_i, [C.POINTER(GuideParams), _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.POINTER(C.c_float)]),
     "mpdx_traj_metrics": (_i, [C.POINTER(GuideParams), _vp, _vp, _i, _i, _i, _i, _vp]),
     "mpdx_traj_metrics_mask": (_i, [C.POINTER(GuideParams), _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mpdx_traj_tool_metrics": (_i, [C.POINTER(GuideParams), _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mpdx_guide_trace": (_i, [C.POINTER(GuideParams), _vp, _vp, _i, _i, _i, _vp, C.POINTER(C.c_longlong)]),
     "mpdx_absmax": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "mpdx_sdf_grid_bake": (_i, [C.POINTER(GuideParams), _i, _vp, _vp, C.POINTER(C.c_int * 3), C.POINTER(C.c_float * 3), _f, _vp]),

@@ -14,6 +14,15 @@
 //   phase 1  FK once per interpolated point: O_k, z_k, P_s -> LDS (odd stride per point)
 //   phase 2  wave = (point half, field): forces on every link sphere (or pair), folded to joint gradients -> LDS
 //   phase 3  wave f gathers field f to the supports, clips, weights          phase 4  sum over fields, GP prior, apply (guide_gp_apply)
+//
+// The tool-axis term (the tool members of mpdx_guide_params, arithmetic in include/mpdx.h; dev_tool below) is a fifth cost next to the fields: the
+// TOOL instantiations, chosen by the launcher when tool_frame != 0.  Phase 1 also stores w_i = Rot_f(q_i) a while frame f's rotation is in registers,
+// phase 2 treats the term as slot n_fields of the (point half, slot) loop (with four fields: a second pass for two of the eight waves), phase 3
+// gives it wave n_fields, phase 4 sums one slot more.  With four fields the gather takes five waves and three draw the step's noise instead of four:
+// the draw is addressed by Philox counter, so its values do not depend on the partition.  TOOL is a template parameter because the measured off-path
+// cost said so: as a wave-uniform branch on the kernel argument the term cost the 7-joint kernel 19 VGPRs and a launch WITHOUT the term 1.1 - 1.2 %;
+// the TOOL = false instantiations have the register counts the kernel had before the term, and 0.7 - 0.9 % of that remain at 7 joints, unexplained
+// (profiles/tool_axis_probe.md).  traj_tool_chain_kernel reports the term's d_i per trajectory (mpdx_traj_tool_metrics).
 #pragma once
 #include "guide.hpp"
 
@@ -22,10 +31,24 @@ namespace mpdx {
 constexpr int kChainHdr = MPDX_ROBOT_CHAIN_HEADER_FLOATS, kChainJF = MPDX_ROBOT_CHAIN_JOINT_FLOATS, kChainSF = MPDX_ROBOT_CHAIN_SPHERE_FLOATS;
 constexpr int kChainMaxS = MPDX_ROBOT_CHAIN_MAX_SPHERES, kChainMaxP = MPDX_ROBOT_CHAIN_MAX_PAIRS;
 
+// the tool members of mpdx_guide_params (a validated block: frame 0 = no term, else 1 ... n_joints; unit axes)
+struct dev_tool {
+    int32_t frame;
+    float axis[3], world[3];
+    float cos_min, weight;
+};
+inline dev_tool dev_tool_of(const mpdx_guide_params& gp) {
+    dev_tool t;
+    t.frame = gp.tool_frame; t.cos_min = gp.tool_cos_min; t.weight = gp.tool_weight;
+    for (int j = 0; j < 3; ++j) { t.axis[j] = gp.tool_axis[j]; t.world[j] = gp.tool_world[j]; }
+    return t;
+}
+
 struct ChainGuideArgs {
     GuideArgs g;            // as the other guide kernels take it
     const float* table;     // the chain table (device)
     int n_table_floats;     // floats a workgroup stages: header + joints + spheres + pairs of the validated table
+    dev_tool tool;          // the tool-axis term: read by the TOOL instantiations only
 };
 
 // sphere / pair counts of the staged table: the header's, clamped to the caps and to what the staged floats hold (scalar registers)
@@ -45,9 +68,10 @@ __device__ __forceinline__ ChainCounts chain_counts(const float* __restrict__ ta
 // l0 * qa + l1 * qb of two rows of the LDS-staged state, read joint by joint (the joint loop is a real loop: its index addresses LDS only).
 // oz (or null): O_k at oz[3 k + r], z_k at oz[3 QD + 3 k + r]; pp: sphere centre s at pp[3 s + r].  The spheres of a frame are placed while that
 // frame's transform is in registers (the frame of a sphere is wave-uniform: a scalar branch per (frame, sphere)).
+// tool (or null) with tool->frame = f in 1 ... QD: w_out[r] <- (Rot_f a)[r], the tool axis in the world, stored while frame f's rotation is in registers.
 template <int QD, bool WRITE_OZ>
 __device__ __forceinline__ void chain_fk(const float* __restrict__ stab, int ns, const float* __restrict__ qa, const float* __restrict__ qb, float l0, float l1,
-                                         float* __restrict__ oz, float* __restrict__ pp) {
+                                         float* __restrict__ oz, float* __restrict__ pp, const dev_tool* __restrict__ tool = nullptr, float* __restrict__ w_out = nullptr) {
     const int32_t* tabi = reinterpret_cast<const int32_t*>(stab);
     const float* sph = stab + kChainHdr + QD * kChainJF;
     float R[3][3] = {{1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, {0.f, 0.f, 1.f}}, T[3] = {0.f, 0.f, 0.f};
@@ -74,6 +98,10 @@ __device__ __forceinline__ void chain_fk(const float* __restrict__ stab, int ns,
                 R[r][2] = A[r][2];
                 T[r] = Tn[r] + dz * A[r][2];
                 if constexpr (WRITE_OZ) { oz[k * 3 + r] = T[r]; oz[QD * 3 + k * 3 + r] = R[r][2]; }
+            }
+            if (tool && tool->frame == k + 1) {   // (tool: null unless a TOOL instantiation; the frame is a kernel argument: wave-uniform)
+#pragma unroll
+                for (int r = 0; r < 3; ++r) w_out[r] = R[r][0] * tool->axis[0] + R[r][1] * tool->axis[1] + R[r][2] * tool->axis[2];
             }
         }
 #pragma unroll 1
@@ -151,7 +179,25 @@ __device__ __forceinline__ void chain_point_field(const dev_guide_params& gp, co
     }
 }
 
-template <int QD, bool MULTI_SCENE>
+// phase 2 of the tool-axis term for one interpolated point: d = u . w, hinge relu(cos_min - d), and for a revolute joint k < frame (0-based: joint
+// k + 1 <= f) g_k = -[hinge > 0] z_k . (w x u); 0 for a prismatic joint and above the frame.  fk: the point's FK record (Z at 3 QD), w: its tool axis.
+template <int QD>
+__device__ __forceinline__ void chain_point_tool(const dev_tool& tool, const float* __restrict__ stab, const float* __restrict__ fk, const float* __restrict__ w,
+                                                 float* __restrict__ g_out) {
+    const int32_t* tabi = reinterpret_cast<const int32_t*>(stab);
+    const float wx = w[0], wy = w[1], wz = w[2];
+    const float d = tool.world[0] * wx + tool.world[1] * wy + tool.world[2] * wz;
+    const bool active = tool.cos_min - d > 0.f;
+    const float cx = wy * tool.world[2] - wz * tool.world[1], cy = wz * tool.world[0] - wx * tool.world[2], cz = wx * tool.world[1] - wy * tool.world[0];
+#pragma unroll
+    for (int k = 0; k < QD; ++k) {
+        const bool prismatic = __builtin_amdgcn_readfirstlane(tabi[kChainHdr + k * kChainJF + 12]) != 0;
+        const float zc = fk[3 * QD + k * 3] * cx + fk[3 * QD + k * 3 + 1] * cy + fk[3 * QD + k * 3 + 2] * cz;
+        g_out[k] = (active && !prismatic && k < tool.frame) ? -zc : 0.f;
+    }
+}
+
+template <int QD, bool MULTI_SCENE, bool TOOL>
 __global__ __launch_bounds__(512, 2) void guide_step_chain_kernel(const ChainGuideArgs ca) {
     constexpr int D = 2 * QD, MAXF = MPDX_MAX_FIELDS, WPT = 8, FKS = chain_fk_stride(QD);
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -168,12 +214,14 @@ __global__ __launch_bounds__(512, 2) void guide_step_chain_kernel(const ChainGui
     int tr_i = 0;
     G_STAMP();  // 0 entry
     const int ntab = ca.n_table_floats;
-    const GuideLds L = guide_lds_layout(kGuideChain, H, D, N, gp.n_prim_floats, ntab);
+    const int n_slots = gp.n_fields + (TOOL ? 1 : 0);   // the tool-axis term: one more cost slot behind the fields
+    const GuideLds L = guide_lds_layout(kGuideChain, H, D, N, gp.n_prim_floats, ntab, TOOL);
     float* sx = sm + L.sx;        // [H][D]  unnormalised state
     float* stab = sm + L.stab;    // the chain table
     float* sfk = sm + L.sfk;      // [N][FKS]  O | Z | P per interpolated point
-    float* sG = sm + L.sG;        // [MAXF][N][QD]  joint gradients per (field, point)
-    float* sC = sm + L.sC;        // [MAXF][H][QD]  clipped, weighted per-field support-point gradients
+    float* sW = sm + L.sW;        // tool term: [N][3]  the tool axis in the world per interpolated point
+    float* sG = sm + L.sG;        // [MAXF (+ 1)][N][QD]  joint gradients per (slot, point)
+    float* sC = sm + L.sC;        // [MAXF (+ 1)][H][QD]  clipped, weighted per-slot support-point gradients
     float* snz = sm + L.snz;      // 16-byte aligned: [H * D + 8] the step's noise, drawn in whole groups of four (H * D need not be a multiple of 4 here)
     float* snz_x = sm + L.snz_x;  // [H * D] the normalised state
     float* sprim = sm + L.sprim;
@@ -194,7 +242,7 @@ __global__ __launch_bounds__(512, 2) void guide_step_chain_kernel(const ChainGui
     for (int i = wv * 64 + lane; i < N; i += 64 * WPT) {
         const InterpPair ip = interp_pair(gp.interpolate, scale, i, H);
         float* fk = sfk + i * FKS;
-        chain_fk<QD, true>(stab, cn.ns, sx + ip.i0 * D, sx + ip.i1 * D, ip.l0, ip.l1, fk, fk + 6 * QD);
+        chain_fk<QD, true>(stab, cn.ns, sx + ip.i0 * D, sx + ip.i1 * D, ip.l0, ip.l1, fk, fk + 6 * QD, TOOL ? &ca.tool : nullptr, sW + 3 * i);
     }
     __syncthreads();
     G_STAMP();  // 2 FK in LDS
@@ -202,29 +250,98 @@ __global__ __launch_bounds__(512, 2) void guide_step_chain_kernel(const ChainGui
     // ---- phase 2: wave = (point half, field slot): every link sphere / pair of the field, folded to joint gradients
     {
         const int half = wv & 1, slot = wv >> 1;
-        for (int f = slot; f < gp.n_fields; f += WPT / 2) {
-            dev_field fld;
-            if constexpr (MULTI_SCENE) fld = scene_field(gp, sc_n, f); else fld = gp.fields[f];
-            for (int i = half * 64 + lane; i < N; i += 128) chain_point_field<QD>(gp, fld, sprim, stab, cn, sfk + i * FKS, sG + (f * N + i) * QD);
+        for (int f = slot; f < n_slots; f += WPT / 2) {
+            if (!TOOL || f < gp.n_fields) {
+                dev_field fld;
+                if constexpr (MULTI_SCENE) fld = scene_field(gp, sc_n, f); else fld = gp.fields[f];
+                for (int i = half * 64 + lane; i < N; i += 128) chain_point_field<QD>(gp, fld, sprim, stab, cn, sfk + i * FKS, sG + (f * N + i) * QD);
+            } else {   // the tool-axis term (slot n_fields)
+                for (int i = half * 64 + lane; i < N; i += 128) chain_point_tool<QD>(ca.tool, stab, sfk + i * FKS, sW + 3 * i, sG + (f * N + i) * QD);
+            }
         }
     }
     G_STAMP();  // 3 this wave's forces done
     __syncthreads();
     G_STAMP();  // 4 all waves done
 
-    // the step's noise (last guide iteration, drawn in place): by the waves that do not gather, under the gather
+    // the step's noise (last guide iteration, drawn in place): by the waves that do not gather, under the gather.  Element k of the draw is a function
+    // of its Philox counter alone: the values do not depend on how many waves draw (four, or three when four fields and the tool term gather)
     const unsigned long long ne0 = a.rng.elem0 + (unsigned long long)b * H * D;
-    if (a.rng.on && !a.grad_out && wv >= MAXF) guide_draw_noise(a.rng, ne0, H * D, snz, threadIdx.x - 64 * MAXF, 64 * (WPT - MAXF));
+    const int wdraw = TOOL && n_slots > MAXF ? MAXF + 1 : MAXF;
+    if (a.rng.on && !a.grad_out && wv >= wdraw) guide_draw_noise(a.rng, ne0, H * D, snz, threadIdx.x - 64 * wdraw, 64 * (WPT - wdraw));
 
     // ---- phase 3: wave f gathers field f to the support points (transpose of the interpolation, fixed order), clips, weights
     if (wv < gp.n_fields) {
         const int f = wv;
         gather_clip_weight<QD>(gp, f, nsw, lane, H, N, scale, sC, [&](int i, int j) { return sG[(f * N + i) * QD + j]; });
+    } else if (TOOL && wv < n_slots) {   // the tool-axis term: a wave of its own, the term's own weight
+        const int f = wv;
+        gather_clip_weight_as<QD>(gp, f, ca.tool.weight, nsw, lane, H, N, scale, sC, [&](int i, int j) { return sG[(f * N + i) * QD + j]; });
     }
     __syncthreads();
     G_STAMP();  // 5 gathered + clipped
     if (wv >= nsw) return;
-    sum_fields_and_apply<QD>(a, b, ctx, lane, wv, hs_, H, live, sx, snz_x, sC, snz + (int)(ne0 & 3ull), shc);
+    sum_fields_and_apply<QD>(a, n_slots, b, ctx, lane, wv, hs_, H, live, sx, snz_x, sC, snz + (int)(ne0 & 3ull), shc);
+}
+
+// The tool-axis figures of mpdx_traj_tool_metrics: one wave per trajectory, lane = checked point (the pattern of traj_metrics_chain_kernel).  The rotation
+// recurrence of chain_fk (the same statements; the translations and the spheres are not needed) up to frame f only, d_i = u . Rot_f(q_i) a; out2 =
+// {min_i d_i, number of points with d_i < cos_min} by the fixed butterfly; mask (or null): the per-point flags.
+template <int QD>
+__global__ __launch_bounds__(64) void traj_tool_chain_kernel(const dev_tool tool, const float* __restrict__ x, float* __restrict__ out2, uint8_t* __restrict__ mask,
+                                                             int B, int H, int n_check, const float* __restrict__ table, int ntab) {
+    constexpr int D = 2 * QD;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int lane = threadIdx.x, b = blockIdx.x;
+    float* sx = sm;                // [H][D]
+    float* stab = sm + H * D;      // the joints of the chain table (header + QD joint records)
+    for (int i = lane; i < ntab; i += 64) stab[i] = table[i];
+    for (int i = lane; i < H * D; i += 64) sx[i] = x[(size_t)b * H * D + i];
+    __syncthreads();
+    const int32_t* tabi = reinterpret_cast<const int32_t*>(stab);
+    const int fr = __builtin_amdgcn_readfirstlane(min(max(tool.frame, 0), QD));
+    const int N = n_check;
+    const float scale = interp_scale(H, N);
+    float dmin = 3.0e38f, nbad = 0.f;
+    for (int i = lane; i < N; i += 64) {
+        const InterpPair ip = interp_pair(true, scale, i, H);
+        const float* qa = sx + ip.i0 * D;
+        const float* qb = sx + ip.i1 * D;
+        float R[3][3] = {{1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, {0.f, 0.f, 1.f}};
+#pragma unroll 1
+        for (int k = 0; k < fr; ++k) {
+            const float* J = stab + kChainHdr + k * kChainJF;
+            const bool prismatic = __builtin_amdgcn_readfirstlane(tabi[kChainHdr + k * kChainJF + 12]) != 0;
+            const float qk = ip.l0 * qa[k] + ip.l1 * qb[k];
+            float A[3][3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) A[r][c] = R[r][0] * J[c] + R[r][1] * J[3 + c] + R[r][2] * J[6 + c];
+            }
+            float st = 0.f, ct = 1.f;
+            if (!prismatic) { st = sinf(qk); ct = cosf(qk); }
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                R[r][0] = A[r][0] * ct + A[r][1] * st;
+                R[r][1] = A[r][1] * ct - A[r][0] * st;
+                R[r][2] = A[r][2];
+            }
+        }
+        float d = 0.f;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) d += tool.world[r] * (R[r][0] * tool.axis[0] + R[r][1] * tool.axis[1] + R[r][2] * tool.axis[2]);
+        const bool bad = d < tool.cos_min;
+        dmin = fminf(dmin, d);
+        nbad += bad ? 1.f : 0.f;
+        if (mask) mask[(size_t)b * N + i] = bad ? 1 : 0;
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        dmin = fminf(dmin, __shfl_xor(dmin, s, 64));
+        nbad += __shfl_xor(nbad, s, 64);
+    }
+    if (lane == 0) { out2[(size_t)b * 2 + 0] = dmin; out2[(size_t)b * 2 + 1] = nbad; }
 }
 
 // traj_metrics_kernel (guide.hpp) for a chain: the same out4 and mask; collision flags with the link radii, no margin, over the objects,
@@ -355,8 +472,13 @@ inline const char* chain_table_problem(const mpdx_guide_params& gp, const float*
 
 // ---- k_guide.hip: the checks of a MPDX_ROBOT_CHAIN block, the table read where it lies (a device table: copied to the host once per (pointer, size))
 const char* chain_params_check(const mpdx_guide_params& gp, ChainInfo* info);
-// ---- k_chain.hip: every guide_step_chain_kernel / traj_metrics_chain_kernel instantiation
-int launch_chain_guide(const GuideArgs& a, const float* table, const ChainInfo& ci, bool multi, size_t lds, int B, hipStream_t st);
+// the checks of the tool members (nothing is dereferenced): nullptr = fine or no tool term (tool_frame == 0), else what is wrong, naming the member.
+// For a chain robot call it behind chain_params_check (q_dim == n_joints by then).
+const char* tool_params_problem(const mpdx_guide_params& gp);
+// ---- k_chain.hip: every guide_step_chain_kernel / traj_metrics_chain_kernel / traj_tool_chain_kernel instantiation
+int launch_chain_guide(const GuideArgs& a, const dev_tool& tool, const float* table, const ChainInfo& ci, bool multi, size_t lds, int B, hipStream_t st);
+int launch_chain_tool_metrics(const dev_tool& tool, const float* x, float* out2, uint8_t* mask, int n_check, int B, int H, const float* table, const ChainInfo& ci,
+                              hipStream_t st);
 int launch_chain_metrics(const dev_guide_params& g, const float* x, float* out4, uint8_t* mask, int n_check, int B, int H, const dev_scenes& sc, const float* table,
                          const ChainInfo& ci, bool multi, hipStream_t st);
 

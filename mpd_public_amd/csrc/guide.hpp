@@ -541,8 +541,10 @@ __device__ __forceinline__ void guide_draw_noise(const NoiseRng& rng, unsigned l
 // Phase 3 of the Panda and chain kernels: the wave of field f gathers the field's point gradients to the support points (transpose of the
 // interpolation, fixed order; one or two blocks of 64 supports), clips over ALL D dims of (g + 1e-6) (the velocity dims of a collision gradient
 // are 0), zeroes the endpoints, weights -> sC[f][H][QD].  point_grad(i, j): joint gradient j of interpolated point i, summed over what holds it.
+// gather_clip_weight_as: the same for a term that is no entry of gp.fields (the chain's tool-axis term): slot f of sC, the weight given.
 template <int QD, class PointGrad>
-__device__ __forceinline__ void gather_clip_weight(const dev_guide_params& gp, int f, int nsw, int lane, int H, int N, float scale, float* sC, PointGrad point_grad) {
+__device__ __forceinline__ void gather_clip_weight_as(const dev_guide_params& gp, int f, float weight, int nsw, int lane, int H, int N, float scale, float* sC,
+                                                      PointGrad point_grad) {
     for (int sb = 0; sb < nsw; ++sb) {
         const int hg_ = sb * 64 + lane;
         if (hg_ >= H) continue;
@@ -565,15 +567,20 @@ __device__ __forceinline__ void gather_clip_weight(const dev_guide_params& gp, i
         clip_waypoint_grad<QD>(gp, g, QD);
         const bool interior = hg_ > 0 && hg_ < H - 1;
 #pragma unroll
-        for (int j = 0; j < QD; ++j) sC[(f * H + hg_) * QD + j] = interior ? gp.fields[f].weight * g[j] : 0.f;
+        for (int j = 0; j < QD; ++j) sC[(f * H + hg_) * QD + j] = interior ? weight * g[j] : 0.f;
     }
 }
+template <int QD, class PointGrad>
+__device__ __forceinline__ void gather_clip_weight(const dev_guide_params& gp, int f, int nsw, int lane, int H, int N, float scale, float* sC, PointGrad point_grad) {
+    gather_clip_weight_as<QD>(gp, f, gp.fields[f].weight, nsw, lane, H, N, scale, sC, point_grad);
+}
 
-// Phase 4 of the chain kernel (the support wave(s); the Panda kernel keeps its own copy, see there): sum over fields, GP prior, apply.  sx = the unnormalised state the prologue staged,
+// Phase 4 of the chain kernel (the support wave(s); the Panda kernel keeps its own copy, see there): sum over the n_slots terms of sC (the fields,
+// then the tool-axis term when it is on), GP prior, apply.  sx = the unnormalised state the prologue staged,
 // sxn = the normalised state as loaded (nothing has written x since); snoise, shc: see guide_gp_apply.
 template <int QD>
-__device__ __forceinline__ void sum_fields_and_apply(const GuideArgs& a, int b, int ctx, int lane, int wv, int hs_, int H, bool live, const float* sx, const float* sxn,
-                                                     const float* sC, const float* snoise, const float* shc) {
+__device__ __forceinline__ void sum_fields_and_apply(const GuideArgs& a, int n_slots, int b, int ctx, int lane, int wv, int hs_, int H, bool live, const float* sx,
+                                                     const float* sxn, const float* sC, const float* snoise, const float* shc) {
     constexpr int D = 2 * QD;
     __builtin_assume(shc != nullptr);   // (both callers stage the hard conditions: guide_gp_apply's global-memory fallback, 2 D loads on the kernel's tail, drops out)
     float total[D], xu[D], xn[D];
@@ -585,7 +592,7 @@ __device__ __forceinline__ void sum_fields_and_apply(const GuideArgs& a, int b, 
         xn[d] = live ? sxn[hs_ * D + d] : 0.f;
     }
     if (live) {
-        for (int f = 0; f < a.gp.n_fields; ++f) {
+        for (int f = 0; f < n_slots; ++f) {
 #pragma unroll
             for (int j = 0; j < QD; ++j) total[j] += sC[(f * H + hs_) * QD + j];
         }
@@ -1038,7 +1045,7 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(co
 // bytes of dynamic LDS of a guide launch (n_prim_floats / n_chain_floats of gp: what a workgroup stages)
 inline size_t guide_lds_bytes(const mpdx_guide_params& gp, int H, int D, bool dense = false) {
     const GuideKind kind = gp.robot == MPDX_ROBOT_CHAIN ? kGuideChain : gp.robot != MPDX_ROBOT_PANDA ? kGuidePointMass : dense ? kGuidePandaDense : kGuidePandaSparse;
-    return guide_lds_layout(kind, H, D, gp.interpolate ? gp.n_interp : H, gp.n_prim_floats, gp.n_chain_floats).total * sizeof(float);
+    return guide_lds_layout(kind, H, D, gp.interpolate ? gp.n_interp : H, gp.n_prim_floats, gp.n_chain_floats, gp.tool_frame != 0).total * sizeof(float);
 }
 
 }  // namespace mpdx

@@ -123,15 +123,18 @@ struct GuideLds {
     int sA, sB;       // point mass: [MAXF][N][QD] point forces weighted l0 / l1 (sC overlays sB)
     int stab;         // chain: the chain table
     int sfk;          // Panda sparse, chain: [N][stride] FK record per interpolated point
-    int sG;           // Panda: [MAXF][parts][N][QD], chain: [MAXF][N][QD]  joint gradients per point
-    int sC;           // [MAXF][H][QD] clipped, weighted per-field support-point gradients
+    int sW;           // chain with the tool-axis term: [N][3] the tool axis in the world, the part of a point's FK record the term adds (odd stride)
+    int sG;           // Panda: [MAXF][parts][N][QD], chain: [MAXF (+ 1 with the tool term)][N][QD]  joint gradients per point
+    int sC;           // [MAXF (+ 1: chain with the tool term)][H][QD] clipped, weighted per-field support-point gradients
     int snz, snz_x;   // Panda, chain: 16-byte aligned [H * D + pad] the step's noise, drawn in whole groups of four | [H * D] the normalised state
     int sprim, shc;   // the primitive table | Panda, chain: [2][D] hard conditions
     size_t total;
 };
 // n_prim / n_tab: the floats a workgroup stages of the primitive table / the chain table.  total of the Panda and chain layouts: every round-up to
 // 16 bytes is counted as + 3 floats, as the launchers always have (the 80-KB dense and 160-KB refusal thresholds were set with it): >= shc + 2 D.
-__host__ __device__ inline GuideLds guide_lds_layout(GuideKind kind, int H, int D, int N, int n_prim, int n_tab = 0) {
+// tool (chain only): the tool-axis term is on - a fifth gradient slot in sG and sC and [N][3] floats of FK record (sW); off: the offsets and the total
+// are what they were before the term existed.
+__host__ __device__ inline GuideLds guide_lds_layout(GuideKind kind, int H, int D, int N, int n_prim, int n_tab = 0, bool tool = false) {
     constexpr int MAXF = MPDX_MAX_FIELDS;
     const int QD = D / 2;
     GuideLds l = {};
@@ -145,15 +148,17 @@ __host__ __device__ inline GuideLds guide_lds_layout(GuideKind kind, int H, int 
     }
     const bool chain = kind == kGuideChain;
     const int pad = chain ? 8 : 4;   // (chain: H * D need not be a multiple of 4, the draw starts up to 3 floats early and ends up to 3 late)
+    const int slots = MAXF + (chain && tool ? 1 : 0);
     l.stab = H * D;
     l.sfk = l.stab + (chain ? round_up4(n_tab) : 0);
-    l.sG = l.sfk + (chain ? N * chain_fk_stride(QD) : kind == kGuidePandaSparse ? N * kPandaFKS : 0);
-    l.sC = l.sG + MAXF * (chain ? 1 : kPandaParts) * N * QD;
-    l.snz = round_up4(l.sC + MAXF * H * QD);
+    l.sW = l.sfk + (chain ? N * chain_fk_stride(QD) : kind == kGuidePandaSparse ? N * kPandaFKS : 0);
+    l.sG = l.sW + (chain && tool ? 3 * N : 0);
+    l.sC = l.sG + slots * (chain ? 1 : kPandaParts) * N * QD;
+    l.snz = round_up4(l.sC + slots * H * QD);
     l.snz_x = l.snz + H * D + pad;
     l.sprim = l.snz_x + H * D;
     l.shc = l.sprim + round_up4(n_prim);
-    l.total = (size_t)H * D + (size_t)(chain ? n_tab + 3 : 0) + (size_t)(l.sC - l.sfk) + (size_t)MAXF * H * QD + (size_t)(2 * H * D + pad + 3) + (size_t)n_prim + 3 + 2 * D;
+    l.total = (size_t)H * D + (size_t)(chain ? n_tab + 3 : 0) + (size_t)(l.sC - l.sfk) + (size_t)slots * H * QD + (size_t)(2 * H * D + pad + 3) + (size_t)n_prim + 3 + 2 * D;
     return l;
 }
 

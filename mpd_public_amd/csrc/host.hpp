@@ -209,6 +209,7 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
                  uint32_t* amax_out, int n_per_ctx, int B, int H, int D, hipStream_t st, const float* noise = nullptr, float noise_scale = 0.f,
                  float noise_extra = 0.f, float* chain = nullptr, float guide_scale = 1.0f, const NoiseRng* rng = nullptr);
 const char* chain_params_problem(const mpdx_guide_params& gp);   // nullptr, or why a MPDX_ROBOT_CHAIN block is refused (any other robot: nullptr)
+const char* tool_params_problem(const mpdx_guide_params& gp);    // nullptr, or why the tool members are refused (tool_frame == 0: nullptr); chain.hpp
 struct ChainInfo;
 // The checks every launcher applies to a guide parameter block: D == 2 q_dim, n_fields, the primitive table; with chain_info (the guide, its timer
 // and the metrics; filled for a chain robot, else zeroed) also the chain, grid and scene members.  0, or fail(MPDX_E_INVALID, ...).

@@ -49,6 +49,31 @@ const char* chain_params_check(const mpdx_guide_params& gp, ChainInfo* info) {
     return nullptr;
 }
 
+// The checks of the tool members (the tool-axis term, include/mpdx.h): members only, nothing is dereferenced.  A chain block has passed
+// chain_params_check by now, so q_dim is the table's n_joints.
+const char* tool_params_problem(const mpdx_guide_params& gp) {
+    static thread_local char msg[200];
+    if (gp.tool_frame == 0) return nullptr;
+    if (gp.robot != MPDX_ROBOT_CHAIN) {
+        snprintf(msg, sizeof(msg), "tool_frame %d: the tool-axis term needs robot == MPDX_ROBOT_CHAIN (robot %d; the Panda takes it as RobotChain.panda())", gp.tool_frame, gp.robot);
+        return msg;
+    }
+    if (gp.tool_frame < 1 || gp.tool_frame > gp.q_dim) { snprintf(msg, sizeof(msg), "tool_frame %d outside 1 ... n_joints (%d)", gp.tool_frame, gp.q_dim); return msg; }
+    const float* axes[2] = {gp.tool_axis, gp.tool_world};
+    const char* names[2] = {"tool_axis", "tool_world"};
+    for (int k = 0; k < 2; ++k) {
+        float n2 = 0.f;
+        for (int j = 0; j < 3; ++j) {
+            if (!(fabsf(axes[k][j]) < 3.0e38f)) { snprintf(msg, sizeof(msg), "%s is not finite", names[k]); return msg; }
+            n2 += axes[k][j] * axes[k][j];
+        }
+        if (!(fabsf(sqrtf(n2) - 1.f) <= 1e-4f)) { snprintf(msg, sizeof(msg), "%s is not a unit vector to 1e-4 (norm %g)", names[k], (double)sqrtf(n2)); return msg; }
+    }
+    if (!(gp.tool_cos_min >= -1.f && gp.tool_cos_min <= 1.f)) { snprintf(msg, sizeof(msg), "tool_cos_min %g outside [-1, 1]", (double)gp.tool_cos_min); return msg; }
+    if (!(fabsf(gp.tool_weight) < 3.0e38f)) return "tool_weight is not finite";
+    return nullptr;
+}
+
 const char* chain_params_problem(const mpdx_guide_params& gp) {
     if (gp.robot != MPDX_ROBOT_CHAIN) return nullptr;
     ChainInfo ci;
@@ -70,10 +95,14 @@ int guide_block_problem(const mpdx_guide_params* gp, int D, ChainInfo* chain_inf
     if (D != 2 * gp->q_dim || D > 16) return fail(MPDX_E_INVALID, "state dim %d != 2*q_dim (%d)", D, gp->q_dim);
     if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS) return fail(MPDX_E_INVALID, "n_fields %d", gp->n_fields);
     if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
-    if (!chain_info) return 0;   // (the baseline planners: built-in robots, one scene, no grid - refusals of their own)
+    if (!chain_info) {   // (the baseline planners: built-in robots, one scene, no grid - refusals of their own)
+        if (gp->tool_frame != 0) return fail(MPDX_E_INVALID, "tool_frame %d: the baseline planners do not take the tool-axis term (guide, mpdx_plan and mpdx_traj_tool_metrics only)", gp->tool_frame);
+        return 0;
+    }
     memset(chain_info, 0, sizeof(*chain_info));
     if (gp->robot == MPDX_ROBOT_CHAIN)   // (a chain robot's own refusals first: it takes no grid field at all)
         if (const char* why = chain_params_check(*gp, chain_info)) return fail(MPDX_E_INVALID, "%s", why);
+    if (const char* why = tool_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
     if (const char* why = grid_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
     if (const char* why = scene_params_problem(*gp)) return fail(MPDX_E_INVALID, "%s", why);
     return 0;
@@ -113,7 +142,7 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
     const bool dense = gp->robot == MPDX_ROBOT_PANDA && (dense_env >= 0 ? dense_env != 0 : B >= 512) && guide_lds_bytes(staged, H, D, true) <= 80 * 1024;
     const size_t lds = guide_lds_bytes(staged, H, D, dense);
     if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "guide needs %zu B of LDS (n_interp %d too large)", lds, gp->n_interp);
-    if (gp->robot == MPDX_ROBOT_CHAIN) return launch_chain_guide(a, gp->chain, chain_info, multi, lds, B, st);   // (q_dim == n_joints, ws_dim == 3: checked above)
+    if (gp->robot == MPDX_ROBOT_CHAIN) return launch_chain_guide(a, dev_tool_of(*gp), gp->chain, chain_info, multi, lds, B, st);   // (q_dim == n_joints, ws_dim == 3: checked above)
     int rc = 0;
     const bool known = with_builtin_robot(*gp, [&](auto qd, auto, auto robot) {
         if constexpr (decltype(robot)::value == MPDX_ROBOT_PANDA)
@@ -190,6 +219,19 @@ int mpdx_traj_metrics_mask(const mpdx_guide_params* gp, const float* x_unnormali
     return 0;
 }
 
+int mpdx_traj_tool_metrics(const mpdx_guide_params* gp, const float* x_unnormalised, float* out2, uint8_t* mask, int n_check, int B, int H, int D,
+                           void* stream) {
+    if (!gp || !x_unnormalised || !out2 || B <= 0) return fail(MPDX_E_INVALID, "bad argument");
+    if (H > 128 || H < 2) return fail(MPDX_E_INVALID, "H=%d unsupported (max 128)", H);
+    if (gp->tool_frame == 0) return fail(MPDX_E_INVALID, "tool_frame 0: mpdx_traj_tool_metrics needs the tool members of the block");
+    ChainInfo chain_info;
+    if (int rc = guide_block_problem(gp, D, &chain_info)) return rc;   // (a built-in robot with tool_frame != 0 is refused there)
+    if (n_check < 2) n_check = H;
+    if (int rc = launch_chain_tool_metrics(dev_tool_of(*gp), x_unnormalised, out2, mask, n_check, B, H, gp->chain, chain_info, (hipStream_t)stream)) return rc;
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int mpdx_guide_time(const mpdx_guide_params* gp, float* x, float* grad_out, const uint32_t* absmax_in, int n_per_ctx, int B, int H, int D,
                     int reps, void* stream, float* ms_avg) {
     if (!gp || !x || !grad_out || !absmax_in || !ms_avg || reps < 1) return fail(MPDX_E_INVALID, "bad argument");
@@ -239,6 +281,7 @@ int mpdx_sdf_grid_bake(const mpdx_guide_params* gp, int field, float* sdf_out, f
     if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS || field < 0 || field >= gp->n_fields) return fail(MPDX_E_INVALID, "field %d of %d", field, gp->n_fields);
     const mpdx_field& f = gp->fields[field];
     if (f.kind != MPDX_FIELD_OBJECTS) return fail(MPDX_E_INVALID, "grid bake: field %d is not an OBJECTS field", field);
+    if (gp->tool_frame != 0) return fail(MPDX_E_INVALID, "grid bake: tool_frame %d (the tool-axis term belongs to the guide; a grid is baked from an OBJECTS field)", gp->tool_frame);
     if (has_scenes(*gp)) return fail(MPDX_E_INVALID, "grid bake: one scene only (n_scenes = %d): a grid stands for the fixed environment", gp->n_scenes);
     if (gp->ws_dim != 2 && gp->ws_dim != 3) return fail(MPDX_E_INVALID, "grid bake: ws_dim %d", gp->ws_dim);
     if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");

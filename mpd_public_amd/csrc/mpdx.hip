@@ -1259,6 +1259,8 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
         if (const char* why = scene_params_problem(*guide)) return fail(MPDX_E_INVALID, "%s", why);
     if (guide)   // ... and so is a chain robot's table (a device table is read here, once, outside the loop)
         if (const char* why = chain_params_problem(*guide)) return fail(MPDX_E_INVALID, "%s", why);
+    if (guide)   // ... and the tool-axis members
+        if (const char* why = tool_params_problem(*guide)) return fail(MPDX_E_INVALID, "%s", why);
     if (int rc = check_ready(u)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int H = u->cfg.n_support_points, D = u->cfg.state_dim;

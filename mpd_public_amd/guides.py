@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .planning import CostCollision, CostComposite, CostGPTrajectory, GRID_MODES
+from .planning import CostCollision, CostComposite, CostGPTrajectory, CostToolAxis, GRID_MODES
 
 
 def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight_l, interpolate, n_interp, clip_grad, max_grad_norm, device,
@@ -96,6 +96,14 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
                 raise NotImplementedError("one CostGPTrajectory term")
             gp.use_gp, gp.gp_weight, gp.dt, gp.sigma_gp = 1, float(w), float(c.dt), float(c.sigma_gp)
             gp.gp_half_factor = int(bool(getattr(c, "half_factor", False)))
+        elif isinstance(c, CostToolAxis):   # the tool members at the end of the block (no entry of fields[]): frame, unit axes, cos(max_tilt), weight
+            if gp.tool_frame:
+                raise NotImplementedError("one CostToolAxis term")
+            if c.robot is not robot and (robot.robot_id != _lib.ROBOT_CHAIN or c.robot.q_dim != robot.q_dim):
+                raise ValueError("the CostToolAxis was built for another robot than the guide's")
+            gp.tool_frame, gp.tool_cos_min, gp.tool_weight = c.frame, c.cos_min, float(w)
+            for j in range(3):
+                gp.tool_axis[j], gp.tool_world[j] = float(c.axis[j]), float(c.world_axis[j])
         else:
             raise NotImplementedError(type(c))
     gp.n_fields = nf

@@ -32,14 +32,56 @@ def _synthetic_args():
                 unet_dim_mults_option=1, use_ema=True, include_velocity=True)
 
 
+def _tool_axis_endpoints(task, dataset, cost, gen, seed, device, max_tries=100):
+    """Start and goal configurations under a CostToolAxis: each is a task.ik_coll_free_q solution for a reachable target whose orientation satisfies
+    the constraint - position and rotation of the frame at a random collision-free configuration, the rotation turned by the smallest rotation that
+    takes the tool axis onto the world axis (tilt 0).  The goal is the solution nearest to the start among those farther than the dataset's
+    threshold_start_goal_pos (the pattern of goal_ee_pos)."""
+    import numpy as np
+    robot = task.robot
+    start = None
+    for k in range(max_tries):
+        q = task.random_coll_free_q(n_samples=1, device=device, generator=gen)[0]
+        p, R = robot.fk(q.cpu().numpy(), frame=cost.frame)
+        w, u = R @ cost.axis, cost.world_axis
+        v, c = np.cross(w, u), float(w @ u)
+        if c < -1.0 + 1e-9:          # exactly opposite: half a turn about any axis perpendicular to u
+            e = np.eye(3)[int(np.argmin(np.abs(u)))]
+            n = np.cross(u, e) / np.linalg.norm(np.cross(u, e))
+            Rmin = 2.0 * np.outer(n, n) - np.eye(3)
+        else:                        # Rodrigues, written in v = w x u (|v| = sin, c = cos)
+            K = np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+            Rmin = np.eye(3) + K + K @ K / (1.0 + c)
+        try:
+            q_ik = task.ik_coll_free_q(torch.from_numpy(p).float(), torch.from_numpy(Rmin @ R).float(), n_samples=16, device=device, seed=seed + k, frame=cost.frame)
+        except ValueError:
+            continue
+        if start is None:
+            start = q_ik[0]
+            continue
+        dist = torch.linalg.norm(q_ik - start, dim=-1)
+        far = dist > dataset.threshold_start_goal_pos
+        if bool(far.any()):
+            return start, q_ik[far][torch.argmin(dist[far])]
+    raise ValueError("No pair of collision free configurations satisfies the tool-axis constraint")
+
+
 def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mpd", use_guide_on_extra_objects_only: bool = False,
                n_samples: int = 50, start_guide_steps_fraction: float = 0.25, n_guide_steps: int = 5,
                n_diffusion_steps_without_noise: int = 5, weight_grad_cost_collision: float = 1e-2,
                weight_grad_cost_smoothness: float = 1e-7, factor_num_interpolated_points_for_collision: float = 1.5,
                trajectory_duration: float = 5.0, device: str = "cuda", debug: bool = True, render: bool = False, seed: int = 30,
                results_dir: str = "logs", model_dir: str = None, model_args: dict = None, sdf_grid_cell_size: float = None,
-               sdf_grid_mode: str = "linear", robot=None, goal_ee_pos=None, goal_ee_rot=None, goal_ee_frame=None, **kwargs):
-    """goal_ee_pos / goal_ee_rot / goal_ee_frame (extension; None = a random goal configuration, as before): the goal as an end-effector target -
+               sdf_grid_mode: str = "linear", robot=None, goal_ee_pos=None, goal_ee_rot=None, goal_ee_frame=None, tool_axis=None,
+               weight_grad_cost_tool_axis: float = 1e-2, **kwargs):
+    """tool_axis (extension; None = no such term, as before): dict(frame=, axis=, world_axis=, max_tilt=) - the arguments of planning.CostToolAxis, every
+    key optional - adds the tool-axis constraint to the guide with weight `weight_grad_cost_tool_axis` ("carry it upright": the frame's axis stays
+    within max_tilt radians of the world axis along the whole trajectory).  A chain robot (the Panda as robot=RobotChain.panda()).  Start and goal are
+    then task.ik_coll_free_q solutions for two reachable end-effector targets whose orientation satisfies the constraint exactly (the pose of a random
+    collision-free configuration, turned by the smallest rotation that aligns the axis); the results gain `tool_tilt_max` ([n_samples], the largest
+    tilt of each final trajectory in radians) and `fraction_within_tilt` (the share of final trajectories with no point beyond max_tilt).  The term
+    acts in the guide only: it is no part of the prior's training, and the baseline planners of generate_trajectories do not honour it.
+    goal_ee_pos / goal_ee_rot / goal_ee_frame (extension; None = a random goal configuration, as before): the goal as an end-effector target -
     the point [x, y, z] (and the [3, 3] orientation) the frame `goal_ee_frame` (default: the last) is to reach.  The goal configuration is then the
     task.ik_coll_free_q solution nearest to the start in joint space among those farther than the dataset's threshold_start_goal_pos; the results
     gain `goal_ee_pos` and `goal_ee_error` (|FK(goal) - target| in float64).  A chain robot or the Panda.
@@ -72,6 +114,13 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
     n_support_points, robot, task = dataset.n_support_points, dataset.robot, dataset.task
     dt = trajectory_duration / n_support_points
     robot.dt = dt
+    tool_cost = None
+    if tool_axis is not None:   # (checked before the model is built: a robot that cannot take the term is refused at once)
+        from .planning import CostToolAxis
+        unknown = set(tool_axis) - {"frame", "axis", "world_axis", "max_tilt"}
+        if unknown:
+            raise ValueError(f"tool_axis takes frame, axis, world_axis, max_tilt (got {sorted(tool_axis)})")
+        tool_cost = CostToolAxis(robot, n_support_points, tensor_args=tensor_args, **tool_axis)
 
     unet = TemporalUnet(state_dim=dataset.state_dim, n_support_points=n_support_points, unet_input_dim=args["unet_input_dim"],
                         dim_mults=UNET_DIM_MULTS[args["unet_dim_mults_option"]],
@@ -124,6 +173,8 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
             break
     if start_state_pos is None or goal_state_pos is None:
         raise ValueError("No collision free configuration was found")
+    if tool_cost is not None:
+        start_state_pos, goal_state_pos = _tool_axis_endpoints(task, dataset, tool_cost, gen, seed, tensor_args["device"])
     goal_ee_error = None
     if goal_ee_pos is not None:
         from .ik import chain_of
@@ -141,6 +192,9 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
     collision_fields = task.get_collision_fields_extra_objects() if use_guide_on_extra_objects_only else task.get_collision_fields()
     cost_l = [CostCollision(robot, n_support_points, field=f, sigma_coll=1.0, tensor_args=tensor_args) for f in collision_fields]
     weights = [weight_grad_cost_collision] * len(cost_l)
+    if tool_cost is not None:
+        cost_l.append(tool_cost)
+        weights.append(weight_grad_cost_tool_axis)
     cost_l.append(CostGPTrajectory(robot, n_support_points, dt, sigma_gp=1.0, tensor_args=tensor_args))
     weights.append(weight_grad_cost_smoothness)
     cost_composite = CostComposite(robot, n_support_points, cost_l, weights_cost_l=weights, tensor_args=tensor_args)
@@ -228,6 +282,12 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
     if goal_ee_pos is not None:
         results_data_dict["goal_ee_pos"] = torch.as_tensor(goal_ee_pos, dtype=torch.float32).reshape(3)
         results_data_dict["goal_ee_error"] = goal_ee_error
+    if tool_cost is not None:
+        tilt, n_bad = task.tool_axis_metrics(trajs_final, tool_cost)
+        results_data_dict["tool_tilt_max"] = tilt
+        results_data_dict["fraction_within_tilt"] = float((n_bad == 0).float().mean())
+        if debug:
+            print(f"tool axis: largest tilt {float(tilt.max()):.3f} rad (allowed {tool_cost.max_tilt:.3f}); within the tilt: {results_data_dict['fraction_within_tilt']*100:.2f} %")
     if results_dir:
         out_dir = os.path.join(results_dir, model_id, "results_inference", str(seed))
         os.makedirs(out_dir, exist_ok=True)
@@ -252,5 +312,14 @@ if __name__ == "__main__":
     ap.add_argument("--sdf_grid_mode", default="linear", choices=["linear", "nearest"])
     ap.add_argument("--goal_ee_pos", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
                     help="plan to this end-effector position (inverse kinematics) instead of a random goal configuration")
-    a = ap.parse_args()
-    experiment(**vars(a))
+    ap.add_argument("--tool_upright", type=float, default=None, metavar="MAX_TILT_DEG",
+                    help="carry the tool upright: the last frame's z axis stays within this many degrees of the world's z (a chain robot; RobotPanda runs as RobotChain.panda())")
+    a = vars(ap.parse_args())
+    upright = a.pop("tool_upright")
+    if upright is not None:
+        import math
+        from .planning import RobotChain
+        if not a["model_id"].endswith("-RobotPanda"):
+            raise SystemExit("--tool_upright needs a chain robot: on the command line that is the Panda (model_id ...-RobotPanda)")
+        a.update(robot=RobotChain.panda(), tool_axis=dict(max_tilt=math.radians(upright)))
+    experiment(**a)

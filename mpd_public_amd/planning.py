@@ -477,6 +477,29 @@ class PlanningTask:
                                                       n_check, B, H, D, _lib.current_stream()), "mpdx_traj_metrics_mask")
         return (out, mask.bool()) if return_mask else out
 
+    def tool_axis_metrics(self, trajs, cost, n_check=None, return_mask=False):
+        """trajs: UNNORMALISED [B,H,D] on the GPU, cost: a CostToolAxis of this task's robot -> (max_tilt [B] in radians = acos(clamp(min_i d_i)),
+        n_violating [B] = checked points tilted by more than cost.max_tilt) over n_check interpolated points (default 4 H); with return_mask also
+        the per-point flags [B, n_check] (bool).  mpdx_traj_tool_metrics (csrc/chain.hpp::traj_tool_chain_kernel)."""
+        import ctypes as C
+        if not isinstance(cost, CostToolAxis):
+            raise TypeError("cost: a CostToolAxis is expected")
+        if cost.robot is not self.robot:
+            raise ValueError("the CostToolAxis was built for another robot than this task's")
+        trajs = trajs.to(torch.float32).contiguous()
+        if not trajs.is_cuda:
+            raise RuntimeError("tool-axis metrics run on the GPU (libmpdx); there is no CPU fallback")
+        B, H, D = trajs.shape
+        n_check = int(n_check or 4 * H)
+        from .guides import build_device_params
+        gp, _keep = build_device_params(self.robot, self.env.dim, self.obstacle_cutoff_margin, None, None, [cost], [1.0], True, 128, True, 1.0, trajs.device)
+        out = torch.empty((B, 2), dtype=torch.float32, device=trajs.device)
+        mask = torch.empty((B, n_check), dtype=torch.uint8, device=trajs.device) if return_mask else None
+        _lib.check(_lib.load().mpdx_traj_tool_metrics(C.byref(gp), trajs.data_ptr(), out.data_ptr(), mask.data_ptr() if return_mask else None,
+                                                      n_check, B, H, D, _lib.current_stream()), "mpdx_traj_tool_metrics")
+        tilt, n_bad = torch.acos(out[:, 0].clamp(-1.0, 1.0)), out[:, 1]
+        return (tilt, n_bad, mask.bool()) if return_mask else (tilt, n_bad)
+
     def get_trajs_collision_and_free(self, trajs, return_indices=False, **kw):
         m = self.trajectory_metrics(trajs)
         coll = m[:, 0] > 0
@@ -859,6 +882,37 @@ class CostGPTrajectory:
     def __init__(self, robot, n_support_points, dt, sigma_gp=1.0, tensor_args=None, half_factor=False, **kw):
         self.robot, self.n_support_points, self.dt, self.sigma_gp = robot, n_support_points, float(dt), float(sigma_gp)
         self.half_factor = bool(half_factor)
+
+
+class CostToolAxis:
+    """Tool-axis constraint of a chain robot along the whole trajectory ("carry it upright"; an extension: the reference has no task-space
+    cost).  On every interpolated point the unit axis `axis` of frame `frame` (1 ... n_joints, default the last), rotated into the world, is held
+    within `max_tilt` radians of the unit world axis `world_axis`:  cost = sum_i relu(cos(max_tilt) - world_axis . Rot_frame(q_i) axis).
+    The arithmetic and its gradient are stated in include/mpdx.h (the tool members of mpdx_guide_params).  Both axes are normalised here, in float64.
+    At a tilt of exactly pi the gradient vanishes (the axis points exactly the other way: a saddle); nothing works around it.
+    The baseline planners (RRT-Connect, GPMP2) do not honour the constraint; there is no position constraint and no training-time use."""
+
+    def __init__(self, robot, n_support_points, frame=None, axis=(0, 0, 1), world_axis=(0, 0, 1), max_tilt=0.1, tensor_args=None):
+        if not isinstance(robot, RobotChain):
+            raise ValueError(f"CostToolAxis needs a RobotChain, got {getattr(robot, 'name', type(robot).__name__)}: the Panda takes it as RobotChain.panda()")
+        frame = robot.q_dim if frame is None else frame
+        if isinstance(frame, (bool, float)) or int(frame) != frame or not 1 <= int(frame) <= robot.q_dim:
+            raise ValueError(f"frame {frame!r} outside 1 ... n_joints ({robot.q_dim})")
+        unit = []
+        for what, v in (("axis", axis), ("world_axis", world_axis)):
+            a = np.asarray(v, np.float64).reshape(-1)
+            if a.shape != (3,) or not np.isfinite(a).all() or not np.linalg.norm(a) > 0:
+                raise ValueError(f"{what} must be a finite non-zero 3-vector, got {v!r}")
+            unit.append(a / np.linalg.norm(a))
+        max_tilt = float(max_tilt)
+        if not 0.0 <= max_tilt <= math.pi:
+            raise ValueError(f"max_tilt {max_tilt!r} outside [0, pi] radians")
+        self.robot, self.n_support_points, self.frame = robot, n_support_points, int(frame)
+        self.axis, self.world_axis, self.max_tilt = unit[0], unit[1], max_tilt
+
+    @property
+    def cos_min(self) -> float:
+        return math.cos(self.max_tilt)
 
 
 class CostComposite:
