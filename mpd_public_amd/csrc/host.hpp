@@ -1,6 +1,6 @@
 // host.hpp - the host-side model (layer plan, parameter table, fused segments) and the launcher interface between the translation
-// units of libmpdx.so.  The library is built from one host TU (mpdx.hip: model building, tile choice and the launch units of a pass, the
-// planning loop, the C ABI, the small streaming kernels; it alone includes fused_build.hpp - the fused-segment builder and build_units - and
+// units of libmpdx.so.  The library is built from one host TU (mpdx.hip: model building, tile choice, the launch units of a pass and the ONE walk
+// over them, mpdx_plan's launch schedule and loop, the C ABI, the small streaming kernels; it alone includes fused_build.hpp - the fused-segment builder and build_units - and
 // unet_measure.hpp - the timing / trace entry points and the launch-unit queries) and one TU per kernel family - k_conv.hip (conv_block.hpp), k_ws.hip (conv_ws.hpp), k_fused.hip /
 // k_fused_train.hip (fused_level.hpp), k_guide.hip (guide.hpp), k_chain.hip (chain.hpp), k_ik.hip (ik.hpp), k_attn.hip (attn.hpp), k_inner_run.hip (inner_run.hpp), k_train.hip (train.hpp + train_host.hpp), k_planner.hip
 // (planner.hpp + planner_host.hpp) - so that an edit to one kernel family recompiles that family only (mpd_public_amd/build.py
@@ -118,21 +118,22 @@ struct mpdx_unet {
     // the network input is copied into workspace slot `xpad_slot` ([B][Hc][D], zero rows behind the H real ones) at the head of a pass
     int Hc = 0, xpad_slot = -1;
     bool masked() const { return Hc != cfg.n_support_points; }
-    int plan_joined = 0;      // joined launches of the last mpdx_plan call (mpdx_unet_plan_joined)
     int plan_join = 1;        // mpdx_unet_set_plan_join: mpdx_plan may run a step's up program and the next step's down program as one launch
-    // mpdx_plan: the seven 256 -> 256 layers of the innermost level as one persistent launch (inner_run.hpp)
-    int inner_run = 1;        // mpdx_unet_set_inner_run
-    int inner_runs = 0;       // run launches of the last mpdx_plan call (mpdx_unet_inner_runs)
-    int run_capacity = -1;    // workgroups of the run kernel resident at once on this device (-1: not asked yet; 0: none - no run)
-    long long run_budget = 0; // s_memtime ticks of 4 ms
-    unsigned* run_counters = nullptr;   // device: one arrival counter per cluster (not reset between launches: run_base advances by 8 x layers per launch)
-    unsigned run_base = 0;
-    int run_live = 1 << 30;             // clusters whose counters hold run_base (all of them while every counter is zero)
-    bool run_rezero = false;            // the counters hold a give-up's poison: zero them (and run_base) before the next launch
-    unsigned* run_status = nullptr;     // host-mapped pinned sticky word a workgroup that gives up sets; run_status_dev: the device's address of it
-    unsigned* run_status_dev = nullptr;
-    unsigned status_host = 0;           // stands in for *run_status until the device state exists
-    unsigned status_word() const { return run_status ? __atomic_load_n(run_status, __ATOMIC_RELAXED) : status_host; }
+    int inner_run = 1;        // mpdx_unet_set_inner_run: mpdx_plan may run the seven 256 -> 256 layers of the innermost level as one persistent launch (inner_run.hpp)
+    int plan_joined = 0, inner_runs = 0;   // joined / run launches of the last mpdx_plan call (mpdx_unet_plan_joined, mpdx_unet_inner_runs)
+    // The run's device state, made at the first mpdx_plan call that may take the run (a handle is created without a device).  mpdx.hip's
+    // inner_run_create / _begin / _free and mpdx_unet_set_status alone write it: every counter of a launch's clusters holds `base` when the launch starts.
+    struct InnerRunState {
+        int capacity = -1;            // workgroups of the run kernel resident at once on this device (-1: not asked yet; 0: none - no run)
+        long long budget = 0;         // s_memtime ticks of 4 ms
+        unsigned* counters = nullptr; // device: one arrival counter per cluster (not reset between launches: base advances by 8 x layers per launch)
+        unsigned base = 0;
+        int live = 1 << 30;           // clusters whose counters hold base (all of them while every counter is zero)
+        bool rezero = false;          // the counters hold a give-up's poison: zero them (and base) before the next launch
+        unsigned *status = nullptr, *status_dev = nullptr;   // host-mapped pinned sticky word a workgroup that gives up sets; the device's address of it
+        unsigned status_host = 0;     // stands in for *status until the device state exists
+        unsigned status_word() const { return status ? __atomic_load_n(status, __ATOMIC_RELAXED) : status_host; }
+    } run;
     // launch units: fused whole-trajectory segments (fused_level.hpp) or single layers
     struct CopyJob { size_t src, dst; int n0, ss0, ds0, n1, ss1, ds1, n_inner; };   // strided copy inside `packed` (float units)
     struct Fused {
@@ -153,7 +154,10 @@ struct mpdx_unet {
     int n_jobs = 0;
     const float* streams_for = nullptr; // `packed` buffer the fused streams were last assembled in
     int pack_version = 0, streams_version = -1;
-    struct Unit { int fused; int layer; bool pair; };   // fused >= 0: fused[fused]; else layers[layer] (pair: + layers[layer+1] in one launch)
+    // one launch of a pass: it covers layers [layer, layer + count) - a program its segment fused[fused], a pair blocks[0] + the block's residual 1x1
+    // conv, the inner run (mpdx_plan's schedule only, never in current_units) its kInnerRunLayers
+    enum UnitKind { kProgram, kLayer, kPair, kInnerRun };
+    struct Unit { UnitKind kind; int fused; int layer; int count; };
     std::vector<int> owner;                  // layer -> fused segment (-1: per-layer launch)
     // training (train_host.hpp)
     struct TrainLayer {

@@ -659,7 +659,7 @@ unsigned fused_mask(int B) {
     (void)B;
     return sw::fused() ? sw::fused_mask() : 0u;   // both live: tests and A/B runs switch the path inside one process
 }
-// launch units for batch B
+// launch units for batch B, one per program / pair / single layer (the form the timing entries and the unit queries index)
 static std::vector<mpdx_unet::Unit> current_units(const mpdx_unet* u, int B, bool* final_in_fused) {
     std::vector<mpdx_unet::Unit> out;
     const unsigned m = fused_mask(B);
@@ -669,16 +669,16 @@ static std::vector<mpdx_unet::Unit> current_units(const mpdx_unet* u, int B, boo
     for (int i = 0; i < nlay; ++i) {
         const int o = u->owner[i];
         if (fused_on(i)) {
-            if (i == u->fused[o].first) { out.push_back({o, i, false}); fin |= u->fused[o].has_final; }
+            if (i == u->fused[o].first) { out.push_back({mpdx_unet::kProgram, o, i, u->fused[o].count}); fin |= u->fused[o].has_final; }
             continue;
         }
         int MT, NT;
         if (i + 1 < nlay && !fused_on(i + 1) && pair_tile(u->layers[i], u->layers[i + 1], B, MT, NT)) {
-            out.push_back({-1, i, true});   // blocks[0] followed by the same block's residual 1x1 conv: one launch
+            out.push_back({mpdx_unet::kPair, -1, i, 2});   // blocks[0] followed by the same block's residual 1x1 conv: one launch
             ++i;
             continue;
         }
-        out.push_back({-1, i, false});
+        out.push_back({mpdx_unet::kLayer, -1, i, 1});
     }
     if (final_in_fused) *final_in_fused = fin;
     return out;
@@ -800,22 +800,76 @@ static int run_fused_join(mpdx_unet* u, const mpdx_unet::Fused& up, const mpdx_u
     return launch_fused_join(ja, B, st);
 }
 
+// ---- the device state of the inner-level run (mpdx_unet::InnerRunState, host.hpp)
+static size_t inner_run_counter_bytes(int capacity) { return (size_t)((capacity + 7) / 8 + 8) * kInnerRunCounterStride * sizeof(unsigned); }
+// One occupancy query, then - one workgroup per compute unit (the occupancy answer says that one fits): the batches the per-layer tiles were measured
+// at - the cluster counters and the host-mapped status word.  A device that cannot be asked leaves capacity 0: no run on this handle.
+static int inner_run_create(mpdx_unet::InnerRunState& r, int cus) {
+    if (r.capacity >= 0) return 0;
+    r.capacity = 0;
+    int dev = 0, khz = 0;
+    if (cus <= 0 || hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeClockRate, dev) != hipSuccess ||
+        inner_run_workgroups_per_cu() <= 0)
+        return (void)hipGetLastError(), 0;
+    HIP_TRY(hipMalloc((void**)&r.counters, inner_run_counter_bytes(cus)));
+    HIP_TRY(hipMemset(r.counters, 0, inner_run_counter_bytes(cus)));
+    HIP_TRY(hipHostMalloc((void**)&r.status, 64, hipHostMallocMapped));
+    *r.status = r.status_host;
+    HIP_TRY(hipHostGetDevicePointer((void**)&r.status_dev, r.status, 0));
+    r.budget = 4LL * (khz > 0 ? khz : 2400000);   // 4 ms of shader-clock ticks (s_memtime); a lower actual clock only lengthens it
+    r.capacity = cus;
+    return 0;
+}
+// A launch of nc clusters starts.  It advances the counters of ITS clusters only, so a batch with more clusters than the launch before (or a give-up's
+// poison) zeroes them all, stream-ordered, and starts from base 0 again: at most once per plan.  Layer i > 0 waits for *base_out + 8 i: 8 arrivals per layer.
+static int inner_run_begin(mpdx_unet::InnerRunState& r, int nc, hipStream_t st, unsigned* base_out) {
+    if (r.rezero || nc > r.live) {
+        HIP_TRY(hipMemsetAsync(r.counters, 0, inner_run_counter_bytes(r.capacity), st));
+        r.base = 0; r.rezero = false;
+    }
+    r.live = nc;
+    *base_out = r.base;
+    r.base += 8u * kInnerRunLayers;
+    return 0;
+}
+static void inner_run_free(mpdx_unet::InnerRunState& r) {
+    if (r.counters) (void)hipFree(r.counters);
+    if (r.status) (void)hipHostFree(r.status);
+}
+static int handle_status_error(const mpdx_unet* u, const char* fn) {
+    const unsigned w = u->run.status_word();
+    if (!w) return 0;
+    return fail(MPDX_E_DEVICE, "%s: a workgroup of the inner-level run gave up its wait (status 0x%x: layer %u of the run); the outputs of that plan hold NaN. "
+                "mpdx_unet_set_status(u, 0) clears the word", fn, w, w >> 8);
+}
+// mpdx_plan only: the seven 256 -> 256 Conv1dBlocks of the innermost level, layers [first, first + kInnerRunLayers), as ONE persistent launch (inner_run.hpp)
+static int run_inner_run(mpdx_unet* u, int first, const float* packed, const float* row, const float* x, float* ws, int B, hipStream_t st) {
+    InnerRunArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    for (int k = 0; k < kInnerRunLayers; ++k) {
+        if (int rc = make_conv_args(u, u->layers[first + k], packed, row, x, ws, B, 0, ra.layer[k])) return rc;
+        ra.layer[k].n_tiles_n = (B + 3) / 4;
+        ra.layer[k].trace = nullptr;
+    }
+    ra.n_layers = kInnerRunLayers; ra.nc = (B + 3) / 4;
+    if (int rc = inner_run_begin(u->run, ra.nc, st, &ra.base)) return rc;
+    ra.counters = u->run.counters; ra.status = u->run.status_dev; ra.budget = u->run.budget;
+    u->inner_runs++;
+    return launch_inner_run(ra, B, st);
+}
 
 // one launch unit of the pass (the SAME function serves the planning path, the profiler and the in-situ timer)
 static int run_unit(mpdx_unet* u, const mpdx_unet::Unit& un, const float* packed, const float* row, const float* x, float* ws, int B,
                     const FinalArgs* fa, hipStream_t st) {
-    if (un.fused >= 0) return run_fused(u, u->fused[un.fused], packed, row, x, ws, B, fa, st);
-    if (un.pair) return run_pair(u, u->layers[un.layer], u->layers[un.layer + 1], packed, row, x, ws, B, st);
+    if (un.kind == mpdx_unet::kProgram) return run_fused(u, u->fused[un.fused], packed, row, x, ws, B, fa, st);
+    if (un.kind == mpdx_unet::kPair) return run_pair(u, u->layers[un.layer], u->layers[un.layer + 1], packed, row, x, ws, B, st);
+    if (un.kind == mpdx_unet::kInnerRun) return run_inner_run(u, un.layer, packed, row, x, ws, B, st);
     return run_layer(u, u->layers[un.layer], packed, row, x, ws, B, st);
 }
 static double unit_flops(const mpdx_unet* u, const mpdx_unet::Unit& un, int B) {
-    if (un.fused >= 0) {
-        const auto& f = u->fused[un.fused];
-        double fl = 0.0;
-        for (int k = f.first; k < f.first + f.count; ++k) fl += layer_flops(u->layers[k], B);
-        return fl;
-    }
-    return layer_flops(u->layers[un.layer], B) + (un.pair ? layer_flops(u->layers[un.layer + 1], B) : 0.0);
+    double fl = 0.0;
+    for (int k = un.layer; k < un.layer + un.count; ++k) fl += layer_flops(u->layers[k], B);
+    return fl;
 }
 
 // ALGORITHMIC bytes of a launch unit: every weight / parameter it needs once + the activations that cross its boundary once (inputs,
@@ -829,7 +883,7 @@ static double layer_param_bytes(const mpdx_unet* u, const Layer& l) {
 }
 static double unit_bytes(const mpdx_unet* u, const mpdx_unet::Unit& un, int B) {
     auto act = [&](int L, int C) { return 4.0 * B * (double)L * C; };
-    if (un.fused >= 0) {
+    if (un.kind == mpdx_unet::kProgram) {
         const auto& f = u->fused[un.fused];
         const Layer& l0 = u->layers[f.first];
         double b = act(l0.L_in, l0.c1 + l0.c2);
@@ -844,28 +898,36 @@ static double unit_bytes(const mpdx_unet* u, const mpdx_unet::Unit& un, int B) {
         return b;
     }
     double b = 0.0;
-    for (int k = un.layer; k < un.layer + (un.pair ? 2 : 1); ++k) {
+    for (int k = un.layer; k < un.layer + un.count; ++k) {
         const Layer& l = u->layers[k];
         b += layer_param_bytes(u, l) + act(l.L_out, l.cout) + (l.res != SRC_NONE ? act(l.L_out, l.cout) : 0.0);
-        if (k == un.layer) b += act(l.L_in, l.c1 + l.c2);   // a paired launch reads its input once
+        if (k == un.layer || un.kind != mpdx_unet::kPair) b += act(l.L_in, l.c1 + l.c2);   // a paired launch reads its input once
     }
     return b;
 }
 
-// One pass over the launch units, then the final kernel unless a program had it - the ONE walk of the planning path and of the timing entries
-// (unet_measure.hpp).  hook(kSkipUnit, i) != 0 leaves unit i out; hook(kBeforeLaunch / kAfterLaunch, i) runs around every launch and returns an error
-// code; the final kernel counts as launch units.size().  A skipped program that holds the final op still stands for it: no separate final kernel either.
+// One pass over the launch units, then the final kernel unless a program had it - the ONE loop over launch units: mpdx_plan, the single-pass entry
+// points and the timing / trace entries (unet_measure.hpp) all come through here.  hook(kSkipUnit, i) != 0 leaves unit i out; hook(kBeforeLaunch /
+// kAfterLaunch, i) runs around every launch and returns an error code; the final kernel counts as launch units.size().  A skipped program that holds
+// the final op still stands for it: no separate final kernel either.  The two facts a pass of mpdx_plan adds (PlanSchedule::join holds for both):
+// first_done - the first unit, the down program, has already run as the tail of the pass before; next_row != null - the last unit, the up program,
+// runs joined with the NEXT pass's down program on that time-table row (join_trace: mpdx_fused_trace's stamps of that launch).
 enum PassEvent { kSkipUnit, kBeforeLaunch, kAfterLaunch };
+static int no_hook(PassEvent, int) { return 0; }
 template <class Hook>
 static int walk_pass(mpdx_unet* u, const std::vector<mpdx_unet::Unit>& units, const float* packed, const float* row, const float* x, float* ws,
-                     int B, FinalArgs& fa, hipStream_t st, Hook&& hook) {
+                     int B, FinalArgs& fa, hipStream_t st, Hook&& hook, bool first_done = false, const float* next_row = nullptr,
+                     long long* join_trace = nullptr) {
     const int n = (int)units.size();
     bool final_done = false;
-    for (int i = 0; i < n; ++i) {
-        if (units[i].fused >= 0) final_done |= u->fused[units[i].fused].has_final;
+    for (int i = first_done ? 1 : 0; i < n; ++i) {
+        const mpdx_unet::Unit& un = units[i];
+        if (un.kind == mpdx_unet::kProgram) final_done |= u->fused[un.fused].has_final;
         if (hook(kSkipUnit, i)) continue;
         if (int rc = hook(kBeforeLaunch, i)) return rc;
-        if (int rc = run_unit(u, units[i], packed, row, x, ws, B, &fa, st)) return rc;
+        const int rc = next_row && i == n - 1 ? run_fused_join(u, u->fused[un.fused], u->fused[units[0].fused], packed, row, next_row, x, ws, B, &fa, st, join_trace)
+                                              : run_unit(u, un, packed, row, x, ws, B, &fa, st);
+        if (rc) return rc;
         if (int rc = hook(kAfterLaunch, i)) return rc;
     }
     if (final_done) return 0;
@@ -874,31 +936,30 @@ static int walk_pass(mpdx_unet* u, const std::vector<mpdx_unet::Unit>& units, co
     return hook(kAfterLaunch, n);
 }
 
+// the input a pass reads: x, or - a horizon in a container - the zero-padded copy of it this makes in the workspace
+static const float* padded_input(const mpdx_unet* u, const float* x, float* ws, int B, hipStream_t st) {
+    if (!u->masked()) return x;
+    float* xc = ws + u->slot_floats * (size_t)B * u->xpad_slot;
+    const size_t nx = (size_t)B * u->Hc * u->cfg.state_dim;
+    hipLaunchKernelGGL(pad_input_kernel, dim3((unsigned)std::min<size_t>((nx + 255) / 256, 2048)), dim3(256), 0, st, x, xc, B, u->cfg.n_support_points, u->Hc,
+                       u->cfg.state_dim);
+    return xc;
+}
 // one U-Net pass + the final 1x1 conv / DDPM step described by `fa` (fa.mode 0: eps only)
 static int run_unet_and_final(mpdx_unet* u, const float* packed, const float* timetab, int T, const float* x, int t, int B,
                               float* ws, FinalArgs& fa, hipStream_t st) {
     if (int rc = check_ready(u)) return rc;
     if (t < 0 || t >= T) return fail(MPDX_E_INVALID, "timestep %d outside [0,%d)", t, T);
     if (B <= 0) return fail(MPDX_E_INVALID, "B must be positive");
-    const float* row = timetab + (size_t)t * u->tt_row;
-    if (u->masked()) {   // the network reads its input from the zero-padded container copy
-        float* xc = ws + u->slot_floats * (size_t)B * u->xpad_slot;
-        const size_t nx = (size_t)B * u->Hc * u->cfg.state_dim;
-        hipLaunchKernelGGL(pad_input_kernel, dim3((unsigned)std::min<size_t>((nx + 255) / 256, 2048)), dim3(256), 0, st, x, xc, B, u->cfg.n_support_points, u->Hc,
-                           u->cfg.state_dim);
-        x = xc;
-    }
-    return walk_pass(u, current_units(u, B, nullptr), packed, row, x, ws, B, fa, st, [](PassEvent, int) { return 0; });
+    return walk_pass(u, current_units(u, B, nullptr), packed, timetab + (size_t)t * u->tt_row, padded_input(u, x, ws, B, st), ws, B, fa, st, no_hook);
 }
 
-// ---- mpdx_plan only: the seven consecutive 256 -> 256 Conv1dBlocks of the innermost level as ONE persistent launch (inner_run.hpp).
-// First launch unit of that run among `units`, or -1: the standard four-level network on H = 64 without self-attention, unmasked, every layer of the run
-// a K-split 256 -> 256 block with compile-time geometry, and at most one workgroup of the launch per compute unit - all resident at once (u->run_capacity: B <= 128 on 256 CUs).
-static int inner_run_first(const mpdx_unet* u, const std::vector<mpdx_unet::Unit>& units, int B) {
-    if (!u->inner_run || u->masked() || u->cfg.self_attention || u->cfg.n_levels != 4 || u->cfg.n_support_points != 64) return -1;
-    if (u->run_capacity <= 0 || inner_run_grid(B) > u->run_capacity || !sw::geo() || sw::debug()) return -1;
+// ---- mpdx_plan's launch schedule
+// First of kInnerRunLayers consecutive single-layer units that the inner-level run (inner_run.hpp) can stand for, or -1: every one a K-split
+// 256 -> 256 Conv1dBlock on 8 positions with compile-time geometry.
+static int inner_run_first(const mpdx_unet* u, const std::vector<mpdx_unet::Unit>& units) {
     auto fits = [&](const mpdx_unet::Unit& un) {
-        if (un.fused >= 0 || un.pair) return false;
+        if (un.kind != mpdx_unet::kLayer) return false;
         const Layer& l = u->layers[un.layer];
         if (l.attn || !(l.mode == CONV_S1 && l.ks == 5 && l.epi == EPI_GN_MISH) || l.Lv_out) return false;
         if (!(l.c1 == 256 && l.c2 == 0 && l.src2 == SRC_NONE && l.cout == 256 && l.L_in == 8 && l.L_out == 8 && l.gs == 32 && l.cin_pad == 256 && l.rs == 264)) return false;
@@ -915,100 +976,42 @@ static int inner_run_first(const mpdx_unet* u, const std::vector<mpdx_unet::Unit
     }
     return -1;
 }
-// The handle's device state of the run, made at the first mpdx_plan call (a handle is created without a device): one occupancy query x the CU count,
-// the cluster counters, the host-mapped status word.
-static int ensure_inner_run_state(mpdx_unet* u) {
-    if (u->run_capacity >= 0) return 0;
-    u->run_capacity = 0;
-    int dev = 0, cus = 0, khz = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipDeviceGetAttribute(&khz, hipDeviceAttributeClockRate, dev) != hipSuccess) {
-        (void)hipGetLastError();
+static int device_cus() {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) (void)hipGetLastError();
+    return cus;
+}
+// What mpdx_plan enqueues per pass at batch B, made once per call (the switches and the device are read here, not per pass): the launch units with the
+// seven run layers as ONE unit where the run is selected, and whether passes can be joined.
+struct PlanSchedule {
+    std::vector<mpdx_unet::Unit> units;
+    bool run = false;    // units holds a kInnerRun unit
+    bool join = false;   // an unguided pass that has a successor ends in fused_join_kernel; the successor starts at its second unit
+    int build(mpdx_unet* u, int B, bool with_run = true) {   // with_run = false: the per-layer units whatever the handle says (mpdx_fused_trace)
+        units = current_units(u, B, nullptr);
+        const int cus = device_cus();
+        // The run: the standard four-level network on H = 64 without self-attention, unmasked, and at most one workgroup of the launch per compute unit -
+        // all resident at once (B <= 128 on 256 CUs).
+        if (with_run && u->inner_run && !u->masked() && !u->cfg.self_attention && u->cfg.n_levels == 4 && u->cfg.n_support_points == 64) {
+            if (int rc = inner_run_create(u->run, cus)) return rc;
+            const int rf = u->run.capacity > 0 && inner_run_grid(B) <= u->run.capacity && sw::geo() && !sw::debug() ? inner_run_first(u, units) : -1;
+            if (rf >= 0) {
+                units[rf] = {mpdx_unet::kInnerRun, -1, units[rf].layer, kInnerRunLayers};
+                units.erase(units.begin() + rf + 1, units.begin() + rf + kInnerRunLayers);
+                run = true;
+            }
+        }
+        // The join: the pass starts with the three-level down program from the network input and ends with the two-level up program that holds the final op
+        // (the standard four-level network on a power-of-two horizon of 64), and one workgroup per CU runs anyway: the joined kernel's 84 KB of LDS admit
+        // one workgroup per CU where the separate programs (59.1 / 63.5 KB) admit two.
+        if (!u->plan_join || u->masked() || units.size() < 2) return 0;
+        const mpdx_unet::Unit &first = units.front(), &last = units.back();
+        if (first.kind != mpdx_unet::kProgram || last.kind != mpdx_unet::kProgram || first.fused == last.fused) return 0;
+        const mpdx_unet::Fused &dn = u->fused[first.fused], &up = u->fused[last.fused];
+        join = dn.program == 5 && dn.in1 == SRC_X && dn.in2 == SRC_NONE && !dn.has_final && up.program == 3 && up.has_final && B <= cus;
         return 0;
     }
-    const int per_cu = inner_run_workgroups_per_cu();
-    if (per_cu <= 0 || cus <= 0) return 0;
-    const int cap = cus;   // one workgroup per compute unit (the occupancy answer says that one fits): the batches the per-layer tiles were measured at
-    const size_t words = (size_t)((cap + 7) / 8 + 8) * kInnerRunCounterStride;
-    HIP_TRY(hipMalloc((void**)&u->run_counters, words * sizeof(unsigned)));
-    HIP_TRY(hipMemset(u->run_counters, 0, words * sizeof(unsigned)));
-    HIP_TRY(hipHostMalloc((void**)&u->run_status, 64, hipHostMallocMapped));
-    *u->run_status = u->status_host;
-    HIP_TRY(hipHostGetDevicePointer((void**)&u->run_status_dev, u->run_status, 0));
-    u->run_budget = 4LL * (khz > 0 ? khz : 2400000);   // 4 ms of shader-clock ticks (s_memtime); a lower actual clock only lengthens it
-    u->run_capacity = cap;
-    return 0;
-}
-static int handle_status_error(const mpdx_unet* u, const char* fn) {
-    const unsigned w = u->status_word();
-    if (!w) return 0;
-    return fail(MPDX_E_DEVICE, "%s: a workgroup of the inner-level run gave up its wait (status 0x%x: layer %u of the run); the outputs of that plan hold NaN. "
-                "mpdx_unet_set_status(u, 0) clears the word", fn, w, w >> 8);
-}
-static int run_inner_run(mpdx_unet* u, const std::vector<mpdx_unet::Unit>& units, int first, const float* packed, const float* row, const float* x,
-                         float* ws, int B, hipStream_t st) {
-    InnerRunArgs ra;
-    memset(&ra, 0, sizeof(ra));
-    for (int k = 0; k < kInnerRunLayers; ++k) {
-        if (int rc = make_conv_args(u, u->layers[units[first + k].layer], packed, row, x, ws, B, 0, ra.layer[k])) return rc;
-        ra.layer[k].n_tiles_n = (B + 3) / 4;
-        ra.layer[k].trace = nullptr;
-    }
-    // Every counter of a launch must hold run_base when it starts.  A launch advances the counters of ITS clusters only, so a batch with more clusters
-    // than the launch before (or a give-up's poison) zeroes them all, stream-ordered, and starts from base 0 again: at most once per plan.
-    const int nc = (B + 3) / 4;
-    if (u->run_rezero || nc > u->run_live) {
-        HIP_TRY(hipMemsetAsync(u->run_counters, 0, (size_t)((u->run_capacity + 7) / 8 + 8) * kInnerRunCounterStride * sizeof(unsigned), st));
-        u->run_base = 0; u->run_rezero = false;
-    }
-    u->run_live = nc;
-    ra.counters = u->run_counters; ra.status = u->run_status_dev; ra.budget = u->run_budget;
-    ra.base = u->run_base;   // every counter holds this when the launch starts; layer i > 0 waits for base + 8 i, the 8 arrivals of each layer before it
-    ra.n_layers = kInnerRunLayers; ra.nc = (B + 3) / 4;
-    u->run_base += 8u * kInnerRunLayers;
-    u->inner_runs++;
-    return launch_inner_run(ra, B, st);
-}
-
-// One pass of mpdx_plan's loop.  skip_down: the pass's first unit - the down program - has already run as the tail of the pass before; tt_next != null:
-// the pass's last unit - the up program - runs joined with the next pass's down program (can_join_passes holds); use_run: the inner-level run replaces
-// its seven units.  None of them: run_unet_and_final.
-static int run_plan_pass(mpdx_unet* u, const float* packed, const float* timetab, int T, const float* x, int t, int B, float* ws, FinalArgs& fa,
-                         hipStream_t st, bool skip_down, const float* tt_next, bool use_run) {
-    if (!skip_down && !tt_next && !use_run) return run_unet_and_final(u, packed, timetab, T, x, t, B, ws, fa, st);
-    if (t < 0 || t >= T) return fail(MPDX_E_INVALID, "timestep %d outside [0,%d)", t, T);
-    const float* row = timetab + (size_t)t * u->tt_row;
-    const auto units = current_units(u, B, nullptr);
-    const int n = (int)units.size();
-    const int rf = use_run ? inner_run_first(u, units, B) : -1;
-    bool final_done = false;
-    for (int i = skip_down ? 1 : 0; i < n - (tt_next ? 1 : 0); ++i) {
-        if (i == rf) {
-            if (int rc = run_inner_run(u, units, rf, packed, row, x, ws, B, st)) return rc;
-            i += kInnerRunLayers - 1;
-            continue;
-        }
-        if (units[i].fused >= 0) final_done |= u->fused[units[i].fused].has_final;
-        if (int rc = run_unit(u, units[i], packed, row, x, ws, B, &fa, st)) return rc;
-    }
-    if (tt_next) return run_fused_join(u, u->fused[units[n - 1].fused], u->fused[units[0].fused], packed, row, tt_next, x, ws, B, &fa, st);
-    if (!final_done) return run_final(u, packed, fa, B, ws, st);
-    return 0;
-}
-// Can mpdx_plan join passes at batch B?  The pass starts with the three-level down program from the network input and ends with the two-level up
-// program that holds the final op (the standard four-level network on a power-of-two horizon of 64), and one workgroup per CU runs anyway: the
-// joined kernel's 84 KB of LDS admit one workgroup per CU where the separate programs (59.1 / 63.5 KB) admit two.
-static bool can_join_passes(const mpdx_unet* u, int B) {
-    if (!u->plan_join || u->masked()) return false;
-    const auto units = current_units(u, B, nullptr);
-    if (units.size() < 2 || units.front().fused < 0 || units.back().fused < 0 || units.front().fused == units.back().fused) return false;
-    const mpdx_unet::Fused& dn = u->fused[units.front().fused];
-    const mpdx_unet::Fused& up = u->fused[units.back().fused];
-    if (dn.program != 5 || dn.in1 != SRC_X || dn.in2 != SRC_NONE || dn.has_final || up.program != 3 || !up.has_final) return false;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-    return B <= cus;
-}
+};
 
 // the trace / ablation entry points exist in a development build only: 0 there, else the error that says how to make one
 int dev_hooks_missing(const char* fn) {
@@ -1097,9 +1100,9 @@ int mpdx_unet_status(const mpdx_unet* u) {
 }
 int mpdx_unet_set_status(mpdx_unet* u, unsigned word) {
     if (!u) return fail(MPDX_E_INVALID, "null argument");
-    if (u->run_status) __atomic_store_n(u->run_status, word, __ATOMIC_RELAXED);
-    u->status_host = word;
-    if (!word && u->run_counters) u->run_rezero = true;   // whatever a give-up left in the counters goes before the next run
+    if (u->run.status) __atomic_store_n(u->run.status, word, __ATOMIC_RELAXED);
+    u->run.status_host = word;
+    if (!word && u->run.counters) u->run.rezero = true;   // whatever a give-up left in the counters goes before the next run
     return 0;
 }
 
@@ -1107,8 +1110,7 @@ void mpdx_unet_destroy(mpdx_unet* u) {
     if (u && u->pack_descs_dev) (void)hipFree(u->pack_descs_dev);
     if (u && u->pack_chunks_dev) (void)hipFree(u->pack_chunks_dev);
     if (u && u->jobs_dev) (void)hipFree(u->jobs_dev);
-    if (u && u->run_counters) (void)hipFree(u->run_counters);
-    if (u && u->run_status) (void)hipHostFree(u->run_status);
+    if (u) inner_run_free(u->run);
     delete u;
 }
 
@@ -1262,6 +1264,12 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
     if (guide)   // ... and the tool-axis members
         if (const char* why = tool_params_problem(*guide)) return fail(MPDX_E_INVALID, "%s", why);
     if (int rc = check_ready(u)) return rc;
+    // An unguided iteration that has a successor runs its up program and the successor's down program as ONE launch (nothing modifies x between the
+    // two); the successor then starts at its second unit.  Whether the successor is guided does not matter.  The seven 256 -> 256 layers of the
+    // innermost level are one persistent launch in guided iterations too: the inner levels do not see the guide.
+    PlanSchedule ps;
+    if (int rc = ps.build(u, B)) return rc;
+    u->inner_runs = u->plan_joined = 0;
     hipStream_t st = (hipStream_t)stream;
     const int H = u->cfg.n_support_points, D = u->cfg.state_dim;
     const size_t n = (size_t)B * H * D;
@@ -1279,23 +1287,12 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
     // x_T with hard conditioning; chain[0]
     hipLaunchKernelGGL(add_noise_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, st, x, (const float*)nullptr,
                        hard_start, hard_goal, 0.f, 0.f, chain, B, H, D);
-    // An unguided iteration that has a successor runs its up program and the successor's down program as ONE launch (nothing modifies x between the
-    // two); the successor then starts at its second unit.  Whether the successor is guided does not matter.
-    const bool join_ok = can_join_passes(u, B);
-    // The seven 256 -> 256 layers of the innermost level as one persistent launch (guided iterations too: the inner levels do not see the guide)
-    u->inner_runs = 0;
-    bool use_run = false;
-    if (u->inner_run && !u->masked() && !u->cfg.self_attention && u->cfg.n_levels == 4 && H == 64) {
-        if (int rc = ensure_inner_run_state(u)) return rc;
-        use_run = inner_run_first(u, current_units(u, B, nullptr), B) >= 0;
-    }
     bool down_done = false;   // this iteration's down program ran as the tail of the iteration before
-    u->plan_joined = 0;
     int k = 0;
     for (int i = T - 1; i >= -n_without_noise; --i, ++k) {
         const int t = i < 0 ? 0 : i;
         const bool guided = guide && i < t_start_guide;  // sample_functions.py:39 compares the un-clamped index
-        const bool join = join_ok && !guided && i > -n_without_noise;
+        const bool join = ps.join && !guided && i > -n_without_noise;
         const float* tt_next = join ? timetab + (size_t)(i - 1 < 0 ? 0 : i - 1) * u->tt_row : nullptr;
         const float* nz = (t == 0 || !noise) ? nullptr : noise + (size_t)k * n;  // noise[t == 0] = 0  (sample_functions.py:52)
         // noise == NULL: the step's draw is generated in place; iteration k uses elements [(k+1) n, (k+2) n) of the stream whose
@@ -1316,7 +1313,8 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
         } else {
             fa.mode = 2; fa.absmax = fl;  // posterior mean + its max|.| per context
         }
-        if (int rc = run_plan_pass(u, packed, timetab, T, x, t, B, ws, fa, st, down_done, tt_next, use_run)) return rc;
+        if (int rc = walk_pass(u, ps.units, packed, timetab + (size_t)t * u->tt_row, padded_input(u, x, ws, B, st), ws, B, fa, st, no_hook, down_done, tt_next))
+            return rc;
         down_done = join;
         u->plan_joined += join ? 1 : 0;
         if (guided) {
@@ -1338,7 +1336,7 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
         }
     }
     HIP_TRY(hipGetLastError());
-    return use_run ? handle_status_error(u, "mpdx_plan") : 0;   // (what has already given up by now; the rest shows at the next call or in mpdx_unet_status)
+    return ps.run ? handle_status_error(u, "mpdx_plan") : 0;   // (what has already given up by now; the rest shows at the next call or in mpdx_unet_status)
 }
 
 int mpdx_randn(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream) {

@@ -1,5 +1,5 @@
 // unet_measure.hpp - the measurement and trace entry points of the U-Net pass (bench.py's roofline leg, tools/*_trace.py, tools/time_layer.py) and the
-// launch-unit queries, over the launch functions of mpdx.hip: it includes this header behind run_unet_and_final, and it alone.  No device code.
+// launch-unit queries, over the launch functions of mpdx.hip: it includes this header behind walk_pass and PlanSchedule, and it alone.  No device code.
 #pragma once
 #include "host.hpp"
 
@@ -86,7 +86,7 @@ int mpdx_unet_profile(mpdx_unet* u, const float* packed, const float* timetab, i
     fused_names.resize(u->fused.size());
     for (int i = 0; i < nl; ++i) {
         const char* name = "final_conv.1+ddpm_step";
-        if (i < nu && p.units[i].fused >= 0) name = (fused_names[p.units[i].fused] = fused_unit_name(u, u->fused[p.units[i].fused])).c_str();
+        if (i < nu && p.units[i].kind == mpdx_unet::kProgram) name = (fused_names[p.units[i].fused] = fused_unit_name(u, u->fused[p.units[i].fused])).c_str();
         else if (i < nu) name = u->layers[p.units[i].layer].name.c_str();
         if (names_out) names_out[i] = name;
         if (flops_out) flops_out[i] = i < nu ? unit_flops(u, p.units[i], B) : 0.0;
@@ -128,8 +128,11 @@ int mpdx_fused_trace(mpdx_unet* u, const float* packed, const float* timetab, co
                      long long* stamps_out, int cap, int* n_out, int* nops_out) {
     if (int rc = dev_hooks_missing(__func__)) return rc;
     if (!u || seg < 0 || seg > (int)u->fused.size()) return fail(MPDX_E_INVALID, "bad segment");
+    if (B <= 0) return fail(MPDX_E_INVALID, "B must be positive");
     const bool joined = seg == (int)u->fused.size();
-    if (joined && !can_join_passes(u, B)) return fail(MPDX_E_INVALID, "bad segment (this network / batch has no joined launch)");
+    PlanSchedule ps;   // (without the inner run: the per-layer units of the single-pass entry points)
+    if (int rc = ps.build(u, B, false)) return rc;
+    if (joined && !ps.join) return fail(MPDX_E_INVALID, "bad segment (this network / batch has no joined launch)");
     if (int rc = check_ready(u)) return rc;
     hipStream_t st = (hipStream_t)stream;
     DevStamps dev;
@@ -140,24 +143,17 @@ int mpdx_fused_trace(mpdx_unet* u, const float* packed, const float* timetab, co
     // predecessors, cache and clock state as in production, no host synchronisation in between
     ResetOnExit<long long*> untrace{g_fused_trace, nullptr};
     ResetOnExit<int> unselect{g_fused_trace_seg, -1};
-    for (int pass = 0; pass < 3; ++pass) {
-        if (pass == 2 && joined) {   // the pass as mpdx_plan runs it when the next one follows unguided: its last unit is the joined launch
-            const auto units = current_units(u, B, nullptr);
-            const int nu = (int)units.size();
-            for (int i = 0; i + 1 < nu; ++i)
-                if (int rc = run_unit(u, units[i], packed, timetab, x, ws, B, &fa, st)) return rc;
-            if (int rc = run_fused_join(u, u->fused[units[nu - 1].fused], u->fused[units[0].fused], packed, timetab, timetab, x, ws, B, &fa, st, dev.p)) return rc;
-            break;
-        }
-        if (pass == 2) { g_fused_trace = dev.p; g_fused_trace_seg = seg; }
-        if (int rc = run_unet_and_final(u, packed, timetab, 1 << 30, x, 0, B, ws, fa, st)) return rc;
+    for (int pass = 0; pass < 3; ++pass) {   // joined: the third pass as mpdx_plan runs it when the next one follows unguided - its last unit is the joined launch
+        if (pass == 2 && !joined) { g_fused_trace = dev.p; g_fused_trace_seg = seg; }
+        const float* next_row = pass == 2 && joined ? timetab : nullptr;
+        if (int rc = walk_pass(u, ps.units, packed, timetab, padded_input(u, x, ws, B, st), ws, B, fa, st, no_hook, false, next_row, dev.p)) return rc;
     }
     HIP_TRY(hipStreamSynchronize(st));
     const int n = std::min(cap, 1024);   // 8 waves x 128 slots
     HIP_TRY(hipMemcpy(stamps_out, dev.p, n * sizeof(long long), hipMemcpyDeviceToHost));
     if (n_out) *n_out = n;
     if (nops_out) {
-        if (joined) { const auto units = current_units(u, B, nullptr); *nops_out = u->fused[units.back().fused].tmpl.nops + u->fused[units.front().fused].tmpl.nops; }
+        if (joined) *nops_out = u->fused[ps.units.back().fused].tmpl.nops + u->fused[ps.units.front().fused].tmpl.nops;
         else *nops_out = u->fused[seg].tmpl.nops;
     }
     return 0;
@@ -221,7 +217,7 @@ int mpdx_unet_time_without(mpdx_unet* u, const float* packed, const float* timet
 /* layer index of launch unit i (-1 for a fused unit / the final kernel): lets bench.py query the tile of a unit */
 int mpdx_unet_unit_layer(const mpdx_unet* u, int B, int i) {
     mpdx_unet::Unit un;
-    return (unit_at(u, B, i, un) && un.fused < 0) ? un.layer : -1;
+    return (unit_at(u, B, i, un) && un.kind != mpdx_unet::kProgram) ? un.layer : -1;
 }
 
 /* which kernel runs fused segment `seg`: 0..5 = a static program (fused_program_kernel<FusedSeq...>; 0, 3, 5 read their LDS geometry from the
@@ -240,7 +236,7 @@ double mpdx_unet_unit_bytes(const mpdx_unet* u, int B, int i) {
 /* 1 when launch unit i is a paired launch (blocks[0] + the block's residual 1x1 conv in one conv_pair_kernel) */
 int mpdx_unet_unit_is_pair(const mpdx_unet* u, int B, int i) {
     mpdx_unet::Unit un;
-    return (unit_at(u, B, i, un) && un.fused < 0 && un.pair) ? 1 : 0;
+    return (unit_at(u, B, i, un) && un.kind == mpdx_unet::kPair) ? 1 : 0;
 }
 
 int mpdx_bench_layer(mpdx_unet* u, const float* packed, const float* timetab, const float* x, int layer, int B, float* ws,
