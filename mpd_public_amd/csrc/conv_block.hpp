@@ -153,7 +153,15 @@ __device__ __forceinline__ float mish(float x) {
 
 // The same without the select (fused programs, round 4: one v_min instead of v_cmp + v_cndmask per element): the exponent is clamped at
 // 2^30, where n / (n + 2) is 1 to the last bit (from x = 8.7 on), so x > 20.8 gives x * (n * rcp(n)) = x * (1 +- 1 ulp) instead of
-// exactly x - and never overflows.  Bit-identical to mish() for x <= 20; GroupNorm outputs (|v - mean| * rstd <= 16) do not reach 20.
+// exactly x - and never overflows.  Bit-identical to mish() for x <= 20.
+// Mish arguments DO pass 20.8 and 44: the argument is gamma * (v - mean) * rstd + beta, and only the normalised value is bounded (by 16, the square root
+// of the largest region); a checkpoint's gamma and beta multiply and shift it.  With gamma in 2 ... 10 and beta in +- 20 (tests/regime_ref.py, `bigaffine`)
+// 5 % of the arguments lie above 20.8, 6 % below -20 and some above 44.4.  What the three forms return there:
+//   torch (softplus threshold 20): x tanh(x), which is x to the last bit from x = 20 on;
+//   mish():       x > 20: exactly x (the select; from 44.4 on n is inf and r is NaN, never taken);
+//   mish_nosel(): x > 20.8: x (1 +- 1 ulp), finite for every finite x - within 2^-23 |x| of the others, the floor the regime tests hold it to;
+//   x < -20, all three: x e^x (1 + O(e^x)), |y| < 5e-8, going to -0 where e^x leaves the float32 range.
+// Every forward epilogue takes mish_nosel (fused programs, conv_block 128 / 256 / _GEN / run, conv_ws, conv_wsn, conv_wsp): tests/test_gpu_unet_regimes.py.
 __device__ __forceinline__ float mish_nosel(float x) {
     const float e = __builtin_amdgcn_exp2f(fminf(x * 1.4426950408889634f, 30.0f));
     const float n = e * (e + 2.0f);
