@@ -388,6 +388,9 @@ int mpdx_guide_time(const mpdx_guide_params* gp, float* x, float* grad_out, cons
  * (the production kernels carry no hooks); otherwise they return MPDX_E_STATE. */
 int mpdx_guide_trace(const mpdx_guide_params* gp, float* x, const uint32_t* absmax_in, int B, int H, int D, void* stream,
                      long long* stamps128);
+/* Which kernel variant mpdx_guide_step takes for this block at batch B: 1 = the Panda's dense variant (large batches, or MPDX_GUIDE_DENSE=1, where
+ * its LDS layout fits 80 KB), 0 = every other kernel (the Panda's table variant, point mass, chain); negative: the block is refused.  No launch. */
+int mpdx_guide_variant(const mpdx_guide_params* gp, int B, int H, int D);
 /* absmax_out[ctx] <- atomicMax over the context's trajectories (caller zeroes absmax_out first) */
 int mpdx_absmax(const float* x, uint32_t* absmax_out, int n_per_ctx, int B, int H, int D, void* stream);
 

@@ -281,7 +281,7 @@ __global__ __launch_bounds__(512, 2) void guide_step_chain_kernel(const ChainGui
     __syncthreads();
     G_STAMP();  // 5 gathered + clipped
     if (wv >= nsw) return;
-    sum_fields_and_apply<QD>(a, n_slots, b, ctx, lane, wv, hs_, H, live, sx, snz_x, sC, snz + (int)(ne0 & 3ull), shc);
+    sum_fields_and_apply<QD>(a, n_slots, b, ctx, lane, wv, hs_, H, live, snz_x, sC, snz + (int)(ne0 & 3ull), shc);
 }
 
 // The tool-axis figures of mpdx_traj_tool_metrics: one wave per trajectory, lane = checked point (the pattern of traj_metrics_chain_kernel).  The rotation

@@ -451,37 +451,45 @@ __device__ __forceinline__ void clip_waypoint_grad(const dev_guide_params& gp, f
 
 // GP prior (constant-velocity, GPMP2: 3-point stencil over the horizon) added to the gathered collision gradient, then
 //     x = x + (-grad);  [+ the step's noise term on the last guide iteration];  hard conditioning;  max|x| for the next
-// range test.  One wave, lane = support point.  tr: optional two cycle stamps (dev tool).
+// range test.  One wave, lane = support point.  sxn: the normalised state [H][D] in LDS, as loaded.  tr: optional two cycle stamps (dev tool).
 // snoise (or null): the step's noise of THIS trajectory, drawn by idle waves into LDS (guide_draw_noise: element k of the trajectory at
 // snoise[k + (e0 & 3)]) - the same Philox values philox_normal_at gives, one counter per FOUR elements instead of one per element.
 template <int QD>
 __device__ __forceinline__ void guide_gp_apply(const GuideArgs& a, int b, int ctx, int lane, int h, int H, bool live, const float (&xn)[2 * QD],
-                                               const float (&xu)[2 * QD], const float* sx, float (&total)[2 * QD], size_t base, long long* tr,
+                                               const float* sxn, float (&total)[2 * QD], size_t base, long long* tr,
                                                const float* snoise = nullptr, const float* shc = nullptr) {
     constexpr int D = 2 * QD;
     const bool interior = live && h > 0 && h < H - 1;
     if (a.gp.use_gp) {
-        const float dt = a.gp.dt, s2 = (a.gp.gp_half_factor ? 0.5f : 1.0f) / (a.gp.sigma_gp * a.gp.sigma_gp);
-        const float c_qq = 24.0f / (dt * dt * dt), c_qv = 12.0f / (dt * dt), c_vv = 8.0f / dt;
+        // In float64 from the float32 normalised state: the residuals e_q = q' - q - dt v are differences of O(1) values that 24 / dt^3 (1e4 ... 1e5)
+        // multiplies, and the terms of the two segments cancel again - with the float32 unnormalised state the un-clipped gradient was off by
+        // 1e-2 ... 3e-1 absolute per element (profiles/guide_terms.md).  A few dozen float64 operations per lane of the support wave(s).
+        const double dt = (double)a.gp.dt, s2 = (a.gp.gp_half_factor ? 0.5 : 1.0) / ((double)a.gp.sigma_gp * (double)a.gp.sigma_gp);
+        const double c_qq = 24.0 / (dt * dt * dt), c_qv = 12.0 / (dt * dt), c_vv = 8.0 / dt;
+        const bool clipall = __uint_as_float(a.amax_in[ctx]) > 1.0001f;
         // a_h = d c_h / d e_q,  b_h = d c_h / d e_v  for the segment (h, h+1); (ap, bp) the same for the segment (h-1, h).  Both are
-        // computed from the LDS-staged state (the neighbour's registers hold exactly these floats): no cross-lane traffic, so the
-        // support index may cross a wave boundary (H up to 128: two waves of supports)
+        // computed from the LDS-staged normalised state: no cross-lane traffic, so the support index may cross a wave boundary
+        // (H up to 128: two waves of supports)
+        const int hc = live ? h : 0, hp = hc > 0 ? hc - 1 : 0, hn = hc < H - 1 ? hc + 1 : hc;
         float g[D];
 #pragma unroll
         for (int j = 0; j < QD; ++j) {
-            float eq = 0.f, ev = 0.f, eqp = 0.f, evp = 0.f;
+            const auto un = [&](int hh, int d) { return unnormalise_one_f64(a.gp.identity_normalizer, sxn[hh * D + d], a.gp.mins[d], a.gp.maxs[d], clipall); };
+            const double q0 = un(hc, j), v0 = un(hc, QD + j);
+            double eq = 0., ev = 0., eqp = 0., evp = 0.;
             if (live && h < H - 1) {
-                eq = sx[(h + 1) * D + j] - xu[j] - dt * xu[QD + j];
-                ev = sx[(h + 1) * D + QD + j] - xu[QD + j];
+                eq = un(hn, j) - q0 - dt * v0;
+                ev = un(hn, QD + j) - v0;
             }
             if (live && h > 0) {
-                eqp = sx[h * D + j] - sx[(h - 1) * D + j] - dt * sx[(h - 1) * D + QD + j];
-                evp = sx[h * D + QD + j] - sx[(h - 1) * D + QD + j];
+                const double qm = un(hp, j), vm = un(hp, QD + j);
+                eqp = q0 - qm - dt * vm;
+                evp = v0 - vm;
             }
-            const float av = (c_qq * eq - c_qv * ev) * s2, bv = (-c_qv * eq + c_vv * ev) * s2;
-            const float ap = (c_qq * eqp - c_qv * evp) * s2, bp = (-c_qv * eqp + c_vv * evp) * s2;
-            g[j] = ap - av;
-            g[QD + j] = bp - bv - dt * av;
+            const double av = (c_qq * eq - c_qv * ev) * s2, bv = (-c_qv * eq + c_vv * ev) * s2;
+            const double ap = (c_qq * eqp - c_qv * evp) * s2, bp = (-c_qv * eqp + c_vv * evp) * s2;
+            g[j] = (float)(ap - av);
+            g[QD + j] = (float)(bp - bv - dt * av);
         }
         clip_waypoint_grad<D>(a.gp, g, 0);
         if (interior) {
@@ -576,19 +584,18 @@ __device__ __forceinline__ void gather_clip_weight(const dev_guide_params& gp, i
 }
 
 // Phase 4 of the chain kernel (the support wave(s); the Panda kernel keeps its own copy, see there): sum over the n_slots terms of sC (the fields,
-// then the tool-axis term when it is on), GP prior, apply.  sx = the unnormalised state the prologue staged,
+// then the tool-axis term when it is on), GP prior, apply.
 // sxn = the normalised state as loaded (nothing has written x since); snoise, shc: see guide_gp_apply.
 template <int QD>
-__device__ __forceinline__ void sum_fields_and_apply(const GuideArgs& a, int n_slots, int b, int ctx, int lane, int wv, int hs_, int H, bool live, const float* sx,
+__device__ __forceinline__ void sum_fields_and_apply(const GuideArgs& a, int n_slots, int b, int ctx, int lane, int wv, int hs_, int H, bool live,
                                                      const float* sxn, const float* sC, const float* snoise, const float* shc) {
     constexpr int D = 2 * QD;
     __builtin_assume(shc != nullptr);   // (both callers stage the hard conditions: guide_gp_apply's global-memory fallback, 2 D loads on the kernel's tail, drops out)
-    float total[D], xu[D], xn[D];
+    float total[D], xn[D];
     const size_t base = ((size_t)b * H + (live ? hs_ : 0)) * D;
 #pragma unroll
     for (int d = 0; d < D; ++d) {
         total[d] = 0.f;
-        xu[d] = live ? sx[hs_ * D + d] : 0.f;
         xn[d] = live ? sxn[hs_ * D + d] : 0.f;
     }
     if (live) {
@@ -597,7 +604,7 @@ __device__ __forceinline__ void sum_fields_and_apply(const GuideArgs& a, int n_s
             for (int j = 0; j < QD; ++j) total[j] += sC[(f * H + hs_) * QD + j];
         }
     }
-    guide_gp_apply<QD>(a, b, ctx, lane, hs_, H, live, xn, xu, sx, total, base, (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 6 : nullptr, snoise, shc);
+    guide_gp_apply<QD>(a, b, ctx, lane, hs_, H, live, xn, sxn, total, base, (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 6 : nullptr, snoise, shc);
 }
 
 // Point-mass robots (QD = DIM = 2 or 3).  WPT = waves per trajectory.  The collision part (SDF force per interpolated point
@@ -624,9 +631,10 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
     const bool live = hs_ < H;
     int tr_i = 0;
     G_STAMP();  // 0 entry
-    // LDS carve: unnormalised state [H][D] | point forces A,B [MAXF][N][QD] each | primitive table
+    // LDS carve: unnormalised state [H][D] | point forces A,B [MAXF][N][QD] each | primitive table | normalised state [H][D] (the GP prior's)
     const GuideLds L = guide_lds_layout(kGuidePointMass, H, D, N, gp.n_prim_floats);
     float* sx = sm + L.sx;
+    float* sxn = sm + L.snz_x;
     float* sA = sm + L.sA;
     float* sB = sm + L.sB;
     float* sprim = sm + L.sprim;
@@ -641,7 +649,7 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
     for (int d = 0; d < D; ++d) {
         xn[d] = live ? a.x[base + d] : 0.f;
         xu[d] = unnormalise_one(gp.identity_normalizer, xn[d], gp.mins[d], gp.maxs[d], clipall);
-        if (live && wv < nsw) sx[hs_ * D + d] = xu[d];
+        if (live && wv < nsw) { sx[hs_ * D + d] = xu[d]; sxn[hs_ * D + d] = xn[d]; }
     }
     __syncthreads();
     G_STAMP();  // 1 state unnormalised + staged
@@ -747,7 +755,7 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
         }
     }
     G_STAMP();  // 4 gathered + clipped
-    guide_gp_apply<QD>(a, b, ctx, lane, hs_, H, live, xn, xu, sx, total, base, (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 5 : nullptr);
+    guide_gp_apply<QD>(a, b, ctx, lane, hs_, H, live, xn, sxn, total, base, (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 5 : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1024,12 +1032,11 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(co
     if (wv >= nsw) return;
 
     // ---- phase 4 (the support wave(s)): sum over fields, GP prior, apply
-    float total[D], xu[D], xn[D];
+    float total[D], xn[D];
     const size_t base = ((size_t)b * H + (live ? hs_ : 0)) * D;
 #pragma unroll
     for (int d = 0; d < D; ++d) {
         total[d] = 0.f;
-        xu[d] = live ? sx[hs_ * D + d] : 0.f;        // = the unnormalised state the prologue staged
         xn[d] = live ? snz_x[hs_ * D + d] : 0.f;     // = the normalised state as loaded (nothing has written x since)
     }
     if (live) {
@@ -1038,7 +1045,7 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(co
             for (int j = 0; j < QD; ++j) total[j] += sC[(f * H + hs_) * QD + j];
         }
     }
-    guide_gp_apply<QD>(a, b, ctx, lane, hs_, H, live, xn, xu, sx, total, base, (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 6 : nullptr,
+    guide_gp_apply<QD>(a, b, ctx, lane, hs_, H, live, xn, snz_x, total, base, (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 6 : nullptr,
                        snz + (int)(ne0 & 3ull), shc);
 }
 

@@ -78,6 +78,14 @@ __device__ __forceinline__ float unnormalise_one(int identity_normalizer, float 
     return identity_normalizer == 1 ? xn : identity_normalizer == 2 ? __fadd_rn(__fmul_rn(xn, hi), lo) : __fadd_rn(__fmul_rn(u01, __fsub_rn(hi, lo)), lo);
 }
 
+// The same element in float64 from the float32 normalised value (the GP prior: guide_gp_apply).  The limits stay float32 and so does their difference:
+// that is what a float64 evaluation of normalization.py gives, whose mins / maxs are float32 tensors.
+__device__ __forceinline__ double unnormalise_one_f64(int identity_normalizer, float xn, float lo, float hi, bool clipall) {
+    const float c = clipall ? fminf(fmaxf(xn, -1.f), 1.f) : xn;
+    const double u01 = ((double)c + 1.0) * 0.5;
+    return identity_normalizer == 1 ? (double)xn : identity_normalizer == 2 ? (double)xn * (double)hi + (double)lo : u01 * (double)__fsub_rn(hi, lo) + (double)lo;
+}
+
 // ---- this trajectory's hard conditions into shc: [start | goal] x D (apply mode only); their loads fly with the state's
 __device__ __forceinline__ void stage_hard_conds(const float* __restrict__ hs, const float* __restrict__ hg, bool apply, int b, int D, float* __restrict__ shc) {
     if (apply && (int)threadIdx.x < 2 * D) {
@@ -126,7 +134,7 @@ struct GuideLds {
     int sW;           // chain with the tool-axis term: [N][3] the tool axis in the world, the part of a point's FK record the term adds (odd stride)
     int sG;           // Panda: [MAXF][parts][N][QD], chain: [MAXF (+ 1 with the tool term)][N][QD]  joint gradients per point
     int sC;           // [MAXF (+ 1: chain with the tool term)][H][QD] clipped, weighted per-field support-point gradients
-    int snz, snz_x;   // Panda, chain: 16-byte aligned [H * D + pad] the step's noise, drawn in whole groups of four | [H * D] the normalised state
+    int snz, snz_x;   // Panda, chain: 16-byte aligned [H * D + pad] the step's noise, drawn in whole groups of four | all: [H * D] the normalised state
     int sprim, shc;   // the primitive table | Panda, chain: [2][D] hard conditions
     size_t total;
 };
@@ -143,7 +151,8 @@ __host__ __device__ inline GuideLds guide_lds_layout(GuideKind kind, int H, int 
         l.sB = l.sA + MAXF * N * QD;
         l.sC = l.sB;
         l.sprim = l.sB + MAXF * N * QD;
-        l.total = (size_t)l.sprim + (size_t)n_prim;
+        l.snz_x = l.sprim + round_up4(n_prim);
+        l.total = (size_t)l.snz_x + (size_t)H * D;
         return l;
     }
     const bool chain = kind == kGuideChain;

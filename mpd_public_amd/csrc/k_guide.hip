@@ -108,6 +108,19 @@ int guide_block_problem(const mpdx_guide_params* gp, int D, ChainInfo* chain_inf
     return 0;
 }
 
+// What a workgroup of a guide launch stages (the LDS carve is sized by it), and whether the launch takes the Panda's dense variant (no FK table, 128
+// VGPRs: two workgroups per CU): at large batch, or as MPDX_GUIDE_DENSE=0/1 forces it off / on - and only where its layout fits 80 KB.
+static mpdx_guide_params guide_params_staged(const mpdx_guide_params& gp, const ChainInfo& chain_info) {
+    mpdx_guide_params staged = gp;
+    staged.n_prim_floats = staged_prim_floats(gp);
+    if (gp.robot == MPDX_ROBOT_CHAIN) staged.n_chain_floats = chain_info.n_floats;
+    return staged;
+}
+static bool guide_takes_dense(const mpdx_guide_params& staged, int B, int H, int D) {
+    const int dense_env = sw::guide_dense();
+    return staged.robot == MPDX_ROBOT_PANDA && (dense_env >= 0 ? dense_env != 0 : B >= 512) && guide_lds_bytes(staged, H, D, true) <= 80 * 1024;
+}
+
 int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const float* hs, const float* hg,
                         const uint32_t* amax_in, uint32_t* amax_out, int n_per_ctx, int B, int H, int D, hipStream_t st,
                         const float* noise, float noise_scale, float noise_extra, float* chain, float guide_scale, const NoiseRng* rng) {
@@ -134,12 +147,8 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
     // several scenes select the MULTI_SCENE instantiations (scene_table.hpp), for the same reason; a workgroup stages one scene block + the shared tail
     const bool multi = has_scenes(*gp);
     a.scene = dev_scenes_of(*gp);
-    mpdx_guide_params staged = *gp;   // (the LDS carve is sized by what a workgroup stages)
-    staged.n_prim_floats = staged_prim_floats(*gp);
-    if (gp->robot == MPDX_ROBOT_CHAIN) staged.n_chain_floats = chain_info.n_floats;
-    // Panda at large batch: the dense variant (no FK table, 128 VGPRs: two workgroups per CU); MPDX_GUIDE_DENSE=0/1 forces it off / on
-    const int dense_env = sw::guide_dense();
-    const bool dense = gp->robot == MPDX_ROBOT_PANDA && (dense_env >= 0 ? dense_env != 0 : B >= 512) && guide_lds_bytes(staged, H, D, true) <= 80 * 1024;
+    const mpdx_guide_params staged = guide_params_staged(*gp, chain_info);
+    const bool dense = guide_takes_dense(staged, B, H, D);
     const size_t lds = guide_lds_bytes(staged, H, D, dense);
     if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "guide needs %zu B of LDS (n_interp %d too large)", lds, gp->n_interp);
     if (gp->robot == MPDX_ROBOT_CHAIN) return launch_chain_guide(a, dev_tool_of(*gp), gp->chain, chain_info, multi, lds, B, st);   // (q_dim == n_joints, ws_dim == 3: checked above)
@@ -307,6 +316,13 @@ int mpdx_sdf_grid_bake(const mpdx_guide_params* gp, int field, float* sdf_out, f
     else hipLaunchKernelGGL(sdf_grid_bake_kernel<3>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int mpdx_guide_variant(const mpdx_guide_params* gp, int B, int H, int D) {
+    if (!gp) return fail(MPDX_E_INVALID, "null argument");
+    ChainInfo chain_info;
+    if (int rc = guide_block_problem(gp, D, &chain_info)) return rc;
+    return guide_takes_dense(guide_params_staged(*gp, chain_info), B, H, D) ? 1 : 0;
 }
 
 int mpdx_absmax(const float* x, uint32_t* absmax_out, int n_per_ctx, int B, int H, int D, void* stream) {

@@ -15,12 +15,14 @@ B_CASE = 4
 ETA_CEIL, ETA_FACTOR = 2e-6, 32.0      # eta_gpu <= 32 eta_ref32 and never above 2e-6 (a factor 4.5 under the smallest defect measured: 9.1e-6)
 
 PM, PANDA = ("EnvDense2D", "RobotPointMass"), ("EnvSpheres3D", "RobotPanda")
+PM3 = ("EnvSpheres3D", "RobotPointMass3D")     # the 3-D point mass (q_dim 3 / ws_dim 3 instantiation of the step kernel)
 # (env, robot, H, n_interp [None: interpolation off], lambda).  Level sizes of the solver's tree: n = H - 2, halved until 1.  The two
 # lambda = 1e-6 repeats: point mass with uneven segments and odd levels (46, 23, 11, 5, 2, 1), Panda with the all-even tree (16, 8, 4, 2, 1).
 STEP_CASES = ([PM + (H, N, 1e-2) for H, N in ((4, 8), (5, 10), (6, 12), (10, 20), (18, 36), (24, 128), (34, 68), (40, 80), (48, 128), (96, 128),
                                               (128, 128), (128, 256), (24, None))]
             + [PANDA + (H, N, 1e-2) for H, N in ((4, 8), (5, 10), (6, 12), (10, 20), (18, 36), (24, 48), (34, 68), (40, 128), (48, 96))]
-            + [PM + (48, 128, 1e-6), PANDA + (18, 36, 1e-6)])
+            + [PM + (48, 128, 1e-6), PANDA + (18, 36, 1e-6)]
+            + [PM3 + (H, N, 1e-2) for H, N in ((5, 10), (24, 48))])
 
 
 def level_sizes(H):
@@ -34,7 +36,7 @@ def level_sizes(H):
 def linearisation_parts(robot_id, H, N):
     """the thread mapping gpmp_lm_kernel's linearisation takes (csrc/planner.hpp): four threads per point when 4 N fit the 512 threads and
     the two extra term arrays fit the system's storage, else two."""
-    qd = 7 if robot_id == "RobotPanda" else 2
+    qd = {"RobotPanda": 7, "RobotPointMass3D": 3}.get(robot_id, 2)
     msz, dd = qd * (qd + 1) // 2 + qd + 1, 4 * qd * qd
     return 4 if (4 * N <= 512 and 2 * N * msz <= 2 * (H - 2) * dd) else 2
 

@@ -1,0 +1,434 @@
+"""Reference side of the per-term guide tests (tests/test_guide_ref_cpu.py, tests/test_gpu_guide_terms.py, tests/test_gpu_guide.py): which waypoints
+of a comparison with the fp64 oracle are decidable, which decisions of the collision terms a set of trajectories reaches, the yardstick applied to
+every decidable waypoint, and the coverage environments / trajectories that reach every decision.  Reference only: nothing here touches the GPU.
+
+Ambiguity.  The guide increment is a discontinuous function of the trajectory: a hinge switches on at zero slack, the arg-min primitive changes at
+a tie, the interior gradient of a box changes axis where its two largest d_j tie and sign at the centre plane of that axis, and the gradient of a
+sphere's distance has no direction at the centre.  fp32 places a point to about 1e-7; an interpolated point whose fp64 distance to such a tie is at
+most DELTA = 1e-5 (the band the metrics flags and the grid-field test use) may take the other branch in any fp32 evaluation, and so may every
+support waypoint it contributes to.  Those support waypoints are AMBIGUOUS; they are decided from the fp64 reference alone, their share is capped
+by the tests, and every other waypoint must agree under the yardstick of DESIGN.md section 6 - none left out.
+"""
+import copy
+import functools
+
+import numpy as np
+import torch
+
+from mpd_public_amd import synthetic as syn
+from mpd_public_amd.planning import Env, ObjectSet, PlanningTask
+
+from helpers import oracle_guide
+
+DELTA = 1e-5
+CAP = {"RobotPointMass": 0.01, "RobotPanda": 0.02}     # largest share of ambiguous support waypoints a comparison may have (a condition of the tests)
+RTOL, ATOL = 1e-3, 2e-6                                  # the yardstick: 1e-3 relative, 2e-6 absolute at w_coll = 1e-2
+
+
+def yardstick_atol(w_coll):
+    return ATOL * max(w_coll, 1e-2) / 1e-2
+
+
+def collision_terms(comp):
+    from oracle import costs as oc
+    return [(i, c) for i, c in enumerate(comp.cost_l) if isinstance(c, oc.CostCollision)]
+
+
+# ------------------------------------------------------------------------------------------------------------ the decisions of one term
+def _objects(term, pts):
+    """pts [..., K, dim] -> (d [..., K, P] signed distance to every primitive (spheres, then boxes, as ObjectField.sdf), margin [K], ns, field)"""
+    from oracle import costs as oc
+    f = term.field
+    parts, ns = [], int(f.sphere_radii.numel())
+    if ns:
+        parts.append(oc.sdf_spheres(pts, f.sphere_centers.to(pts.dtype), f.sphere_radii.to(pts.dtype)))
+    if f.box_centers.numel():
+        parts.append(oc.sdf_boxes(pts, f.box_centers.to(pts.dtype), f.box_half.to(pts.dtype)))
+    return torch.cat(parts, -1), term.robot.radii.to(pts.dtype) + term.cutoff, ns, f
+
+
+def _box_axes(f, pts, bi):
+    """of the boxes bi [..., K] (index into the field's boxes): d_j = |p - c| - h [..., K, dim] and |p - c| [..., K, dim]"""
+    c, h = f.box_centers.to(pts.dtype)[bi], f.box_half.to(pts.dtype)[bi]
+    off = (pts - c).abs()
+    return off - h, off
+
+
+def _workspace_slack(term, pts):
+    """[..., K, 2 dim]: margin - distance to the face, lower faces first (the order of CostCollision.factors)"""
+    f = term.field
+    m = (term.robot.radii.to(pts.dtype) + term.cutoff).unsqueeze(-1)
+    return torch.cat([m - (pts - f.ws_min.to(pts.dtype)), m - (f.ws_max.to(pts.dtype) - pts)], -1)
+
+
+def _self_slack(term, pts):
+    f, r = term.field, term.robot.radii.to(pts.dtype)
+    a, b = pts[..., f.pairs[:, 0], :], pts[..., f.pairs[:, 1], :]
+    return r[f.pairs[:, 0]] + r[f.pairs[:, 1]] - torch.linalg.norm(a - b, dim=-1)
+
+
+def decision_distance(comp, xi, band=DELTA):
+    """[B, N]: per interpolated point of the fp64 UNNORMALISED trajectories xi [B, N, D], the smallest distance to a tie over every decision of every
+    collision term of the oracle composite `comp` - the discontinuities of the formulas in oracle/costs.py:
+      hinge slack     |margin - sdf| per link sphere (objects field), per sphere and face (workspace), per pair (self): relu switches on at 0
+      arg-min gap     second-best minus best primitive sdf, where the hinge is active or within `band` of it: min() hands the gradient to another primitive
+      box interior    of the deciding box, where the point is inside it (or within `band` of its surface): the gap between its two largest d_j (amax
+                      hands the gradient to another axis), and the distance to the centre plane of the deciding axis (|p - c| changes sign there)
+      sphere centre   of the deciding sphere: |p - c| (the gradient of the norm has no limit at 0)
+    A decision that cannot matter (hinge off and outside the band) does not count."""
+    xi = xi.to(torch.float64)
+    inf = torch.tensor(float("inf"), dtype=torch.float64)
+    dist = torch.full(xi.shape[:2], float("inf"), dtype=torch.float64)
+    for _, term in collision_terms(comp):
+        rob = term.robot
+        pts = rob.link_points(xi[..., : rob.q_dim])
+        kind = term.field.kind
+        if kind == "objects":
+            d, margin, ns, f = _objects(term, pts)
+            k = min(2, d.shape[-1])
+            two, idx = d.topk(k, dim=-1, largest=False)
+            slack = margin - two[..., 0]
+            dd = slack.abs()
+            near = slack > -band
+            if k == 2:
+                dd = torch.minimum(dd, torch.where(near, two[..., 1] - two[..., 0], inf))
+            best = idx[..., 0]
+            if ns:
+                is_s = near & (best < ns)
+                c = f.sphere_centers.to(torch.float64)[best.clamp(max=ns - 1)]
+                dd = torch.minimum(dd, torch.where(is_s, torch.linalg.norm(pts - c, dim=-1), inf))
+            if f.box_centers.numel():
+                is_b = near & (best >= ns)
+                dj, off = _box_axes(f, pts, (best - ns).clamp(min=0))
+                kk = min(2, dj.shape[-1])
+                top, jm = dj.topk(kk, dim=-1)
+                inside = is_b & (top[..., 0] < band)
+                dd = torch.minimum(dd, torch.where(inside, top[..., 0] - top[..., 1], inf))
+                dd = torch.minimum(dd, torch.where(inside, off.gather(-1, jm[..., :1]).squeeze(-1), inf))
+            dist = torch.minimum(dist, dd.amin(-1))
+        elif kind == "workspace":
+            dist = torch.minimum(dist, _workspace_slack(term, pts).abs().flatten(-2).amin(-1))
+        elif kind == "self":
+            dist = torch.minimum(dist, _self_slack(term, pts).abs().amin(-1))
+        else:
+            raise NotImplementedError(kind)
+    return dist
+
+
+def ambiguous_supports(dist, H, delta=DELTA):
+    """[B, N] distances of interpolated points -> [B, H] bool: support h is ambiguous if an interpolated point with non-zero interpolation weight on
+    it, |i (H - 1) / (N - 1) - h| < 1, has dist <= delta.  (A point that falls exactly on a support has weight on that support alone.)"""
+    dist = torch.as_tensor(dist)
+    N = dist.shape[-1]
+    u = torch.arange(N, dtype=torch.float64) * (H - 1) / max(N - 1, 1)
+    w = (u.reshape(1, N) - torch.arange(H, dtype=torch.float64).reshape(H, 1)).abs() < 1        # [H, N]
+    return ((dist <= delta).unsqueeze(-2) & w).any(-1)
+
+
+def class_hinges(comp, xi):
+    """{decision class: [...] largest active hinge of the class at each configuration of xi [..., D] (0: not active)}.  The classes of a composite:
+      'f<i> prim<k>'  primitive k (spheres, then boxes) of objects field i (index in comp.cost_l) is the active arg-min of some link sphere
+      'f<i> link<l>'  link sphere l has an active hinge on objects field i
+      'f<i> inbox'    a link sphere with an active hinge on objects field i is inside its arg-min box
+      'f<i> face<j>-' / 'f<i> face<j>+'   lower / upper workspace face of axis j
+      'f<i> pair<p>'  self-collision pair p"""
+    out = {}
+    xi = xi.to(torch.float64)
+    for i, term in collision_terms(comp):
+        rob = term.robot
+        pts = rob.link_points(xi[..., : rob.q_dim])
+        kind = term.field.kind
+        if kind == "objects":
+            d, margin, ns, f = _objects(term, pts)
+            best, bi = d.min(-1)
+            hinge = torch.relu(margin - best)                                  # [..., K]
+            for k in range(d.shape[-1]):
+                out[f"f{i} prim{k}"] = (hinge * (bi == k)).amax(-1)
+            for l in range(hinge.shape[-1]):
+                out[f"f{i} link{l}"] = hinge[..., l]
+            if f.box_centers.numel():
+                dj, _ = _box_axes(f, pts, (bi - ns).clamp(min=0))
+                out[f"f{i} inbox"] = (hinge * ((bi >= ns) & (dj.amax(-1) < 0))).amax(-1)
+            else:
+                out[f"f{i} inbox"] = torch.zeros_like(hinge[..., 0])
+        elif kind == "workspace":
+            s = torch.relu(_workspace_slack(term, pts))                        # [..., K, 2 dim]
+            dim = s.shape[-1] // 2
+            for j in range(dim):
+                out[f"f{i} face{j}-"], out[f"f{i} face{j}+"] = s[..., j].amax(-1), s[..., dim + j].amax(-1)
+        elif kind == "self":
+            s = torch.relu(_self_slack(term, pts))
+            for p in range(s.shape[-1]):
+                out[f"f{i} pair{p}"] = s[..., p]
+    return out
+
+
+def coverage(comp, xi):
+    """{decision class: number of interpolated points of xi [B, N, D] at which it is active}"""
+    return {k: int((v > 0).sum()) for k, v in class_hinges(comp, xi).items()}
+
+
+def outside(got, ref, w_coll):
+    """[B, H] bool: the waypoints of got with an element outside the yardstick around ref.  Written as `not inside`, so that a NaN or an infinity in
+    got is outside (a comparison `diff > tol` is False for NaN and would count it as agreeing)."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    return ~(np.abs(got - ref) <= yardstick_atol(w_coll) + RTOL * np.abs(ref)).all(-1)
+
+
+def judge(got, ref, ambiguous, w_coll, what=""):
+    """The yardstick of DESIGN.md section 6 (1e-3 relative, 2e-6 * max(w, 1e-2) / 1e-2 absolute) on EVERY non-ambiguous waypoint of the increments
+    got / ref [B, H, D]; every element finite, the end points exactly zero.  Prints the figures, then asserts; returns them."""
+    got, ref, amb = np.asarray(got, np.float64), np.asarray(ref, np.float64), np.asarray(ambiguous, bool)
+    assert got.shape == ref.shape and amb.shape == got.shape[:2], (got.shape, ref.shape, amb.shape)
+    atol = yardstick_atol(w_coll)
+    diff = np.abs(got - ref)
+    bad = outside(got, ref, w_coll)
+    fig = {"ambiguous_share": float(amb.mean()), "differ_inside": int((bad & amb).sum()), "differ_outside": int((bad & ~amb).sum()),
+           "max_abs_diff": float(diff[~amb].max()) if (~amb).any() else 0.0, "max_abs_ref": float(np.abs(ref).max())}
+    print(f"{what}: ambiguous {int(amb.sum())} of {amb.size} waypoints ({100 * fig['ambiguous_share']:.2f} %); differing inside {fig['differ_inside']}, "
+          f"outside {fig['differ_outside']}; max|diff| outside = {fig['max_abs_diff']:.3e}; max|ref| = {fig['max_abs_ref']:.3e}")
+    assert np.isfinite(got).all(), f"{what}: {int((~np.isfinite(got)).sum())} elements are not finite"      # (ambiguous waypoints included)
+    assert not got[:, 0].any() and not got[:, -1].any(), f"{what}: the end points are not zero"
+    assert fig["differ_outside"] == 0, f"{what}: {fig['differ_outside']} non-ambiguous waypoints outside {RTOL} rel / {atol:.1e} abs"
+    return fig
+
+
+def input_ambiguity(og, comp, x, robot_id, what=""):
+    """[B, H] numpy bool: the ambiguous support waypoints of the normalised trajectories x under the fp64 oracle guide `og` / composite `comp`
+    (helpers.oracle_guide(..., dtype=torch.float64)), for tests on inputs of their own; asserts the cap on their share."""
+    from oracle.guide import interpolate_points_v1
+    xu = og.normalizer.unnormalize(x.double())
+    xi = interpolate_points_v1(xu, og.n_interp) if og.interpolate else xu
+    amb = ambiguous_supports(decision_distance(comp, xi), x.shape[1]).numpy()
+    assert amb.mean() <= cap_of(robot_id), f"{what}: {100 * amb.mean():.2f} % of the waypoints are ambiguous (cap {100 * cap_of(robot_id):.0f} %)"
+    return amb
+
+
+def rejected(got, ref, ambiguous, w_coll):
+    """True if judge refuses got (the mutant tests; quiet)"""
+    import contextlib
+    import io
+    try:
+        with contextlib.redirect_stdout(io.StringIO()):
+            judge(got, ref, ambiguous, w_coll)
+    except AssertionError:
+        return True
+    return False
+
+
+# ------------------------------------------------------------------------------------------------------------ coverage environments
+# One table for both workspaces (the 2-D environment takes x, y): 5 fixed spheres (the kernels scan spheres in batches of 4: a ragged tail), 3 fixed
+# boxes with unequal half extents (batches of 2: a ragged tail; a different interior axis per box), 1 extra sphere and 1 extra box (tables shorter
+# than a batch).  The first sphere sits next to the Panda's base column, where the upper-arm spheres can touch it.
+_FIXED_SPHERES = ((0.12, 0.05, 0.42, 0.04), (-0.30, 0.25, 0.70, 0.12), (0.35, -0.30, 0.30, 0.11), (-0.25, -0.35, 0.55, 0.09), (0.30, 0.35, 0.80, 0.13))
+_FIXED_BOXES = (((-0.40, 0.00, 0.35), (0.06, 0.10, 0.14)), ((0.00, -0.42, 0.75), (0.12, 0.05, 0.08)), ((0.42, 0.05, 0.60), (0.05, 0.13, 0.07)))
+_EXTRA_SPHERES = ((-0.05, 0.40, 0.45, 0.10),)
+_EXTRA_BOXES = (((0.10, -0.15, 0.85), (0.08, 0.05, 0.11)),)
+_WS = ((-0.55, -0.55, 0.05), (0.55, 0.55, 0.95))     # shrunk: every face can be left inside the normaliser's range
+
+
+def _object_set(spheres, boxes, dim):
+    sp = np.asarray(spheres, np.float32).reshape(-1, 4)
+    bc = np.asarray([b[0] for b in boxes], np.float32).reshape(-1, 3)
+    bh = np.asarray([b[1] for b in boxes], np.float32).reshape(-1, 3)
+    sc = sp[:, :3].copy()
+    if dim == 2:      # rows padded to 3-D: centres on the plane, boxes unbounded along the unused axis (planning.make_env)
+        sc[:, 2], bc[:, 2], bh[:, 2] = 0.0, 0.0, 1.0
+    return ObjectSet(sc, sp[:, 3].copy(), bc, bh)
+
+
+def cover_env(dim):
+    env = Env(f"Cover{dim}D", dim, _object_set(_FIXED_SPHERES, _FIXED_BOXES, dim), _object_set(_EXTRA_SPHERES, _EXTRA_BOXES, dim))
+    env.limits = (np.asarray(_WS[0][:dim], np.float32), np.asarray(_WS[1][:dim], np.float32))
+    return env
+
+
+ROBOTS = {"RobotPointMass": ("EnvSimple2D", 2), "RobotPointMass3D": ("EnvSpheres3D", 3), "RobotPanda": ("EnvSpheres3D", 3)}
+
+
+def cover_dataset(robot_id, H=64, device="cpu"):
+    """A TrajectoryDataset of `robot_id` (its normaliser, its robot) whose environment and task are the coverage ones (the way
+    scene_ref.scene_dataset replaces a task)."""
+    import mpd_public_amd as m
+    env_id, dim = ROBOTS[robot_id]
+    ds = m.TrajectoryDataset(env_id, robot_id, n_support_points=H, tensor_args={"device": device, "dtype": torch.float32})
+    d = copy.copy(ds)
+    d.env = cover_env(dim)
+    d.task = PlanningTask(d.env, d.robot, obstacle_cutoff_margin=ds.task.obstacle_cutoff_margin, tensor_args=ds.tensor_args)
+    return d
+
+
+def cap_of(robot_id):
+    return CAP["RobotPanda" if robot_id == "RobotPanda" else "RobotPointMass"]
+
+
+# Decision classes no configuration of the scan reaches (geometry: the Panda's base spheres 0 and 1 do not move, and the listed pairs cannot
+# close); asserted equal to what the scan finds (tests/test_guide_ref_cpu.py).
+UNREACHABLE = {
+    "RobotPointMass": (),
+    "RobotPointMass3D": (),
+    "RobotPanda": ("f0 pair2", "f0 pair5", "f0 pair6", "f0 pair10", "f0 pair11", "f1 link0", "f3 link0", "f3 link1", "f3 link2"),
+}
+N_SCAN = 20000
+# share of the normaliser's position range the scan covers.  Point masses: 0.9, so that probes + noise stay inside +-1 (the normaliser's in-range
+# branch; the workspace faces lie at 0.55); Panda: all of it (self pair 1 closes only near a joint limit), so the noise leaves +-1 (the clip branch)
+SPREAD = {"RobotPointMass": 0.9, "RobotPointMass3D": 0.9, "RobotPanda": 1.0}
+
+
+@functools.lru_cache(maxsize=None)
+def probe_configs(robot_id):
+    """(labels, q [P, q_dim] fp64 un-normalised, unreachable labels): for every decision class that a hash-uniform scan of N_SCAN configurations
+    reaches, the scanned configuration with the largest hinge of that class."""
+    ds = cover_dataset(robot_id)
+    _, comp = oracle_guide(ds, dtype=torch.float64)
+    qd = ds.robot.q_dim
+    lo, hi = ds.normalizer.mins[:qd].double(), ds.normalizer.maxs[:qd].double()
+    u = torch.from_numpy(syn.hash_uniform(f"guide_cover/{robot_id}/scan", N_SCAN * qd, -SPREAD[robot_id], SPREAD[robot_id]).reshape(N_SCAN, qd))
+    q = lo + (hi - lo) * (u + 1) / 2
+    labels, rows, missing = [], [], []
+    for name, v in class_hinges(comp, q).items():
+        if float(v.max()) > 0:
+            labels.append(name)
+            rows.append(q[int(v.argmax())])
+        else:
+            missing.append(name)
+    return tuple(labels), torch.stack(rows), tuple(missing)
+
+
+def cover_trajs(robot_id, H, seed="0"):
+    """Normalised fp32 [B, H, D] trajectories, B = ceil(P / 2): trajectory b runs in a straight line from probe 2 b to probe 2 b + 1 (hash-normal
+    noise of 0.02 on the way); supports 0 and 1 sit on the first probe, H - 2 and H - 1 on the second (the end points' increments are zeroed, so
+    the probes must also be seen from a support that is not).  Velocities: 0.2 x hash-normal."""
+    ds = cover_dataset(robot_id, H)
+    _, q, _ = probe_configs(robot_id)
+    qd = ds.robot.q_dim
+    lo, hi = ds.normalizer.mins[:qd].double(), ds.normalizer.maxs[:qd].double()
+    qn = 2 * (q - lo) / (hi - lo) - 1
+    if qn.shape[0] % 2:
+        qn = torch.cat([qn, qn[:1]])
+    a, b = qn[0::2].unsqueeze(1), qn[1::2].unsqueeze(1)
+    B = a.shape[0]
+    tag = f"guide_cover/{robot_id}/{H}/{seed}"
+    pos = torch.empty((B, H, qd), dtype=torch.float64)
+    n_in = H - 2
+    s = torch.linspace(0, 1, n_in, dtype=torch.float64).reshape(1, n_in, 1)
+    noise = 0.02 * torch.from_numpy(syn.hash_normal(f"{tag}/n", B * n_in * qd).reshape(B, n_in, qd))
+    noise[:, 0], noise[:, -1] = 0.0, 0.0
+    pos[:, 1:H - 1] = a + (b - a) * s + noise
+    pos[:, 0], pos[:, -1] = a[:, 0], b[:, 0]
+    vel = 0.2 * torch.from_numpy(syn.hash_normal(f"{tag}/v", B * H * qd).reshape(B, H, qd))
+    return torch.cat([pos, vel], -1).float().contiguous()
+
+
+# the cases of tests/test_gpu_guide_terms.py; H = 96 / 128: two waves of supports (the GP neighbours cross the wave boundary); H = 48: a wave not
+# full; H = 9 (3-D point mass): H * D = 54 is no multiple of 4, and 128 interpolated points are more than 8 H
+GPU_CASES = [("RobotPointMass", 64), ("RobotPointMass", 128), ("RobotPointMass", 96), ("RobotPointMass", 48),
+             ("RobotPointMass3D", 64), ("RobotPointMass3D", 96), ("RobotPointMass3D", 9), ("RobotPanda", 64), ("RobotPanda", 96)]
+
+
+def n_interp_of(H):
+    """Interpolated points of a case: the product guide's 128 where the kernel takes it (H <= n_interp <= 8 H), else 2 H + 1
+    (tests/test_gpu_chain.py::_n_interp)."""
+    return 128 if H <= 128 <= 8 * H else 2 * H + 1
+
+
+# ------------------------------------------------------------------------------------------------------------ the runs of one case
+def term_names(ds):
+    """names of the cost terms in the order of the composites (helpers.oracle_guide / helpers.product_guide): the collision fields, then 'gp'"""
+    return [f.name for f in ds.task.get_collision_fields()] + ["gp"]
+
+
+def runs_of(ds):
+    """The comparisons of one case, [(name, kwargs)]: the composite at both weight pairs, then every term ALONE at weight 1.0 with the norm clip on
+    and off (the GP prior also with gp_half_factor).  kwargs: weights (w_coll, w_smooth), only (term index or None), clip_grad, gp_half_factor."""
+    names = term_names(ds)
+    runs = [("composite w=(1e-2, 1e-7)", dict(weights=(1e-2, 1e-7), only=None, clip_grad=True, gp_half_factor=False)),
+            ("composite w=(1.0, 1e-4)", dict(weights=(1.0, 1e-4), only=None, clip_grad=True, gp_half_factor=False))]
+    for k, nm in enumerate(names):
+        for clip in (True, False):
+            for half in ((False, True) if nm == "gp" else (False,)):
+                runs.append((f"{nm} alone, clip {'on' if clip else 'off'}{', half factor' if half else ''}",
+                             dict(weights=(1.0, 1.0), only=k, clip_grad=clip, gp_half_factor=half)))
+    return runs
+
+
+def is_unclipped_gp(ds, run):
+    """the GP prior alone with the norm clip off: increments of O(1e3 ... 1e4) whose elements cancel (see tests/test_guide_ref_cpu.py::
+    test_fp32_oracle_error_on_the_unclipped_gp_prior_alone); the tests keep these runs apart from the others"""
+    return run["only"] is not None and term_names(ds)[run["only"]] == "gp" and not run["clip_grad"]
+
+
+def oracle_run(ds, x, run, dtype=torch.float64, n_interp=128, mutate=None):
+    """The oracle's increment [B, H, D] (numpy, in dtype) of one run of runs_of on the normalised trajectories x.  mutate(guide, composite): a
+    change applied to the oracle before the term selection (the mutants of tests/test_guide_ref_cpu.py)."""
+    og, comp = oracle_guide(ds, *run["weights"], clip_grad=run["clip_grad"], dtype=dtype, n_interp=n_interp, gp_half_factor=run["gp_half_factor"])
+    if mutate is not None:
+        mutate(og, comp)
+    if run["only"] is not None:
+        k = run["only"]
+        comp.cost_l, comp.weight_l = [comp.cost_l[k]], [1.0]
+    return og(x.to(dtype)).numpy()
+
+
+def product_run(ds, run, n_interp=128):
+    """The product guide (not yet on a device) of one run of runs_of, built as helpers.product_guide builds it with the run's terms."""
+    import mpd_public_amd as m
+    H = ds.n_support_points
+    costs = [m.CostCollision(ds.robot, H, field=f, sigma_coll=1.0) for f in ds.task.get_collision_fields()]
+    weights = [run["weights"][0]] * len(costs)
+    costs.append(m.CostGPTrajectory(ds.robot, H, 5.0 / H, sigma_gp=1.0, half_factor=run["gp_half_factor"]))
+    weights.append(run["weights"][1])
+    if run["only"] is not None:
+        costs, weights = [costs[run["only"]]], [1.0]
+    comp = m.CostComposite(ds.robot, H, costs, weights_cost_l=weights)
+    return m.GuideManagerTrajectoriesWithVelocity(ds, comp, clip_grad=run["clip_grad"], interpolate_trajectories_for_collision=True,
+                                                  num_interpolated_points_for_collision=n_interp)
+
+
+def run_ambiguity(run, ds, amb):
+    """the ambiguous set of a run: the collision decisions' for every run that holds a collision term, none for the GP prior alone (it has no decision)"""
+    if run["only"] is not None and term_names(ds)[run["only"]] == "gp":
+        return np.zeros_like(amb)
+    return amb
+
+
+@functools.lru_cache(maxsize=None)
+def case(robot_id, H, seed="0"):
+    """Everything the reference says about one case, computed once: dict(ds (CPU), x, n_interp, xi (fp64 interpolated un-normalised), dist, amb [B, H]
+    numpy, cover, comp)."""
+    from oracle.guide import interpolate_points_v1
+    ds = cover_dataset(robot_id, H)
+    x = cover_trajs(robot_id, H, seed)
+    n = n_interp_of(H)
+    og, comp = oracle_guide(ds, dtype=torch.float64, n_interp=n)
+    xi = interpolate_points_v1(og.normalizer.unnormalize(x.double()), n)
+    dist = decision_distance(comp, xi)
+    amb = ambiguous_supports(dist, H).numpy()
+    amb.setflags(write=False)
+    return dict(ds=ds, x=x, n_interp=n, xi=xi, dist=dist, amb=amb, cover=coverage(comp, xi), comp=comp)
+
+
+@functools.lru_cache(maxsize=None)
+def case_reference(robot_id, H, run_index, seed="0"):
+    """fp64 increment of run `run_index` of runs_of for a case (read-only numpy array), computed once and shared"""
+    c = case(robot_id, H, seed)
+    ref = oracle_run(c["ds"], c["x"], runs_of(c["ds"])[run_index][1], torch.float64, c["n_interp"])
+    ref.setflags(write=False)
+    return ref
+
+
+def check_reference_conditions(robot_id, H, seed="0"):
+    """What every comparison of a case presupposes, from the reference alone (asserted by the CPU test for every GPU case, and again by the GPU
+    tests before the kernel's output is looked at): every reachable class is active, the ambiguous share is under its cap, and max|x| is not
+    within 1e-3 of the normaliser's whole-tensor range test."""
+    c = case(robot_id, H, seed)
+    labels, _, missing = probe_configs(robot_id)
+    idle = [k for k in labels if c["cover"][k] == 0]
+    share = float(c["amb"].mean())
+    amax = float(c["x"].abs().max())
+    print(f"{robot_id} H={H}: B = {c['x'].shape[0]}, {len(labels)} of {len(labels) + len(missing)} classes reachable, idle on the trajectories: {idle}; "
+          f"ambiguous share {100 * share:.2f} % (cap {100 * cap_of(robot_id):.0f} %); max|x| = {amax:.4f}")
+    assert not idle, idle
+    assert share <= cap_of(robot_id), share
+    assert abs(amax - 1.0) > 1e-3, amax
+    return c

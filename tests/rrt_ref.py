@@ -272,6 +272,9 @@ CASES = {
     # the Panda: link spheres and self-collision pairs split over the threads of a check; the straight line start -> goal (1.8 rad) collides
     "panda": dict(_PM, env="EnvSpheres3D", robot="RobotPanda", n=3, step=0.25, max_iters=150, gen_seed=2 ** 40 + 3, launch=2,
                   start=(0.03, -0.3, -0.46, -0.96, 1.25, 3.65, 2.56), goal=(0.06, 0.63, 0.4, -2.04, 1.15, 2.99, 2.25)),
+    # the 3-D point mass (the q_dim 3 / ws_dim 3 instantiation): three coordinates per sample, across the sphere field of EnvSpheres3D
+    "pm3": dict(_PM, env="EnvSpheres3D", robot="RobotPointMass3D", n=4, step=0.15, max_iters=300, gen_seed=11, launch=4, start=(-0.9, 0.0, 0.6),
+                goal=(0.9, 0.1, 0.6)),
 }
 
 

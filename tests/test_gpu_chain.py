@@ -101,6 +101,51 @@ def test_guide_increment_vs_fp64_oracle(name, H):
     assert torch.equal(flag_out.view(torch.float32), want.abs().reshape(1, -1).max(1)[0])
 
 
+# ---------------------------------------------------------------------------------------------------------------- 1b. the GP prior alone
+def _gp_alone(H, clip):
+    """(kernel increment, fp64 oracle increment, float32 oracle increment) of a guide that holds the GP prior alone at weight 1.0, R3"""
+    import mpd_public_amd as m
+    ds, desc, x, _, _, _ = _case("R3", H)
+    out = []
+    for dtype in (torch.float64, torch.float32):
+        og, comp = oracle_guide_chain(ds, desc, dtype=dtype, n_interp=_n_interp(H))
+        og.clip_grad, comp.cost_l, comp.weight_l = clip, [comp.cost_l[-1]], [1.0]
+        out.append(og(x.to(dtype)).numpy())
+    comp = m.CostComposite(ds.robot, H, [m.CostGPTrajectory(ds.robot, H, 5.0 / H, sigma_gp=1.0)], weights_cost_l=[1.0])
+    pg = m.GuideManagerTrajectoriesWithVelocity(ds, comp, clip_grad=clip, interpolate_trajectories_for_collision=True,
+                                                num_interpolated_points_for_collision=_n_interp(H)).cuda()
+    return pg(x.cuda()).cpu().numpy(), out[0], out[1]
+
+
+@pytest.mark.parametrize("H", [64, 96])
+def test_gp_prior_alone_vs_fp64_oracle(H):
+    """In every composite comparison the GP prior is below the absolute tolerance (its clipped gradient is at most 1, its weight 1e-7): here it runs
+    ALONE at weight 1.0 with the norm clip on, every waypoint inside the yardstick at that weight (1e-3 rel / 2e-4 abs; tests/guide_ref.py::judge).
+    H = 96: the neighbours of supports 63 / 64 lie across the wave boundary."""
+    from guide_ref import judge
+    got, ref, ref32 = _gp_alone(H, True)
+    assert np.abs(ref).max() > 0.5
+    judge(got, ref, np.zeros(got.shape[:2], bool), 1.0, f"R3 H={H} gp alone, clip on")
+    print(f"  float32 oracle max|diff| = {np.abs(ref32 - ref).max():.3e}")
+
+
+def test_gp_prior_alone_unclipped_vs_fp64_oracle():
+    """The same with the norm clip OFF, H = 64 and 96, under the same bound.  The float32 ORACLE does not meet it on every waypoint (printed next to
+    the kernel): the un-clipped increment is 1e3 ... 1e5 with elements that cancel, and the float32 rounding of the un-normalised state times 24 / dt^3
+    is an absolute error of 1e-2 ... 1e-1 in each.  The kernel evaluates the GP term in float64 from the float32 normalised state (guide_gp_apply); with
+    the float32 term it missed the bound on 1 of 288 waypoints at H = 96 (max|diff| 1.62e-1, the float32 oracle 1.66e-1; max|ref| 1.8e5)."""
+    from guide_ref import outside
+    total = 0
+    for H in (64, 96):
+        got, ref, ref32 = _gp_alone(H, False)
+        assert np.isfinite(got).all() and not got[:, 0].any() and not got[:, -1].any()
+        bad, bad32 = (outside(g, ref, 1.0) for g in (got, ref32))
+        print(f"R3 H={H} gp alone, clip off: kernel {int(bad.sum())} of {bad.size} waypoints outside, max|diff| {np.abs(got - ref).max():.3e}; float32 oracle "
+              f"{int(bad32.sum())} outside, max|diff| {np.abs(ref32 - ref).max():.3e}; max|ref| {np.abs(ref).max():.3e}")
+        total += int(bad.sum())
+    assert total == 0, f"{total} waypoints of the un-clipped GP increments are outside 1e-3 rel / 2e-4 abs"
+
+
 # ---------------------------------------------------------------------------------------------------------------- 2. Panda as a chain
 def test_panda_chain_next_to_the_panda_kernel():
     """The same trajectories through RobotPanda (its own kernel) and RobotChain.panda(): both inside the yardstick against the same fp64 reference;

@@ -8,7 +8,7 @@ from helpers import obstacle_hugging_trajs, oracle_guide
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("env_id,robot_id", [("EnvNarrowPassageDense2D", "RobotPointMass"), ("EnvSpheres3D", "RobotPanda")])
+@pytest.mark.parametrize("env_id,robot_id", [("EnvNarrowPassageDense2D", "RobotPointMass"), ("EnvSpheres3D", "RobotPanda"), ("EnvSpheres3D", "RobotPointMass3D")])
 def test_trajectory_metrics_vs_oracle(env_id, robot_id):
     import mpd_public_amd as m
     from oracle import costs as oc

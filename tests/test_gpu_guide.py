@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from guide_ref import input_ambiguity, judge
 from helpers import synth_sd, t, oracle_guide, product_guide, obstacle_hugging_trajs, DIM_MULTS
 
 pytestmark = pytest.mark.gpu
@@ -13,11 +14,7 @@ pytestmark = pytest.mark.gpu
 CASES = [("EnvNarrowPassageDense2D", "RobotPointMass"), ("EnvSimple2D", "RobotPointMass"), ("EnvSpheres3D", "RobotPanda")]
 
 
-def _mismatch(a, b, atol, rtol=1e-3):
-    return np.abs(a - b) > atol + rtol * np.abs(b)
-
-
-@pytest.mark.parametrize("env_id,robot_id", CASES)
+@pytest.mark.parametrize("env_id,robot_id", CASES + [("EnvSpheres3D", "RobotPointMass3D")])
 @pytest.mark.parametrize("scale", [0.9, 1.06])  # in range / beyond +-1 (whole-tensor clip branch of the normaliser)
 @pytest.mark.parametrize("weights", [(1e-2, 1e-7), (1.0, 1e-4)])  # reference defaults (inference.py:55-56) / un-attenuated
 def test_guide_increment_vs_oracle(env_id, robot_id, scale, weights):
@@ -31,13 +28,10 @@ def test_guide_increment_vs_oracle(env_id, robot_id, scale, weights):
     got = pg(x.cuda()).cpu().numpy()
     assert got.shape == ref.shape == (B, 64, ds.state_dim)
     assert np.abs(ref).max() > 0
-    # endpoints are zeroed exactly
-    assert not got[:, 0].any() and not got[:, -1].any()
-    # hinge/argmin decisions of points within 1e-6 of a margin may legitimately differ between fp32 and fp64: allow a
-    # handful of waypoints to differ, everything else must agree to fp32 rounding of the per-term gradients
-    bad = _mismatch(got, ref, atol=2e-6 * max(weights[0], 1e-2) / 1e-2).any(-1)
-    assert bad.mean() < 0.01, f"{bad.sum()} of {bad.size} waypoints differ; max|diff|={np.abs(got-ref).max():.3e}"
-    np.testing.assert_allclose(got[~bad], ref[~bad], rtol=1e-3, atol=2e-6 * max(weights[0], 1e-2) / 1e-2)
+    # endpoints are zeroed exactly; hinge / arg-min decisions of points within 1e-5 of a tie may legitimately differ between fp32 and fp64: the
+    # support waypoints they reach are ambiguous (tests/guide_ref.py, decided from the fp64 reference alone); EVERY other waypoint must agree to
+    # fp32 rounding of the per-term gradients
+    judge(got, ref, input_ambiguity(og, comp, x, robot_id, env_id), weights[0], f"{env_id} {robot_id} scale {scale} w {weights}")
 
 
 @pytest.mark.parametrize("env_id,robot_id", [("EnvSimple2D", "RobotPointMass"), ("EnvSpheres3D", "RobotPanda")])
@@ -61,13 +55,11 @@ def test_guide_increment_with_the_other_normalizers_vs_oracle(env_id, robot_id, 
     x = obstacle_hugging_trajs(ds0, 7, seed=f"gn/{env_id}", scale=1.3 if name == "GaussianNormalizer" else 0.9)
     if name == "Identity":
         x = ds0.normalizer.unnormalize(x.cuda()).cpu()
-    og, _ = oracle_guide(ds, dtype=torch.float64)
+    og, comp = oracle_guide(ds, dtype=torch.float64)
     ref = og(x.double()).numpy()
     got = product_guide(ds).cuda()(x.cuda()).cpu().numpy()
-    assert np.abs(ref).max() > 0 and not got[:, 0].any() and not got[:, -1].any()
-    bad = _mismatch(got, ref, atol=2e-6).any(-1)
-    assert bad.mean() < 0.01, f"{bad.sum()} of {bad.size} waypoints differ; max|diff|={np.abs(got-ref).max():.3e}"
-    np.testing.assert_allclose(got[~bad], ref[~bad], rtol=1e-3, atol=2e-6)
+    assert np.abs(ref).max() > 0
+    judge(got, ref, input_ambiguity(og, comp, x, robot_id, name), 1e-2, f"{env_id} {robot_id} {name}")
 
 
 def test_guided_plan_under_gaussian_normalizer_fused_equals_stepwise_and_oracle_start():
@@ -109,14 +101,11 @@ def test_guide_increment_other_horizons_vs_oracle(env_id, robot_id, H):
     sgrid = torch.linspace(0, 1, H).reshape(1, H, 1)
     x = torch.cat([a_ + (b_ - a_) * sgrid + 0.04 * t(f"gh/{env_id}/n{H}", (B, H, qd)), 0.3 * t(f"gh/{env_id}/v{H}", (B, H, qd))], -1).contiguous()
     w = (1e-2, 1e-7)
-    og, _ = oracle_guide(ds, *w, dtype=torch.float64)
+    og, comp = oracle_guide(ds, *w, dtype=torch.float64)
     ref = og(x.double()).numpy()
     got = product_guide(ds, *w).cuda()(x.cuda()).cpu().numpy()
     assert got.shape == ref.shape == (B, H, D) and np.abs(ref).max() > 0
-    assert not got[:, 0].any() and not got[:, -1].any()
-    bad = _mismatch(got, ref, atol=2e-6).any(-1)
-    assert bad.mean() < 0.01, f"{bad.sum()} of {bad.size} waypoints differ; max|diff|={np.abs(got-ref).max():.3e}"
-    np.testing.assert_allclose(got[~bad], ref[~bad], rtol=1e-3, atol=2e-6)
+    judge(got, ref, input_ambiguity(og, comp, x, robot_id, f"H={H}"), w[0], f"{env_id} {robot_id} H={H}")
     # the post-loop metrics kernel on the same horizons: path length / smoothness sums over all H - 1 segments
     from oracle.normalizer import LimitsNormalizer
     xu = LimitsNormalizer(ds.normalizer.mins.cpu(), ds.normalizer.maxs.cpu()).unnormalize(x)
@@ -390,14 +379,12 @@ def test_guide_clip_by_value_vs_oracle(env_id, robot_id):
     ds = m.TrajectoryDataset(env_id, robot_id, tensor_args={"device": "cuda", "dtype": torch.float32})
     x = obstacle_hugging_trajs(ds, 6, seed=f"clipv/{env_id}", scale=0.95)
     for mv in (0.1, 0.35):
-        og, _ = oracle_guide(ds, 1.0, 1e-4, dtype=torch.float64, clip_grad_rule="value", max_grad_value=mv)
+        og, comp = oracle_guide(ds, 1.0, 1e-4, dtype=torch.float64, clip_grad_rule="value", max_grad_value=mv)
         ref = og(x.double()).numpy()
         got = product_guide(ds, 1.0, 1e-4, clip_grad_rule="value", max_grad_value=mv).cuda()(x.cuda()).cpu().numpy()
         norm_ref = product_guide(ds, 1.0, 1e-4).cuda()(x.cuda()).cpu().numpy()
         assert np.abs(got - norm_ref).max() > 1e-3, "the two clip rules must differ on this input"
-        bad = _mismatch(got, ref, atol=2e-4).any(-1)
-        assert bad.mean() < 0.01, f"{bad.sum()} of {bad.size} waypoints differ; max|diff|={np.abs(got-ref).max():.3e}"
-        np.testing.assert_allclose(got[~bad], ref[~bad], rtol=1e-3, atol=2e-4)
+        judge(got, ref, input_ambiguity(og, comp, x, robot_id, f"value clip {mv}"), 1.0, f"{env_id} {robot_id} value clip {mv}")
     with pytest.raises(NotImplementedError):
         m.GuideManagerTrajectoriesWithVelocity(ds, product_guide(ds).cost, clip_grad=True, clip_grad_rule="median")
 

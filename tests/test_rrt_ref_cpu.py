@@ -40,7 +40,7 @@ def test_start_and_goal_are_clear_of_obstacles(name):
 
 
 # (case, problems replayed): every problem of the cheap cases; of the long ones a solved problem with a tree beyond 256 nodes and a short one
-SELF = [("dense", None), ("narrow", (1, 3)), ("narrow_small_budget", None), ("dense_24_checks", None), ("ties", None), ("panda", (1,))]
+SELF = [("dense", None), ("narrow", (1, 3)), ("narrow_small_budget", None), ("dense_24_checks", None), ("ties", None), ("panda", (1,)), ("pm3", None)]
 
 
 @pytest.mark.parametrize("name,problems", SELF)
@@ -93,6 +93,9 @@ def test_cases_have_the_properties_the_gpu_tests_rely_on():
             assert len(at) > 256 and (ties.parent[b, t, at[1:]] == at[0]).all()
     panda = _free("panda")
     assert (panda.link[:, 0] >= 0).any() and int(panda.count.sum()) > 100 and sum(panda.ambiguous) == 0
-    for name, trees in (("narrow", narrow), ("panda", panda)):      # first extensions: inserted in at least half the problems, directions not degenerate
+    pm3 = _free("pm3")      # every problem solved, in three dimensions (first extensions below: the directions span all three axes)
+    assert (pm3.link[:, 0] >= 0).all() and pm3.nodes.shape[-1] == 3 and int(pm3.count.sum()) > 40 and sum(pm3.ambiguous) == 0
+    assert (pm3.iters < rrt_ref.CASES["pm3"]["max_iters"]).all() and int(pm3.iters.max()) > 10
+    for name, trees in (("narrow", narrow), ("panda", panda), ("pm3", pm3)):      # first extensions: inserted in at least half the problems, directions not degenerate
         dirs = [d for d in trees.first_dirs if d is not None]
         assert len(dirs) >= len(trees.count) // 2 and rrt_ref.directions_span(dirs), name
