@@ -421,6 +421,36 @@ int mpdx_traj_tool_metrics(const mpdx_guide_params* gp, const float* x_unnormali
 int mpdx_sdf_grid_bake(const mpdx_guide_params* gp, int field, float* sdf_out, float* grad_out, const int n[3], const float origin[3], float cell,
                        void* stream);
 
+/* ---- a signed-distance grid from an occupancy grid or a point cloud: an exact Euclidean distance transform on the device (csrc/edt.hpp).  Replaces
+ * nothing in the reference (its environments are primitives); it produces the planes the MPDX_FIELD_GRID lookups read from what a depth camera or an
+ * occupancy map gives.  Every step is exactly reproducible in numpy (tests/edt_ref.py).
+ *
+ * Nodes are voxel centres: node (ix, iy, iz) sits at origin + i * cell, as for every grid; occ[iz][iy][ix] is one byte, x fastest, non-zero = occupied;
+ * n[2] = 1 in 2-D (there is no ws_dim here: n[2] == 1 IS the 2-D case), else 2 ... 4096 nodes along every axis, at most 2^29 nodes.
+ *   d2    free node n: min |n - m|^2 over OCCUPIED nodes m; occupied node: min over FREE nodes m - in cells, exact integers (int32).  Without any
+ *         such m (all free / all occupied): d2 = (n[0] + n[1] + n[2])^2, which exceeds every distance inside the grid (and fits int32 with every
+ *         intermediate of the separable passes at 4096 nodes per axis).
+ *   s     fp32, every operation rounded (no contraction), IEEE sqrtf:  free  s =   cell * (sqrtf((float)d2) - 0.5f)  - inflate
+ *                                                                     occupied  s = -(cell * (sqrtf((float)d2) - 0.5f)) - inflate
+ *         the half cell puts the surface on the voxel FACE (a free node beside an occupied one: +cell / 2); inflate >= 0 thickens every obstacle.
+ *   grad  [nz][ny][nx][4] or NULL (MPDX_GRID_NEAREST needs it, LINEAR does not): along each used axis (s[i+1] - s[i-1]) * k2 at an interior node,
+ *         (s[i+1] - s[i]) * k1 / (s[i] - s[i-1]) * k1 at a face node, k1 = 1.0f / cell, k2 = 0.5f / cell (fp32, taken once on the host); one rounded
+ *         subtraction and one rounded product each; the unused axis and the fourth word are 0.
+ *   d2_out (or NULL, for tests): the d2 above per node.
+ * ws: mpdx_sdf_grid_edt_ws_bytes(n) bytes of device memory (4-byte aligned; the library allocates nothing and never synchronises); the size function
+ * returns 0 for a refused n.  sdf_out / grad_out may be planes of a grids buffer (grad_out 16-byte aligned).
+ *
+ * mpdx_occupancy_from_points: points [P][3] fp32 (z ignored in 2-D); u_j = (p_j - origin_j) * inv, inv = 1.0f / cell (the two rounded operations of the
+ * lookups' cell coordinate), i_j = rintf(u_j) (half to even).  A point with a non-finite used coordinate or an i_j outside [0, n_j - 1] is DROPPED (not
+ * clamped); otherwise occ[node] = 1.  Bytes are only ever set, so several clouds accumulate into one map; clear it yourself.  n_points == 0: no-op.
+ *
+ * Refused on the host, before any launch (MPDX_E_INVALID, the message names the argument): a null pointer (grad_out, d2_out may be null), n outside
+ * the ranges above, cell not positive and finite, inflate negative or non-finite, a misaligned grad_out, ws_bytes too small, n_points < 0. */
+size_t mpdx_sdf_grid_edt_ws_bytes(const int n[3]);
+int mpdx_sdf_grid_from_occupancy(const uint8_t* occ, float* sdf_out, float* grad_out, int32_t* d2_out, const int n[3], float cell, float inflate, void* ws,
+                                 size_t ws_bytes, void* stream);
+int mpdx_occupancy_from_points(const float* points, int n_points, uint8_t* occ, const int n[3], const float origin[3], float cell, void* stream);
+
 /* ---- baseline planners of the dataset-generation script: replaces `HybridPlanner(RRTConnect x n via
  * MultiSampleBasedPlanner, GPMP2).optimize()` of scripts/generate_data/generate_trajectories.py:68-120.  The planners are
  * un-vendored in the reference (mp_baselines submodule empty: PARITY UNPINNED); the published algorithms are restated

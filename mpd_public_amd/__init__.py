@@ -8,7 +8,7 @@ from .diffusion_model import GaussianDiffusionModel  # noqa: F401
 from .sample_functions import ddpm_sample_fn, guide_gradient_steps, apply_hard_conditioning, extract  # noqa: F401
 
 from .guides import GuideManagerTrajectoriesWithVelocity  # noqa: F401
-from .planning import CostCollision, CostGPTrajectory, CostComposite, CostToolAxis, ObjectSet, PlanningScenes, PlanningTask, RobotChain, make_env, make_robot  # noqa: F401
+from .planning import CostCollision, CostGPTrajectory, CostComposite, CostToolAxis, GridSDF, ObjectSet, PlanningScenes, PlanningTask, RobotChain, make_env, make_robot  # noqa: F401
 from .ik import IKResult, solve_ik  # noqa: F401
 from .datasets import (TrajectoryDataset, LimitsNormalizer, SafeLimitsNormalizer, FixedLimitsNormalizer, GaussianNormalizer, Identity,  # noqa: F401
                        make_normalizer)
@@ -16,4 +16,4 @@ from .datasets import (TrajectoryDataset, LimitsNormalizer, SafeLimitsNormalizer
 __all__ = ["TemporalUnet", "UNET_DIM_MULTS", "GaussianDiffusionModel", "ddpm_sample_fn", "guide_gradient_steps",
            "apply_hard_conditioning", "extract", "GuideManagerTrajectoriesWithVelocity", "CostCollision", "CostGPTrajectory", "CostToolAxis",
            "CostComposite", "PlanningTask", "TrajectoryDataset", "LimitsNormalizer", "SafeLimitsNormalizer", "FixedLimitsNormalizer", "GaussianNormalizer", "Identity",
-           "make_normalizer", "make_env", "make_robot", "ObjectSet", "PlanningScenes", "RobotChain", "solve_ik", "IKResult"]
+           "make_normalizer", "make_env", "make_robot", "ObjectSet", "PlanningScenes", "RobotChain", "solve_ik", "IKResult", "GridSDF"]

@@ -121,6 +121,9 @@ SIGNATURES = {
     "mpdx_guide_variant": (_i, [C.POINTER(GuideParams), _i, _i, _i]),
     "mpdx_absmax": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "mpdx_sdf_grid_bake": (_i, [C.POINTER(GuideParams), _i, _vp, _vp, C.POINTER(C.c_int * 3), C.POINTER(C.c_float * 3), _f, _vp]),
+    "mpdx_sdf_grid_edt_ws_bytes": (_sz, [C.POINTER(C.c_int * 3)]),
+    "mpdx_sdf_grid_from_occupancy": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int * 3), _f, _f, _vp, _sz, _vp]),
+    "mpdx_occupancy_from_points": (_i, [_vp, _i, _vp, C.POINTER(C.c_int * 3), C.POINTER(C.c_float * 3), _f, _vp]),
     "mpdx_unet_profile": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, C.POINTER(C.c_float), C.POINTER(C.c_double),
                                 C.POINTER(C.c_char_p), C.POINTER(C.c_int)]),
     "mpdx_layer_trace": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(C.c_longlong)]),

@@ -45,6 +45,7 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
     varied = []    # scenes: (field index, [ObjectSet per scene]) of the fields that differ per scene
     shared = []    # scenes: (field index, sphere floats, box floats) of the OBJECTS fields every scene sees
     planes, goff = [], 0     # grid planes, each padded to a multiple of 4 floats (16-byte aligned gradient planes)
+    placed = []              # (float offset in the grid buffer, plane) of the planes proper (refresh_grid_planes)
     gp.use_gp = 0
     for c, w in zip(cost_l, weight_l):
         if isinstance(c, CostCollision):
@@ -85,6 +86,7 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
                         continue
                     if pl is grad_p:
                         f.grid_grad_off = goff
+                    placed.append((goff, pl))
                     planes.append(pl)
                     goff += pl.numel()
                     if goff % 4:
@@ -120,6 +122,7 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
         grid_t = planes[0] if len(planes) == 1 else torch.cat(planes)   # (a single plane is used in place: no second copy of a 7.8-MB grid)
         gp.grids, gp.n_grid_floats = grid_t.data_ptr(), goff
     gp.grids_tensor = grid_t   # a Python attribute of the ctypes object: the buffer lives as long as the params that point into it
+    gp.grid_planes = placed
     gp.chain_tensor = None
     if robot.robot_id == _lib.ROBOT_CHAIN:   # the kinematic table of a planning.RobotChain (layout in include/mpdx.h), kept alive the same way
         if planes:
@@ -127,6 +130,17 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
         gp.chain_tensor = torch.from_numpy(robot.table()).to(device)
         gp.chain, gp.n_chain_floats = gp.chain_tensor.data_ptr(), gp.chain_tensor.numel()
     return gp, prim_t
+
+
+def refresh_grid_planes(gp):
+    """The planes of a GridSDF were rewritten in place (GridSDF.update_occupancy): copy them again into the grid buffer of `gp` where that buffer is
+    a concatenation; nothing to do where the single plane is the buffer."""
+    buf = gp.grids_tensor
+    if buf is None:
+        return
+    for off, pl in gp.grid_planes:
+        if buf.data_ptr() + 4 * off != pl.data_ptr():
+            buf[off: off + pl.numel()].copy_(pl)
 
 
 def _scene_table(gp, n_scenes, varied, shared):
@@ -260,6 +274,12 @@ class GuideManagerTrajectoriesWithVelocity(nn.Module):
             self._scene_table = torch.tensor(self._scene_of_context, dtype=torch.int32, device=device)
             self._params.scene_of_ctx, self._params.scene_n_per_ctx = self._scene_table.data_ptr(), self._n_per_context
         return self._params
+
+    def refresh_grids(self):
+        """After GridSDF.update_occupancy on a grid of this guide's fields: copy the planes again where the guide's grid buffer is a concatenation
+        (several planes: nearest mode, or more than one grid); a no-op where the single plane is used in place."""
+        if self._params is not None:
+            refresh_grid_planes(self._params)
 
     # ------------------------------------------------------------------------------------------- guide protocol
     def _forward_autograd(self, x_normalized):

@@ -73,7 +73,7 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
                trajectory_duration: float = 5.0, device: str = "cuda", debug: bool = True, render: bool = False, seed: int = 30,
                results_dir: str = "logs", model_dir: str = None, model_args: dict = None, sdf_grid_cell_size: float = None,
                sdf_grid_mode: str = "linear", robot=None, goal_ee_pos=None, goal_ee_rot=None, goal_ee_frame=None, tool_axis=None,
-               weight_grad_cost_tool_axis: float = 1e-2, **kwargs):
+               weight_grad_cost_tool_axis: float = 1e-2, sdf_grid=None, **kwargs):
     """tool_axis (extension; None = no such term, as before): dict(frame=, axis=, world_axis=, max_tilt=) - the arguments of planning.CostToolAxis, every
     key optional - adds the tool-axis constraint to the guide with weight `weight_grad_cost_tool_axis` ("carry it upright": the frame's axis stays
     within max_tilt radians of the world axis along the whole trajectory).  A chain robot (the Panda as robot=RobotChain.panda()).  Start and goal are
@@ -87,7 +87,9 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
     gain `goal_ee_pos` and `goal_ee_error` (|FK(goal) - target| in float64).  A chain robot or the Panda.
     robot (extension): a planning.RobotChain that replaces the robot named in `model_id` (the environment is still taken from it).
     sdf_grid_cell_size / sdf_grid_mode (extension): None (default) keeps the primitive tables; a cell size makes the task's FIXED objects a
-    signed-distance grid baked on the device ('linear' interpolation or 'nearest' node, planning.PlanningTask(sdf_grid=...))."""
+    signed-distance grid baked on the device ('linear' interpolation or 'nearest' node, planning.PlanningTask(sdf_grid=...)).
+    sdf_grid (extension; None = as above): a planning.GridSDF - GridSDF.from_occupancy / from_points - passed through to the task as its objects field;
+    not together with sdf_grid_cell_size."""
     torch.manual_seed(seed)
     if not torch.cuda.is_available():
         raise RuntimeError("mpd_public_amd.inference needs an AMD GPU (no CPU fallback)")
@@ -108,7 +110,10 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
         args.update(model_args)
     env_id, robot_id = model_id.split("-")
 
-    sdf_grid = None if sdf_grid_cell_size is None else dict(cell_size=float(sdf_grid_cell_size), mode=sdf_grid_mode)
+    if sdf_grid is not None and sdf_grid_cell_size is not None:
+        raise ValueError("sdf_grid (a GridSDF) and sdf_grid_cell_size (bake one from the primitives) exclude each other")
+    if sdf_grid is None and sdf_grid_cell_size is not None:
+        sdf_grid = dict(cell_size=float(sdf_grid_cell_size), mode=sdf_grid_mode)
     dataset = TrajectoryDataset(env_id=env_id, robot_id=robot if robot is not None else robot_id, use_extra_objects=True, obstacle_cutoff_margin=0.05,
                                 include_velocity=args["include_velocity"], tensor_args=tensor_args, sdf_grid=sdf_grid)
     n_support_points, robot, task = dataset.n_support_points, dataset.robot, dataset.task

@@ -298,7 +298,9 @@ class GridSDF:
 
     sdf    [nz, ny, nx] (3-D) or [ny, nx] (2-D) node values, x fastest; node (ix, iy, iz) sits at origin + (ix, iy, iz) * cell
     grad   None (linear mode needs none) or [..., dim] / [..., 4] node gradients, same leading shape as sdf
-    A grid to be baked on first use from primitives (`PlanningTask(sdf_grid=...)`) has sdf = None and carries `source` / `shape` instead."""
+    A grid to be baked on first use from primitives (`PlanningTask(sdf_grid=...)`) has sdf = None and carries `source` / `shape` instead.
+    A grid made from an occupancy map or a point cloud (`from_occupancy`, `from_points`: an exact Euclidean distance transform on the device,
+    mpdx_sdf_grid_from_occupancy) holds its planes on the device from the start and can be re-run in place (`update_occupancy`)."""
     sdf: Optional[torch.Tensor]
     origin: np.ndarray
     cell: float
@@ -306,6 +308,7 @@ class GridSDF:
     grad: Optional[torch.Tensor] = None
     source: Optional[ObjectSet] = None      # bake from these primitives (mpdx_sdf_grid_bake) when sdf is None
     shape: Optional[tuple] = None           # (nx, ny[, nz]) of a grid still to be baked
+    inflate: float = 0.0                    # occupancy grids: every obstacle thickened by this much (a point cloud has no thickness of its own)
 
     def __post_init__(self):
         if self.mode not in GRID_MODES:
@@ -332,6 +335,8 @@ class GridSDF:
         if len(self.shape) != self.origin.size or min(self.shape) < 2:
             raise ValueError("GridSDF: one origin coordinate per axis and at least 2 nodes along every axis")
         self._planes = None
+        self._occ = None      # occupancy grids: the byte map [n_nodes] and the transform's workspace, both on the device of the planes
+        self._ws = None
 
     @property
     def dim(self) -> int:
@@ -344,6 +349,11 @@ class GridSDF:
     def planes(self, device):
         """(sdf plane [n_nodes] fp32, gradient plane [n_nodes * 4] fp32 or None) on `device`, baked there first if need be."""
         device = torch.device(device)
+        if self._occ is not None:   # an occupancy grid lives where it was made: the planes update_occupancy writes are the planes every user reads
+            here = self._planes[0].device
+            if device.type != here.type or device.index not in (None, here.index):
+                raise RuntimeError(f"this GridSDF was made from an occupancy map on {here}; it is not copied to {device}")
+            return self._planes
         if self._planes is not None and self._planes[0].device == device:
             return self._planes
         if self.sdf is None:
@@ -381,11 +391,113 @@ class GridSDF:
             torch.cuda.current_stream().synchronize()   # (prims may be freed after this)
         return sdf, grad
 
+    # ---- occupancy maps and point clouds: the exact Euclidean distance transform of csrc/edt.hpp (arithmetic in include/mpdx.h)
+    @classmethod
+    def _empty_occupancy(cls, shape, origin, cell, mode, inflate, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("a signed-distance grid is made from an occupancy map on the GPU (mpdx_sdf_grid_from_occupancy); there is no CPU fallback")
+        if not (float(inflate) >= 0 and np.isfinite(float(inflate))):
+            raise ValueError("GridSDF inflate must be non-negative and finite")
+        rev = tuple(reversed([int(v) for v in shape]))
+        sdf = torch.empty(rev, dtype=torch.float32, device=device)
+        grad = torch.empty(rev + (4,), dtype=torch.float32, device=device) if mode == "nearest" else None   # linear mode reads none
+        g = cls(sdf, origin, cell, mode=mode, grad=grad, inflate=float(inflate))
+        g._occ = torch.zeros(g.n_nodes, dtype=torch.uint8, device=device)
+        n = g._n3()
+        g._ws = torch.empty(max(1, _lib.load().mpdx_sdf_grid_edt_ws_bytes(n) // 4), dtype=torch.int32, device=device)
+        g._planes = (g.sdf.reshape(-1), None if grad is None else g.grad.reshape(-1))
+        return g
+
+    @classmethod
+    def from_occupancy(cls, occ, origin, cell, mode="linear", inflate=0.0, device="cuda"):
+        """occ: bool / uint8 array or tensor [ny, nx] or [nz, ny, nx] (x fastest; non-zero = occupied; node (ix, iy, iz) is the voxel centre
+        origin + i * cell).  Returns a GridSDF whose planes already live on `device`; the gradient plane is written for mode='nearest' only."""
+        occ = _occupancy_bytes(occ)
+        g = cls._empty_occupancy(tuple(reversed(occ.shape)), origin, cell, mode, inflate, device)
+        g._occ.copy_(occ.reshape(-1))
+        g._transform()
+        return g
+
+    @classmethod
+    def from_points(cls, points, ws_min, ws_max, cell_size, padding=0.3, mode="linear", inflate=0.0, device="cuda"):
+        """points [P, 3] (z ignored in 2-D), voxelised on the device into the grid box `grid_spec_for` places around the
+        workspace (a point outside the box, or with a non-finite coordinate, is dropped), then transformed."""
+        shape, origin = grid_spec_for(ws_min, ws_max, cell_size, padding)
+        g = cls._empty_occupancy(shape, origin, cell_size, mode, inflate, device)
+        g._voxelise(points)
+        g._transform()
+        return g
+
+    def update_occupancy(self, occ=None, points=None):
+        """Re-run the transform INTO THE PLANES THIS GRID ALREADY HOLDS (a perception loop): `occ` (same shape as before) replaces the map, `points`
+        are voxelised into it (into an empty map when occ is None).  A guide or task whose grid buffer is a concatenation of planes copies them
+        again with its refresh_grids(); where the single plane is used in place there is nothing to copy."""
+        if self._occ is None:
+            raise ValueError("update_occupancy: this GridSDF was not made by from_occupancy / from_points")
+        if occ is None and points is None:
+            raise ValueError("update_occupancy: give occ, points or both")
+        if occ is not None:
+            occ = _occupancy_bytes(occ)
+            if tuple(occ.shape) != tuple(reversed(self.shape)):
+                raise ValueError(f"update_occupancy: occ has shape {tuple(occ.shape)}, the grid {tuple(reversed(self.shape))} (the planes are re-used: same shape)")
+        if points is not None:
+            points = self._points(points)      # (both inputs are checked before the map is touched)
+        if occ is not None:
+            self._occ.copy_(occ.reshape(-1))
+        else:
+            self._occ.zero_()
+        if points is not None:
+            self._voxelise(points)
+        self._transform()
+        return self
+
+    def occupancy(self):
+        """the byte map [nz, ny, nx] | [ny, nx] on the device (None for a grid that was not made from one)"""
+        return None if self._occ is None else self._occ.reshape(tuple(reversed(self.shape)))
+
+    def _n3(self):
+        import ctypes as C
+        return (C.c_int * 3)(*(list(self.shape) + [1] * (3 - self.dim)))
+
+    def _points(self, points):
+        pts = torch.as_tensor(points)
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError(f"points are [P, 3] (z is ignored in 2-D), got {tuple(pts.shape)}")
+        return pts.to(device=self._occ.device, dtype=torch.float32).contiguous()
+
+    def _voxelise(self, points):
+        import ctypes as C
+        pts = self._points(points)
+        org = (C.c_float * 3)(*([float(v) for v in self.origin] + [0.0] * (3 - self.dim)))
+        with torch.cuda.device(self._occ.device):
+            _lib.check(_lib.load().mpdx_occupancy_from_points(pts.data_ptr(), int(pts.shape[0]), self._occ.data_ptr(), C.byref(self._n3()), C.byref(org),
+                                                              self.cell, _lib.current_stream()), "mpdx_occupancy_from_points")
+            pts.record_stream(torch.cuda.current_stream())
+
+    def _transform(self):
+        import ctypes as C
+        sdf, grad = self._planes
+        with torch.cuda.device(self._occ.device):
+            _lib.check(_lib.load().mpdx_sdf_grid_from_occupancy(self._occ.data_ptr(), sdf.data_ptr(), None if grad is None else grad.data_ptr(), None,
+                                                                C.byref(self._n3()), self.cell, self.inflate, self._ws.data_ptr(), self._ws.numel() * 4,
+                                                                _lib.current_stream()), "mpdx_sdf_grid_from_occupancy")
+
     def node_values(self, device="cuda"):
         """(sdf [nz, ny, nx] | [ny, nx], grad [..., 4] or None) as the kernels read them (downloaded by the tests for their fp64 reference)."""
         sdf, grad = self.planes(device)
         shp = tuple(reversed(self.shape))
         return sdf.reshape(shp), (None if grad is None else grad.reshape(shp + (4,)))
+
+
+def _occupancy_bytes(occ):
+    """bool / integer array or tensor [ny, nx] | [nz, ny, nx] -> contiguous uint8 tensor (non-zero = occupied), where it lives"""
+    occ = torch.as_tensor(occ)
+    if occ.dim() not in (2, 3):
+        raise ValueError("occupancy is [ny, nx] or [nz, ny, nx]")
+    if occ.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"occupancy is a bool or uint8 array (got {occ.dtype})")
+    return occ.to(torch.uint8).contiguous()
 
 
 def grid_spec_for(ws_min, ws_max, cell_size, padding=0.3, shift=0.37):
@@ -418,7 +530,8 @@ class PlanningTask:
         objects become a signed-distance grid (baked from the primitives on the device on first use, mpdx_sdf_grid_bake) and
         get_collision_fields() returns a FIELD_GRID field in their place; extra objects, workspace and self fields stay as they are (as
         torch_robotics does, as recalled: the precomputed grid is for the fixed objects only).  An environment that already carries a grid
-        (env.grid_fixed, set by task_from_torch_robotics) uses it as it is."""
+        (env.grid_fixed, set by task_from_torch_robotics) uses it as it is.  A `GridSDF` instance (GridSDF.from_occupancy / from_points, or node
+        values of the caller's own) is used as the objects field as it is, the way env.grid_fixed is."""
         self.env, self.robot, self.obstacle_cutoff_margin = env, robot, obstacle_cutoff_margin
         if isinstance(robot, RobotChain):
             if env.dim != 3:
@@ -427,8 +540,13 @@ class PlanningTask:
                 raise ValueError("a RobotChain takes primitive, workspace and self fields: no signed-distance grid")
         self.tensor_args = tensor_args or {"device": "cpu", "dtype": torch.float32}
         self.ws_min, self.ws_max = env.limits
-        self.sdf_grid = dict(sdf_grid) if sdf_grid is not None else None
-        if getattr(env, "grid_fixed", None) is not None:
+        given = sdf_grid if isinstance(sdf_grid, GridSDF) else None
+        self.sdf_grid = given if given is not None else dict(sdf_grid) if sdf_grid is not None else None
+        if given is not None:
+            if given.dim != env.dim:
+                raise ValueError(f"sdf_grid: a {given.dim}-D GridSDF for the {env.dim}-D workspace of {getattr(env, 'name', 'the environment')}")
+            self.df_collision_objects = CollisionField(_lib.FIELD_GRID, grid=given, name="objects")
+        elif getattr(env, "grid_fixed", None) is not None:
             self.df_collision_objects = CollisionField(_lib.FIELD_GRID, grid=env.grid_fixed, name="objects")
         elif self.sdf_grid is not None:
             unknown = set(self.sdf_grid) - {"cell_size", "mode", "padding"}
@@ -460,6 +578,12 @@ class PlanningTask:
                                                            [1.0] * len(costs), True, 128, True, 1.0, device)
             self._gp_grids = self._gp.grids_tensor   # (None without a grid field) kept alive next to the primitive table
         return self._gp
+
+    def refresh_grids(self):
+        """after GridSDF.update_occupancy: copy the planes again where the metrics' grid buffer is a concatenation (guides.refresh_grid_planes)"""
+        if getattr(self, "_gp", None) is not None:
+            from .guides import refresh_grid_planes
+            refresh_grid_planes(self._gp)
 
     def trajectory_metrics(self, trajs, n_check=None, return_mask=False):
         """trajs: UNNORMALISED [B,H,D] on the GPU -> float tensor [B,4]: (#colliding waypoints, path length, smoothness,
