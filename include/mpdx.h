@@ -88,9 +88,17 @@ int    mpdx_unet_plan_joined(const mpdx_unet* u);
  * host memory and never synchronise.  The window: the word is written while the plan's launches EXECUTE, so mpdx_plan's own return value only
  * covers launches that have already run when it returns; ask mpdx_unet_status after synchronising the stream to cover the whole plan.
  * mpdx_unet_set_status(u, 0) clears the word (the counters are re-zeroed before the next run); a non-zero word marks the handle failed as
- * a give-up would (bit 0 set, bits 8.. the layer of the run that waited). */
+ * a give-up would (bit 0 set, bits 8.. the layer of the run that waited).
+ *
+ * The tail run: under the same conditions the tail of up level 0 - the three 128 -> 128 Conv1dBlocks ups.0.0.blocks.1, ups.0.1.blocks.0,
+ * ups.0.1.blocks.1 and Upsample1d(128) - is a second persistent launch of the same kind (same counters, status word, bounds and bit-identical results).
+ * mpdx_unet_set_inner_run(u, 1) selects every run that is eligible, 0 none.  mpdx_unet_set_inner_run_parts selects them separately: bit 0 the seven
+ * layers, bit 1 the tail (A/B runs and tests; other bits: MPDX_E_INVALID).  mpdx_unet_inner_runs counts the seven-layer launches only;
+ * mpdx_unet_inner_run_layers: how many layers ran inside run launches of either kind in the last mpdx_plan call (11 per pass with both selected). */
 int    mpdx_unet_set_inner_run(mpdx_unet* u, int on);
+int    mpdx_unet_set_inner_run_parts(mpdx_unet* u, int parts);
 int    mpdx_unet_inner_runs(const mpdx_unet* u);
+int    mpdx_unet_inner_run_layers(const mpdx_unet* u);
 int    mpdx_unet_status(const mpdx_unet* u);
 int    mpdx_unet_set_status(mpdx_unet* u, unsigned word);
 /* number of state-dict tensors the model expects; their names/shapes (identical to the reference's keys) */
@@ -591,7 +599,9 @@ int mpdx_unet_profile(mpdx_unet* u, const float* packed_dev, const float* timeta
 /* dev tool: per-phase s_memtime stamps (7 each) of the first and the last workgroup of one launch of layer `layer` */
 int mpdx_layer_trace(mpdx_unet* u, const float* packed_dev, const float* timetab_dev, const float* x, int layer, int B, float* ws,
                      void* stream, long long* stamps32);
-/* dev tool: per-phase s_memtime stamps (workgroup 0; 8 waves x 128 slots) of one launch of fused segment `seg` */
+/* dev tool: per-phase s_memtime stamps (workgroup 0; 8 waves x 128 slots) of one launch of fused segment `seg`; seg == number of segments: the
+ * joined launch; + 1 / + 2: the seven-layer run / the tail run of mpdx_plan - 32 slots per layer, ten stamps of workgroup 0 / thread 0 each (entry,
+ * requests issued, predecessor published, staging issued, staged, k-loop, all waves, partials visible, epilogue, published); *nops_out = its layers */
 int mpdx_fused_trace(mpdx_unet* u, const float* packed_dev, const float* timetab_dev, const float* x, int seg, int B,
                      float* ws, void* stream, long long* stamps_out, int cap, int* n_out, int* nops_out);
 /* in-situ timing of launch units [unit_first, unit_last] inside `reps` real U-Net passes (one event pair per pass around the

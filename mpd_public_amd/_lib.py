@@ -93,7 +93,9 @@ SIGNATURES = {
     "mpdx_unet_set_plan_join": (_i, [_vp, _i]),
     "mpdx_unet_plan_joined": (_i, [_vp]),
     "mpdx_unet_set_inner_run": (_i, [_vp, _i]),
+    "mpdx_unet_set_inner_run_parts": (_i, [_vp, _i]),
     "mpdx_unet_inner_runs": (_i, [_vp]),
+    "mpdx_unet_inner_run_layers": (_i, [_vp]),
     "mpdx_unet_status": (_i, [_vp]),
     "mpdx_unet_set_status": (_i, [_vp, C.c_uint]),
     "mpdx_unet_num_params": (_i, [_vp]),

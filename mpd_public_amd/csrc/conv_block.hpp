@@ -273,14 +273,22 @@ struct RunCtx {
     unsigned target = 0;
     int wait = 0;            // 0: the run's first layer (its inputs come from earlier launches)
     long long budget = 0;    // s_memtime ticks a poll may take before the workgroup gives up
+    // 16-channel tiles only (MT == 16 on 128 channels, 8 positions): tensors handed over INSIDE the run are kept tile-major, [B][C / 16][8][16], so that a
+    // workgroup's 16 channels of a trajectory are 512 contiguous bytes and every 128-byte line is written whole by one store instruction of one wave
+    // (in [B][8][C] two workgroups on different CUs - under load on different XCDs - would each write-through half of every line).
+    // Bit 0: src1 is tile-major, bit 1: res, bit 2: dst.  The values do not change, only where they lie.
+    int tiled = 0;
 };
+// float offset of element (position row pos = b * 8 + l, channel c) of a tile-major [B][8][8][16] tensor
+__device__ __forceinline__ int run_tiled_off(int pos, int c) { return ((pos >> 3) << 10) + ((c >> 4) << 7) + ((pos & 7) << 4) + (c & 15); }
 constexpr unsigned kRunPoison = 0x10000000u;        // a workgroup that gave up stores target + this into the counter: its peers leave their polls at once
 constexpr unsigned kRunPoisonSeen = 0x08000000u;    // a counter this far PAST its target is poisoned (an honest one is at most 8 x layers past it)
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // TBRES: what a GroupNorm epilogue adds behind Mish, when known at compile time (-1: read the pointers; 0 nothing, 1 time bias, 2 residual)
-// RUN (inner_run.hpp; EPI_GN_MISH on GeoL8 with one GroupNorm group per channel tile, TBRES -1, exactly one of time bias / residual): the layer is one of
+// RUN (inner_run.hpp; EPI_GN_MISH on GeoL8 with one GroupNorm group per channel tile - MT == 32: regions of 256 elements, MT == 16: of 128 -, TBRES -1,
+// exactly one of time bias / residual; or CONV_UPT with EPI_BIAS on GeoUp8 as a run's LAST layer: plain stores, one destination): the layer is one of
 // a run.  The arithmetic and every summation order are the ones of RUN = false; what changes is how bytes move between workgroups (recipe R1 of
 // write-through stores + counter, sc1 loads in place of an acquire):
 //   - every load of bytes another workgroup may have written in this launch (the staged window, the residual tile) is a buffer load with sc1;
@@ -374,16 +382,30 @@ __device__ __forceinline__ bool conv_block_body(const ConvArgs& a, const int blo
 #endif
     // RUN: what does not depend on the layer before - requested / done while its last workgroups are still publishing
     f32x4 run_bi = {0.f, 0.f, 0.f, 0.f}, run_ga = run_bi, run_be = run_bi, run_tb = run_bi;
+    f32x2 run_bi2 = {0.f, 0.f}, run_ga2 = run_bi2, run_be2 = run_bi2, run_tb2 = run_bi2;   // the same for regions of 128 elements (MT == 16)
+    constexpr bool RUN_UP = RUN && MODE == CONV_UPT;   // the transposed conv with the bias epilogue: a run's LAST layer
     if constexpr (RUN) {
-        static_assert(GK && MODE == CONV_S1 && EPI == EPI_GN_MISH && TBRES < 0 && WN == 1, "a run layer: stride-1 GroupNorm block with compile-time geometry");
+        static_assert(GK && TBRES < 0 && WN == 1 && ((MODE == CONV_S1 && EPI == EPI_GN_MISH && (MT == 32 || MT == 16)) || (MODE == CONV_UPT && EPI == EPI_BIAS)),
+                      "a run layer: stride-1 GroupNorm block or transposed conv + bias, compile-time geometry");
 #ifndef MPDX_RING_FIRST
         ring_init();
 #endif
+        if constexpr (RUN_UP) {
+            // (the bias epilogue's channel of a thread does not depend on its position: NTHR is a multiple of MT / 4)
+            static_assert(NTHR % (MT / 4) == 0 && NT * (MT / 4) <= NTHR, "bias epilogue: one element per thread");
+            run_bi = *(const f32x4*)(a.bias + mt * MT + (tid & (MT / 4 - 1)) * 4);
+        } else if constexpr (MT == 32) {
         // (one GroupNorm group per channel tile - gs == MT, checked on the host: the epilogue's channel of a lane does not depend on the region)
         const int co = mt * MT + ((lane * 4) & (MT - 1));
         run_bi = *(const f32x4*)(a.bias + co);
         run_ga = *(const f32x4*)(a.gamma + co); run_be = *(const f32x4*)(a.beta + co);
         run_tb = *(const f32x4*)((a.tbias ? a.tbias : a.bias) + co);   // (unconditional load: a load in a branch costs a vmcnt(0))
+        } else {   // regions of 128 elements: two channels per lane
+            const int co = mt * MT + ((lane * 2) & (MT - 1));
+            run_bi2 = *(const f32x2*)(a.bias + co);
+            run_ga2 = *(const f32x2*)(a.gamma + co); run_be2 = *(const f32x2*)(a.beta + co);
+            run_tb2 = *(const f32x2*)((a.tbias ? a.tbias : a.bias) + co);
+        }
         {   // zero halo rows (the staging phase's loop, below)
             constexpr int P2 = 2 * PAD;
             const int htot = (spt * P2) << lg_c4n;
@@ -399,7 +421,9 @@ __device__ __forceinline__ bool conv_block_body(const ConvArgs& a, const int blo
             // ONE wave polls the tile's counter (relaxed, agent scope: global_load_dword sc1), then the workgroup barrier, then every wave's sc1 loads.
             // `>= target` as a signed difference, not `== target`: a peer that has seen the target may add its NEXT arrival before a slow poller
             // looks again, and the counters are never reset (base wraps around).
-            int* const flag = (int*)(smem + (GEO::NC16 * 16 + GEO::RSPAD) * (NT / GEO::L) * (GEO::L + 2 * PAD));   // behind the staged window
+            // behind the larger of the staged window and the K-partial buffer (the transposed conv's 8 x 64 x 20 partials outgrow its window)
+            constexpr int STAGE_FL = (GEO::NC16 * 16 + GEO::RSPAD) * (NT / GLO) * (GEO::L + 2 * PAD), RED_FL = WK * NT * MTP;
+            int* const flag = (int*)(smem + (STAGE_FL > RED_FL ? STAGE_FL : RED_FL));
             if (wave == 0) {
                 const long long t0 = (long long)__builtin_amdgcn_s_memtime();
                 int ok;
@@ -457,6 +481,10 @@ __device__ __forceinline__ bool conv_block_body(const ConvArgs& a, const int blo
             for (int u = 0; u < SB; ++u) {
                 if constexpr (RUN) {   // one source of C_in channels (checked on the host), read past this CU's L1
                     const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc((void*)a.src1, 0, 0x7fffffff, 0x00020000);
+                    if constexpr (GEO::NC16 == 8) {   // (a 128-channel source may be tile-major: RunCtx::tiled)
+                        const int fo = (rc.tiled & 1) ? run_tiled_off((int)pos[u], cc[u]) : (int)(pos[u] * (GEO::NC16 * 16) + cc[u]);
+                        v[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srs, fo * 4, 0, 16));
+                    } else
                     v[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srs, (int)(pos[u] * (GEO::NC16 * 16) + cc[u]) * 4, 0, 16));
                 } else if constexpr (VEC) {
                     const float* src = (cc[u] < a.c1) ? a.src1 + pos[u] * a.c1 + cc[u] : a.src2 + pos[u] * a.c2 + (cc[u] - a.c1);
@@ -781,6 +809,40 @@ __device__ __forceinline__ bool conv_block_body(const ConvArgs& a, const int blo
         for (int r = wave; r < nreg; r += NWAVE) {
             const int s = r >> lg_gpt, gl = r & (gpt - 1);
             const int b = s0 + s;
+            if constexpr (RUN && MT == 16) {
+                // the re == 128 arithmetic below, operand for operand (gs == MT == 16 on 8 positions), moved as in the re == 256 run layer
+                const int e0 = lane * 2;
+                const int l = e0 >> a.lg_gs, c = gl * gs + (e0 & (gs - 1));
+                const int n = s * L_out + l, co = mt * MT + c;
+                const int bb = b < a.B ? b : 0;
+                const int o = (bb * L_out + l) * a.C_out + co;                      // [B][8][C]
+                const int ot = run_tiled_off(bb * 8 + l, co);                        // tile-major (RunCtx::tiled)
+                const int o_res = (rc.tiled & 2) ? ot : o, o_dst = (rc.tiled & 4) ? ot : o;
+                // (two 4-byte loads: the residual tile is handed-off bytes, and the forms measured for them are 4- and 16-byte sc1 loads)
+                const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.res ? a.res : a.src1), 0, 0x7fffffff, 0x00020000);
+                f32x2 rs2;
+                rs2[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrs, (a.res ? o_res : 0) * 4, 0, 16));
+                // (the second one's 4 bytes are a scalar offset: hipcc merges two loads that differ in the immediate into one 8-byte load)
+                rs2[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrs, (a.res ? o_res : 0) * 4, __builtin_amdgcn_readfirstlane(4), 16));
+                const f32x2 ex = has_tb ? run_tb2 : rs2;
+                f32x2 v = *(const f32x2*)(red + (size_t)n * MTP + c);
+#pragma unroll
+                for (int k = 1; k < WK; ++k) v += *(const f32x2*)(red + ((size_t)(k * NT + n)) * MTP + c);
+                v += run_bi2;
+                const float mean = wave_sum(v[0] + v[1]) * inv_re;
+                const f32x2 d = v - mean;
+                const float var = wave_sum(d[0] * d[0] + d[1] * d[1]) * inv_re;
+                const float rstd = gn_rstd(var);
+                f32x2 y;
+#pragma unroll
+                for (int e = 0; e < 2; ++e) y[e] = mish_nosel(d[e] * rstd * run_ga2[e] + run_be2[e]);
+                y += ex;
+                if (b < a.B) {
+                    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+                    const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc((void*)a.dst, 0, 0x7fffffff, 0x00020000);
+                    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, y), drs, o_dst * 4, 0, 16);
+                }
+            } else
             if constexpr (RUN) {
                 // the re == 256 arithmetic below, operand for operand; bias / gamma / beta / time bias were requested before the poll, the residual
                 // tile (written in this launch) is read with sc1, the output stored write-through
@@ -873,6 +935,13 @@ __device__ __forceinline__ bool conv_block_body(const ConvArgs& a, const int blo
             f32x4 v = smem4[ri];
 #pragma unroll
             for (int k = 1; k < WK; ++k) v += smem4[ri + k * NT * MTP4];
+            if constexpr (RUN_UP) {
+                // one destination, whole horizon, nothing added (checked on the host); the bias was requested before the poll.  A plain store: the
+                // consumer is the next launch.
+                v += run_bi;
+                if (b < a.B) *(f32x4*)(a.dst + ((size_t)b * L_out + l) * a.C_out + co) = v;
+                continue;
+            }
             v += *(const f32x4*)(a.bias + co);
             float* d = a.dst;
             int ld = a.C_out, cc = co;

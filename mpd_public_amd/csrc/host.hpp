@@ -119,12 +119,17 @@ struct mpdx_unet {
     int Hc = 0, xpad_slot = -1;
     bool masked() const { return Hc != cfg.n_support_points; }
     int plan_join = 1;        // mpdx_unet_set_plan_join: mpdx_plan may run a step's up program and the next step's down program as one launch
-    int inner_run = 1;        // mpdx_unet_set_inner_run: mpdx_plan may run the seven 256 -> 256 layers of the innermost level as one persistent launch (inner_run.hpp)
-    int plan_joined = 0, inner_runs = 0;   // joined / run launches of the last mpdx_plan call (mpdx_unet_plan_joined, mpdx_unet_inner_runs)
+    // mpdx_unet_set_inner_run / _set_inner_run_parts: the runs mpdx_plan may take (inner_run.hpp) - kRunSeven: the seven 256 -> 256 layers of the
+    // innermost level, kRunTail: the tail of up level 0 - as one persistent launch each
+    enum RunPart { kRunSeven = 1, kRunTail = 2 };
+    int inner_run = kRunSeven | kRunTail;
+    int plan_joined = 0, inner_runs = 0;   // joined / seven-layer run launches of the last mpdx_plan call (mpdx_unet_plan_joined, mpdx_unet_inner_runs)
+    int inner_run_layers = 0;              // layers that ran inside run launches of either kind in the last mpdx_plan call (mpdx_unet_inner_run_layers)
     // The run's device state, made at the first mpdx_plan call that may take the run (a handle is created without a device).  mpdx.hip's
     // inner_run_create / _begin / _free and mpdx_unet_set_status alone write it: every counter of a launch's clusters holds `base` when the launch starts.
     struct InnerRunState {
         int capacity = -1;            // workgroups of the run kernel resident at once on this device (-1: not asked yet; 0: none - no run)
+        bool seven_ok = false, tail_ok = false;   // each run kernel answered its own occupancy query: one workgroup per compute unit fits
         long long budget = 0;         // s_memtime ticks of 4 ms
         unsigned* counters = nullptr; // device: one arrival counter per cluster (not reset between launches: base advances by 8 x layers per launch)
         unsigned base = 0;
@@ -155,8 +160,8 @@ struct mpdx_unet {
     const float* streams_for = nullptr; // `packed` buffer the fused streams were last assembled in
     int pack_version = 0, streams_version = -1;
     // one launch of a pass: it covers layers [layer, layer + count) - a program its segment fused[fused], a pair blocks[0] + the block's residual 1x1
-    // conv, the inner run (mpdx_plan's schedule only, never in current_units) its kInnerRunLayers
-    enum UnitKind { kProgram, kLayer, kPair, kInnerRun };
+    // conv, the inner run and the tail run (mpdx_plan's schedule only, never in current_units) their kInnerRunLayers / kTailRunLayers
+    enum UnitKind { kProgram, kLayer, kPair, kInnerRun, kTailRun };
     struct Unit { UnitKind kind; int fused; int layer; int count; };
     std::vector<int> owner;                  // layer -> fused segment (-1: per-layer launch)
     // training (train_host.hpp)
@@ -192,10 +197,12 @@ int launch_conv_layer(const Layer& l, ConvArgs& a, int B, hipStream_t st);
 bool pair_tile(const Layer& l1, const Layer& l2, int B, int& MT, int& NT);   // (mpdx.hip) do blocks[0] + the block's residual 1x1 conv run as one launch, on which tile?
 int launch_conv_pair(int MT, int NT, const ConvArgs& a1, const ConvArgs& a2, const Layer& l1, const Layer& l2, hipStream_t st);   // 1 launched, 0 does not fit, -1 error
 // ---- k_inner_run.hip: the persistent run of the innermost level's 256 -> 256 layers (inner_run.hpp)
-struct InnerRunArgs;
-int inner_run_grid(int B);                 // workgroups of a launch for batch B (the placement's surplus ones included)
-int inner_run_workgroups_per_cu();         // one occupancy query; 0: failed
-int launch_inner_run(const InnerRunArgs& ra, int B, hipStream_t st);
+template <int N> struct RunArgs;
+int inner_run_grid(int B);                 // workgroups of a launch for batch B (the placement's surplus ones included); the same for both runs
+int inner_run_workgroups_per_cu();         // one occupancy query per run kernel; 0: failed
+int tail_run_workgroups_per_cu();
+int launch_inner_run(const RunArgs<7>& ra, int B, hipStream_t st);   // InnerRunArgs
+int launch_tail_run(const RunArgs<4>& ra, int B, hipStream_t st);    // TailRunArgs
 // ---- k_attn.hip: the linear self-attention block (attn.hpp); a.x and the five parameter pointers set by the caller
 struct AttnArgs;
 const char* attn_unsupported(int C, int L);   // null, or why attn_kernel cannot run a level of C channels on L positions

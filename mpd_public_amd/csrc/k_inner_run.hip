@@ -1,4 +1,4 @@
-// k_inner_run.hip - the persistent run of the innermost level's 256 -> 256 layers (inner_run.hpp) behind two plain functions.
+// k_inner_run.hip - the persistent runs of inner-level layers (inner_run.hpp: the seven 256 -> 256 layers, the tail of up level 0) behind plain functions.
 #include "host.hpp"
 #include "inner_run.hpp"
 
@@ -16,20 +16,26 @@ int inner_run_grid(int B) {
     return kSameXcd ? ((nc + 7) / 8) * 64 : nc * 8;
 }
 
-// workgroups of the run kernel one compute unit holds at once (0: the query failed - the run is then never selected)
-int inner_run_workgroups_per_cu() {
+template <class SEQ>
+static int workgroups_per_cu() {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)inner_run_kernel<kSameXcd>, 512, kInnerRunLds) != hipSuccess) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)inner_run_kernel<SEQ, kSameXcd>, 512, SEQ::lds()) != hipSuccess) {
         (void)hipGetLastError();
         return 0;
     }
     return n;
 }
+// workgroups of a run kernel one compute unit holds at once (0: the query failed - that run is then never selected)
+int inner_run_workgroups_per_cu() { return workgroups_per_cu<RunSeqSeven>(); }
+int tail_run_workgroups_per_cu() { return workgroups_per_cu<RunSeqTail>(); }
 
-int launch_inner_run(const InnerRunArgs& ra, int B, hipStream_t st) {
-    if (ra.n_layers < 1 || ra.n_layers > kInnerRunLayers || ra.nc != (B + 3) / 4) return fail(MPDX_E_INVALID, "inner run: %d layers, %d clusters for B=%d", ra.n_layers, ra.nc, B);
-    hipLaunchKernelGGL(inner_run_kernel<kSameXcd>, dim3(inner_run_grid(B)), dim3(512), kInnerRunLds, st, ra);
+template <class SEQ>
+static int launch_run(const typename SEQ::Args& ra, int B, hipStream_t st, const char* what) {
+    if (ra.n_layers != SEQ::kLayers || ra.nc != (B + 3) / 4) return fail(MPDX_E_INVALID, "%s: %d layers, %d clusters for B=%d", what, ra.n_layers, ra.nc, B);
+    hipLaunchKernelGGL((inner_run_kernel<SEQ, kSameXcd>), dim3(inner_run_grid(B)), dim3(512), SEQ::lds(), st, ra);
     return 0;
 }
+int launch_inner_run(const InnerRunArgs& ra, int B, hipStream_t st) { return launch_run<RunSeqSeven>(ra, B, st, "inner run"); }
+int launch_tail_run(const TailRunArgs& ra, int B, hipStream_t st) { return launch_run<RunSeqTail>(ra, B, st, "tail run"); }
 
 }  // namespace mpdx

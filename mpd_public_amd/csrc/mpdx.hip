@@ -808,9 +808,11 @@ static int inner_run_create(mpdx_unet::InnerRunState& r, int cus) {
     if (r.capacity >= 0) return 0;
     r.capacity = 0;
     int dev = 0, khz = 0;
-    if (cus <= 0 || hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeClockRate, dev) != hipSuccess ||
-        inner_run_workgroups_per_cu() <= 0)
+    if (cus <= 0 || hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeClockRate, dev) != hipSuccess)
         return (void)hipGetLastError(), 0;
+    r.seven_ok = inner_run_workgroups_per_cu() > 0;
+    r.tail_ok = tail_run_workgroups_per_cu() > 0;
+    if (!r.seven_ok && !r.tail_ok) return 0;
     HIP_TRY(hipMalloc((void**)&r.counters, inner_run_counter_bytes(cus)));
     HIP_TRY(hipMemset(r.counters, 0, inner_run_counter_bytes(cus)));
     HIP_TRY(hipHostMalloc((void**)&r.status, 64, hipHostMallocMapped));
@@ -822,14 +824,16 @@ static int inner_run_create(mpdx_unet::InnerRunState& r, int cus) {
 }
 // A launch of nc clusters starts.  It advances the counters of ITS clusters only, so a batch with more clusters than the launch before (or a give-up's
 // poison) zeroes them all, stream-ordered, and starts from base 0 again: at most once per plan.  Layer i > 0 waits for *base_out + 8 i: 8 arrivals per layer.
-static int inner_run_begin(mpdx_unet::InnerRunState& r, int nc, hipStream_t st, unsigned* base_out) {
+// The handle's runs share the counters: each launch of n_layers layers leaves its clusters' counters at its base + 8 n_layers, the base of the next
+// launch of either kind (launches of one plan are stream-ordered and cover the same clusters).
+static int inner_run_begin(mpdx_unet::InnerRunState& r, int nc, int n_layers, hipStream_t st, unsigned* base_out) {
     if (r.rezero || nc > r.live) {
         HIP_TRY(hipMemsetAsync(r.counters, 0, inner_run_counter_bytes(r.capacity), st));
         r.base = 0; r.rezero = false;
     }
     r.live = nc;
     *base_out = r.base;
-    r.base += 8u * kInnerRunLayers;
+    r.base += 8u * (unsigned)n_layers;
     return 0;
 }
 static void inner_run_free(mpdx_unet::InnerRunState& r) {
@@ -843,19 +847,39 @@ static int handle_status_error(const mpdx_unet* u, const char* fn) {
                 "mpdx_unet_set_status(u, 0) clears the word", fn, w, w >> 8);
 }
 // mpdx_plan only: the seven 256 -> 256 Conv1dBlocks of the innermost level, layers [first, first + kInnerRunLayers), as ONE persistent launch (inner_run.hpp)
-static int run_inner_run(mpdx_unet* u, int first, const float* packed, const float* row, const float* x, float* ws, int B, hipStream_t st) {
-    InnerRunArgs ra;
+static long long* g_run_trace = nullptr;   // dev tool (mpdx_fused_trace on a run): kRunTraceSlots stamps per layer of the run kind g_run_trace_kind
+static int g_run_trace_kind = -1;
+constexpr int kRunTraceSlots = 32;
+template <int N>
+static int fill_run_args(mpdx_unet* u, int kind, int first, const float* packed, const float* row, const float* x, float* ws, int B, hipStream_t st, RunArgs<N>& ra) {
     memset(&ra, 0, sizeof(ra));
-    for (int k = 0; k < kInnerRunLayers; ++k) {
+    for (int k = 0; k < N; ++k) {
         if (int rc = make_conv_args(u, u->layers[first + k], packed, row, x, ws, B, 0, ra.layer[k])) return rc;
         ra.layer[k].n_tiles_n = (B + 3) / 4;
-        ra.layer[k].trace = nullptr;
+        ra.layer[k].trace = g_run_trace && g_run_trace_kind == kind ? g_run_trace + k * kRunTraceSlots : nullptr;
     }
-    ra.n_layers = kInnerRunLayers; ra.nc = (B + 3) / 4;
-    if (int rc = inner_run_begin(u->run, ra.nc, st, &ra.base)) return rc;
+    ra.n_layers = N; ra.nc = (B + 3) / 4;
+    if (int rc = inner_run_begin(u->run, ra.nc, N, st, &ra.base)) return rc;
     ra.counters = u->run.counters; ra.status = u->run.status_dev; ra.budget = u->run.budget;
+    u->inner_run_layers += N;
+    return 0;
+}
+static int run_inner_run(mpdx_unet* u, int first, const float* packed, const float* row, const float* x, float* ws, int B, hipStream_t st) {
+    InnerRunArgs ra;
+    if (int rc = fill_run_args(u, mpdx_unet::kInnerRun, first, packed, row, x, ws, B, st, ra)) return rc;
     u->inner_runs++;
     return launch_inner_run(ra, B, st);
+}
+// mpdx_plan only: the tail of up level 0 - three 128 -> 128 Conv1dBlocks and Upsample1d(128), layers [first, first + kTailRunLayers) - as ONE persistent
+// launch (inner_run.hpp).  It does not count in mpdx_unet_inner_runs.
+static int run_tail_run(mpdx_unet* u, int first, int spare, const float* packed, const float* row, const float* x, float* ws, int B, hipStream_t st) {
+    TailRunArgs ra;
+    if (spare < 0 || spare >= u->n_slots) return fail(MPDX_E_STATE, "tail run without a spare slot");
+    if (int rc = fill_run_args(u, mpdx_unet::kTailRun, first, packed, row, x, ws, B, st, ra)) return rc;
+    // layer 0's output, private to the run (layer 1's input, layer 2's residual), lives in the spare slot: tail_run_first says why
+    float* const sp = ws + u->slot_floats * (size_t)B * spare;
+    ra.layer[0].dst = sp; ra.layer[1].src1 = sp; ra.layer[2].res = sp;
+    return launch_tail_run(ra, B, st);
 }
 
 // one launch unit of the pass (the SAME function serves the planning path, the profiler and the in-situ timer)
@@ -864,6 +888,7 @@ static int run_unit(mpdx_unet* u, const mpdx_unet::Unit& un, const float* packed
     if (un.kind == mpdx_unet::kProgram) return run_fused(u, u->fused[un.fused], packed, row, x, ws, B, fa, st);
     if (un.kind == mpdx_unet::kPair) return run_pair(u, u->layers[un.layer], u->layers[un.layer + 1], packed, row, x, ws, B, st);
     if (un.kind == mpdx_unet::kInnerRun) return run_inner_run(u, un.layer, packed, row, x, ws, B, st);
+    if (un.kind == mpdx_unet::kTailRun) return run_tail_run(u, un.layer, un.fused, packed, row, x, ws, B, st);
     return run_layer(u, u->layers[un.layer], packed, row, x, ws, B, st);
 }
 static double unit_flops(const mpdx_unet* u, const mpdx_unet::Unit& un, int B) {
@@ -976,6 +1001,74 @@ static int inner_run_first(const mpdx_unet* u, const std::vector<mpdx_unet::Unit
     }
     return -1;
 }
+// First of the kTailRunLayers consecutive single-layer units the tail run (inner_run.hpp) can stand for, or -1: three K-split 128 -> 128 Conv1dBlocks
+// on 8 positions (one GroupNorm group per 16-channel tile, one source, exactly one of time bias / residual), then Upsample1d(128) on 8 -> 16 positions
+// over the whole horizon.  (make_conv_args leaves pre / accum / dst2 / c_split / decim / stuff zero on the planning path: what the GeoUp8 launch asks.)
+// *spare: the workspace slot layer 0's output goes to inside the run (below).
+static int tail_run_first(const mpdx_unet* u, const std::vector<mpdx_unet::Unit>& units, int* spare) {
+    *spare = -1;
+    auto layer_of = [&](const mpdx_unet::Unit& un) -> const Layer* {
+        if (un.kind != mpdx_unet::kLayer) return nullptr;
+        const Layer& l = u->layers[un.layer];
+        if (l.attn || l.Lv_out || !(l.c1 == 128 && l.c2 == 0 && l.src2 == SRC_NONE && l.cout == 128 && l.L_in == 8 && l.cin_pad == 128)) return nullptr;
+        return &l;
+    };
+    auto fits_gn = [&](const mpdx_unet::Unit& un) {
+        const Layer* l = layer_of(un);
+        if (!l || !(l->mode == CONV_S1 && l->ks == 5 && l->epi == EPI_GN_MISH && l->L_out == 8 && l->gs == 16 && l->rs == 136)) return false;
+        if ((l->tb_off >= 0) == (l->res != SRC_NONE)) return false;   // exactly one of time bias / residual
+        return layer_ksplit(*l);
+    };
+    auto fits_up = [&](const mpdx_unet::Unit& un) {
+        const Layer* l = layer_of(un);
+        return l && l->mode == CONV_UPT && l->ks == 4 && l->epi == EPI_BIAS && l->L_out == 16 && l->rs == 132 && l->res == SRC_NONE && l->tb_off < 0;
+    };
+    const int n = (int)units.size();
+    for (int i = 0; i + kTailRunLayers <= n; ++i) {
+        int k = 0;
+        while (k < kTailRunLayers - 1 && fits_gn(units[i + k])) ++k;
+        if (!(k == kTailRunLayers - 1 && fits_up(units[i + k]))) continue;
+        // The three GroupNorm outputs are handed over tile-major inside the launch (RunCtx::tiled, RunSeqTail::tiled): the dataflow must be the one that
+        // pattern is written for - a chain, layer 2's residual layer 0's output, layer 0 fed from earlier launches - and no layer behind the run may
+        // read one of those three slots before it is written again.
+        const int f = units[i].layer;
+        const Layer &l0 = u->layers[f], &l1 = u->layers[f + 1], &l2 = u->layers[f + 2], &l3 = u->layers[f + 3];
+        if (units[i + 1].layer != f + 1 || units[i + 2].layer != f + 2 || units[i + 3].layer != f + 3) continue;
+        if (!(l1.src1 == l0.dst && l2.src1 == l1.dst && l2.res == l0.dst && l3.src1 == l2.dst && l0.res != SRC_NONE && l1.res == SRC_NONE)) continue;
+        std::vector<int> kept = {l0.dst, l1.dst, l2.dst};   // slots that hold tile-major bytes when the run ends
+        auto drop = [&](int s) { kept.erase(std::remove(kept.begin(), kept.end(), s), kept.end()); };
+        auto held = [&](int s) { return std::find(kept.begin(), kept.end(), s) != kept.end(); };
+        // (layer 0's own inputs come from earlier launches in [B][L][C]; a later layer of the run may reuse their slots, as between per-layer launches)
+        if (l0.dst == l1.dst || l1.dst == l2.dst || l0.dst == l2.dst) continue;
+        drop(l3.dst);
+        bool read_later = false;
+        for (int j = f + kTailRunLayers; j < (int)u->layers.size() && !read_later; ++j) {
+            const Layer& l = u->layers[j];
+            read_later = held(l.src1) || held(l.src2) || held(l.res);
+            drop(l.dst);
+        }
+        if (read_later || held(u->final_slot)) continue;
+        // Upsample1d's output is twice a trajectory's size of the other tensors: in its slot, trajectory b lies where trajectories 2 b and 2 b + 1 of a
+        // [B][8][128] tensor lie, and those belong to ANOTHER cluster, which may still be reading them (the slot plan gives it layer 0's output slot: safe
+        // only where layer 3 starts after ALL of layer 2).  So layer 0's output - private to the run - goes to a spare slot instead: one that none of
+        // the four layers names and that is dead here (written before it is read again, if at all), e.g. the skip tensor the block before consumed.
+        auto named = [&](const Layer& l, int s) { return l.src1 == s || l.src2 == s || l.res == s || l.dst == s; };
+        for (int s = 0; s < u->n_slots && *spare < 0; ++s) {
+            if (s == u->xpad_slot || named(l0, s) || named(l1, s) || named(l2, s) || named(l3, s)) continue;
+            bool dead = s != u->final_slot;
+            for (int j = f + kTailRunLayers; j < (int)u->layers.size() && dead; ++j) {
+                const Layer& l = u->layers[j];
+                if (l.src1 == s || l.src2 == s || l.res == s) dead = false;
+                else if (l.dst == s) break;
+            }
+            if (dead) *spare = s;
+        }
+        // with layer 0's output moved, layer 3's destination must be a slot no other layer of the run touches
+        if (*spare < 0 || l3.dst == l1.dst || l3.dst == l2.dst || l3.dst == l0.src1 || l3.dst == l0.res) { *spare = -1; continue; }
+        return i;
+    }
+    return -1;
+}
 static int device_cus() {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) (void)hipGetLastError();
@@ -985,7 +1078,7 @@ static int device_cus() {
 // seven run layers as ONE unit where the run is selected, and whether passes can be joined.
 struct PlanSchedule {
     std::vector<mpdx_unet::Unit> units;
-    bool run = false;    // units holds a kInnerRun unit
+    bool run = false;    // units holds a kInnerRun or a kTailRun unit
     bool join = false;   // an unguided pass that has a successor ends in fused_join_kernel; the successor starts at its second unit
     int build(mpdx_unet* u, int B, bool with_run = true) {   // with_run = false: the per-layer units whatever the handle says (mpdx_fused_trace)
         units = current_units(u, B, nullptr);
@@ -994,10 +1087,19 @@ struct PlanSchedule {
         // all resident at once (B <= 128 on 256 CUs).
         if (with_run && u->inner_run && !u->masked() && !u->cfg.self_attention && u->cfg.n_levels == 4 && u->cfg.n_support_points == 64) {
             if (int rc = inner_run_create(u->run, cus)) return rc;
-            const int rf = u->run.capacity > 0 && inner_run_grid(B) <= u->run.capacity && sw::geo() && !sw::debug() ? inner_run_first(u, units) : -1;
+            const bool fits = u->run.capacity > 0 && inner_run_grid(B) <= u->run.capacity && sw::geo() && !sw::debug();
+            const int rf = fits && u->run.seven_ok && (u->inner_run & mpdx_unet::kRunSeven) ? inner_run_first(u, units) : -1;
             if (rf >= 0) {
                 units[rf] = {mpdx_unet::kInnerRun, -1, units[rf].layer, kInnerRunLayers};
                 units.erase(units.begin() + rf + 1, units.begin() + rf + kInnerRunLayers);
+                run = true;
+            }
+            // the tail of up level 0, under the same conditions and on its own: the seven layers need not have been taken
+            int spare = -1;   // (Unit::fused of a kTailRun unit: the spare slot of layer 0's output)
+            const int tf = fits && u->run.tail_ok && (u->inner_run & mpdx_unet::kRunTail) ? tail_run_first(u, units, &spare) : -1;
+            if (tf >= 0) {
+                units[tf] = {mpdx_unet::kTailRun, spare, units[tf].layer, kTailRunLayers};
+                units.erase(units.begin() + tf + 1, units.begin() + tf + kTailRunLayers);
                 run = true;
             }
         }
@@ -1090,10 +1192,17 @@ int mpdx_unet_plan_joined(const mpdx_unet* u) { return u ? u->plan_joined : 0; }
 
 int mpdx_unet_set_inner_run(mpdx_unet* u, int on) {
     if (!u) return fail(MPDX_E_INVALID, "null argument");
-    u->inner_run = on ? 1 : 0;
+    u->inner_run = on ? (mpdx_unet::kRunSeven | mpdx_unet::kRunTail) : 0;   // everything that is eligible, or nothing
+    return 0;
+}
+int mpdx_unet_set_inner_run_parts(mpdx_unet* u, int parts) {
+    if (!u) return fail(MPDX_E_INVALID, "null argument");
+    if (parts & ~(mpdx_unet::kRunSeven | mpdx_unet::kRunTail)) return fail(MPDX_E_INVALID, "inner-run parts 0x%x: bit 0 the seven 256 -> 256 layers, bit 1 the tail of up level 0", parts);
+    u->inner_run = parts;
     return 0;
 }
 int mpdx_unet_inner_runs(const mpdx_unet* u) { return u ? u->inner_runs : 0; }
+int mpdx_unet_inner_run_layers(const mpdx_unet* u) { return u ? u->inner_run_layers : 0; }
 int mpdx_unet_status(const mpdx_unet* u) {
     if (!u) return fail(MPDX_E_INVALID, "null argument");
     return handle_status_error(u, "mpdx_unet_status");
@@ -1269,7 +1378,7 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
     // innermost level are one persistent launch in guided iterations too: the inner levels do not see the guide.
     PlanSchedule ps;
     if (int rc = ps.build(u, B)) return rc;
-    u->inner_runs = u->plan_joined = 0;
+    u->inner_runs = u->inner_run_layers = u->plan_joined = 0;
     hipStream_t st = (hipStream_t)stream;
     const int H = u->cfg.n_support_points, D = u->cfg.state_dim;
     const size_t n = (size_t)B * H * D;

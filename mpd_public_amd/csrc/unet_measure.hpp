@@ -127,12 +127,19 @@ int mpdx_layer_trace(mpdx_unet* u, const float* packed, const float* timetab, co
 int mpdx_fused_trace(mpdx_unet* u, const float* packed, const float* timetab, const float* x, int seg, int B, float* ws, void* stream,
                      long long* stamps_out, int cap, int* n_out, int* nops_out) {
     if (int rc = dev_hooks_missing(__func__)) return rc;
-    if (!u || seg < 0 || seg > (int)u->fused.size()) return fail(MPDX_E_INVALID, "bad segment");
+    if (!u || seg < 0 || seg > (int)u->fused.size() + 2) return fail(MPDX_E_INVALID, "bad segment");
     if (B <= 0) return fail(MPDX_E_INVALID, "B must be positive");
-    const bool joined = seg == (int)u->fused.size();
-    PlanSchedule ps;   // (without the inner run: the per-layer units of the single-pass entry points)
-    if (int rc = ps.build(u, B, false)) return rc;
+    const int nseg = (int)u->fused.size();
+    const bool joined = seg == nseg;
+    // seg == number of segments + 1 / + 2: the seven-layer run / the tail run of mpdx_plan (inner_run.hpp) - kRunTraceSlots stamps per layer, workgroup 0
+    const int run_kind = seg == nseg + 1 ? (int)mpdx_unet::kInnerRun : seg == nseg + 2 ? (int)mpdx_unet::kTailRun : -1;
+    PlanSchedule ps;   // (a program / the joined launch: without the runs - the per-layer units of the single-pass entry points)
+    if (int rc = ps.build(u, B, run_kind >= 0)) return rc;
     if (joined && !ps.join) return fail(MPDX_E_INVALID, "bad segment (this network / batch has no joined launch)");
+    int run_layers = 0;
+    for (const auto& un : ps.units)
+        if ((int)un.kind == run_kind) run_layers = un.count;
+    if (run_kind >= 0 && !run_layers) return fail(MPDX_E_INVALID, "bad segment (this network / batch / handle setting does not select that run)");
     if (int rc = check_ready(u)) return rc;
     hipStream_t st = (hipStream_t)stream;
     DevStamps dev;
@@ -143,8 +150,11 @@ int mpdx_fused_trace(mpdx_unet* u, const float* packed, const float* timetab, co
     // predecessors, cache and clock state as in production, no host synchronisation in between
     ResetOnExit<long long*> untrace{g_fused_trace, nullptr};
     ResetOnExit<int> unselect{g_fused_trace_seg, -1};
+    ResetOnExit<long long*> untrace_run{g_run_trace, nullptr};
+    ResetOnExit<int> unselect_run{g_run_trace_kind, -1};
     for (int pass = 0; pass < 3; ++pass) {   // joined: the third pass as mpdx_plan runs it when the next one follows unguided - its last unit is the joined launch
-        if (pass == 2 && !joined) { g_fused_trace = dev.p; g_fused_trace_seg = seg; }
+        if (pass == 2 && run_kind >= 0) { g_run_trace = dev.p; g_run_trace_kind = run_kind; }
+        else if (pass == 2 && !joined) { g_fused_trace = dev.p; g_fused_trace_seg = seg; }
         const float* next_row = pass == 2 && joined ? timetab : nullptr;
         if (int rc = walk_pass(u, ps.units, packed, timetab, padded_input(u, x, ws, B, st), ws, B, fa, st, no_hook, false, next_row, dev.p)) return rc;
     }
@@ -153,7 +163,8 @@ int mpdx_fused_trace(mpdx_unet* u, const float* packed, const float* timetab, co
     HIP_TRY(hipMemcpy(stamps_out, dev.p, n * sizeof(long long), hipMemcpyDeviceToHost));
     if (n_out) *n_out = n;
     if (nops_out) {
-        if (joined) *nops_out = u->fused[ps.units.back().fused].tmpl.nops + u->fused[ps.units.front().fused].tmpl.nops;
+        if (run_kind >= 0) *nops_out = run_layers;
+        else if (joined) *nops_out =u->fused[ps.units.back().fused].tmpl.nops + u->fused[ps.units.front().fused].tmpl.nops;
         else *nops_out = u->fused[seg].tmpl.nops;
     }
     return 0;

@@ -187,13 +187,24 @@ class TemporalUnet(nn.Module):
         return int(_lib.load().mpdx_unet_plan_joined(self._handle()))
 
     def set_inner_run(self, on: bool):
-        """mpdx_unet_set_inner_run: may the fused planning loop run the seven 256 -> 256 layers of the innermost level as one persistent launch
-        (default: yes, where the network and the batch admit it)?  Results are bit-identical either way.  A handle option, like set_plan_join."""
+        """mpdx_unet_set_inner_run: may the fused planning loop run the seven 256 -> 256 layers of the innermost level, and the tail of up level 0
+        (three 128 -> 128 layers + Upsample1d), as one persistent launch each (default: yes, where the network and the batch admit it)?  Results are
+        bit-identical either way.  A handle option, like set_plan_join."""
         _lib.check(_lib.load().mpdx_unet_set_inner_run(self._handle(), int(bool(on))), "mpdx_unet_set_inner_run")
 
+    RUN_SEVEN, RUN_TAIL = 1, 2
+
+    def set_inner_run_parts(self, parts: int):
+        """mpdx_unet_set_inner_run_parts: select the runs separately - RUN_SEVEN | RUN_TAIL is what set_inner_run(True) selects, 0 nothing."""
+        _lib.check(_lib.load().mpdx_unet_set_inner_run_parts(self._handle(), int(parts)), "mpdx_unet_set_inner_run_parts")
+
     def inner_runs(self) -> int:
-        """Inner-level run launches of the last fused plan on this model (mpdx_unet_inner_runs)."""
+        """Seven-layer run launches of the last fused plan on this model (mpdx_unet_inner_runs); the tail run does not count here."""
         return int(_lib.load().mpdx_unet_inner_runs(self._handle()))
+
+    def inner_run_layers(self) -> int:
+        """Layers that ran inside run launches of either kind in the last fused plan on this model (mpdx_unet_inner_run_layers)."""
+        return int(_lib.load().mpdx_unet_inner_run_layers(self._handle()))
 
     def status(self) -> int:
         """mpdx_unet_status: 0, or MPDX_E_DEVICE (-4) when a kernel of this handle gave up a bounded wait (sticky; no synchronisation)."""
