@@ -2,6 +2,7 @@
 restatement of their forward kinematics with homogeneous matrices (written from the description, not from RobotChain.table()), and the oracle
 guide assembled on it (oracle/costs.py and oracle/guide.py as they are: the oracle is duck-typed on q_dim / radii / name / link_points)."""
 import math
+import re
 
 import numpy as np
 import torch
@@ -50,6 +51,14 @@ def description(name):
         from mpd_public_amd import synthetic as syn
         return dict(joints=joints, spheres=[(k, [0.0, 0.0, off], r) for k, off, r in oc.PANDA_SPHERES], pairs=list(oc.PANDA_SELF_PAIRS),
                     q_limits=(syn.PANDA_Q_MIN, syn.PANDA_Q_MAX), v_limit=2.5)
+    m_ = re.fullmatch(r"R8\[:(\d)\]", name)
+    if m_:               # R8 cut after its first k joints: the spheres whose frame is at most k and the pairs among them, renumbered
+        k, d = int(m_.group(1)), description("R8")
+        keep = [s for s, sp in enumerate(d["spheres"]) if sp[0] <= k]
+        new = {s: i for i, s in enumerate(keep)}
+        return dict(joints=d["joints"][:k], spheres=[d["spheres"][s] for s in keep],
+                    pairs=[(new[a], new[b]) for a, b in d["pairs"] if a in new and b in new],
+                    q_limits=(d["q_limits"][0][:k], d["q_limits"][1][:k]), v_limit=d["v_limit"])
     raise KeyError(name)
 
 
@@ -101,7 +110,7 @@ class RobotChainRef:
         return torch.stack(pts, dim=-2)
 
 
-def oracle_guide_chain(dataset, desc, w_coll=1e-2, w_smooth=1e-7, dtype=torch.float64, n_interp=128):
+def oracle_guide_chain(dataset, desc, w_coll=1e-2, w_smooth=1e-7, dtype=torch.float64, n_interp=128, clip_grad=True, gp_half_factor=False):
     """The oracle's guide for the task of `dataset` with the robot of `desc` (the pattern of helpers.oracle_guide); returns (guide, composite)."""
     from oracle import costs as oc
     from oracle.guide import GuideManager
@@ -120,12 +129,12 @@ def oracle_guide_chain(dataset, desc, w_coll=1e-2, w_smooth=1e-7, dtype=torch.fl
             fld = oc.SelfField(torch.tensor(desc["pairs"], dtype=torch.long).reshape(-1, 2))
         cl.append(oc.CostCollision(robot, 64, field=fld, sigma_coll=1.0, cutoff_margin=dataset.task.obstacle_cutoff_margin))
         wl.append(w_coll)
-    cl.append(oc.CostGPTrajectory(robot, 64, 5.0 / dataset.n_support_points, sigma_gp=1.0))
+    cl.append(oc.CostGPTrajectory(robot, 64, 5.0 / dataset.n_support_points, sigma_gp=1.0, half_factor=gp_half_factor))
     wl.append(w_smooth)
     comp = oc.CostComposite(robot, 64, cl, weights_cost_l=wl)
     nrm = LimitsNormalizer(dataset.normalizer.mins.cpu(), dataset.normalizer.maxs.cpu())
     nrm.mins, nrm.maxs = nrm.mins.to(dtype), nrm.maxs.to(dtype)
-    return GuideManager(nrm, comp, clip_grad=True, interpolate=True, n_interp=n_interp), comp
+    return GuideManager(nrm, comp, clip_grad=clip_grad, interpolate=True, n_interp=n_interp), comp
 
 
 _PROBES = {}
@@ -179,6 +188,14 @@ def chain_trajs(q_dim, B, H, seed, spread=0.95, noise=0.05, probes=None):
     return torch.cat([pos, vel], -1).contiguous()
 
 
+def chain_case_inputs(name, H, seed, B=3, device="cpu"):
+    """The inputs of tests/test_gpu_chain.py: (dataset of the test robot on EnvSpheres3D, description, normalised x [B, H, D] on the CPU)."""
+    import mpd_public_amd as m
+    ds = m.TrajectoryDataset("EnvSpheres3D", product_robot(name), n_support_points=H, tensor_args={"device": device, "dtype": torch.float32})
+    x = chain_trajs(ds.robot.q_dim, B, H, f"chain/{name}/{H}/{seed}", probes=probe_configs(name, ds))
+    return ds, description(name), x
+
+
 def active_kinds(comp, xu_interp):
     """{field kind: number of active hinges} of the collision terms of an oracle composite on interpolated UNNORMALISED trajectories."""
     from oracle import costs as oc
@@ -189,11 +206,12 @@ def active_kinds(comp, xu_interp):
     return out
 
 
-def hinge_slack(comp, xi):
-    """slack[b, i] = max over every collision hinge (margin = link radius, no cutoff) of (margin - signed distance), in the composite's dtype:
-    helpers.oracle_hinge_slack for a chain composite.  xi: interpolated UNNORMALISED trajectories."""
+def hinge_slacks(comp, xi):
+    """[(field kind, s [B, N, n]): margin - signed distance (margin = link radius, no cutoff) of every hinge of a collision term - per link sphere
+    (objects), per sphere and face (workspace), per pair (self)] in the order of the composite; hinge_slack is the maximum over all of them.
+    xi: interpolated UNNORMALISED trajectories."""
     from oracle import costs as oc
-    slack = torch.full(xi.shape[:2], -float("inf"), dtype=xi.dtype)
+    out = []
     for term in comp.cost_l:
         if not isinstance(term, oc.CostCollision):
             continue
@@ -208,8 +226,14 @@ def hinge_slack(comp, xi):
         else:
             a, b = pts[..., f.pairs[:, 0], :], pts[..., f.pairs[:, 1], :]
             s = radii[f.pairs[:, 0]] + radii[f.pairs[:, 1]] - torch.linalg.norm(a - b, dim=-1)
-        slack = torch.maximum(slack, s.amax(-1))
-    return slack
+        out.append((f.kind, s))
+    return out
+
+
+def hinge_slack(comp, xi):
+    """slack[b, i] = max over every collision hinge (margin = link radius, no cutoff) of (margin - signed distance), in the composite's dtype:
+    helpers.oracle_hinge_slack for a chain composite.  xi: interpolated UNNORMALISED trajectories."""
+    return torch.stack([s.amax(-1) for _, s in hinge_slacks(comp, xi)]).amax(0)
 
 
 def mismatch_fraction(got, ref, w_coll=1e-2):

@@ -1,4 +1,5 @@
-"""Reference side of the per-term guide tests (tests/test_guide_ref_cpu.py, tests/test_gpu_guide_terms.py, tests/test_gpu_guide.py): which waypoints
+"""Reference side of the per-term guide tests (tests/test_guide_ref_cpu.py, tests/test_gpu_guide_terms.py, tests/test_gpu_guide.py; the chain robots:
+tests/test_chain_ref_cpu.py, tests/test_gpu_chain_terms.py, tests/test_gpu_chain.py): which waypoints
 of a comparison with the fp64 oracle are decidable, which decisions of the collision terms a set of trajectories reaches, the yardstick applied to
 every decidable waypoint, and the coverage environments / trajectories that reach every decision.  Reference only: nothing here touches the GPU.
 
@@ -244,22 +245,51 @@ def cover_env(dim):
 
 
 ROBOTS = {"RobotPointMass": ("EnvSimple2D", 2), "RobotPointMass3D": ("EnvSpheres3D", 3), "RobotPanda": ("EnvSpheres3D", 3)}
+# A chain robot of tests/chain_ref.py is the case id "chain:<name>": R1, R3, R8, Panda (RobotChain.panda()) and R8[:k], R8 cut after k joints, so
+# that every joint count 1 ... 8 of the chain kernels has a case
+CHAIN = "chain:"
+CHAIN_ROBOTS = tuple(CHAIN + n for n in ("R1", "R3", "R8", "Panda", "R8[:2]", "R8[:4]", "R8[:5]", "R8[:6]"))
+
+
+def is_chain(robot_id):
+    return robot_id.startswith(CHAIN)
+
+
+def hash_tag(robot_id):
+    """the robot's part of the hash-tensor names: the id itself; a chain's name with R8[:k] spelt R8_k"""
+    return robot_id[len(CHAIN):].replace("[:", "_").replace("]", "") if is_chain(robot_id) else robot_id
+
+
+def oracle_of(ds, *args, **kw):
+    """(guide, composite) of the oracle for a dataset of cover_dataset: helpers.oracle_guide, or chain_ref.oracle_guide_chain on the reference FK of
+    the description where the dataset holds a chain robot"""
+    name = getattr(ds, "chain_name", None)
+    if name is None:
+        return oracle_guide(ds, *args, **kw)
+    import chain_ref
+    return chain_ref.oracle_guide_chain(ds, chain_ref.description(name), *args, **kw)
 
 
 def cover_dataset(robot_id, H=64, device="cpu"):
     """A TrajectoryDataset of `robot_id` (its normaliser, its robot) whose environment and task are the coverage ones (the way
     scene_ref.scene_dataset replaces a task)."""
     import mpd_public_amd as m
-    env_id, dim = ROBOTS[robot_id]
-    ds = m.TrajectoryDataset(env_id, robot_id, n_support_points=H, tensor_args={"device": device, "dtype": torch.float32})
+    if is_chain(robot_id):
+        import chain_ref
+        env_id, dim, robot = "EnvSpheres3D", 3, chain_ref.product_robot(robot_id[len(CHAIN):])
+    else:
+        (env_id, dim), robot = ROBOTS[robot_id], robot_id
+    ds = m.TrajectoryDataset(env_id, robot, n_support_points=H, tensor_args={"device": device, "dtype": torch.float32})
     d = copy.copy(ds)
+    if is_chain(robot_id):
+        d.chain_name = robot_id[len(CHAIN):]
     d.env = cover_env(dim)
     d.task = PlanningTask(d.env, d.robot, obstacle_cutoff_margin=ds.task.obstacle_cutoff_margin, tensor_args=ds.tensor_args)
     return d
 
 
 def cap_of(robot_id):
-    return CAP["RobotPanda" if robot_id == "RobotPanda" else "RobotPointMass"]
+    return CAP["RobotPanda" if robot_id == "RobotPanda" or is_chain(robot_id) else "RobotPointMass"]       # every chain case: the Panda's cap
 
 
 # Decision classes no configuration of the scan reaches (geometry: the Panda's base spheres 0 and 1 do not move, and the listed pairs cannot
@@ -268,10 +298,26 @@ UNREACHABLE = {
     "RobotPointMass": (),
     "RobotPointMass3D": (),
     "RobotPanda": ("f0 pair2", "f0 pair5", "f0 pair6", "f0 pair10", "f0 pair11", "f1 link0", "f3 link0", "f3 link1", "f3 link2"),
+    # the chains (tests/test_chain_ref_cpu.py).  A robot without pairs has no self field: f0 is the fixed objects, f1 the workspace, f2 the extra
+    # objects.  R1's sphere sweeps one circle; the base-frame spheres (R3: 0; R8: 0 and 1) do not move; a short R8 stays near its base column
+    CHAIN + "R1": ("f0 prim1", "f0 prim2", "f0 prim3", "f0 prim5", "f0 prim7", "f0 inbox", "f1 face0-", "f1 face2-", "f1 face2+", "f2 prim0", "f2 prim1",
+                   "f2 link0", "f2 inbox"),
+    CHAIN + "R3": ("f0 pair0", "f1 link0", "f3 link0", "f3 link1", "f3 inbox"),
+    CHAIN + "R8": ("f0 pair0", "f0 pair1", "f0 pair2", "f0 pair3", "f0 pair4", "f0 pair7", "f0 pair13", "f0 pair14", "f0 pair15", "f0 pair17", "f0 pair18",
+                   "f0 pair19", "f0 pair20", "f0 pair22", "f0 pair23", "f1 link0", "f1 link1", "f3 link0", "f3 link1", "f3 link2", "f3 link3", "f3 link4"),
+    CHAIN + "Panda": ("f0 pair2", "f0 pair5", "f0 pair6", "f0 pair10", "f0 pair11", "f1 link0", "f3 link0", "f3 link1", "f3 link2"),      # RobotPanda's
+    CHAIN + "R8[:2]": ("f0 prim1", "f0 prim3", "f0 prim4", "f0 prim5", "f0 prim6", "f0 link0", "f0 link1", "f0 inbox", "f1 face0-", "f1 face0+", "f1 face1-",
+                       "f1 face1+", "f1 face2+", "f2 prim0", "f2 prim1", "f2 link0", "f2 link1", "f2 link2", "f2 link3", "f2 link4", "f2 inbox"),
+    CHAIN + "R8[:4]": ("f0 prim5", "f0 link0", "f0 link1", "f1 face0-", "f2 link0", "f2 link1", "f2 link2", "f2 link3", "f2 link4"),
+    CHAIN + "R8[:5]": ("f0 pair0", "f0 pair1", "f0 pair2", "f0 pair3", "f1 link0", "f1 link1", "f2 face0-", "f3 link0", "f3 link1", "f3 link2", "f3 link3",
+                       "f3 link4"),
+    CHAIN + "R8[:6]": ("f0 pair0", "f0 pair1", "f0 pair2", "f0 pair3", "f0 pair8", "f0 pair9", "f1 link0", "f1 link1", "f3 link0", "f3 link1", "f3 link2",
+                       "f3 link3", "f3 link4"),
 }
 N_SCAN = 20000
 # share of the normaliser's position range the scan covers.  Point masses: 0.9, so that probes + noise stay inside +-1 (the normaliser's in-range
 # branch; the workspace faces lie at 0.55); Panda: all of it (self pair 1 closes only near a joint limit), so the noise leaves +-1 (the clip branch)
+# a chain: all of it, as the Panda
 SPREAD = {"RobotPointMass": 0.9, "RobotPointMass3D": 0.9, "RobotPanda": 1.0}
 
 
@@ -280,10 +326,10 @@ def probe_configs(robot_id):
     """(labels, q [P, q_dim] fp64 un-normalised, unreachable labels): for every decision class that a hash-uniform scan of N_SCAN configurations
     reaches, the scanned configuration with the largest hinge of that class."""
     ds = cover_dataset(robot_id)
-    _, comp = oracle_guide(ds, dtype=torch.float64)
+    _, comp = oracle_of(ds, dtype=torch.float64)
     qd = ds.robot.q_dim
     lo, hi = ds.normalizer.mins[:qd].double(), ds.normalizer.maxs[:qd].double()
-    u = torch.from_numpy(syn.hash_uniform(f"guide_cover/{robot_id}/scan", N_SCAN * qd, -SPREAD[robot_id], SPREAD[robot_id]).reshape(N_SCAN, qd))
+    u = torch.from_numpy(syn.hash_uniform(f"guide_cover/{hash_tag(robot_id)}/scan", N_SCAN * qd, -SPREAD.get(robot_id, 1.0), SPREAD.get(robot_id, 1.0)).reshape(N_SCAN, qd))
     q = lo + (hi - lo) * (u + 1) / 2
     labels, rows, missing = [], [], []
     for name, v in class_hinges(comp, q).items():
@@ -308,7 +354,7 @@ def cover_trajs(robot_id, H, seed="0"):
         qn = torch.cat([qn, qn[:1]])
     a, b = qn[0::2].unsqueeze(1), qn[1::2].unsqueeze(1)
     B = a.shape[0]
-    tag = f"guide_cover/{robot_id}/{H}/{seed}"
+    tag = f"guide_cover/{hash_tag(robot_id)}/{H}/{seed}"
     pos = torch.empty((B, H, qd), dtype=torch.float64)
     n_in = H - 2
     s = torch.linspace(0, 1, n_in, dtype=torch.float64).reshape(1, n_in, 1)
@@ -324,6 +370,15 @@ def cover_trajs(robot_id, H, seed="0"):
 # full; H = 9 (3-D point mass): H * D = 54 is no multiple of 4, and 128 interpolated points are more than 8 H
 GPU_CASES = [("RobotPointMass", 64), ("RobotPointMass", 128), ("RobotPointMass", 96), ("RobotPointMass", 48),
              ("RobotPointMass3D", 64), ("RobotPointMass3D", 96), ("RobotPointMass3D", 9), ("RobotPanda", 64), ("RobotPanda", 96)]
+
+
+# the cases of tests/test_gpu_chain_terms.py, (robot, H, seed): every joint count 1 ... 8 of guide_step_chain_kernel; H = 9: H * D = 18 is no multiple
+# of 4; H = 24: a padded container; H = 96: two waves of supports; H = 128: as many supports as interpolated points (interpolation scale 1).
+# Seed: "0" wherever it meets the 2 % cap on ambiguous waypoints; R3 H = 24 has 8 of 312 (2.56 %) with "0" and 6 (1.92 %) with "1", the first that does
+CHAIN_CASES = [(CHAIN + "R1", 64, "0"), (CHAIN + "R1", 9, "0"), (CHAIN + "R3", 64, "0"), (CHAIN + "R3", 24, "1"), (CHAIN + "R3", 96, "0"),
+               (CHAIN + "R3", 128, "0"), (CHAIN + "R8", 64, "0"), (CHAIN + "Panda", 64, "0"), (CHAIN + "R8[:2]", 64, "0"), (CHAIN + "R8[:4]", 64, "0"),
+               (CHAIN + "R8[:5]", 64, "0"), (CHAIN + "R8[:6]", 64, "0")]
+CHAIN_IDS = [f"{r[len(CHAIN):]}-H{h}" for r, h, _ in CHAIN_CASES]
 
 
 def n_interp_of(H):
@@ -361,7 +416,7 @@ def is_unclipped_gp(ds, run):
 def oracle_run(ds, x, run, dtype=torch.float64, n_interp=128, mutate=None):
     """The oracle's increment [B, H, D] (numpy, in dtype) of one run of runs_of on the normalised trajectories x.  mutate(guide, composite): a
     change applied to the oracle before the term selection (the mutants of tests/test_guide_ref_cpu.py)."""
-    og, comp = oracle_guide(ds, *run["weights"], clip_grad=run["clip_grad"], dtype=dtype, n_interp=n_interp, gp_half_factor=run["gp_half_factor"])
+    og, comp = oracle_of(ds, *run["weights"], clip_grad=run["clip_grad"], dtype=dtype, n_interp=n_interp, gp_half_factor=run["gp_half_factor"])
     if mutate is not None:
         mutate(og, comp)
     if run["only"] is not None:
@@ -392,6 +447,16 @@ def run_ambiguity(run, ds, amb):
     return amb
 
 
+# Runs of ONE collision field whose fp64 increment is exactly zero (so must the kernel's be), asserted equal to what the reference finds: R1 and R8[:2]
+# never come near the extra objects and none of the 4 pairs of R8[:5] closes (no class of that field is reachable), and the only workspace hinge
+# R8[:2] reaches is the lower z face under its two base-frame spheres, which no joint moves
+ZERO_RUNS = {CHAIN + "R1": ("extra_objects",), CHAIN + "R8[:2]": ("workspace", "extra_objects"), CHAIN + "R8[:5]": ("self",)}
+
+
+def run_is_zero(robot_id, ds, run):
+    return run["only"] is not None and term_names(ds)[run["only"]] in ZERO_RUNS.get(robot_id, ())
+
+
 @functools.lru_cache(maxsize=None)
 def case(robot_id, H, seed="0"):
     """Everything the reference says about one case, computed once: dict(ds (CPU), x, n_interp, xi (fp64 interpolated un-normalised), dist, amb [B, H]
@@ -400,7 +465,7 @@ def case(robot_id, H, seed="0"):
     ds = cover_dataset(robot_id, H)
     x = cover_trajs(robot_id, H, seed)
     n = n_interp_of(H)
-    og, comp = oracle_guide(ds, dtype=torch.float64, n_interp=n)
+    og, comp = oracle_of(ds, dtype=torch.float64, n_interp=n)
     xi = interpolate_points_v1(og.normalizer.unnormalize(x.double()), n)
     dist = decision_distance(comp, xi)
     amb = ambiguous_supports(dist, H).numpy()
@@ -415,6 +480,46 @@ def case_reference(robot_id, H, run_index, seed="0"):
     ref = oracle_run(c["ds"], c["x"], runs_of(c["ds"])[run_index][1], torch.float64, c["n_interp"])
     ref.setflags(write=False)
     return ref
+
+
+# The metrics comparisons of tests/test_gpu_chain_terms.py, (robot, environment), H = 64, 256 checked points on the coverage trajectories.  'cover':
+# the coverage environment.  There EVERY checked point of R8 and R8[:4] collides, whatever the joints do (the base-frame sphere 0, radius 0.05 at
+# z = 0.03, reaches 0.07 below the workspace's lower z face at 0.05), so the flags can only be all set: METRICS_ALL_COLLIDE.  'own': the same robots
+# and trajectories in EnvSpheres3D's own task (workspace +-1, spheres only), where both flag values occur and the self field decides flags.
+METRICS_CASES = [(CHAIN + "R3", "cover"), (CHAIN + "R8", "cover"), (CHAIN + "Panda", "cover"), (CHAIN + "R8[:4]", "cover"), (CHAIN + "R8", "own"),
+                 (CHAIN + "R8[:4]", "own")]
+METRICS_ALL_COLLIDE = ((CHAIN + "R8", "cover"), (CHAIN + "R8[:4]", "cover"))
+
+
+def metrics_dataset(robot_id, env="cover", device="cpu"):
+    if env == "cover":
+        return cover_dataset(robot_id, 64, device)
+    import chain_ref
+    import mpd_public_amd as m
+    ds = m.TrajectoryDataset("EnvSpheres3D", chain_ref.product_robot(robot_id[len(CHAIN):]), n_support_points=64, tensor_args={"device": device, "dtype": torch.float32})
+    ds.chain_name = robot_id[len(CHAIN):]
+    return ds
+
+
+@functools.lru_cache(maxsize=None)
+def chain_metrics_reference(robot_id, env="cover", n_check=256):
+    """(xu32 [B, 64, D]: the un-normalised float32 coverage trajectories of a chain case at H = 64, what the metrics kernel is given;
+    slacks: chain_ref.hinge_slacks of the fp64 oracle of the environment's task on their n_check-point interpolation) - computed once"""
+    import chain_ref
+    from oracle.guide import interpolate_points_v1
+    og, comp = oracle_of(metrics_dataset(robot_id, env), dtype=torch.float64)
+    xu32 = og.normalizer.unnormalize(case(robot_id, 64)["x"].double()).float()
+    return xu32, chain_ref.hinge_slacks(comp, interpolate_points_v1(xu32.double(), n_check))
+
+
+def check_metrics_conditions(slack, all_collide=False, what=""):
+    """what a comparison of metrics flags presupposes of the fp64 slack [B, n_check]: at most 1 % of the checked points within DELTA of a margin,
+    and decided points of both kinds (all_collide: a case of METRICS_ALL_COLLIDE - none that is free); returns the band"""
+    band = slack.abs() <= DELTA
+    print(f"{what}: {int(band.sum())} of {band.numel()} checked points within 1e-5 of a margin; {int((slack > 0).sum())} collide")
+    assert float(band.double().mean()) <= 0.01 and bool((slack > DELTA).any())
+    assert bool((slack < -DELTA).any()) != all_collide and (not all_collide or bool((slack > DELTA).all()))
+    return band
 
 
 def check_reference_conditions(robot_id, H, seed="0"):
