@@ -95,7 +95,7 @@ struct ConvArgs {
     // padding, so the k-loop and the staging are untouched: only the epilogues mask (GroupNorm statistics over the valid rows,
     // zeros stored beyond them).  Lv_out == L_out (or 0): nothing masked.  Honoured by EPI_GN_MISH_GEN and EPI_BIAS.
     int Lv_out;
-    // training, EPI_BIAS input-gradient convolutions of the resampling layers (round 4: were a zero_stuff_kernel / acc_slice_kernel launch each):
+    // training, EPI_BIAS input-gradient convolutions of the resampling layers (round 4: the zero-stuffing and the decimation were a launch of their own each):
     //   stuff: src1 is [B][L_in / 2][c1] and is read ZERO-STUFFED (row li of the window = source row li / 2 for even li, zero for odd li): the
     //          input gradient of a stride-2 convolution is a stride-1 convolution of the stuffed output gradient;
     //   decim: only the even output rows are stored, at row l / 2 of a [B][L_out / 2][.] destination: the input gradient of ConvTranspose1d(4, 2, 1)

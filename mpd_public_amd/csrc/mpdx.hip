@@ -703,17 +703,6 @@ int launch_final_step(const FinalArgs& fa, hipStream_t st) {
 static long long* g_fused_trace = nullptr;  // dev tool (mpdx_fused_trace)
 static int g_fused_trace_seg = -1;
 
-// strided copy inside `packed`: dst[i0*ds0 + i1*ds1 + k] = src[i0*ss0 + i1*ss1 + k]
-__global__ void restream_kernel(float* __restrict__ packed, size_t src, size_t dst, int n0, int ss0, int ds0, int n1, int ss1, int ds1, int n_inner) {
-    const size_t total = (size_t)n0 * n1 * n_inner;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int k = (int)(i % n_inner);
-        const size_t r = i / n_inner;
-        const int i1 = (int)(r % n1), i0 = (int)(r / n1);
-        packed[dst + (size_t)i0 * ds0 + (size_t)i1 * ds1 + k] = packed[src + (size_t)i0 * ss0 + (size_t)i1 * ss1 + k];
-    }
-}
-
 // all strided copies of every fused segment in ONE launch (blockIdx.y = job; the table lives in device memory; CopyJobDev, restream_job: train_types.hpp)
 __global__ __launch_bounds__(256) void restream_all_kernel(float* __restrict__ packed, const CopyJobDev* __restrict__ jobs) {
     restream_job(packed, jobs[blockIdx.y], blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u);

@@ -54,22 +54,13 @@ constexpr int kUnset = INT_MIN;   // default of an INT switch that has to tell "
     X(ws_ns,               "MPDX_WS_NS",                INT,     0,       ONCE, "256 -> 256 weight-stationary kernel: 1 / 2 force one / two 32-position tiles per step, 0 by batch") \
     /* ---- training: development A/B knobs, each decided; the default is the winner */ \
     X(train_deferred,      "MPDX_TRAIN_DEFERRED",       ON,      true,    ONCE, "0: weight-gradient partial sums reduced per layer, not deferred to one reduction at the end of the pass") \
-    X(train_bias_fold,     "MPDX_TRAIN_BIAS_FOLD",      ON,      true,    ONCE, "0: a convolution's bias gradient as its own two launches, not on its weight-gradient job") \
-    X(wgrad_two,           "MPDX_WGRAD_TWO",            ON,      true,    ONCE, "0: one wave group per weight-gradient block inside bwd_pair_kernel's 512-thread workgroups, not two") \
-    X(train_bwd_mid,       "MPDX_TRAIN_BWD_MID",        ON,      true,    ONCE, "0: three levels: the two middle blocks stay out of the backward down program (variant 2, not 3)") \
-    X(train_fused_fwd,     "MPDX_TRAIN_FUSED_FWD",      ON,      true,    ONCE, "0: the training forward runs one launch per layer, not the planning path's fused level programs") \
     X(train_restream_ride, "MPDX_TRAIN_RESTREAM_RIDE",  ON,      true,    ONCE, "0: the fused programs' weight streams are re-assembled by a launch of their own, not by side blocks of time_train_fwd_kernel") \
-    X(train_pair_fwd,      "MPDX_TRAIN_PAIR_FWD",       ON,      true,    ONCE, "0: training forward, blocks[0] + residual 1x1 as two launches (paired: two launches of ~4.8 us less per pass on the four-level network)") \
     X(train_gn_fuse,       "MPDX_TRAIN_GN_FUSE",        ON,      true,    ONCE, "0: Mish + GroupNorm backward as its own launch, not the epilogue of the consumer's input-gradient convolution") \
-    X(train_gn_inplace,    "MPDX_TRAIN_GN_INPLACE",     ON,      true,    ONCE, "0: an un-fused GroupNorm backward writes the shared dU scratch, not the layer's own gradient slot (in place: 22.6 -> 12.5 us for the one such 256 -> 256 layer at batch 128)") \
     X(train_bwd_prog,      "MPDX_TRAIN_BWD_PROG",       INT,     1,       ONCE, "whole-trajectory backward programs of the outer levels (fused_bwd.hpp): 0 off, 2 the down program only") \
     X(train_bwd_prog_max_b,"MPDX_TRAIN_BWD_PROG_MAX_B", INT,     512,     ONCE, "largest batch that runs the backward programs") \
     X(wgrad_late_div,      "MPDX_WGRAD_LATE_DIV",       INT,     kUnset,  ONCE, "divisor (>= 1) of the batch splits of the weight gradients that run behind the chain and of the backward programs'; unset: 4 / 8 / 4 at batch < 64 / <= 128 / beyond (profiles/r06_train_late_div_ab.txt)") \
     X(wgrad_prog_mul,      "MPDX_WGRAD_PROG_MUL",       INT,     1,       ONCE, "batch < 64: split multiplier (<= 4) of the backward programs' weight gradients (2: 0.513 against 0.49 ms, profiles/r06_train_b32_split_ab.txt)") \
-    X(train_pair_res,      "MPDX_TRAIN_PAIR_RES",       ON,      true,    ONCE, "0: the residual 1x1 convolution's input gradient as its own launch, not riding on blocks[1]'s (one launch less per residual block)") \
-    X(train_pair,          "MPDX_TRAIN_PAIR",           ON,      true,    ONCE, "0: a layer's weight-gradient blocks never ride on its input-gradient launch (bwd_pair_kernel off)") \
     X(train_wgrad_late,    "MPDX_TRAIN_WGRAD_LATE",     INT,     -1,      ONCE, "weight gradients leave the chain and run behind it in one launch: 0 / 1 force, -1 from batch 48 on (batch 32 no gain, 48 0.58 -> 0.543 ms, 128 -3 %, 512 -4.6 %)") \
-    X(train_resample_fold, "MPDX_TRAIN_RESAMPLE_FOLD",  ON,      true,    ONCE, "0: the zero-stuffing in front of a Downsample1d's input gradient as its own launch, not folded into the convolution's loads") \
     X(train_wgrad_multi,   "MPDX_TRAIN_WGRAD_MULTI",    ON,      true,    ONCE, "0: the late weight-gradient jobs three per launch, not all in one wgrad_multi_kernel launch") \
     X(train_reduce_join,   "MPDX_TRAIN_REDUCE_JOIN",    ON,      true,    ONCE, "0: the column sums as their own launch, not side blocks of the weight-gradient reduction's") \
     X(time_tail_split,     "MPDX_TIME_TAIL_SPLIT",      ON,      true,    ONCE, "0: the time encoder's backward tail inside time_bwd_all_kernel, not as time_tail_kernel's 8 blocks behind it")

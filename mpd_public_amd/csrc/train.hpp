@@ -270,30 +270,6 @@ __global__ __launch_bounds__(256) void rowsum_part_kernel(const float* __restric
     }
 }
 
-// dst[b][l][c] += src[b][l * step][c_off + c]      dst dense [B][L][Cd];  src [B][Ls][Cs]
-__global__ __launch_bounds__(256) void acc_slice_kernel(float* __restrict__ dst, const float* __restrict__ src, int B, int L, int Cd, int Ls, int Cs,
-                                                        int c_off, int step, int store) {
-    const size_t total = (size_t)B * L * Cd;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % Cd);
-        const size_t r = i / Cd;
-        const int l = (int)(r % L), b = (int)(r / L);
-        const float v = src[((size_t)b * Ls + (size_t)l * step) * Cs + c_off + c];
-        dst[i] = store ? v : dst[i] + v;
-    }
-}
-
-// z[b][2j][c] = x[b][j][c], z[b][2j+1][c] = 0   (input gradient of a stride-2 convolution = stride-1 convolution of this)
-__global__ __launch_bounds__(256) void zero_stuff_kernel(const float* __restrict__ x, float* __restrict__ z, int B, int L, int C) {
-    const size_t total = (size_t)B * 2 * L * C;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C);
-        const size_t r = i / C;
-        const int l2 = (int)(r % (2 * L)), b = (int)(r / (2 * L));
-        z[i] = (l2 & 1) ? 0.f : x[((size_t)b * L + (l2 >> 1)) * C + c];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // Weight gradient of a 1-D convolution:   G[m][n][k] = sum_{b, t < LA}  A[b][t][m] * Bm[b][sb * t + k + ob][n]     (zero outside [0, LB))
 //   Conv1d(k5 / k1, stride 1):   A = dU (m = c_out), Bm = x (n = c_in), sb = 1, ob = -pad           -> G = dW[c_out][c_in][k]
@@ -1308,39 +1284,10 @@ __global__ __launch_bounds__(512) void time_tail_kernel(const TimeBwdArgs a) {
 // ------------------------------------------------------------------------------------------------------------------
 // Loss gradient (helpers.py:71-99; mean over B*H*D of |e| or e^2 [* weights]):  dE = s * w * d|e|^p / de / (B H D), zero where
 // apply_hard_conditioning overwrote the prediction with a constant (diffusion_model_base.py:343).
-__global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict__ pred, const float* __restrict__ targ, const float* __restrict__ weights_hd,
-                                                        int has_hs, int has_hg, int l1, float scale, float* __restrict__ dE, int B, int H, int D) {
-    const size_t total = (size_t)B * H * D;
-    const float inv = scale / (float)total;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int hd = (int)(i % ((size_t)H * D)), h = hd / D;
-        float g = 0.f;
-        if (!((has_hs && h == 0) || (has_hg && h == H - 1))) {
-            const float e = pred[i] - targ[i];
-            g = l1 ? (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f)) : 2.0f * e;
-            if (weights_hd) g *= weights_hd[hd];
-            g *= inv;
-        }
-        dE[i] = g;
-    }
-}
-
-// final_conv[1] (Conv1d 1x1, C -> D) input gradient:  gH[b][l][c] = sum_d dE[b][l][d] W[d][c]
-__global__ __launch_bounds__(256) void final_dgrad_kernel(const float* __restrict__ dE, const float* __restrict__ w, float* __restrict__ gH, size_t n_rows, int D,
-                                                          int C) {
-    const size_t total = n_rows * C;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C);
-        const size_t r = i / C;
-        float s = 0.f;
-        for (int d = 0; d < D; ++d) s = fmaf(dE[r * D + d], w[(size_t)d * C + c], s);
-        gH[i] = s;
-    }
-}
-
-// The loss value, its gradient and the gradient's way back through final_conv[1] in ONE launch (round 4: were three).  Blocks [0, gridDim.x - 1):
-// gH[r][c] = sum_d dE[r][d] W[d][c] with dE computed on the fly (loss_grad_kernel's arithmetic; the lane with c == d also stores dE[r][d], which
-// the weight / bias gradients of final_conv[1] read) - needs C >= D.  The LAST 16 blocks: the loss value, weighted_loss_kernel's summation order.
+// The loss value, its gradient and the gradient's way back through final_conv[1] (Conv1d 1x1, C -> D) in ONE launch (round 4: were three).  Blocks
+// [0, gridDim.x - 16): gH[r][c] = sum_d dE[r][d] W[d][c], an fmaf chain over d from 0, with dE computed on the fly in this order: e = pred - targ;
+// g = sign(e) (l1) or 2 e; g *= weights_hd[h][d] where given; g *= scale / (B H D).  The lane with c == d also stores dE[r][d], which the weight / bias
+// gradients of final_conv[1] read - needs C >= D.  The LAST 16 blocks: the loss value, weighted_loss_kernel's summation order.
 __global__ __launch_bounds__(1024) void train_loss_kernel(const float* __restrict__ pred, const float* __restrict__ targ, const float* __restrict__ weights_hd,
                                                           const float* __restrict__ hs, const float* __restrict__ hg, int l1, float scale, float* __restrict__ dE,
                                                           const float* __restrict__ w, float* __restrict__ gH, int B, int H, int D, int C, float* __restrict__ loss_out,
@@ -1473,22 +1420,9 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
-// norm[0] = sqrt(sum part), norm[1] = clip coefficient min(1, max_norm / (norm + 1e-6))   (one block)
-__global__ __launch_bounds__(256) void norm_finish_kernel(const float* __restrict__ part, int n_part, float max_norm, float* __restrict__ norm) {
-    __shared__ float red[4];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n_part; i += 256) s += part[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float nrm = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
-        norm[0] = nrm;
-        norm[1] = max_norm > 0.f ? fminf(1.0f, max_norm / (nrm + 1e-6f)) : 1.0f;
-    }
-}
-// `part` (n_part sumsq_kernel partial sums; null: no clipping): every block adds them up in norm_finish_kernel's order (same bits) instead of
-// waiting for a one-block launch in between; block 0 publishes norm[0] = |g|, norm[1] = the clip coefficient.
+// `part` (n_part sumsq_kernel partial sums; null: no clipping): every block adds them up itself, in one fixed order (thread t takes part[t], part[t + 256],
+// ... in ascending order, then the wave sum, then (wave 0 + wave 1) + (wave 2 + wave 3): the same bits in every block), instead of waiting for a one-block
+// launch in between; block 0 publishes norm[0] = |g| = sqrt(sum part), norm[1] = the clip coefficient min(1, max_norm / (|g| + 1e-6)).
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
                                                    float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt, const float* __restrict__ part, int n_part,
                                                    float max_norm, float* __restrict__ norm, const int* __restrict__ cnt) {

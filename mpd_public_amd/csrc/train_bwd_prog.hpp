@@ -43,7 +43,7 @@ static int bwd_down_applicable(const mpdx_unet* u) {
     }
     if (variant == 2 && (int)u->layers.size() == 34) {   // 3: ... and the two middle blocks (layers 17 .. 20: identity residuals, 128 channels on 16 positions) in front
         const auto& tl = u->tl;
-        bool ok = sw::train_bwd_mid();
+        bool ok = true;
         for (int i = 17; i <= 20 && ok; ++i) {
             const Layer& l = u->layers[i];
             ok = l.mode == CONV_S1 && l.ks == 5 && l.epi == EPI_GN_MISH && l.c1 == 128 && l.c2 == 0 && l.cout == 128 && l.L_out == 16 && l.gs == 16 && tl[i].src1_l == i - 1 && tl[i].need_dgrad &&

@@ -90,7 +90,7 @@ static int ensure_pack_descs(mpdx_unet* u) {
 
 // workspace layout for a batch of B (float offsets)
 struct TrainWs {
-    size_t xn, eps, dE, out0, pre0, grad0, tmpX, dU, zst, pvec, wpart, rpart, emb, h1, temb, tm, h1m, tb, dT, dtm, dh1, zeros, ticket, norm, lossp, total;
+    size_t xn, eps, dE, out0, pre0, grad0, dU, pvec, wpart, rpart, emb, h1, temb, tm, h1m, tb, dT, dtm, dh1, zeros, ticket, lossp, total;
     size_t slotB;          // floats of one activation slot for the batch
     size_t wpart_floats;
     // deferred reductions (one launch each at the end of the backward pass): every layer keeps its own partial sums
@@ -142,9 +142,7 @@ static TrainWs train_ws(const mpdx_unet* u, int B) {
     w.out0 = take(n * w.slotB);
     w.pre0 = take(n * w.slotB);
     w.grad0 = take(n * w.slotB);
-    w.tmpX = take(2 * w.slotB);
     w.dU = take(w.slotB);
-    w.zst = take(2 * w.slotB);
     w.pvec = take((size_t)4 * B * 512);
     size_t wp = 0;
     for (const Layer& l : u->layers) {
@@ -179,20 +177,22 @@ static TrainWs train_ws(const mpdx_unet* u, int B) {
     w.dtm = take((size_t)B * 32); w.dh1 = take((size_t)B * 128);
     w.zeros = take(1024);
     w.ticket = take(4);      // directly behind `zeros`: one memset clears both
-    w.norm = take(1024 + 8);
     w.lossp = take(32);       // 16 doubles: the loss value's wave sums (train_loss_kernel); offsets are multiples of 4 floats: 8-byte aligned
     w.total = o;
     return w;
 }
 
-static int launch_layer(const Layer& l, ConvArgs& a, int B, hipStream_t st) { return launch_conv_layer(l, a, B, st); }
+static int lg2(int v) {   // the smallest k with 2^k >= v
+    int k = 0;
+    while ((1 << k) < v) ++k;
+    return k;
+}
 
 static int fill_geom(const Layer& l, int B, ConvArgs& a) {
     a.c1 = l.c1; a.c2 = l.c2;
     a.B = B; a.L_in = l.L_in; a.L_out = l.L_out; a.C_out = l.cout;
     a.cin_pad = l.cin_pad; a.rs = l.rs; a.gs = l.gs;
     a.Lv_out = l.Lv_out;
-    auto lg2 = [](int v) { int k = 0; while ((1 << k) < v) ++k; return k; };
     a.lg_c4n = lg2(l.cin_pad / 4); a.lg_Lin = lg2(l.L_in); a.lg_Lout = lg2(l.L_out); a.lg_gs = l.gs > 0 ? lg2(l.gs) : 0;
     if ((1 << a.lg_c4n) != l.cin_pad / 4 || (1 << a.lg_Lin) != l.L_in || (1 << a.lg_Lout) != l.L_out || (l.gs > 0 && (1 << a.lg_gs) != l.gs))
         return fail(MPDX_E_INVALID, "layer %s: channel/length/group sizes must be powers of two", l.name.c_str());
@@ -246,7 +246,7 @@ static int make_wgrad(const float* A, int LA, int lda, int a_off, int M, const f
 }
 // let a (deferred) weight-gradient job add up its convolution's bias gradient too: true if attached (else the caller runs launch_rowsum)
 static bool attach_bias(WgradJob& j, Deferred* df, float* gbias, bool from_b) {
-    if (!sw::train_bias_fold() || !df || !df->on || !j.deferred || df->col.n >= 120) return false;
+    if (!df || !df->on || !j.deferred || df->col.n >= 120) return false;
     const int C = from_b ? j.a.N : j.a.M;
     j.a.bias_part = df->ws + df->pcur;
     j.a.bias_from_b = from_b ? 1 : 0;
@@ -271,19 +271,33 @@ static void run_wgrad(const WgradJob& j, hipStream_t st) {
     }
     finish_wgrad(j, st);
 }
-static int launch_wgrad(const float* A, int LA, int lda, int a_off, int M, const float* Bm, int LB, int ldb, int b_off, int N, int sb, int ob, int KS,
-                        int B, float* part, float* g, int n_tot, int n_off, hipStream_t st, Deferred* df = nullptr) {
-    WgradJob j;
-    if (int rc = make_wgrad(A, LA, lda, a_off, M, Bm, LB, ldb, b_off, N, sb, ob, KS, B, part, g, n_tot, n_off, df, j)) return rc;
-    run_wgrad(j, st);
-    return 0;
-}
 
 // two wave groups per weight-gradient block inside bwd_pair_kernel's 512-thread workgroups (train.hpp wgrad_body, ngrp = 2): shapes of the prefetching loop
 static bool wgrad_two_groups(const WgradJob& j) {
-    if (!sw::wgrad_two()) return false;
     const int LA = j.a.LA, LB = j.a.LB, nr = LA >> 3;
     return (LA & 7) == 0 && LB == ((j.KS == 3 || j.KS == 4) ? 2 * LA : LA) && (nr == 1 || nr == 2 || nr == 4 || nr == 8);
+}
+// the LDS a job needs inside a 512-thread workgroup (bwd_pair_kernel, wgrad_multi_kernel)
+static size_t wgrad_job_lds(const WgradJob& j) {
+    return wgrad_two_groups(j) ? std::max(2 * j.lds, (size_t)(256 * j.KS * 4 + 256) * sizeof(float)) : j.lds;
+}
+// the weight-gradient blocks of a bwd_pair_kernel launch: jobs -> a.w[0 .. njobs); returns their block count and raises `lds` to what they need
+static int add_pair_jobs(BwdPairArgs& a, const WgradJob* jobs, int njobs, size_t& lds) {
+    int blocks = 0;
+    for (int k = 0; k < njobs; ++k) {
+        a.w[k] = jobs[k].a; a.ks_w[k] = jobs[k].KS;
+        a.gx[k] = jobs[k].grid.x; a.gy[k] = jobs[k].grid.y;
+        a.nw[k] = jobs[k].grid.x * jobs[k].grid.y * jobs[k].grid.z;
+        blocks += a.nw[k];
+        a.two[k] = wgrad_two_groups(jobs[k]) ? 1 : 0;
+        lds = std::max(lds, wgrad_job_lds(jobs[k]));
+    }
+    return blocks;
+}
+// a launch's dynamic LDS: more than 160 KB fails, more than 64 KB raises the kernel's limit
+static int fit_lds(size_t lds, const void* kern, const char* what) {
+    if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "%s needs %zu B of LDS", what, lds);
+    return lds > 64 * 1024 ? raise_lds_limit(kern) : 0;
 }
 
 // the tile of an input-gradient convolution: the forward engine's choice, 16 rows where the layer's channels are no multiple of it (dispatch_tile's rule, k_conv.hip)
@@ -335,23 +349,13 @@ static int launch_bwd_pair(const Layer& dgl, ConvArgs& cd, int B, const WgradJob
         a.cd2 = *cd2;
         a.n_dgrad2 = (dgl2->cout / MT) * cd2->n_tiles_n;
     }
-    int total = a.n_dgrad + a.n_dgrad2;
-    for (int k = 0; k < njobs; ++k) {
-        a.w[k] = jobs[k].a; a.ks_w[k] = jobs[k].KS;
-        a.gx[k] = jobs[k].grid.x; a.gy[k] = jobs[k].grid.y;
-        a.nw[k] = jobs[k].grid.x * jobs[k].grid.y * jobs[k].grid.z;
-        total += a.nw[k];
-        a.two[k] = wgrad_two_groups(jobs[k]) ? 1 : 0;
-        lds = std::max(lds, a.two[k] ? std::max(2 * jobs[k].lds, (size_t)(256 * jobs[k].KS * 4 + 256) * sizeof(float)) : jobs[k].lds);
-    }
+    const int total = a.n_dgrad + a.n_dgrad2 + add_pair_jobs(a, jobs, njobs, lds);
 #define MPDX_BP_TILE(mt, nt)                                                                              \
     if (MT == mt && NT == nt) {                                                                           \
         lds = std::max(lds, conv_block_lds_bytes<CONV_S1, KS_D, mt, nt, 8>(cd.L_in, cd.L_out, cd.rs));      \
         if (dgl2) lds = std::max(lds, conv_block_lds_bytes<CONV_S1, 1, mt, nt, 8>(cd2->L_in, cd2->L_out, cd2->rs)); \
-        if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "backward pair needs %zu B of LDS", lds);        \
         auto kern = bwd_pair_kernel<KS_D, mt, nt, GN_BWD ? EPI_GN_BWD : EPI_BIAS>;                         \
-        if (lds > 64 * 1024)                                                                              \
-            if (int rc = raise_lds_limit((const void*)kern)) return rc;                                   \
+        if (int rc = fit_lds(lds, (const void*)kern, "backward pair")) return rc;                         \
         hipLaunchKernelGGL(kern, dim3(total), dim3(512), lds, st, a);                                     \
         tiles.add(mt, nt, dgl2 ? 2 : 1, GN_BWD);                                                          \
         for (int k = 0; k < njobs; ++k) finish_wgrad(jobs[k], st);                                        \
@@ -369,19 +373,9 @@ static int launch_lone_wgrads(const WgradJob* jobs, int njobs, hipStream_t st) {
     BwdPairArgs a;
     memset(&a, 0, sizeof(a));
     size_t lds = 0;
-    int total = 0;
-    for (int k = 0; k < njobs; ++k) {
-        a.w[k] = jobs[k].a; a.ks_w[k] = jobs[k].KS;
-        a.gx[k] = jobs[k].grid.x; a.gy[k] = jobs[k].grid.y;
-        a.nw[k] = jobs[k].grid.x * jobs[k].grid.y * jobs[k].grid.z;
-        total += a.nw[k];
-        a.two[k] = wgrad_two_groups(jobs[k]) ? 1 : 0;
-        lds = std::max(lds, a.two[k] ? std::max(2 * jobs[k].lds, (size_t)(256 * jobs[k].KS * 4 + 256) * sizeof(float)) : jobs[k].lds);
-    }
+    const int total = add_pair_jobs(a, jobs, njobs, lds);
     auto kern = bwd_pair_kernel<1, 16, 16, EPI_BIAS>;
-    if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "weight-gradient launch needs %zu B of LDS", lds);
-    if (lds > 64 * 1024)
-        if (int rc = raise_lds_limit((const void*)kern)) return rc;
+    if (int rc = fit_lds(lds, (const void*)kern, "weight-gradient launch")) return rc;
     hipLaunchKernelGGL(kern, dim3(total), dim3(512), lds, st, a);
     for (int k = 0; k < njobs; ++k) finish_wgrad(jobs[k], st);
     return 0;
@@ -409,12 +403,10 @@ static int launch_wgrads_multi(std::vector<WgradJob>& jobs, hipStream_t st) {
             a.start[k] = total;
             total += (int)(j.grid.x * j.grid.y * j.grid.z);
             a.two[k] = wgrad_two_groups(j) ? 1 : 0;
-            lds = std::max(lds, a.two[k] ? std::max(2 * j.lds, (size_t)(256 * j.KS * 4 + 256) * sizeof(float)) : j.lds);
+            lds = std::max(lds, wgrad_job_lds(j));
         }
         for (int k = nj; k <= kWgradMultiMax; ++k) a.start[k] = total;
-        if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "weight-gradient launch needs %zu B of LDS", lds);
-        if (lds > 64 * 1024)
-            if (int rc = raise_lds_limit((const void*)wgrad_multi_kernel)) return rc;
+        if (int rc = fit_lds(lds, (const void*)wgrad_multi_kernel, "weight-gradient launch")) return rc;
         hipLaunchKernelGGL(wgrad_multi_kernel, dim3(total), dim3(512), lds, st, a);
     }
     return 0;
@@ -440,11 +432,6 @@ static void launch_rowsum(const float* x, size_t rows, int C, float* part, float
     hipLaunchKernelGGL(colsum_kernel, dim3((C + 63) / 64, 1), dim3(256), 0, st, c);
 }
 
-static void launch_acc(float* dst, const float* src, int B, int L, int Cd, int Ls, int Cs, int c_off, int step, int store, hipStream_t st) {
-    const size_t total = (size_t)B * L * Cd;
-    hipLaunchKernelGGL(acc_slice_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 2048)), dim3(256), 0, st, dst, src, B, L, Cd, Ls, Cs, c_off, step, store);
-}
-
 // Draw mode of the training pass (mpdx_train_draw below): the seed and the device step counter armed for a network
 struct TrainRng { unsigned long long seed; const int* counter; };
 static std::mutex g_train_rng_mu;
@@ -452,7 +439,7 @@ static std::unordered_map<const mpdx_unet*, TrainRng> g_train_rng;
 
 // round 6: the dgrad launch of a ResidualTemporalBlock's blocks[1] (with the GroupNorm backward of blocks[0] in its epilogue) WAITS one layer for the block's
 // residual 1x1 convolution (the next layer in backward order): its 1x1 dgrad - and at batch < 48 both layers' weight-gradient blocks - ride on the same
-// launch (BwdPairArgs::cd2): one launch less per such block.  MPDX_TRAIN_PAIR_RES=0: one launch per layer as before
+// launch (BwdPairArgs::cd2): one launch less per such block
 struct PendingPair { bool on = false; int i_next = -1; Layer dg; ConvArgs a; WgradJob jobs[3]; int njobs = 0; };
 
 // train_bwd_prog.hpp
@@ -502,7 +489,7 @@ struct __attribute__((visibility("hidden"))) TrainPass {   // (its members are n
     int goff(const float* p) const { return (int)(p - ws); }
     // (no memset of the gradient buffers: the first writer of each in the backward pass stores, the later ones add)
     bool first_write(int j) { const bool f = !written[j]; written[j] = 1; return f; }
-    bool fused_fwd() const { return sw::train_fused_fwd() && fused_mask(B) != 0u && (w.total < ((size_t)1 << 31)); }
+    bool fused_fwd() const { return fused_mask(B) != 0u && (w.total < ((size_t)1 << 31)); }
 
     // forward, every layer's output (and GroupNorm input) kept
     int forward_time_qsample(const float* x_start, const float* noise, const long long* t_dev, const float* sqrt_ac, const float* sqrt_1mac, const float* freqs16,
@@ -643,9 +630,9 @@ inline int TrainPass::forward_layers() {
         ConvArgs a;
         if (int rc = layer_args(i, a)) return rc;
         // blocks[0] and the same block's residual 1x1 convolution (the next layer; both read the block input) as ONE launch - the planning path's conv_pair_kernel
-        // (round 6: two launches of ~4.8 us less per pass on the four-level network; MPDX_TRAIN_PAIR_FWD=0: one launch per layer)
+        // (round 6: two launches of ~4.8 us less per pass on the four-level network)
         int MT = 0, NT = 0;
-        if (sw::train_pair_fwd() && !masked && i + 1 < n && !(fused && u->owner[i + 1] >= 0 && ((fused_mask(B) >> u->owner[i + 1]) & 1u)) && u->tl[i + 1].src1_l == u->tl[i].src1_l &&
+        if (!masked && i + 1 < n && !(fused && u->owner[i + 1] >= 0 && ((fused_mask(B) >> u->owner[i + 1]) & 1u)) && u->tl[i + 1].src1_l == u->tl[i].src1_l &&
             u->tl[i + 1].src2_l == u->tl[i].src2_l && pair_tile(l, u->layers[i + 1], B, MT, NT)) {
             ConvArgs a2;
             if (int rc = layer_args(i + 1, a2)) return rc;
@@ -654,7 +641,7 @@ inline int TrainPass::forward_layers() {
             if (rc < 0) return rc;
             if (rc == 1) { ++i; continue; }
         }
-        if (int rc = launch_layer(l, a, B, st)) return rc;
+        if (int rc = launch_conv_layer(l, a, B, st)) return rc;
     }
     return 0;
 }
@@ -795,7 +782,7 @@ inline int TrainPass::gn_backward(int i, const float*& dy) {
     if (dcol) { g.pg = ws + colsum3(l); g.pb = g.pg + (size_t)B * l.cout; g.pbias = g.pb + (size_t)B * l.cout; }
     if (l.tb_off >= 0) { g.dT = ws + w.dT + l.tb_off; g.dT_stride = u->tt_row; }
     g.B = B; g.L = l.L_out; g.C = l.cout; g.gs = l.gs; g.n_groups = l.cout / l.gs;
-    { int k = 0; while ((1 << k) < l.gs) ++k; g.lg_gs = k; }
+    g.lg_gs = lg2(l.gs);
     if (l.cout > 512) return fail(MPDX_E_INVALID, "layer %s: more than 512 channels", l.name.c_str());
     const int re = l.gs * l.L_out, regions = B * g.n_groups;
     const dim3 ggrid((regions + 3) / 4);
@@ -804,7 +791,7 @@ inline int TrainPass::gn_backward(int i, const float*& dy) {
     // du IN PLACE for the two kernels whose body allows it (a lane reads its elements before it writes them): grd(i) outlives the pass, the shared
     // dU scratch does not - so this layer's weight gradients can run behind the chain too (dy == gy in place_wgrads).  Round 6: the one 256 -> 256 layer whose
     // GroupNorm backward is its own launch kept its weight-gradient blocks riding on its dgrad launch - 22.6 us against its six siblings' 12.5 at batch 128
-    if (sw::train_gn_inplace() && !mrows && (re == 256 || re == 128)) g.du = gy;
+    if (!mrows && (re == 256 || re == 128)) g.du = gy;
     if (re == 256 && !mrows) hipLaunchKernelGGL(gn_mish_bwd_kernel<4>, ggrid, dim3(256), 0, st, g);
     else if (re == 128 && !mrows) hipLaunchKernelGGL(gn_mish_bwd_kernel<2>, ggrid, dim3(256), 0, st, g);
     else if (re == 256 && l.gs >= 4) hipLaunchKernelGGL((gn_mish_bwd_gen_kernel<4, 1>), ggrid, dim3(256), 0, st, g);
@@ -849,27 +836,26 @@ inline int TrainPass::place_wgrads(int i, const float* dy, WgradJob* jobs, int& 
     const Layer& l = u->layers[i];
     const auto& t = u->tl[i];
     const float* gy = grd(i);
-    const bool pair_off = !sw::train_pair();
     // round 6 (MPDX_TRAIN_WGRAD_LATE, dev A/B switch): a layer's weight gradients leave the chain when their dU operand outlives the pass - it does
     // whenever it sits in the layer's own gradient slot (grd(i): written once, never recycled), not in the shared dU scratch of an un-fused
     // GroupNorm backward - and run with everybody else's in wgrad_multi_kernel behind the chain
     const int late_env = sw::train_wgrad_late();   // -1: by batch (measured: batch 32 no gain, 128 -3 %, 512 -4.6 %)
     const bool late_on = late_env < 0 ? B >= 48 : late_env != 0;   // (batch 48: 0.58 -> 0.543 ms, batch 32: within noise: profiles/r06_train_b32_late_ab.txt)
     // will this layer's weight gradients run behind the chain (decided below, once the jobs exist: the same conditions)?  Then with fewer batch splits.
-    const bool late_cand = late_on && t.need_dgrad && !pair_off && df.on && df.red.n + 2 <= 96 && bwd_pair_has_tile(t.dg, B) && dy == gy;
+    const bool late_cand = late_on && t.need_dgrad && df.on && df.red.n + 2 <= 96 && bwd_pair_has_tile(t.dg, B) && dy == gy;
     if (int rc = layer_wgrads(i, dy, late_cand ? wgrad_late_sdiv(B) : 1, jobs, njobs)) return rc;
     // bias gradient = channel sums of dY: rides on the first weight-gradient job, else its own two launches
     if (l.epi != EPI_GN_MISH && !attach_bias(jobs[0], &df, gflat(l.b), l.mode == CONV_UPT))
         launch_rowsum(gy, (size_t)B * l.L_out, l.cout, ws + w.rpart, gflat(l.b), st, &df);
     // one launch for all of them needs every job on its own partial buffer (the deferred mode)
-    paired = t.need_dgrad && !pair_off && jobs[0].deferred && (njobs == 1 || jobs[1].deferred) && bwd_pair_has_tile(t.dg, B);
+    paired = t.need_dgrad && jobs[0].deferred && (njobs == 1 || jobs[1].deferred) && bwd_pair_has_tile(t.dg, B);
     if (late_on && paired && dy == gy) {
         for (int k = 0; k < njobs; ++k) lone.push_back(jobs[k]);
         njobs = 0;
     }
     if (!paired)
         for (int k = 0; k < njobs; ++k) {
-            if (!t.need_dgrad && !pair_off && jobs[k].deferred) lone.push_back(jobs[k]);
+            if (!t.need_dgrad && jobs[k].deferred) lone.push_back(jobs[k]);
             else run_wgrad(jobs[k], st);
         }
     return 0;
@@ -900,14 +886,13 @@ inline int TrainPass::dgrad_with_gn_epilogue(int i, int j, ConvArgs& a, const Wg
     if (u->tl[j].res_l >= 0) { a.bw_gres = grd(u->tl[j].res_l); a.bw_gres_store = first_write(u->tl[j].res_l) ? 1 : 0; }
     a.res = pre(j);
     a.gamma = flat + u->params[lj.gamma].foff; a.beta = flat + u->params[lj.beta].foff;
-    a.gs = lj.gs; a.lg_gs = 0;
-    while ((1 << a.lg_gs) < lj.gs) ++a.lg_gs;
+    a.gs = lj.gs; a.lg_gs = lg2(lj.gs);
     a.bw_pg = ws + colsum3(lj); a.bw_pb = a.bw_pg + (size_t)B * lj.cout; a.bw_pbias = a.bw_pb + (size_t)B * lj.cout;
     if (lj.tb_off >= 0) { a.bw_dT = ws + w.dT + lj.tb_off; a.bw_dT_stride = u->tt_row; }
     du_ready[j] = 1;
     // is the next layer in backward order this block's residual 1x1 convolution?  Then this launch waits for it (PendingPair)
     bool defer = false;
-    if (sw::train_pair_res() && dg2.ks == 5 && i >= 1 && t.res_l == i - 1 && njobs <= 1) {
+    if (dg2.ks == 5 && i >= 1 && t.res_l == i - 1 && njobs <= 1) {
         const Layer& r = u->layers[i - 1];
         defer = r.mode == CONV_S1 && r.ks == 1 && r.epi == EPI_BIAS && u->tl[i - 1].need_dgrad && r.L_out == l.L_out && !(down_variant != 0 && i - 1 <= dn_last);
     }
@@ -943,25 +928,17 @@ inline int TrainPass::input_gradient(int i, const float* dy, const WgradJob* job
     const Layer& l = u->layers[i];
     const auto& t = u->tl[i];
     const Layer& dgl = t.dg;
-    const float* din = dy;
-    const bool fold = sw::train_resample_fold();
-    if (l.mode == CONV_DOWN && !fold) {
-        const size_t tot = (size_t)B * 2 * l.L_out * l.cout;
-        hipLaunchKernelGGL(zero_stuff_kernel, dim3((unsigned)std::min<size_t>((tot + 255) / 256, 2048)), dim3(256), 0, st, dy, ws + w.zst, B, l.L_out, l.cout);
-        din = ws + w.zst;
-    }
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     if (int rc = fill_geom(dgl, B, a)) return rc;
-    a.src1 = din;
-    if (l.mode == CONV_DOWN && fold) a.stuff = 1;   // the staging reads dy zero-stuffed (ConvArgs::stuff)
+    a.src1 = dy;
+    if (l.mode == CONV_DOWN) a.stuff = 1;   // the staging reads dy zero-stuffed (ConvArgs::stuff)
     a.wp = packedT + t.dgrad_woff;
     a.bias = ws + w.zeros;
-    if (l.mode == CONV_UPT && fold && t.src1_l >= 0) {   // even output rows straight into the gradient of the layer's input (ConvArgs::decim)
+    if (l.mode == CONV_UPT) {   // even output rows straight into the gradient of the layer's input (ConvArgs::decim); c2 == 0, so src1_l >= 0 (need_dgrad)
         a.dst = grd(t.src1_l); a.decim = 1;
         if (!first_write(t.src1_l)) a.accum |= 1;
-    } else if (l.mode == CONV_UPT) a.dst = ws + w.tmpX;   // full-resolution result, every second position is the gradient
-    else {   // added straight into the gradient buffer(s) of the layer's input(s)
+    } else {   // added straight into the gradient buffer(s) of the layer's input(s)
         a.dst = t.src1_l >= 0 ? grd(t.src1_l) : nullptr;
         if (t.src1_l >= 0 && !first_write(t.src1_l)) a.accum |= 1;
         if (l.c2 > 0) {
@@ -975,12 +952,11 @@ inline int TrainPass::input_gradient(int i, const float* dy, const WgradJob* job
     } else if (paired) {
         if (int rc = dgrad_paired(dgl, a, jobs, njobs)) return rc;
     } else {   // the un-paired launch: launch_conv_layer picks the tile by the same rule
-        if (int rc = launch_layer(dgl, a, B, st)) return rc;
+        if (int rc = launch_conv_layer(dgl, a, B, st)) return rc;
         int MT, NT;
         dgrad_tile(dgl, B, MT, NT);
         tiles.add(MT, NT, 1, false);
     }
-    if (l.mode == CONV_UPT && t.src1_l >= 0 && !a.decim) launch_acc(grd(t.src1_l), ws + w.tmpX, B, l.L_in, l.c1, dgl.L_out, l.c1 + l.c2, 0, 2, first_write(t.src1_l) ? 1 : 0, st);
     return 0;
 }
 
@@ -1145,7 +1121,7 @@ int mpdx_adam_step(float* params, const float* grads, float* exp_avg, float* exp
         const int nb = (int)std::min<size_t>((n + 255) / 256, 1024);
         hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, st, grads, n, scratch + 8, cnt);
         if (max_norm > 0.f) {
-            clip = scratch + 8;   // the partial sums; adam_kernel finishes the norm itself (norm_finish_kernel's order) and publishes scratch[0..1]
+            clip = scratch + 8;   // the partial sums; adam_kernel finishes the norm itself (every block, the same fixed order: the same bits) and publishes scratch[0..1]
             n_part = nb;
         }
     }

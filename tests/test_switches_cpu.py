@@ -15,11 +15,10 @@ CSRC = ROOT / "mpd_public_amd" / "csrc"
 
 NAMES = """BWD_DBG DEBUG DEBUG_FUSE DEBUG_TRAIN FUSED FUSED_MASK GEO GUIDE_DENSE KSPLIT
    LDS_CAP_KB MERGE_DOWN3 NO_MERGE NO_MERGE_UP NO_MID2 NO_MID3 PAIR
-   STATIC_PROGRAMS TARGET_WGS TILE TIME_TAIL_SPLIT TRAIN_BIAS_FOLD TRAIN_BWD_MID
+   STATIC_PROGRAMS TARGET_WGS TILE TIME_TAIL_SPLIT
    TRAIN_BWD_PROG TRAIN_BWD_PROG_MAX_B TRAIN_DEFERRED
-   TRAIN_FUSED_FWD TRAIN_GN_FUSE TRAIN_GN_INPLACE TRAIN_PAIR TRAIN_PAIR_FWD
-   TRAIN_PAIR_RES TRAIN_REDUCE_JOIN TRAIN_RESAMPLE_FOLD TRAIN_RESTREAM_RIDE
-   TRAIN_WGRAD_LATE TRAIN_WGRAD_MULTI WGRAD_LATE_DIV WGRAD_PROG_MUL WGRAD_TWO WS WSN
+   TRAIN_GN_FUSE TRAIN_REDUCE_JOIN TRAIN_RESTREAM_RIDE
+   TRAIN_WGRAD_LATE TRAIN_WGRAD_MULTI WGRAD_LATE_DIV WGRAD_PROG_MUL WS WSN
    WSN_MIN_B WSP WSP_MIN_B WS_NS""".split()
 
 ROW = re.compile(r'^\s*X\(\s*(\w+),\s*"(MPDX_\w+)",\s*(\w+),\s*([^,]+?),\s*(\w+),\s*"(.*)"\)\s*\\?$')
@@ -50,7 +49,7 @@ def test_getenv_only_in_switches_hpp():
 
 def test_table_is_the_known_set():
     t = table()
-    assert sorted(t) == sorted("MPDX_" + n for n in NAMES) and len(t) == 45
+    assert sorted(t) == sorted("MPDX_" + n for n in NAMES) and len(t) == 36
     for name, (fn, kind, dflt, timing, doc) in t.items():
         assert fn == name[len("MPDX_"):].lower(), (name, fn)
         assert kind in ("PRESENT", "ON", "INT", "UINT", "STR") and timing in ("ONCE", "LIVE") and doc.strip(), name

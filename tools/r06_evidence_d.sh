@@ -27,9 +27,9 @@ print(json.dumps({'batch32_D4': bench.training_leg(), 'batch128_D14': bench.trai
 " 2>/dev/null > $O/training.json
 bash tools/ab_train_env.sh MPDX_TRAIN_BWD_PROG "0 1" 3 2>&1 | tee $O/train_bwd_prog_ab.txt
 { echo "# training iteration (ms) of the THREE-level network (dim_mults option 0), batch 32 x D=4 | 128 x D=14 | 512 x D=14, interleaved on one MI355X"
-  echo "# base: MPDX_TRAIN_BWD_PROG=0 MPDX_TRAIN_FUSED_FWD=0 (one launch per layer both ways) | fwd: forward programs only | all: the default (forward + backward programs)"
+  echo "# base: MPDX_TRAIN_BWD_PROG=0 MPDX_FUSED=0 (one launch per layer both ways) | fwd: forward programs only | all: the default (forward + backward programs)"
   for r in 1 2 3; do for v in "base 0 0" "fwd 0 1" "all 1 1"; do set -- $v
-    MPDX_TRAIN_BWD_PROG=$2 MPDX_TRAIN_FUSED_FWD=$3 python -c "
+    MPDX_TRAIN_BWD_PROG=$2 MPDX_FUSED=$3 python -c "
 import bench
 a = bench.training_leg(steps=100, opt=0, baseline=False); b = bench.training_leg(steps=100, B=128, D=14, opt=0, baseline=False); c = bench.training_leg(steps=40, B=512, D=14, opt=0, baseline=False)
 print('$1', a['ms_per_train_step'], b['ms_per_train_step'], c['ms_per_train_step'])
