@@ -459,6 +459,37 @@ int mpdx_sdf_grid_from_occupancy(const uint8_t* occ, float* sdf_out, float* grad
                                  size_t ws_bytes, void* stream);
 int mpdx_occupancy_from_points(const float* points, int n_points, uint8_t* occ, const int n[3], const float origin[3], float cell, void* stream);
 
+/* ---- a signed-distance grid from a triangle mesh: every grid node against every triangle, on the device (csrc/mesh_sdf.hpp).  Replaces nothing in the
+ * reference; it produces the planes the MPDX_FIELD_GRID lookups read from what a CAD export, a scanned fixture or URDF collision geometry gives, with
+ * the surface where the mesh has it (no half-cell quantisation).  Restated in fp64 numpy in tests/mesh_ref.py; the device is held to it within bounds.
+ * All pointers are device pointers: vertices [V][3] fp32, faces [F][3] int32 (counter-clockwise seen from outside), sdf_out [nz][ny][nx], x fastest.
+ * 3-D only: 2 ... 4096 nodes along every axis, at most 2^29 nodes, 1 ... 2^20 faces.
+ *   p     node (ix, iy, iz) sits at origin_j + (float)i_j * cell (fp32: one rounded product, one rounded sum, as for mpdx_sdf_grid_bake).
+ *   d     min over faces f of |p - cp_f(p)|, cp_f = the closest point of the closed triangle (Ericson's region test: a vertex, an edge or the face),
+ *         evaluated on the vertices relative to the node (A = a - p, B = b - p, C = c - p) and measured FROM THE CLOSEST POINT (r = p - cp, d2 = r . r;
+ *         no projected-distance formula: the error in d stays linear in the rounding even for a node in a triangle's plane).  The best d2 is kept with
+ *         fminf (a NaN from a degenerate face never wins); one IEEE sqrtf per node at the end.
+ *   w     the generalised winding number (1 / 4 pi) sum_f Omega_f, Omega = 2 atan2f(det[A B C], |A||B||C| + (A.B)|C| + (B.C)|A| + (C.A)|B|) (Van Oosterom
+ *         and Strackee), summed in fp32 in face order per node: the same bits from run to run.  A node is inside where w > 0.5.
+ *   s     MPDX_MESH_SIGN_WINDING:  s = (w > 0.5 ? -d : d) - inflate;  MPDX_MESH_SIGN_NONE:  s = d - inflate, w is not evaluated (open sheets and scans:
+ *         inflate >= 0 gives them thickness).
+ *   grad  [nz][ny][nx][4] or NULL (MPDX_GRID_NEAREST needs it, LINEAR does not): the differences of s stated for mpdx_sdf_grid_from_occupancy, by
+ *         the same kernel (k1 = 1.0f / cell, k2 = 0.5f / cell).
+ *   wind_out (or NULL, for tests): w per node; refused with MPDX_MESH_SIGN_NONE.
+ * A face with an index outside [0, n_vertices) or a non-finite vertex is skipped on the device (d2 = +inf, Omega = 0): it is never read out of bounds.
+ * The library allocates nothing, takes no workspace and never synchronises.  The work is nodes x faces pair tests (rates: profiles/mesh_sdf_probe.md):
+ * the host splits the node range into launches of at most 2^33 pairs and refuses a call of more than 2^38 (use a coarser grid or a decimated mesh).
+ *
+ * Refused on the host, before any launch (MPDX_E_INVALID, the message names the argument): a null vertices, faces, sdf_out, n or origin; n_vertices < 3;
+ * n_faces outside 1 ... 2^20; n outside the ranges above (n[2] = 1: "3-D only"); more than 2^29 nodes; cell not positive and finite; inflate negative or
+ * non-finite; a non-finite origin; an unknown sign_mode; wind_out with MPDX_MESH_SIGN_NONE; vertices, faces, sdf_out or wind_out not 4-byte aligned,
+ * grad_out not 16-byte aligned; nodes x n_faces > 2^38. */
+#define MPDX_MESH_SIGN_WINDING 0
+#define MPDX_MESH_SIGN_NONE    1
+int mpdx_sdf_grid_from_mesh(const float* vertices, int n_vertices, const int32_t* faces, int n_faces, float* sdf_out, float* grad_out /* or NULL */,
+                            float* wind_out /* or NULL: w per node, for tests */, const int n[3], const float origin[3], float cell, float inflate,
+                            int sign_mode, void* stream);
+
 /* ---- baseline planners of the dataset-generation script: replaces `HybridPlanner(RRTConnect x n via
  * MultiSampleBasedPlanner, GPMP2).optimize()` of scripts/generate_data/generate_trajectories.py:68-120.  The planners are
  * un-vendored in the reference (mp_baselines submodule empty: PARITY UNPINNED); the published algorithms are restated

@@ -35,6 +35,7 @@ SCENE_HEADER_WORDS = 2 * MAX_FIELDS      # MPDX_SCENE_HEADER_WORDS
 SCENE_MAX_STAGED_FLOATS = 12 * 1024      # MPDX_SCENE_MAX_STAGED_FLOATS
 FIELD_OBJECTS, FIELD_WORKSPACE, FIELD_SELF, FIELD_GRID = 0, 1, 2, 3
 GRID_LINEAR, GRID_NEAREST = 0, 1
+MESH_SIGN_WINDING, MESH_SIGN_NONE = 0, 1     # MPDX_MESH_SIGN_*
 ROBOT_POINTMASS, ROBOT_PANDA, ROBOT_CHAIN = 0, 1, 2
 # MPDX_ROBOT_CHAIN_*: caps and record sizes (floats) of the chain table (layout in include/mpdx.h)
 ROBOT_CHAIN_MAX_JOINTS, ROBOT_CHAIN_MAX_SPHERES, ROBOT_CHAIN_MAX_PAIRS = 8, 16, 24
@@ -126,6 +127,7 @@ SIGNATURES = {
     "mpdx_sdf_grid_edt_ws_bytes": (_sz, [C.POINTER(C.c_int * 3)]),
     "mpdx_sdf_grid_from_occupancy": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int * 3), _f, _f, _vp, _sz, _vp]),
     "mpdx_occupancy_from_points": (_i, [_vp, _i, _vp, C.POINTER(C.c_int * 3), C.POINTER(C.c_float * 3), _f, _vp]),
+    "mpdx_sdf_grid_from_mesh": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, C.POINTER(C.c_int * 3), C.POINTER(C.c_float * 3), _f, _f, _i, _vp]),
     "mpdx_unet_profile": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, C.POINTER(C.c_float), C.POINTER(C.c_double),
                                 C.POINTER(C.c_char_p), C.POINTER(C.c_int)]),
     "mpdx_layer_trace": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(C.c_longlong)]),

@@ -2,7 +2,7 @@
 // units of libmpdx.so.  The library is built from one host TU (mpdx.hip: model building, tile choice, the launch units of a pass and the ONE walk
 // over them, mpdx_plan's launch schedule and loop, the C ABI, the small streaming kernels; it alone includes fused_build.hpp - the fused-segment builder and build_units - and
 // unet_measure.hpp - the timing / trace entry points and the launch-unit queries) and one TU per kernel family - k_conv.hip (conv_block.hpp), k_ws.hip (conv_ws.hpp), k_fused.hip /
-// k_fused_train.hip (fused_level.hpp), k_guide.hip (guide.hpp), k_chain.hip (chain.hpp), k_ik.hip (ik.hpp), k_edt.hip (edt.hpp), k_attn.hip (attn.hpp), k_inner_run.hip (inner_run.hpp), k_train.hip (train.hpp + train_host.hpp), k_planner.hip
+// k_fused_train.hip (fused_level.hpp), k_guide.hip (guide.hpp), k_chain.hip (chain.hpp), k_ik.hip (ik.hpp), k_edt.hip (edt.hpp), k_mesh.hip (mesh_sdf.hpp), k_attn.hip (attn.hpp), k_inner_run.hip (inner_run.hpp), k_train.hip (train.hpp + train_host.hpp), k_planner.hip
 // (planner.hpp + planner_host.hpp) - so that an edit to one kernel family recompiles that family only (mpd_public_amd/build.py
 // compiles the TUs in parallel and keeps the objects).  A kernel template is instantiated in exactly ONE TU, behind a plain function
 // declared here; no device code crosses a TU (no -fgpu-rdc).
@@ -207,6 +207,8 @@ int launch_tail_run(const RunArgs<4>& ra, int B, hipStream_t st);    // TailRunA
 struct AttnArgs;
 const char* attn_unsupported(int C, int L);   // null, or why attn_kernel cannot run a level of C channels on L positions
 int launch_attention(const Layer& l, AttnArgs& a, int B, hipStream_t st);
+// ---- k_edt.hip: the gradient plane [nodes][4] of a finished 3-D sdf plane (edt_grad_kernel<3>; k1 = 1 / cell, k2 = 0.5 / cell)
+void launch_grid_gradient3(const float* sdf, float* grad, const int n[3], float cell, hipStream_t st);
 // ---- k_ws.hip: the weight-stationary persistent kernels
 int launch_weight_stationary(int variant, const Layer& l, ConvArgs& a, const ConvArgs& a2, int B, hipStream_t st);
 // ---- k_fused.hip (planning programs) / k_fused_train.hip (the variants that keep activations for the backward pass)

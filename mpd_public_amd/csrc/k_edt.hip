@@ -20,6 +20,17 @@ static int edt_shape(const char* who, const int n[3], long long* nodes) {
     return 0;
 }
 
+// the gradient plane of a finished 3-D sdf plane, for the other producer of grid planes (k_mesh.hip): edt_grad_kernel is instantiated in this TU only
+void launch_grid_gradient3(const float* sdf, float* grad, const int n[3], float cell, hipStream_t st) {
+    EdtArgs a;
+    memset(&a, 0, sizeof(a));
+    a.sdf = const_cast<float*>(sdf); a.grad = grad;
+    for (int j = 0; j < 3; ++j) a.n[j] = n[j];
+    a.nodes = n[0] * n[1] * n[2];
+    a.k1 = 1.0f / cell; a.k2 = 0.5f / cell;
+    hipLaunchKernelGGL(edt_grad_kernel<3>, dim3((unsigned)((a.nodes + 255) / 256)), dim3(256), 0, st, a);
+}
+
 }  // namespace mpdx
 
 extern "C" {

@@ -88,7 +88,7 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
     robot (extension): a planning.RobotChain that replaces the robot named in `model_id` (the environment is still taken from it).
     sdf_grid_cell_size / sdf_grid_mode (extension): None (default) keeps the primitive tables; a cell size makes the task's FIXED objects a
     signed-distance grid baked on the device ('linear' interpolation or 'nearest' node, planning.PlanningTask(sdf_grid=...)).
-    sdf_grid (extension; None = as above): a planning.GridSDF - GridSDF.from_occupancy / from_points - passed through to the task as its objects field;
+    sdf_grid (extension; None = as above): a planning.GridSDF - GridSDF.from_occupancy / from_points / from_mesh - passed through to the task as its objects field;
     not together with sdf_grid_cell_size."""
     torch.manual_seed(seed)
     if not torch.cuda.is_available():
@@ -303,6 +303,21 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
     return results_data_dict
 
 
+def _mesh_grid_args(a: dict) -> dict:
+    """--sdf_grid_mesh PATH of the command line: the mesh becomes a GridSDF over the task's workspace (GridSDF.from_mesh, at --sdf_grid_cell_size, in
+    --sdf_grid_mode) and goes to experiment(sdf_grid=...); experiment's own sdf_grid_cell_size stays unset (it would bake the primitives)."""
+    path = a.pop("sdf_grid_mesh")
+    if path is None:
+        return a
+    if a["sdf_grid_cell_size"] is None:
+        raise SystemExit("--sdf_grid_mesh needs --sdf_grid_cell_size")
+    from .planning import GridSDF, make_env
+    ws_min, ws_max = make_env(a["model_id"].split("-")[0]).limits
+    a["sdf_grid"] = GridSDF.from_mesh(path, None, ws_min, ws_max, a["sdf_grid_cell_size"], mode=a["sdf_grid_mode"])
+    a["sdf_grid_cell_size"] = None
+    return a
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
@@ -315,11 +330,13 @@ if __name__ == "__main__":
     ap.add_argument("--n_diffusion_steps_without_noise", type=int, default=5)
     ap.add_argument("--sdf_grid_cell_size", type=float, default=None, help="fixed objects as a signed-distance grid of this cell size (default: primitive tables)")
     ap.add_argument("--sdf_grid_mode", default="linear", choices=["linear", "nearest"])
+    ap.add_argument("--sdf_grid_mesh", default=None, metavar="PATH",
+                    help="fixed objects from a triangle mesh (.obj / .stl, closed, in the workspace frame) as a signed-distance grid; needs --sdf_grid_cell_size")
     ap.add_argument("--goal_ee_pos", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
                     help="plan to this end-effector position (inverse kinematics) instead of a random goal configuration")
     ap.add_argument("--tool_upright", type=float, default=None, metavar="MAX_TILT_DEG",
                     help="carry the tool upright: the last frame's z axis stays within this many degrees of the world's z (a chain robot; RobotPanda runs as RobotChain.panda())")
-    a = vars(ap.parse_args())
+    a = _mesh_grid_args(vars(ap.parse_args()))
     upright = a.pop("tool_upright")
     if upright is not None:
         import math

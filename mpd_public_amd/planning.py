@@ -300,7 +300,9 @@ class GridSDF:
     grad   None (linear mode needs none) or [..., dim] / [..., 4] node gradients, same leading shape as sdf
     A grid to be baked on first use from primitives (`PlanningTask(sdf_grid=...)`) has sdf = None and carries `source` / `shape` instead.
     A grid made from an occupancy map or a point cloud (`from_occupancy`, `from_points`: an exact Euclidean distance transform on the device,
-    mpdx_sdf_grid_from_occupancy) holds its planes on the device from the start and can be re-run in place (`update_occupancy`)."""
+    mpdx_sdf_grid_from_occupancy) holds its planes on the device from the start and can be re-run in place (`update_occupancy`).
+    So does a grid made from a triangle mesh (`from_mesh`: every node against every triangle on the device, mpdx_sdf_grid_from_mesh; `update_mesh`);
+    `mesh_info` says what was done to the mesh on the way (None for every other grid)."""
     sdf: Optional[torch.Tensor]
     origin: np.ndarray
     cell: float
@@ -337,6 +339,8 @@ class GridSDF:
         self._planes = None
         self._occ = None      # occupancy grids: the byte map [n_nodes] and the transform's workspace, both on the device of the planes
         self._ws = None
+        self._mesh = None     # mesh grids: (vertices [V, 3] fp32, faces [F, 3] int32, sign mode) on the device of the planes
+        self.mesh_info = None
 
     @property
     def dim(self) -> int:
@@ -349,10 +353,10 @@ class GridSDF:
     def planes(self, device):
         """(sdf plane [n_nodes] fp32, gradient plane [n_nodes * 4] fp32 or None) on `device`, baked there first if need be."""
         device = torch.device(device)
-        if self._occ is not None:   # an occupancy grid lives where it was made: the planes update_occupancy writes are the planes every user reads
+        if self._occ is not None or self._mesh is not None:   # an occupancy or mesh grid lives where it was made: the planes update_* writes are the planes every user reads
             here = self._planes[0].device
             if device.type != here.type or device.index not in (None, here.index):
-                raise RuntimeError(f"this GridSDF was made from an occupancy map on {here}; it is not copied to {device}")
+                raise RuntimeError(f"this GridSDF was made from {'an occupancy map' if self._occ is not None else 'a mesh'} on {here}; it is not copied to {device}")
             return self._planes
         if self._planes is not None and self._planes[0].device == device:
             return self._planes
@@ -483,11 +487,127 @@ class GridSDF:
                                                                 C.byref(self._n3()), self.cell, self.inflate, self._ws.data_ptr(), self._ws.numel() * 4,
                                                                 _lib.current_stream()), "mpdx_sdf_grid_from_occupancy")
 
+    # ---- triangle meshes: every node against every triangle, csrc/mesh_sdf.hpp (arithmetic in include/mpdx.h)
+    @classmethod
+    def from_mesh(cls, vertices, faces, ws_min, ws_max, cell_size, padding=0.3, mode="linear", inflate=0.0, sign="winding", device="cuda"):
+        """vertices [V, 3], faces [F, 3] (integer; arrays or tensors), or a path (.obj / .stl, mesh.load_mesh) in place of vertices with faces=None.
+        The grid box is the one `grid_spec_for` places around the (3-D) workspace.  sign='winding': a closed mesh, negative inside (generalised winding
+        number > 0.5; a mesh whose signed volume is negative is taken as oriented inwards and its faces are reversed); sign='none': the unsigned
+        distance, for open sheets and scans - `inflate` gives them thickness.  Zero-area faces are dropped.  `mesh_info` records dropped_faces,
+        flipped, signed_volume and the counts.  The planes live on `device` from the start; the gradient plane is written for mode='nearest' only."""
+        v32, f32, info = _check_mesh(vertices, faces, sign)
+        ws_min, ws_max = np.asarray(ws_min, np.float64).reshape(-1), np.asarray(ws_max, np.float64).reshape(-1)
+        if ws_min.size != 3 or ws_max.size != 3:
+            raise ValueError(f"from_mesh: a mesh grid is 3-D only (the workspace has {ws_min.size} axes)")
+        if mode not in GRID_MODES:
+            raise ValueError(f"GridSDF mode {mode!r}: 'linear' or 'nearest'")
+        if not (float(inflate) >= 0 and np.isfinite(float(inflate))):
+            raise ValueError("GridSDF inflate must be non-negative and finite")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("a signed-distance grid is made from a mesh on the GPU (mpdx_sdf_grid_from_mesh); there is no CPU fallback")
+        shape, origin = grid_spec_for(ws_min, ws_max, cell_size, padding)
+        rev = tuple(reversed(shape))
+        sdf = torch.empty(rev, dtype=torch.float32, device=device)
+        grad = torch.empty(rev + (4,), dtype=torch.float32, device=device) if mode == "nearest" else None   # linear mode reads none
+        g = cls(sdf, origin, cell_size, mode, grad, inflate=float(inflate))
+        g._planes = (g.sdf.reshape(-1), None if grad is None else g.grad.reshape(-1))
+        g._mesh = (torch.from_numpy(v32).to(device), torch.from_numpy(f32).to(device), MESH_SIGNS[sign])
+        g.mesh_info = info
+        g._mesh_run()
+        return g
+
+    def update_mesh(self, vertices, faces=None):
+        """Re-run INTO THE PLANES THIS GRID ALREADY HOLDS.  faces=None keeps the faces the grid holds (as they were left by from_mesh: zero-area faces
+        dropped, an inward mesh reversed) and takes the same number of vertices - an object that moves rigidly between frames; with faces the mesh is
+        checked, cleaned and oriented afresh.  A guide or task copies the planes again with its refresh_grids(), as after update_occupancy."""
+        if self._mesh is None:
+            raise ValueError("update_mesh: this GridSDF was not made by from_mesh")
+        old_v, old_f, sign_mode = self._mesh
+        sign = [k for k, v in MESH_SIGNS.items() if v == sign_mode][0]
+        if faces is None:
+            v32 = _mesh_vertices(vertices)
+            if v32.shape[0] != old_v.shape[0]:
+                raise ValueError(f"update_mesh: {v32.shape[0]} vertices for the {old_v.shape[0]} the stored faces index (give faces too for another mesh)")
+            self._mesh = (torch.from_numpy(v32).to(old_v.device), old_f, sign_mode)
+        else:
+            v32, f32, info = _check_mesh(vertices, faces, sign)
+            self._mesh = (torch.from_numpy(v32).to(old_v.device), torch.from_numpy(f32).to(old_v.device), sign_mode)
+            self.mesh_info = info
+        self._mesh_run()
+        return self
+
+    def _mesh_run(self):
+        import ctypes as C
+        sdf, grad = self._planes
+        v, f, sign_mode = self._mesh
+        org = (C.c_float * 3)(*[float(x) for x in self.origin])
+        with torch.cuda.device(v.device):
+            _lib.check(_lib.load().mpdx_sdf_grid_from_mesh(v.data_ptr(), int(v.shape[0]), f.data_ptr(), int(f.shape[0]), sdf.data_ptr(),
+                                                           None if grad is None else grad.data_ptr(), None,
+                                                           C.byref(self._n3()), C.byref(org), self.cell, self.inflate, sign_mode, _lib.current_stream()),
+                       "mpdx_sdf_grid_from_mesh")
+            for t in (v, f):
+                t.record_stream(torch.cuda.current_stream())
+
     def node_values(self, device="cuda"):
         """(sdf [nz, ny, nx] | [ny, nx], grad [..., 4] or None) as the kernels read them (downloaded by the tests for their fp64 reference)."""
         sdf, grad = self.planes(device)
         shp = tuple(reversed(self.shape))
         return sdf.reshape(shp), (None if grad is None else grad.reshape(shp + (4,)))
+
+
+MESH_SIGNS = {"winding": _lib.MESH_SIGN_WINDING, "none": _lib.MESH_SIGN_NONE}
+
+
+def _mesh_vertices(vertices):
+    """array or tensor [V, 3] -> contiguous fp32 numpy array, checked in float64: shape, finite"""
+    v = vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else np.asarray(vertices)
+    if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] < 3 or v.dtype.kind not in "fiu":
+        raise ValueError(f"mesh vertices are a [V, 3] array of at least three points (got {v.dtype} {tuple(v.shape)})")
+    v = v.astype(np.float64)
+    if not np.isfinite(v).all() or np.abs(v).max() > 3.0e38:
+        raise ValueError("mesh vertices must be finite (in fp32)")
+    return np.ascontiguousarray(v.astype(np.float32))
+
+
+def _check_mesh(vertices, faces, sign):
+    """The host-side checks of GridSDF.from_mesh, in float64, before anything is uploaded -> (vertices fp32 [V, 3], faces int32 [F, 3], mesh_info).
+    A path goes through mesh.load_mesh.  Zero-area faces (of the fp32 vertices the device gets) are dropped; with sign='winding' a mesh of negative
+    signed volume sum a . (b x c) / 6 is reversed."""
+    if sign not in MESH_SIGNS:
+        raise ValueError(f"from_mesh sign {sign!r}: 'winding' or 'none'")
+    if isinstance(vertices, (str, bytes)) or hasattr(vertices, "__fspath__"):
+        if faces is not None:
+            raise ValueError("from_mesh: a mesh file brings its own faces (give faces=None with a path)")
+        from .mesh import load_mesh
+        vertices, faces = load_mesh(vertices)
+    if faces is None:
+        raise ValueError("from_mesh: faces are missing (only a path brings its own)")
+    v32 = _mesh_vertices(vertices)
+    f = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1:
+        raise ValueError(f"mesh faces are a [F, 3] array of vertex indices (got shape {tuple(f.shape)})")
+    if f.dtype.kind not in "iu":
+        raise ValueError(f"mesh faces are integers (got {f.dtype})")
+    f = f.astype(np.int64)
+    if f.min() < 0 or f.max() >= v32.shape[0]:
+        raise ValueError(f"mesh faces index vertices 0 ... {v32.shape[0] - 1} (got {int(f.min())} ... {int(f.max())})")
+    v = v32.astype(np.float64)
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    keep = (np.cross(b - a, c - a) != 0).any(1)
+    dropped = int((~keep).sum())
+    f, a, b, c = f[keep], a[keep], b[keep], c[keep]
+    if f.shape[0] == 0:
+        raise ValueError("mesh faces: every face has zero area")
+    if f.shape[0] > (1 << 20):
+        raise ValueError(f"mesh faces: {f.shape[0]} faces (at most 2^20: decimate the mesh)")
+    volume = float((a * np.cross(b, c)).sum() / 6.0)
+    flipped = sign == "winding" and volume < 0
+    if flipped:
+        f = f[:, ::-1]
+    info = dict(n_vertices=int(v32.shape[0]), n_faces=int(f.shape[0]), dropped_faces=dropped, flipped=bool(flipped), signed_volume=volume, sign=sign)
+    return v32, np.ascontiguousarray(f.astype(np.int32)), info
 
 
 def _occupancy_bytes(occ):
@@ -530,7 +650,7 @@ class PlanningTask:
         objects become a signed-distance grid (baked from the primitives on the device on first use, mpdx_sdf_grid_bake) and
         get_collision_fields() returns a FIELD_GRID field in their place; extra objects, workspace and self fields stay as they are (as
         torch_robotics does, as recalled: the precomputed grid is for the fixed objects only).  An environment that already carries a grid
-        (env.grid_fixed, set by task_from_torch_robotics) uses it as it is.  A `GridSDF` instance (GridSDF.from_occupancy / from_points, or node
+        (env.grid_fixed, set by task_from_torch_robotics) uses it as it is.  A `GridSDF` instance (GridSDF.from_occupancy / from_points / from_mesh, or node
         values of the caller's own) is used as the objects field as it is, the way env.grid_fixed is."""
         self.env, self.robot, self.obstacle_cutoff_margin = env, robot, obstacle_cutoff_margin
         if isinstance(robot, RobotChain):
@@ -580,7 +700,7 @@ class PlanningTask:
         return self._gp
 
     def refresh_grids(self):
-        """after GridSDF.update_occupancy: copy the planes again where the metrics' grid buffer is a concatenation (guides.refresh_grid_planes)"""
+        """after GridSDF.update_occupancy / update_mesh: copy the planes again where the metrics' grid buffer is a concatenation (guides.refresh_grid_planes)"""
         if getattr(self, "_gp", None) is not None:
             from .guides import refresh_grid_planes
             refresh_grid_planes(self._gp)
