@@ -1,6 +1,6 @@
 // edt.hpp - an exact Euclidean distance transform on the device: an occupancy grid (or a point cloud voxelised here) becomes the sdf and gradient
-// planes the MPDX_FIELD_GRID lookups of grid_field.hpp read (mpdx_sdf_grid_from_occupancy, mpdx_occupancy_from_points; the arithmetic is stated
-// in include/mpdx.h and restated as brute-force numpy in tests/edt_ref.py).  Replaces nothing in the reference: its environments are primitives.
+// planes the MPDX_FIELD_GRID lookups of grid_field.hpp read (mpdx_sdf_grid_from_occupancy, mpdx_occupancy_from_points in k_grid.hip; the arithmetic is
+// stated in include/mpdx.h and restated as brute-force numpy in tests/edt_ref.py).  Replaces nothing in the reference: its environments are primitives.
 //
 // Two squared-distance planes travel through the separable passes in the caller's workspace, ws = [2][nz][ny][nx] int32: plane 0 = distance to the
 // nearest OCCUPIED node, plane 1 = to the nearest FREE node.  A node's own side gives 0 in the other plane, so the signed-side value is plane 0 at a
@@ -16,14 +16,15 @@
 //            and stops at (y - y')^2 >= best.  In place: a workgroup reads its tile before the barrier, writes it after, and no other
 //            workgroup touches those nodes.
 //   final    one thread per node: s from d2 in fp32, every step rounded (the single-operation intrinsics: the build's -ffp-contract=on fuses
-//            within an expression only), then - a second launch - the gradient plane as differences of s, one 16-byte store per node.
+//            within an expression only), then - a second launch, grid_gradient_kernel of grid_field.hpp - the gradient plane as differences of s,
+//            one 16-byte store per node.
 // No atomics; nothing is allocated; no synchronisation.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/mpdx.h"
-#include "grid_field.hpp"   // grid_f32x4
+#include "grid_field.hpp"   // grid_gradient_kernel
 
 namespace mpdx {
 
@@ -33,12 +34,11 @@ struct EdtArgs {
     const uint8_t* occ;   // [nz][ny][nx]
     int32_t* ws;          // [2][nodes]
     float* sdf;           // [nodes]
-    float* grad;          // [nodes][4] or null
-    int32_t* d2;          // [nodes] or null
     int n[3];
     int nodes;            // n[0] * n[1] * n[2] <= 2^29
+    int32_t* d2;          // [nodes] or null.  (Behind the counts, not next to sdf: the order keeps edt_sdf_kernel's argument loads - profiles/grid_producers_refactor.md)
     int none;             // (n[0] + n[1] + n[2])^2
-    float cell, inflate, k1, k2;
+    float cell, inflate;
 };
 
 // distance from bit x to the nearest set bit of w[0 .. nw) (bits beyond the row are clear), or -1
@@ -142,27 +142,6 @@ __global__ __launch_bounds__(256) void edt_sdf_kernel(const EdtArgs a) {
     const int d2 = a.ws[(size_t)(o ? 1 : 0) * a.nodes + node];
     if (a.d2) a.d2[node] = d2;
     a.sdf[node] = edt_signed(a, d2, o);
-}
-
-// gradient plane from the finished sdf plane: central differences inside, one-sided at the faces; the unused axis and the fourth word are 0
-template <int DIM>
-__global__ __launch_bounds__(256) void edt_grad_kernel(const EdtArgs a) {
-    const int node = blockIdx.x * 256 + threadIdx.x;
-    if (node >= a.nodes) return;
-    const int nx = a.n[0], ny = a.n[1];
-    const int ix = node % nx, iy = (node / nx) % ny, iz = node / (nx * ny);
-    const int id[3] = {ix, iy, iz};
-    const int stride[3] = {1, nx, nx * ny};
-    float g[3] = {0.f, 0.f, 0.f};
-    const float s = a.sdf[node];
-#pragma unroll
-    for (int j = 0; j < DIM; ++j) {
-        const bool first = id[j] == 0, last = id[j] == a.n[j] - 1;   // (n[j] >= 2: never both)
-        const float hi = last ? s : a.sdf[node + stride[j]];
-        const float lo = first ? s : a.sdf[node - stride[j]];
-        g[j] = __fmul_rn(__fsub_rn(hi, lo), (first || last) ? a.k1 : a.k2);
-    }
-    *(grid_f32x4*)(a.grad + 4 * (size_t)node) = (grid_f32x4){g[0], g[1], g[2], 0.f};
 }
 
 // ---------------------------------------------------------------------------------------------------------------- voxelise

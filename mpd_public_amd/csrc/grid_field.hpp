@@ -1,5 +1,6 @@
 // grid_field.hpp - MPDX_FIELD_GRID: a precomputed signed-distance grid as a collision field of the guide and metrics kernels, and the kernel
-// that bakes one from the sphere / box tables (mpdx_sdf_grid_bake).
+// that bakes one from the sphere / box tables (mpdx_sdf_grid_bake), and the gradient-by-differences kernel of the producers that have no analytic
+// gradient (occupancy and mesh grids).  The producers' entry points are in k_grid.hip.
 //
 // Replaces torch_robotics' GridMapSDF (the fixed objects' SDF sampled once per environment and looked up per link point) - un-vendored in the
 // reference: the lookup is restated in include/mpdx.h (mpdx_field) with both plausible forms as an explicit
@@ -315,6 +316,37 @@ __global__ __launch_bounds__(256) void sdf_grid_bake_kernel(const GridBakeArgs a
             g[j] = outside ? sg[j] * fmaxf(d[j], 0.f) * inv : (j == jm ? sg[j] : 0.f);
     }
     *(grid_f32x4*)(a.grad + 4 * node) = (grid_f32x4){g[0], g[1], g[2], 0.f};
+}
+
+// ---------------------------------------------------------------------------------------------------------------- gradient by differences
+// The gradient plane of a FINISHED sdf plane, for the producers without an analytic one (occupancy and mesh grids; launched by k_grid.hip after their
+// sdf kernels): central differences inside, one-sided at the faces; the unused axis and the fourth word are 0.
+struct GridGradientArgs {
+    const float* sdf;   // [nodes]
+    float* grad;        // [nodes][4]
+    int n[3];
+    int nodes;          // n[0] * n[1] * n[2] <= 2^29
+    float k1, k2;       // 1 / cell, 0.5 / cell
+};
+
+template <int DIM>
+__global__ __launch_bounds__(256) void grid_gradient_kernel(const GridGradientArgs a) {
+    const int node = blockIdx.x * 256 + threadIdx.x;
+    if (node >= a.nodes) return;
+    const int nx = a.n[0], ny = a.n[1];
+    const int ix = node % nx, iy = (node / nx) % ny, iz = node / (nx * ny);
+    const int id[3] = {ix, iy, iz};
+    const int stride[3] = {1, nx, nx * ny};
+    float g[3] = {0.f, 0.f, 0.f};
+    const float s = a.sdf[node];
+#pragma unroll
+    for (int j = 0; j < DIM; ++j) {
+        const bool first = id[j] == 0, last = id[j] == a.n[j] - 1;   // (n[j] >= 2: never both)
+        const float hi = last ? s : a.sdf[node + stride[j]];
+        const float lo = first ? s : a.sdf[node - stride[j]];
+        g[j] = __fmul_rn(__fsub_rn(hi, lo), (first || last) ? a.k1 : a.k2);
+    }
+    *(grid_f32x4*)(a.grad + 4 * (size_t)node) = (grid_f32x4){g[0], g[1], g[2], 0.f};
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side

@@ -2,7 +2,7 @@
 // units of libmpdx.so.  The library is built from one host TU (mpdx.hip: model building, tile choice, the launch units of a pass and the ONE walk
 // over them, mpdx_plan's launch schedule and loop, the C ABI, the small streaming kernels; it alone includes fused_build.hpp - the fused-segment builder and build_units - and
 // unet_measure.hpp - the timing / trace entry points and the launch-unit queries) and one TU per kernel family - k_conv.hip (conv_block.hpp), k_ws.hip (conv_ws.hpp), k_fused.hip /
-// k_fused_train.hip (fused_level.hpp), k_guide.hip (guide.hpp), k_chain.hip (chain.hpp), k_ik.hip (ik.hpp), k_edt.hip (edt.hpp), k_mesh.hip (mesh_sdf.hpp), k_attn.hip (attn.hpp), k_inner_run.hip (inner_run.hpp), k_train.hip (train.hpp + train_host.hpp), k_planner.hip
+// k_fused_train.hip (fused_level.hpp), k_guide.hip (guide.hpp), k_chain.hip (chain.hpp), k_ik.hip (ik.hpp), k_grid.hip (the grid producers: edt.hpp, mesh_sdf.hpp, grid_field.hpp's bake), k_attn.hip (attn.hpp), k_inner_run.hip (inner_run.hpp), k_train.hip (train.hpp + train_host.hpp), k_planner.hip
 // (planner.hpp + planner_host.hpp) - so that an edit to one kernel family recompiles that family only (mpd_public_amd/build.py
 // compiles the TUs in parallel and keeps the objects).  A kernel template is instantiated in exactly ONE TU, behind a plain function
 // declared here; no device code crosses a TU (no -fgpu-rdc).
@@ -39,6 +39,7 @@ int fail(int code, const char* fmt, ...);
     } while (0)
 int raise_lds_limit(const void* kern);   // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel)
 int dev_hooks_missing(const char* fn);   // 0 in a development build (-DMPDX_DEV_HOOKS); else the MPDX_E_STATE error of a trace / ablation entry point
+inline bool finite_f(float v) { return fabsf(v) < 3.0e38f; }   // an entry point's float argument is usable (false for NaN)
 
 // final_conv[1] (Conv1d(32 -> D, k=1), temporal_unet.py:113-116) fused with the DDPM posterior step
 // (diffusion_model_base.py:121-155, sample_functions.py:31-62) and hard conditioning (sample_functions.py:5-8).
@@ -207,8 +208,6 @@ int launch_tail_run(const RunArgs<4>& ra, int B, hipStream_t st);    // TailRunA
 struct AttnArgs;
 const char* attn_unsupported(int C, int L);   // null, or why attn_kernel cannot run a level of C channels on L positions
 int launch_attention(const Layer& l, AttnArgs& a, int B, hipStream_t st);
-// ---- k_edt.hip: the gradient plane [nodes][4] of a finished 3-D sdf plane (edt_grad_kernel<3>; k1 = 1 / cell, k2 = 0.5 / cell)
-void launch_grid_gradient3(const float* sdf, float* grad, const int n[3], float cell, hipStream_t st);
 // ---- k_ws.hip: the weight-stationary persistent kernels
 int launch_weight_stationary(int variant, const Layer& l, ConvArgs& a, const ConvArgs& a2, int B, hipStream_t st);
 // ---- k_fused.hip (planning programs) / k_fused_train.hip (the variants that keep activations for the backward pass)

@@ -284,40 +284,6 @@ int mpdx_guide_trace(const mpdx_guide_params* gp, float* x, const uint32_t* absm
     return rc;
 }
 
-int mpdx_sdf_grid_bake(const mpdx_guide_params* gp, int field, float* sdf_out, float* grad_out, const int n[3], const float origin[3], float cell,
-                       void* stream) {
-    if (!gp || !sdf_out || !n || !origin) return fail(MPDX_E_INVALID, "null argument");
-    if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS || field < 0 || field >= gp->n_fields) return fail(MPDX_E_INVALID, "field %d of %d", field, gp->n_fields);
-    const mpdx_field& f = gp->fields[field];
-    if (f.kind != MPDX_FIELD_OBJECTS) return fail(MPDX_E_INVALID, "grid bake: field %d is not an OBJECTS field", field);
-    if (gp->tool_frame != 0) return fail(MPDX_E_INVALID, "grid bake: tool_frame %d (the tool-axis term belongs to the guide; a grid is baked from an OBJECTS field)", gp->tool_frame);
-    if (has_scenes(*gp)) return fail(MPDX_E_INVALID, "grid bake: one scene only (n_scenes = %d): a grid stands for the fixed environment", gp->n_scenes);
-    if (gp->ws_dim != 2 && gp->ws_dim != 3) return fail(MPDX_E_INVALID, "grid bake: ws_dim %d", gp->ws_dim);
-    if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
-    if (f.n_spheres < 0 || f.n_boxes < 0 || f.sphere_off < 0 || f.box_off < 0 || f.sphere_off + 4 * f.n_spheres > gp->n_prim_floats ||
-        f.box_off + 6 * f.n_boxes > gp->n_prim_floats || gp->n_prim_floats > 12 * 1024)
-        return fail(MPDX_E_INVALID, "grid bake: the field's primitive tables do not lie inside prims (%d floats, at most 12288)", gp->n_prim_floats);
-    long long nodes = 1;
-    for (int j = 0; j < 3; ++j) {
-        if (j < gp->ws_dim ? (n[j] < 2 || n[j] > 4096) : n[j] != 1)
-            return fail(MPDX_E_INVALID, "grid bake: n[%d] = %d (2 ... 4096 along a used axis, 1 along an unused one)", j, n[j]);
-        nodes *= n[j];
-    }
-    if (nodes > (1ll << 29)) return fail(MPDX_E_INVALID, "grid bake: %lld nodes", nodes);
-    if (!(cell > 0.f) || !(cell < 3.0e38f)) return fail(MPDX_E_INVALID, "grid bake: cell must be positive and finite");
-    if (grad_out && ((uintptr_t)grad_out & 15)) return fail(MPDX_E_INVALID, "grid bake: grad_out must be 16-byte aligned");
-    GridBakeArgs a;
-    memset(&a, 0, sizeof(a));
-    a.f = dev_field_of(f); a.prims = gp->prims; a.n_prim_floats = gp->n_prim_floats; a.sdf = sdf_out; a.grad = grad_out; a.cell = cell;
-    for (int j = 0; j < 3; ++j) { a.n[j] = n[j]; a.origin[j] = j < gp->ws_dim ? origin[j] : 0.f; }
-    const unsigned blocks = (unsigned)((nodes + 255) / 256);
-    const size_t lds = (size_t)gp->n_prim_floats * sizeof(float);
-    if (gp->ws_dim == 2) hipLaunchKernelGGL(sdf_grid_bake_kernel<2>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(sdf_grid_bake_kernel<3>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 int mpdx_guide_variant(const mpdx_guide_params* gp, int B, int H, int D) {
     if (!gp) return fail(MPDX_E_INVALID, "null argument");
     ChainInfo chain_info;

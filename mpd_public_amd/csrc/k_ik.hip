@@ -16,8 +16,6 @@ static int launch_ik_qd(const IkArgs& a, int n_joints, int n, hipStream_t st) {
 
 int launch_ik(const IkArgs& a, int n_joints, int n, hipStream_t st) { return launch_ik_qd(a, n_joints, n, st); }
 
-static bool finite_f(float v) { return fabsf(v) < 3.0e38f; }   // (false for NaN)
-
 }  // namespace mpdx
 
 extern "C" {

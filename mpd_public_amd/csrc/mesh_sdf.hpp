@@ -1,6 +1,6 @@
-// mesh_sdf.hpp - a signed-distance grid from a triangle mesh on the device: every grid node against every triangle (mpdx_sdf_grid_from_mesh; the
-// arithmetic is stated in include/mpdx.h and restated in fp64 numpy in tests/mesh_ref.py).  Replaces nothing in the reference: its environments
-// are primitives.  The gradient plane is written afterwards by edt_grad_kernel<3> (edt.hpp) from the finished sdf plane.
+// mesh_sdf.hpp - a signed-distance grid from a triangle mesh on the device: every grid node against every triangle (mpdx_sdf_grid_from_mesh in
+// k_grid.hip; the arithmetic is stated in include/mpdx.h and restated in fp64 numpy in tests/mesh_ref.py).  Replaces nothing in the reference: its
+// environments are primitives.  The gradient plane is written afterwards by grid_gradient_kernel<3> (grid_field.hpp) from the finished sdf plane.
 //
 // One kernel, 256 threads per workgroup, MESH_NPT nodes per thread (node k of a thread = first node of the workgroup + k * 256 + thread: coalesced
 // stores); one LDS read of a triangle serves MESH_NPT node-triangle pairs.  MESH_NPT = 1 as measured: a pair is about 290 instructions (160 without

@@ -142,7 +142,7 @@ class TrajectoryDataset:
         # robot_id: one of the reference's names, or (extension) a planning.RobotChain - a serial chain described by a table
         chain = isinstance(robot_id, RobotChain)
         self.env, self.robot = make_env(env_id), (robot_id if chain else make_robot(robot_id))
-        # sdf_grid (extension, default None: primitive tables): the task's fixed objects as a baked signed-distance grid - a dict - or a planning.GridSDF used as it is (planning.PlanningTask)
+        # sdf_grid (extension, default None: primitive tables): the task's fixed objects as a baked signed-distance grid - a dict - or a grid_sdf.GridSDF used as it is (planning.PlanningTask)
         self.task = PlanningTask(self.env, self.robot, obstacle_cutoff_margin=obstacle_cutoff_margin,
                                  use_extra_objects=use_extra_objects, tensor_args=self.tensor_args, sdf_grid=sdf_grid)
         self.n_support_points, self.include_velocity = n_support_points, include_velocity

@@ -88,7 +88,7 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
     robot (extension): a planning.RobotChain that replaces the robot named in `model_id` (the environment is still taken from it).
     sdf_grid_cell_size / sdf_grid_mode (extension): None (default) keeps the primitive tables; a cell size makes the task's FIXED objects a
     signed-distance grid baked on the device ('linear' interpolation or 'nearest' node, planning.PlanningTask(sdf_grid=...)).
-    sdf_grid (extension; None = as above): a planning.GridSDF - GridSDF.from_occupancy / from_points / from_mesh - passed through to the task as its objects field;
+    sdf_grid (extension; None = as above): a grid_sdf.GridSDF - GridSDF.from_occupancy / from_points / from_mesh - passed through to the task as its objects field;
     not together with sdf_grid_cell_size."""
     torch.manual_seed(seed)
     if not torch.cuda.is_available():

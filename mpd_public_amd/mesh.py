@@ -1,4 +1,4 @@
-"""Triangle meshes from files, for GridSDF.from_mesh: Wavefront OBJ and STL (binary and ASCII), numpy only.
+"""Triangle meshes from files, for GridSDF.from_mesh (grid_sdf.py): Wavefront OBJ and STL (binary and ASCII), numpy only.
 
 load_mesh(path) -> (vertices float64 [V, 3], faces int32 [F, 3]).  Nothing here touches the device; the checks a mesh must pass before it is uploaded
 (finite vertices, indices in range, zero-area faces, orientation) are GridSDF.from_mesh's."""

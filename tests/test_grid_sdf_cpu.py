@@ -101,6 +101,47 @@ def test_abi_struct_sizes_match_the_c_header(tmp_path):
     assert len(mirrored) >= 8 and all(getattr(_lib, k) == defs[k] for k in mirrored), [k for k in mirrored if getattr(_lib, k) != defs[k]]
 
 
+# ---------------------------------------------------------------------------------------------------------------- the grid module
+def test_planning_re_exports_the_grid_module_names():
+    import mpd_public_amd as m
+    from mpd_public_amd import grid_sdf, planning
+    for name in ("GridSDF", "grid_spec_for", "GRID_MODES", "MESH_SIGNS", "_check_mesh", "_mesh_vertices", "_occupancy_bytes"):
+        assert getattr(planning, name) is getattr(grid_sdf, name), name
+    assert m.GridSDF is grid_sdf.GridSDF
+
+
+@pytest.mark.parametrize("env_id,robot_id", [("EnvSimple2D", "RobotPointMass"), ("EnvSpheres3D", "RobotPanda")])
+def test_for_primitives_is_the_dict_form_of_the_task(env_id, robot_id):
+    import mpd_public_amd as m
+    from mpd_public_amd.grid_sdf import GridSDF
+    spec = dict(cell_size=0.03, mode="nearest", padding=0.25)
+    task = m.TrajectoryDataset(env_id, robot_id, sdf_grid=spec).task
+    want = task.df_collision_objects.grid
+    got = GridSDF.for_primitives(task.env.obj_fixed, task.ws_min, task.ws_max, spec["cell_size"], mode=spec["mode"], padding=spec["padding"])
+    assert got.sdf is None and want.sdf is None and got.dim == task.env.dim
+    assert got.shape == want.shape and got.origin.tobytes() == want.origin.tobytes() and got.origin.dtype == want.origin.dtype
+    assert got.cell == want.cell and got.mode == want.mode == "nearest" and got.source is want.source is task.env.obj_fixed
+    # ... and of the defaults (mode 'linear', padding 0.3)
+    dflt, plain = m.TrajectoryDataset(env_id, robot_id, sdf_grid=dict(cell_size=0.03)).task.df_collision_objects.grid, GridSDF.for_primitives(
+        task.env.obj_fixed, task.ws_min, task.ws_max, 0.03)
+    assert plain.shape == dflt.shape and plain.origin.tobytes() == dflt.origin.tobytes() and plain.mode == dflt.mode == "linear"
+
+
+def test_the_grid_module_does_not_import_planning():
+    """In a fresh interpreter.  The package's __init__ imports planning itself (it exports PlanningTask), so the child gives the package a bare stand-in
+    with the package's path: what `import mpd_public_amd.grid_sdf` then loads is what grid_sdf and its own imports ask for."""
+    import sys
+    code = ("import sys, types\n"
+            "pkg = types.ModuleType('mpd_public_amd'); pkg.__path__ = [sys.argv[1]]; sys.modules['mpd_public_amd'] = pkg\n"
+            "import mpd_public_amd.grid_sdf as g\n"
+            "assert g.GridSDF.__module__ == 'mpd_public_amd.grid_sdf' and callable(g.grid_spec_for)\n"
+            "print(' '.join(sorted(k for k in sys.modules if k.startswith('mpd_public_amd.'))))\n")
+    out = subprocess.run([sys.executable, "-c", code, str(ROOT / "mpd_public_amd")], cwd=ROOT, capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+    loaded = out.stdout.split()
+    assert "mpd_public_amd.grid_sdf" in loaded and "mpd_public_amd.planning" not in loaded, loaded
+
+
 # ---------------------------------------------------------------------------------------------------------------- adapter
 def _grid_map_sdf(dim=2, n=(6, 5, 4)):
     shape = n[:dim]

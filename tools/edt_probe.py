@@ -4,7 +4,7 @@ occupancy on this host's CPU and to the primitive bake (mpdx_sdf_grid_bake, both
 
   python tools/edt_probe.py [--rounds 5] [--window 0.3]
 
-Workspaces: the 2-D one at 1 cm (EnvSimple2D / point mass) and the Panda's at 2 cm (EnvSpheres3D), on the grid box of planning.grid_spec_for.  The
+Workspaces: the 2-D one at 1 cm (EnvSimple2D / point mass) and the Panda's at 2 cm (EnvSpheres3D), on the grid box of grid_sdf.grid_spec_for.  The
 occupancy is (primitive sdf at the node <= 0), taken from the device bake.  Per workspace and variant: `reps` calls back to back between ONE event
 pair after warm-up calls, reps chosen so that a window lasts about --window seconds; the variants alternate within each of `rounds` rounds; median,
 min and max over the rounds.  The device d2 plane is compared with scipy's (rint of the squared distances) before anything is timed.  Prints one
@@ -65,7 +65,7 @@ def main():
         ws_bytes = lib.mpdx_sdf_grid_edt_ws_bytes(C.byref(n3))
         ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device="cuda")
         st = _lib.current_stream()
-        # the primitive bake's parameter block (as planning.GridSDF._bake builds it)
+        # the primitive bake's parameter block (as grid_sdf.GridSDF._bake builds it)
         gp = _lib.GuideParams()
         gp.ws_dim, gp.n_fields = dim, 1
         sp, bx = ds.env.obj_fixed.prim_floats()

@@ -3,7 +3,7 @@
 
   python tools/mesh_probe.py [--rounds 5] [--window 0.3] [--ab name=build_ab/libmpdx_<tag>.so ...] [--ab-faces 5120]
 
-The grid is the Panda's workspace at 2 cm (planning.grid_spec_for: 132 x 132 x 112 nodes); the meshes are icospheres of 1 280, 5 120 and 20 480 faces
+The grid is the Panda's workspace at 2 cm (grid_sdf.grid_spec_for: 132 x 132 x 112 nodes); the meshes are icospheres of 1 280, 5 120 and 20 480 faces
 inside it, in both sign modes.  Per case and variant: `reps` calls back to back between ONE event pair after warm-up calls, reps chosen so that a
 window lasts about --window seconds; the variants alternate within each of `rounds` rounds; median, min and max over the rounds (the protocol of
 tools/edt_probe.py).  --ab adds libraries built with other MPDX_MESH_NPT / MPDX_MESH_TILE (MPDX_BUILD_DEFS) as variants of the --ab-faces case: they
@@ -28,7 +28,7 @@ import mesh_ref  # noqa: E402  (the icosphere)
 
 CENTRE, RADIUS, CELL = (0.3, 0.0, 0.5), 0.25, 0.02
 NAME = "mpdx_sdf_grid_from_mesh"
-LAUNCH_PAIRS = 1 << 33      # the host's cap per launch (csrc/k_mesh.hip)
+LAUNCH_PAIRS = 1 << 33      # the host's cap per launch (csrc/k_grid.hip)
 
 
 def timed(fn, reps):
