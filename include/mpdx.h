@@ -94,9 +94,19 @@ int    mpdx_unet_plan_joined(const mpdx_unet* u);
  * ups.0.1.blocks.1 and Upsample1d(128) - is a second persistent launch of the same kind (same counters, status word, bounds and bit-identical results).
  * mpdx_unet_set_inner_run(u, 1) selects every run that is eligible, 0 none.  mpdx_unet_set_inner_run_parts selects them separately: bit 0 the seven
  * layers, bit 1 the tail (A/B runs and tests; other bits: MPDX_E_INVALID).  mpdx_unet_inner_runs counts the seven-layer launches only;
- * mpdx_unet_inner_run_layers: how many layers ran inside run launches of either kind in the last mpdx_plan call (11 per pass with both selected). */
+ * mpdx_unet_inner_run_layers: how many layers ran inside run launches of either kind in the last mpdx_plan call (11 per pass with both selected).
+ *
+ * The width of the runs: a position tile is 4 whole trajectories (32 positions, one workgroup per compute unit) or 2 (16 positions, 8 x ceil(B / 2)
+ * workgroups, up to two per compute unit; B <= 128 on 256 CUs either way).  mpdx_unet_set_inner_run_width(u, w): w = 0 automatic by batch (the
+ * default), 16 or 32 for both runs; anything else MPDX_E_INVALID.  It takes effect at the next mpdx_plan; the results are the same bits at every
+ * width, and the two counts above keep their values. */
 int    mpdx_unet_set_inner_run(mpdx_unet* u, int on);
 int    mpdx_unet_set_inner_run_parts(mpdx_unet* u, int parts);
+int    mpdx_unet_set_inner_run_width(mpdx_unet* u, int width);
+/* The launch geometry of a run, without a device (tests): the workgroups of a launch for batch B at `width` (the return value; negative: an error),
+ * the cluster (-1: a surplus workgroup of the placement, it leaves at once) and the channel tile 0..7 of workgroup `block`, and the counter lines a
+ * handle keeps for that width on a device of `cus` compute units.  Null outputs are skipped. */
+int    mpdx_inner_run_block(int B, int width, int cus, int block, int32_t* cluster, int32_t* tile, int32_t* counter_lines);
 int    mpdx_unet_inner_runs(const mpdx_unet* u);
 int    mpdx_unet_inner_run_layers(const mpdx_unet* u);
 int    mpdx_unet_status(const mpdx_unet* u);

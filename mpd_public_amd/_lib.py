@@ -95,6 +95,8 @@ SIGNATURES = {
     "mpdx_unet_plan_joined": (_i, [_vp]),
     "mpdx_unet_set_inner_run": (_i, [_vp, _i]),
     "mpdx_unet_set_inner_run_parts": (_i, [_vp, _i]),
+    "mpdx_unet_set_inner_run_width": (_i, [_vp, _i]),
+    "mpdx_inner_run_block": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
     "mpdx_unet_inner_runs": (_i, [_vp]),
     "mpdx_unet_inner_run_layers": (_i, [_vp]),
     "mpdx_unet_status": (_i, [_vp]),

@@ -124,18 +124,26 @@ struct mpdx_unet {
     // innermost level, kRunTail: the tail of up level 0 - as one persistent launch each
     enum RunPart { kRunSeven = 1, kRunTail = 2 };
     int inner_run = kRunSeven | kRunTail;
+    int inner_run_width = 0;   // mpdx_unet_set_inner_run_width: positions per cluster of both runs - 0 automatic (by batch), 16, 32
     int plan_joined = 0, inner_runs = 0;   // joined / seven-layer run launches of the last mpdx_plan call (mpdx_unet_plan_joined, mpdx_unet_inner_runs)
     int inner_run_layers = 0;              // layers that ran inside run launches of either kind in the last mpdx_plan call (mpdx_unet_inner_run_layers)
     // The run's device state, made at the first mpdx_plan call that may take the run (a handle is created without a device).  mpdx.hip's
     // inner_run_create / _begin / _free and mpdx_unet_set_status alone write it: every counter of a launch's clusters holds `base` when the launch starts.
     struct InnerRunState {
-        int capacity = -1;            // workgroups of the run kernel resident at once on this device (-1: not asked yet; 0: none - no run)
-        bool seven_ok = false, tail_ok = false;   // each run kernel answered its own occupancy query: one workgroup per compute unit fits
+        int capacity = -1;            // compute units of this device (-1: not asked yet; 0: no run on this handle)
+        // workgroups per compute unit each run kernel's occupancy query answered, per width ([0]: 32, [1]: 16; 0: the query failed).  A launch
+        // is admitted where its grid is resident at once: one workgroup per compute unit at width 32, up to two at width 16.
+        int seven_wgs[2] = {0, 0}, tail_wgs[2] = {0, 0};
         long long budget = 0;         // s_memtime ticks of 4 ms
         unsigned* counters = nullptr; // device: one arrival counter per cluster (not reset between launches: base advances by 8 x layers per launch)
-        unsigned base = 0;
-        int live = 1 << 30;           // clusters whose counters hold base (all of them while every counter is zero)
-        bool rezero = false;          // the counters hold a give-up's poison: zero them (and base) before the next launch
+        // One set of counters per width ([0]: 32, [1]: 16; both inside `counters`): the launches of one width cover the same clusters and advance
+        // them together, whatever the other run of the plan takes.
+        struct Counters {
+            unsigned* p = nullptr;
+            unsigned base = 0;
+            int live = 1 << 30;       // clusters whose counters hold base (all of them while every counter is zero)
+            bool rezero = false;      // the counters hold a give-up's poison: zero them (and base) before the next launch
+        } ctr[2];
         unsigned *status = nullptr, *status_dev = nullptr;   // host-mapped pinned sticky word a workgroup that gives up sets; the device's address of it
         unsigned status_host = 0;     // stands in for *status until the device state exists
         unsigned status_word() const { return status ? __atomic_load_n(status, __ATOMIC_RELAXED) : status_host; }
@@ -163,7 +171,7 @@ struct mpdx_unet {
     // one launch of a pass: it covers layers [layer, layer + count) - a program its segment fused[fused], a pair blocks[0] + the block's residual 1x1
     // conv, the inner run and the tail run (mpdx_plan's schedule only, never in current_units) their kInnerRunLayers / kTailRunLayers
     enum UnitKind { kProgram, kLayer, kPair, kInnerRun, kTailRun };
-    struct Unit { UnitKind kind; int fused; int layer; int count; };
+    struct Unit { UnitKind kind; int fused; int layer; int count; int width = 0; };   // width: of a kInnerRun / kTailRun unit
     std::vector<int> owner;                  // layer -> fused segment (-1: per-layer launch)
     // training (train_host.hpp)
     struct TrainLayer {
@@ -199,11 +207,14 @@ bool pair_tile(const Layer& l1, const Layer& l2, int B, int& MT, int& NT);   // 
 int launch_conv_pair(int MT, int NT, const ConvArgs& a1, const ConvArgs& a2, const Layer& l1, const Layer& l2, hipStream_t st);   // 1 launched, 0 does not fit, -1 error
 // ---- k_inner_run.hip: the persistent run of the innermost level's 256 -> 256 layers (inner_run.hpp)
 template <int N> struct RunArgs;
-int inner_run_grid(int B);                 // workgroups of a launch for batch B (the placement's surplus ones included); the same for both runs
-int inner_run_workgroups_per_cu();         // one occupancy query per run kernel; 0: failed
-int tail_run_workgroups_per_cu();
-int launch_inner_run(const RunArgs<7>& ra, int B, hipStream_t st);   // InnerRunArgs
-int launch_tail_run(const RunArgs<4>& ra, int B, hipStream_t st);    // TailRunArgs
+bool inner_run_width_ok(int width);                // 32 or 16 positions per cluster (inner_run.hpp kRunWide / kRunNarrow)
+int inner_run_clusters(int B, int width);          // clusters of width / 8 trajectories for batch B
+int inner_run_grid(int B, int width);              // workgroups of a launch (the placement's surplus ones included); the same for both runs
+void inner_run_slot(int block, int* cluster, int* tile);   // the (cluster, channel tile) the kernel gives a block (a cluster >= inner_run_clusters: it leaves)
+int inner_run_workgroups_per_cu(int width);        // one occupancy query per run kernel and width; 0: failed
+int tail_run_workgroups_per_cu(int width);
+int launch_inner_run(const RunArgs<7>& ra, int B, int width, hipStream_t st);   // InnerRunArgs
+int launch_tail_run(const RunArgs<4>& ra, int B, int width, hipStream_t st);    // TailRunArgs
 // ---- k_attn.hip: the linear self-attention block (attn.hpp); a.x and the five parameter pointers set by the caller
 struct AttnArgs;
 const char* attn_unsupported(int C, int L);   // null, or why attn_kernel cannot run a level of C channels on L positions

@@ -11,10 +11,10 @@ namespace mpdx {
 #endif
 static constexpr bool kSameXcd = MPDX_INNER_RUN_SAME_XCD != 0;
 
-int inner_run_grid(int B) {
-    const int nc = (B + 3) / 4;
-    return kSameXcd ? ((nc + 7) / 8) * 64 : nc * 8;
-}
+bool inner_run_width_ok(int width) { return width == kRunWide || width == kRunNarrow; }
+int inner_run_clusters(int B, int width) { return inner_run_width_ok(width) ? run_clusters(B, width) : 0; }
+int inner_run_grid(int B, int width) { return run_grid(inner_run_clusters(B, width), kSameXcd); }
+void inner_run_slot(int block, int* cluster, int* tile) { const RunSlot s = run_slot(block, kSameXcd); *cluster = s.c; *tile = s.m; }
 
 template <class SEQ>
 static int workgroups_per_cu() {
@@ -25,17 +25,30 @@ static int workgroups_per_cu() {
     }
     return n;
 }
-// workgroups of a run kernel one compute unit holds at once (0: the query failed - that run is then never selected)
-int inner_run_workgroups_per_cu() { return workgroups_per_cu<RunSeqSeven>(); }
-int tail_run_workgroups_per_cu() { return workgroups_per_cu<RunSeqTail>(); }
+// workgroups of a run kernel one compute unit holds at once (0: the query failed, or no such width - that run is then never selected)
+int inner_run_workgroups_per_cu(int width) {
+    return width == kRunWide ? workgroups_per_cu<RunSeqSeven<kRunWide>>() : width == kRunNarrow ? workgroups_per_cu<RunSeqSeven<kRunNarrow>>() : 0;
+}
+int tail_run_workgroups_per_cu(int width) {
+    return width == kRunWide ? workgroups_per_cu<RunSeqTail<kRunWide>>() : width == kRunNarrow ? workgroups_per_cu<RunSeqTail<kRunNarrow>>() : 0;
+}
 
 template <class SEQ>
 static int launch_run(const typename SEQ::Args& ra, int B, hipStream_t st, const char* what) {
-    if (ra.n_layers != SEQ::kLayers || ra.nc != (B + 3) / 4) return fail(MPDX_E_INVALID, "%s: %d layers, %d clusters for B=%d", what, ra.n_layers, ra.nc, B);
-    hipLaunchKernelGGL((inner_run_kernel<SEQ, kSameXcd>), dim3(inner_run_grid(B)), dim3(512), SEQ::lds(), st, ra);
+    if (ra.n_layers != SEQ::kLayers || ra.nc != run_clusters(B, SEQ::kWidth))
+        return fail(MPDX_E_INVALID, "%s: %d layers, %d clusters for B=%d at width %d", what, ra.n_layers, ra.nc, B, SEQ::kWidth);
+    hipLaunchKernelGGL((inner_run_kernel<SEQ, kSameXcd>), dim3(run_grid(ra.nc, kSameXcd)), dim3(512), SEQ::lds(), st, ra);
     return 0;
 }
-int launch_inner_run(const InnerRunArgs& ra, int B, hipStream_t st) { return launch_run<RunSeqSeven>(ra, B, st, "inner run"); }
-int launch_tail_run(const TailRunArgs& ra, int B, hipStream_t st) { return launch_run<RunSeqTail>(ra, B, st, "tail run"); }
+int launch_inner_run(const InnerRunArgs& ra, int B, int width, hipStream_t st) {
+    if (width == kRunNarrow) return launch_run<RunSeqSeven<kRunNarrow>>(ra, B, st, "inner run");
+    if (width == kRunWide) return launch_run<RunSeqSeven<kRunWide>>(ra, B, st, "inner run");
+    return fail(MPDX_E_INVALID, "inner run: width %d", width);
+}
+int launch_tail_run(const TailRunArgs& ra, int B, int width, hipStream_t st) {
+    if (width == kRunNarrow) return launch_run<RunSeqTail<kRunNarrow>>(ra, B, st, "tail run");
+    if (width == kRunWide) return launch_run<RunSeqTail<kRunWide>>(ra, B, st, "tail run");
+    return fail(MPDX_E_INVALID, "tail run: width %d", width);
+}
 
 }  // namespace mpdx

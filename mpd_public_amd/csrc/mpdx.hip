@@ -790,20 +790,34 @@ static int run_fused_join(mpdx_unet* u, const mpdx_unet::Fused& up, const mpdx_u
 }
 
 // ---- the device state of the inner-level run (mpdx_unet::InnerRunState, host.hpp)
-static size_t inner_run_counter_bytes(int capacity) { return (size_t)((capacity + 7) / 8 + 8) * kInnerRunCounterStride * sizeof(unsigned); }
-// One occupancy query, then - one workgroup per compute unit (the occupancy answer says that one fits): the batches the per-layer tiles were measured
-// at - the cluster counters and the host-mapped status word.  A device that cannot be asked leaves capacity 0: no run on this handle.
+// Workgroups of a run launch of `width` that are resident at once on `cus` compute units, given the occupancy answer for that instantiation: the
+// wide form stays at one workgroup per compute unit (the batches the per-layer tiles were measured at), the narrow form takes up to two.
+static int run_index(int width) { return width == kRunNarrow ? 1 : 0; }
+static int inner_run_resident(int cus, int width, int wgs_per_cu) { return cus * std::min(width == kRunNarrow ? 2 : 1, wgs_per_cu); }
+// Counter lines of one width: the largest cluster count an admitted (B, width) gives - an admitted grid is whole groups of 8 clusters x 8 workgroups
+// and at most inner_run_resident() workgroups - plus the 8 lines of slack the area always had (40 lines at width 32, 72 at width 16 on 256 CUs).
+static int inner_run_counter_lines(int cus, int width) { return inner_run_resident(cus, width, 2) / 8 + 8; }
+static size_t inner_run_counter_bytes(int cus, int width) { return (size_t)inner_run_counter_lines(cus, width) * kInnerRunCounterStride * sizeof(unsigned); }
+// One occupancy query per run kernel and width, then the cluster counters (one area per width) and the host-mapped status word.  A device that cannot
+// be asked leaves capacity 0: no run on this handle.
 static int inner_run_create(mpdx_unet::InnerRunState& r, int cus) {
     if (r.capacity >= 0) return 0;
     r.capacity = 0;
     int dev = 0, khz = 0;
     if (cus <= 0 || hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeClockRate, dev) != hipSuccess)
         return (void)hipGetLastError(), 0;
-    r.seven_ok = inner_run_workgroups_per_cu() > 0;
-    r.tail_ok = tail_run_workgroups_per_cu() > 0;
-    if (!r.seven_ok && !r.tail_ok) return 0;
-    HIP_TRY(hipMalloc((void**)&r.counters, inner_run_counter_bytes(cus)));
-    HIP_TRY(hipMemset(r.counters, 0, inner_run_counter_bytes(cus)));
+    bool any = false;
+    for (int width : {kRunWide, kRunNarrow}) {
+        r.seven_wgs[run_index(width)] = inner_run_workgroups_per_cu(width);
+        r.tail_wgs[run_index(width)] = tail_run_workgroups_per_cu(width);
+        any = any || r.seven_wgs[run_index(width)] > 0 || r.tail_wgs[run_index(width)] > 0;
+    }
+    if (!any) return 0;
+    const size_t bytes = inner_run_counter_bytes(cus, kRunWide) + inner_run_counter_bytes(cus, kRunNarrow);
+    HIP_TRY(hipMalloc((void**)&r.counters, bytes));
+    HIP_TRY(hipMemset(r.counters, 0, bytes));
+    r.ctr[0].p = r.counters;
+    r.ctr[1].p = r.counters + inner_run_counter_lines(cus, kRunWide) * kInnerRunCounterStride;
     HIP_TRY(hipHostMalloc((void**)&r.status, 64, hipHostMallocMapped));
     *r.status = r.status_host;
     HIP_TRY(hipHostGetDevicePointer((void**)&r.status_dev, r.status, 0));
@@ -811,18 +825,23 @@ static int inner_run_create(mpdx_unet::InnerRunState& r, int cus) {
     r.capacity = cus;
     return 0;
 }
-// A launch of nc clusters starts.  It advances the counters of ITS clusters only, so a batch with more clusters than the launch before (or a give-up's
-// poison) zeroes them all, stream-ordered, and starts from base 0 again: at most once per plan.  Layer i > 0 waits for *base_out + 8 i: 8 arrivals per layer.
-// The handle's runs share the counters: each launch of n_layers layers leaves its clusters' counters at its base + 8 n_layers, the base of the next
-// launch of either kind (launches of one plan are stream-ordered and cover the same clusters).
-static int inner_run_begin(mpdx_unet::InnerRunState& r, int nc, int n_layers, hipStream_t st, unsigned* base_out) {
-    if (r.rezero || nc > r.live) {
-        HIP_TRY(hipMemsetAsync(r.counters, 0, inner_run_counter_bytes(r.capacity), st));
-        r.base = 0; r.rezero = false;
+// A launch of nc clusters of `width` starts.  It advances the counters of ITS clusters only, so a launch with more clusters than the launch of that
+// width before (a larger batch; a give-up's poison likewise) zeroes that width's counters, stream-ordered, and starts from base 0 again: at most once
+// per plan and width.  Layer i > 0 waits for *base_out + 8 i: 8 arrivals per layer.
+// The handle's runs of one width share its counters: each launch of n_layers layers leaves its clusters' counters at its base + 8 n_layers, the base of
+// the next launch of either kind at that width (launches of one plan are stream-ordered and cover the same clusters).  A change of width between plans
+// - or between the two runs of one plan - changes the area, not the rule.
+static int inner_run_begin(mpdx_unet::InnerRunState& r, int width, int nc, int n_layers, hipStream_t st, unsigned** counters_out, unsigned* base_out) {
+    mpdx_unet::InnerRunState::Counters& k = r.ctr[run_index(width)];
+    if (nc > inner_run_counter_lines(r.capacity, width)) return fail(MPDX_E_STATE, "run of width %d: %d clusters, %d counter lines", width, nc, inner_run_counter_lines(r.capacity, width));
+    if (k.rezero || nc > k.live) {
+        HIP_TRY(hipMemsetAsync(k.p, 0, inner_run_counter_bytes(r.capacity, width), st));
+        k.base = 0; k.rezero = false;
     }
-    r.live = nc;
-    *base_out = r.base;
-    r.base += 8u * (unsigned)n_layers;
+    k.live = nc;
+    *counters_out = k.p;
+    *base_out = k.base;
+    k.base += 8u * (unsigned)n_layers;
     return 0;
 }
 static void inner_run_free(mpdx_unet::InnerRunState& r) {
@@ -840,35 +859,37 @@ static long long* g_run_trace = nullptr;   // dev tool (mpdx_fused_trace on a ru
 static int g_run_trace_kind = -1;
 constexpr int kRunTraceSlots = 32;
 template <int N>
-static int fill_run_args(mpdx_unet* u, int kind, int first, const float* packed, const float* row, const float* x, float* ws, int B, hipStream_t st, RunArgs<N>& ra) {
+static int fill_run_args(mpdx_unet* u, int kind, int first, int width, const float* packed, const float* row, const float* x, float* ws, int B, hipStream_t st, RunArgs<N>& ra) {
     memset(&ra, 0, sizeof(ra));
+    if (!inner_run_width_ok(width)) return fail(MPDX_E_STATE, "run unit of width %d", width);
+    const int nc = inner_run_clusters(B, width);
     for (int k = 0; k < N; ++k) {
         if (int rc = make_conv_args(u, u->layers[first + k], packed, row, x, ws, B, 0, ra.layer[k])) return rc;
-        ra.layer[k].n_tiles_n = (B + 3) / 4;
+        ra.layer[k].n_tiles_n = nc;
         ra.layer[k].trace = g_run_trace && g_run_trace_kind == kind ? g_run_trace + k * kRunTraceSlots : nullptr;
     }
-    ra.n_layers = N; ra.nc = (B + 3) / 4;
-    if (int rc = inner_run_begin(u->run, ra.nc, N, st, &ra.base)) return rc;
-    ra.counters = u->run.counters; ra.status = u->run.status_dev; ra.budget = u->run.budget;
+    ra.n_layers = N; ra.nc = nc;
+    if (int rc = inner_run_begin(u->run, width, nc, N, st, &ra.counters, &ra.base)) return rc;
+    ra.status = u->run.status_dev; ra.budget = u->run.budget;
     u->inner_run_layers += N;
     return 0;
 }
-static int run_inner_run(mpdx_unet* u, int first, const float* packed, const float* row, const float* x, float* ws, int B, hipStream_t st) {
+static int run_inner_run(mpdx_unet* u, int first, int width, const float* packed, const float* row, const float* x, float* ws, int B, hipStream_t st) {
     InnerRunArgs ra;
-    if (int rc = fill_run_args(u, mpdx_unet::kInnerRun, first, packed, row, x, ws, B, st, ra)) return rc;
+    if (int rc = fill_run_args(u, mpdx_unet::kInnerRun, first, width, packed, row, x, ws, B, st, ra)) return rc;
     u->inner_runs++;
-    return launch_inner_run(ra, B, st);
+    return launch_inner_run(ra, B, width, st);
 }
 // mpdx_plan only: the tail of up level 0 - three 128 -> 128 Conv1dBlocks and Upsample1d(128), layers [first, first + kTailRunLayers) - as ONE persistent
 // launch (inner_run.hpp).  It does not count in mpdx_unet_inner_runs.
-static int run_tail_run(mpdx_unet* u, int first, int spare, const float* packed, const float* row, const float* x, float* ws, int B, hipStream_t st) {
+static int run_tail_run(mpdx_unet* u, int first, int spare, int width, const float* packed, const float* row, const float* x, float* ws, int B, hipStream_t st) {
     TailRunArgs ra;
     if (spare < 0 || spare >= u->n_slots) return fail(MPDX_E_STATE, "tail run without a spare slot");
-    if (int rc = fill_run_args(u, mpdx_unet::kTailRun, first, packed, row, x, ws, B, st, ra)) return rc;
+    if (int rc = fill_run_args(u, mpdx_unet::kTailRun, first, width, packed, row, x, ws, B, st, ra)) return rc;
     // layer 0's output, private to the run (layer 1's input, layer 2's residual), lives in the spare slot: tail_run_first says why
     float* const sp = ws + u->slot_floats * (size_t)B * spare;
     ra.layer[0].dst = sp; ra.layer[1].src1 = sp; ra.layer[2].res = sp;
-    return launch_tail_run(ra, B, st);
+    return launch_tail_run(ra, B, width, st);
 }
 
 // one launch unit of the pass (the SAME function serves the planning path, the profiler and the in-situ timer)
@@ -876,8 +897,8 @@ static int run_unit(mpdx_unet* u, const mpdx_unet::Unit& un, const float* packed
                     const FinalArgs* fa, hipStream_t st) {
     if (un.kind == mpdx_unet::kProgram) return run_fused(u, u->fused[un.fused], packed, row, x, ws, B, fa, st);
     if (un.kind == mpdx_unet::kPair) return run_pair(u, u->layers[un.layer], u->layers[un.layer + 1], packed, row, x, ws, B, st);
-    if (un.kind == mpdx_unet::kInnerRun) return run_inner_run(u, un.layer, packed, row, x, ws, B, st);
-    if (un.kind == mpdx_unet::kTailRun) return run_tail_run(u, un.layer, un.fused, packed, row, x, ws, B, st);
+    if (un.kind == mpdx_unet::kInnerRun) return run_inner_run(u, un.layer, un.width, packed, row, x, ws, B, st);
+    if (un.kind == mpdx_unet::kTailRun) return run_tail_run(u, un.layer, un.fused, un.width, packed, row, x, ws, B, st);
     return run_layer(u, u->layers[un.layer], packed, row, x, ws, B, st);
 }
 static double unit_flops(const mpdx_unet* u, const mpdx_unet::Unit& un, int B) {
@@ -1041,6 +1062,10 @@ static int tail_run_first(const mpdx_unet* u, const std::vector<mpdx_unet::Unit>
         // [B][8][128] tensor lie, and those belong to ANOTHER cluster, which may still be reading them (the slot plan gives it layer 0's output slot: safe
         // only where layer 3 starts after ALL of layer 2).  So layer 0's output - private to the run - goes to a spare slot instead: one that none of
         // the four layers names and that is dead here (written before it is read again, if at all), e.g. the skip tensor the block before consumed.
+        // (The rule is per trajectory and per slot, so it holds at either cluster width: with layer 0's output moved, NO other layer of the run names
+        //  layer 3's destination slot - the checks below -, so whichever cluster owns trajectories 2 b and 2 b + 1, and however many trajectories a
+        //  cluster has, nothing of the run reads or writes the bytes trajectory b's upsampled rows land on; every other tensor of the run, the spare
+        //  slot included, gives trajectory b the same bytes of its slot, private to b's cluster.)
         auto named = [&](const Layer& l, int s) { return l.src1 == s || l.src2 == s || l.res == s || l.dst == s; };
         for (int s = 0; s < u->n_slots && *spare < 0; ++s) {
             if (s == u->xpad_slot || named(l0, s) || named(l1, s) || named(l2, s) || named(l3, s)) continue;
@@ -1063,6 +1088,18 @@ static int device_cus() {
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) (void)hipGetLastError();
     return cus;
 }
+// The automatic width of each run: a function of the batch alone, read from profiles/inner_run_narrow_ab.md.  The sweep (cfg2-shaped plans, ms per
+// plan, width 16 minus width 32, one run selected, five rounds with spreads of 0.01 - 0.09 ms):
+//     B             16      32      64     100     128
+//     seven alone  -1.36   -1.54   -1.59   -0.17   -0.26
+//     tail alone   -0.21   -0.19   -0.22   -0.04   -0.00
+// Up to B = 64 every narrow workgroup has a compute unit to itself (8 ceil(B / 2) <= 256) and a launch uses twice the compute units of the wide
+// form; beyond, two share a compute unit and the gain is what their phases overlap, bounded by the weight traffic (twice the wide form's per FLOP).
+// The seven-layer run is narrow at every batch it admits: at the headline batch of 100 it meets the interleaved criterion (-0.170 ms per plan
+// against a parent spread of 0.041).  The tail run does not (-0.069), so it is narrow up to B = 64 and keeps the wide form beyond: the measured
+// crossover lies between 64 and 100, where the narrow workgroups stop having a compute unit each.
+static int inner_run_auto_width(int B) { return (void)B, kRunNarrow; }
+static int tail_run_auto_width(int B) { return B <= 64 ? kRunNarrow : kRunWide; }
 // What mpdx_plan enqueues per pass at batch B, made once per call (the switches and the device are read here, not per pass): the launch units with the
 // seven run layers as ONE unit where the run is selected, and whether passes can be joined.
 struct PlanSchedule {
@@ -1072,22 +1109,31 @@ struct PlanSchedule {
     int build(mpdx_unet* u, int B, bool with_run = true) {   // with_run = false: the per-layer units whatever the handle says (mpdx_fused_trace)
         units = current_units(u, B, nullptr);
         const int cus = device_cus();
-        // The run: the standard four-level network on H = 64 without self-attention, unmasked, and at most one workgroup of the launch per compute unit -
-        // all resident at once (B <= 128 on 256 CUs).
+        // The runs: the standard four-level network on H = 64 without self-attention, unmasked, and every workgroup of the launch resident at once
+        // (B <= 128 on 256 CUs).
         if (with_run && u->inner_run && !u->masked() && !u->cfg.self_attention && u->cfg.n_levels == 4 && u->cfg.n_support_points == 64) {
             if (int rc = inner_run_create(u->run, cus)) return rc;
-            const bool fits = u->run.capacity > 0 && inner_run_grid(B) <= u->run.capacity && sw::geo() && !sw::debug();
-            const int rf = fits && u->run.seven_ok && (u->inner_run & mpdx_unet::kRunSeven) ? inner_run_first(u, units) : -1;
+            // The width of a run: the handle's (mpdx_unet_set_inner_run_width), or automatic by batch; a launch is admitted where its whole grid is
+            // resident at once (inner_run_resident) - B <= 128 on 256 compute units at either width.  0: the run is not taken.
+            const bool may = u->run.capacity > 0 && sw::geo() && !sw::debug();
+            auto width_of = [&](const int (&wgs)[2], int automatic) {
+                auto fits = [&](int w) { return may && inner_run_grid(B, w) <= inner_run_resident(u->run.capacity, w, wgs[run_index(w)]); };
+                if (u->inner_run_width) return fits(u->inner_run_width) ? u->inner_run_width : 0;
+                // (a device whose occupancy answer for a narrow kernel is below 2 does not admit B > 64 at width 16: the wide form then)
+                return fits(automatic) ? automatic : fits(kRunWide) ? kRunWide : 0;
+            };
+            const int sw7 = width_of(u->run.seven_wgs, inner_run_auto_width(B)), swt = width_of(u->run.tail_wgs, tail_run_auto_width(B));
+            const int rf = sw7 && (u->inner_run & mpdx_unet::kRunSeven) ? inner_run_first(u, units) : -1;
             if (rf >= 0) {
-                units[rf] = {mpdx_unet::kInnerRun, -1, units[rf].layer, kInnerRunLayers};
+                units[rf] = {mpdx_unet::kInnerRun, -1, units[rf].layer, kInnerRunLayers, sw7};
                 units.erase(units.begin() + rf + 1, units.begin() + rf + kInnerRunLayers);
                 run = true;
             }
             // the tail of up level 0, under the same conditions and on its own: the seven layers need not have been taken
             int spare = -1;   // (Unit::fused of a kTailRun unit: the spare slot of layer 0's output)
-            const int tf = fits && u->run.tail_ok && (u->inner_run & mpdx_unet::kRunTail) ? tail_run_first(u, units, &spare) : -1;
+            const int tf = swt && (u->inner_run & mpdx_unet::kRunTail) ? tail_run_first(u, units, &spare) : -1;
             if (tf >= 0) {
-                units[tf] = {mpdx_unet::kTailRun, spare, units[tf].layer, kTailRunLayers};
+                units[tf] = {mpdx_unet::kTailRun, spare, units[tf].layer, kTailRunLayers, swt};
                 units.erase(units.begin() + tf + 1, units.begin() + tf + kTailRunLayers);
                 run = true;
             }
@@ -1190,6 +1236,23 @@ int mpdx_unet_set_inner_run_parts(mpdx_unet* u, int parts) {
     u->inner_run = parts;
     return 0;
 }
+int mpdx_unet_set_inner_run_width(mpdx_unet* u, int width) {
+    if (!u) return fail(MPDX_E_INVALID, "null argument");
+    if (width != 0 && !inner_run_width_ok(width)) return fail(MPDX_E_INVALID, "inner-run width %d: 0 (automatic), 16 or 32 positions per cluster", width);
+    u->inner_run_width = width;
+    return 0;
+}
+int mpdx_inner_run_block(int B, int width, int cus, int block, int32_t* cluster, int32_t* tile, int32_t* counter_lines) {
+    if (B <= 0 || cus <= 0 || !inner_run_width_ok(width)) return fail(MPDX_E_INVALID, "mpdx_inner_run_block: B=%d width=%d cus=%d", B, width, cus);
+    const int grid = inner_run_grid(B, width);
+    if (block < 0 || block >= grid) return fail(MPDX_E_INVALID, "mpdx_inner_run_block: block %d of %d", block, grid);
+    int c = 0, m = 0;
+    inner_run_slot(block, &c, &m);
+    if (cluster) *cluster = c < inner_run_clusters(B, width) ? c : -1;
+    if (tile) *tile = m;
+    if (counter_lines) *counter_lines = inner_run_counter_lines(cus, width);
+    return grid;
+}
 int mpdx_unet_inner_runs(const mpdx_unet* u) { return u ? u->inner_runs : 0; }
 int mpdx_unet_inner_run_layers(const mpdx_unet* u) { return u ? u->inner_run_layers : 0; }
 int mpdx_unet_status(const mpdx_unet* u) {
@@ -1200,7 +1263,7 @@ int mpdx_unet_set_status(mpdx_unet* u, unsigned word) {
     if (!u) return fail(MPDX_E_INVALID, "null argument");
     if (u->run.status) __atomic_store_n(u->run.status, word, __ATOMIC_RELAXED);
     u->run.status_host = word;
-    if (!word && u->run.counters) u->run.rezero = true;   // whatever a give-up left in the counters goes before the next run
+    if (!word && u->run.counters) u->run.ctr[0].rezero = u->run.ctr[1].rezero = true;   // whatever a give-up left in the counters goes before the next run
     return 0;
 }
 

@@ -198,6 +198,11 @@ class TemporalUnet(nn.Module):
         """mpdx_unet_set_inner_run_parts: select the runs separately - RUN_SEVEN | RUN_TAIL is what set_inner_run(True) selects, 0 nothing."""
         _lib.check(_lib.load().mpdx_unet_set_inner_run_parts(self._handle(), int(parts)), "mpdx_unet_set_inner_run_parts")
 
+    def set_inner_run_width(self, width: int):
+        """mpdx_unet_set_inner_run_width: positions per position tile of both runs - 0 automatic by batch (the default), 16 (2 trajectories, up to two
+        workgroups per compute unit) or 32 (4 trajectories, one per compute unit).  Takes effect at the next plan; the same bits at every width."""
+        _lib.check(_lib.load().mpdx_unet_set_inner_run_width(self._handle(), int(width)), "mpdx_unet_set_inner_run_width")
+
     def inner_runs(self) -> int:
         """Seven-layer run launches of the last fused plan on this model (mpdx_unet_inner_runs); the tail run does not count here."""
         return int(_lib.load().mpdx_unet_inner_runs(self._handle()))
