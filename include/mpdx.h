@@ -74,6 +74,19 @@ void   mpdx_unet_destroy(mpdx_unet* u);
  * mpdx_plan call on this handle issued (0: the option is off or the network / batch does not admit it). */
 int    mpdx_unet_set_plan_join(mpdx_unet* u, int on);
 int    mpdx_unet_plan_joined(const mpdx_unet* u);
+/* Paired form of the joined launch, a handle option of mpdx_plan.  The 128-channel level of the down part (downs.2: five ops of 8 channel tiles on one
+ * position tile) runs on TWO compute units per trajectory: a helper workgroup on the same XCD takes channel tiles 4 - 7, the k-loops halve, and after
+ * each of the level's first four ops the two workgroups trade their 4 KB halves of the output through a handle-owned exchange area (write-through
+ * stores, one counter per trajectory, bounded polls - the runs' recipe, status word and 4 ms budget: see mpdx_unet_status below).  A wave still owns a
+ * whole tile for the whole K and a GroupNorm group is one tile, so the results are bit-identical with the option off.  Admitted where a joined launch
+ * is and both workgroups of every trajectory are resident at once (2 x 8 ceil(B / 8) <= compute units: B <= 128 on 256 CUs).
+ * mpdx_unet_set_level_split(u, on): 0 never, 1 wherever admitted, negative automatic by batch (the default).  mpdx_unet_plan_split: paired launches of
+ * the last mpdx_plan call (0 or mpdx_unet_plan_joined).
+ * mpdx_level_split_block, without a device (tests): the workgroups of a paired launch for batch B (the return value; negative: an error), the trajectory
+ * (-1: a surplus workgroup, it leaves at once) and the role (0 primary, 1 helper) of workgroup `block`.  Null outputs are skipped. */
+int    mpdx_unet_set_level_split(mpdx_unet* u, int on);
+int    mpdx_unet_plan_split(const mpdx_unet* u);
+int    mpdx_level_split_block(int B, int block, int32_t* trajectory, int32_t* role);
 /* Inner-level run, a handle option, default on.  mpdx_plan runs the seven consecutive 256 -> 256 Conv1dBlocks of the innermost level
  * (downs.3.0.blocks.1, downs.3.1, mid_block1, mid_block2) as ONE persistent launch where the standard four-level network on H = 64 runs without
  * self-attention and every workgroup of that launch is resident at once (8 x ceil(B / 4) workgroups, one per compute unit: B <= 128 on 256 CUs);

@@ -93,6 +93,9 @@ SIGNATURES = {
     "mpdx_unet_destroy": (None, [_vp]),
     "mpdx_unet_set_plan_join": (_i, [_vp, _i]),
     "mpdx_unet_plan_joined": (_i, [_vp]),
+    "mpdx_unet_set_level_split": (_i, [_vp, _i]),
+    "mpdx_unet_plan_split": (_i, [_vp]),
+    "mpdx_level_split_block": (_i, [_i, _i, _vp, _vp]),
     "mpdx_unet_set_inner_run": (_i, [_vp, _i]),
     "mpdx_unet_set_inner_run_parts": (_i, [_vp, _i]),
     "mpdx_unet_set_inner_run_width": (_i, [_vp, _i]),

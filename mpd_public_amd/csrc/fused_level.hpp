@@ -40,6 +40,7 @@
 #pragma once
 #include "conv_block.hpp"
 #include "fused_geom.hpp"
+#include "inner_run.hpp"   // kInnerRunCounterStride (the paired joined launch's counters)
 
 namespace mpdx {
 
@@ -84,6 +85,7 @@ struct FusedShape {
     static constexpr int GS = COUT / 8;               // GroupNorm(8 groups): channels per group
     static constexpr int RB = GS / 4;                 // DPP rows (4 channels) per group
     static constexpr int NPARTS = NSn * RB;           // 64-element parts per group: 2 or 4
+    static constexpr bool kSplit = false;             // (FusedHalfShape: the op's tile rows are shared by two workgroups)
     static_assert(T == 4 || T == 8, "4 or 8 tiles");
     static_assert(MSn == 2 || MSn == 4 || MSn == 8, "2, 4 or 8 tile rows");
     static_assert(MP == 1 || (MODE != CONV_UPT && NSn == 1), "M-passes: one position tile");
@@ -91,6 +93,20 @@ struct FusedShape {
     static_assert(MODE != CONV_UPT || NCR == 0, "no folded residual on resampling ops");
     static_assert(!GN || NPARTS == 2 || NPARTS == 4, "GroupNorm region of 128 or 256 elements");
     static_assert(LOUT >= 16 || !GN, "half-used tiles: resampling ops only");
+};
+
+// The HALF-ROW form of an 8-tile-row op on one position tile (shapes 16 - 19, the 128-channel level on 16 positions): two workgroups - roles 0 and 1 - share
+// the op, role r owns tile rows 4 r .. 4 r + 3, a wave ONE tile (row wave + 4 r) for the whole K.  The stream of tile row s is the copy the unsplit op reads
+// (wave-stream s & 3 = [row s & 3 | row (s & 3) + 4]); parameters, residual and outputs are indexed by the real channel.  A GroupNorm group (16 channels) is
+// one tile row, so the statistics stay inside the wave and every summation order is the unsplit op's: the results are bit-identical.
+template <class S>
+struct FusedHalfShape {
+    static constexpr int MODE = S::MODE, KS = S::KS, NC16 = S::NC16, NCR = S::NCR, COUT = S::COUT, LOUT = S::LOUT, GN = S::GN;
+    static constexpr int NTAP = S::NTAP, NBLK = S::NBLK, TOT = S::TOT, MSn = S::MSn, MSW = S::MSW, NSn = S::NSn;
+    static constexpr int MP = 1, T = kFusedWaves, NTW = 1, NSEQ = 1, NJ = 1, SLEN = TOT;
+    static constexpr int GS = S::GS, RB = S::RB, NPARTS = S::NPARTS;
+    static constexpr bool kSplit = true;
+    static_assert(S::MP == 2 && S::NSn == 1 && S::MSW == kFusedWaves && S::MODE != CONV_UPT && S::GS == 16, "half rows: 8 tile rows on one position tile, one group per row");
 };
 
 struct FusedOp {          // runtime part of an op: 13 dwords
@@ -248,15 +264,55 @@ __device__ __forceinline__ float row_sum16(float v) {
     return v;
 }
 
+// What a half-row op (FusedHalfShape) needs to trade its half of the output for the partner workgroup's: recipe R1 as conv_block_body<.., RUN> uses it.
+// The op stores its tile write-through into `xdst` as well as into LDS, every wave drains, the workgroup meets, one lane adds 1 to `counter`; one wave
+// polls for `target` (bounded by `budget`), then every thread reads one float4 of the partner's half at `xsrc` past the L1 into the op's LDS destination.
+// A half is tile-major, [4 tile rows][16 positions][16 channels]: a wave's store instruction writes 1 KiB, eight whole 128-byte lines.
+struct FusedSplitCtx {
+    int role = 0;
+    unsigned* counter = nullptr;
+    unsigned target = 0;
+    long long budget = 0;
+    const float* xsrc = nullptr;
+};
+constexpr int kSplitHalfFloats = kFusedWaves * 16 * 16;   // 4 KB
+
+// One wave polls `counter` for `target`, the verdict goes through the LDS word `flag`, the workgroup meets.  False: out of budget or poisoned (uniform).
+__device__ __forceinline__ bool fused_split_poll(const FusedSplitCtx& sx, int* flag, int wave, int lane) {
+    if (wave == 0) {
+        const long long t0 = (long long)__builtin_amdgcn_s_memtime();
+        int ok;
+        for (;;) {
+            const unsigned v = __hip_atomic_load(sx.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int d = (int)(v - sx.target);   // (a signed difference: the partner may already have added its next arrival; base wraps around)
+            if (d >= 0) { ok = (unsigned)d < kRunPoisonSeen; break; }
+            if ((long long)__builtin_amdgcn_s_memtime() - t0 > sx.budget) { ok = 0; break; }
+            __builtin_amdgcn_s_sleep(1);
+        }
+        if (lane == 0) *flag = ok;
+    }
+    __syncthreads();
+    return *flag != 0;
+}
+// the partner's (or, at the helper's entry, the primary's) 4 KB at `xsrc` into columns [col4, col4 + 16) of the LDS buffer at dst_off4: one float4 per thread
+__device__ __forceinline__ void fused_split_load(const float* xsrc, f32x4* sm4, int dst_off4, int dst_rs4, int col4, int wave, int lane) {
+    const int j = lane & 15, q = lane >> 4;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)xsrc, 0, 0x7fffffff, 0x00020000);
+    const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ((wave * 16 + j) * 16 + q * 4) * 4, 0, 16));   // sc1
+    sm4[dst_off4 + (j + 2) * dst_rs4 + col4 + wave * 4 + q] = v;
+}
+
 // One conv op of static shape S: k-loop over this wave's tile(s) with the ring running on into the next op's stream, epilogue.
 //   nbase: BYTE offset in `packed` of the NEXT conv op's wave-stream (wave-uniform), nmax: its last block index (the ring's cross-over requests are clamped
 //   to it; after the last conv op both describe any valid block)
 // SAVE: the training forward's variant (every op also stores its output and its GroupNorm input through FusedArgs::save); the planning
 // kernels are instantiated without it (measured on one box: 22.54 vs 22.62 ms per cfg-2 plan with the stores merely compiled in)
 // A: the argument block the op reads `packed`, `gout` (and, SAVE, `save`) from: FusedArgs, or FusedJoinDown for the down part of fused_join_kernel
-template <class S, bool SAVE = false, class A = FusedArgs>
-__device__ __forceinline__ void fused_conv_op(const A& a, const FusedLay& lay, const FusedOp& op, f32x4 (&ring)[kFusedRing], float* smem, int wave, int lane, int b,
-                                              int nbase, int nmax, long long* tr_base, int& tr) {
+// XOUT (one-tile-per-wave ops on 16 positions, fused_join_split_kernel only): the op's output also goes to `xdst`, tile-major and write-through (FusedSplitCtx).
+// sx: a half-row op's role and hand-off (S::kSplit).  Returns false when a half-row op gave up its wait (uniform over the workgroup); true otherwise.
+template <class S, bool SAVE = false, class A = FusedArgs, bool XOUT = false>
+__device__ __forceinline__ bool fused_conv_op(const A& a, const FusedLay& lay, const FusedOp& op, f32x4 (&ring)[kFusedRing], float* smem, int wave, int lane, int b,
+                                              int nbase, int nmax, long long* tr_base, int& tr, float* xdst = nullptr, const FusedSplitCtx& sx = FusedSplitCtx()) {
     constexpr int P = kFusedRing, DB = MPDX_FUSED_DB, NTW = S::NTW, NJ = S::NJ;
     f32x4* const sm4 = (f32x4*)smem;
     const int j = lane & 15, q = lane >> 4;
@@ -289,7 +345,8 @@ __device__ __forceinline__ void fused_conv_op(const A& a, const FusedLay& lay, c
     }
     const int rs4 = op.src_rs4;
     const __amdgpu_buffer_rsrc_t wrs = fused_weights_rsrc(a.packed);
-    const int sbase = (op.sbase + ms * (S::SLEN * 256)) * 4;   // BYTE offset of this wave's stream in `packed` (wave-uniform; nbase likewise)
+    int sbase = (op.sbase + ms * (S::SLEN * 256)) * 4;   // BYTE offset of this wave's stream in `packed` (wave-uniform; nbase likewise)
+    if constexpr (S::kSplit) sbase = (op.sbase + (ms * 2 + sx.role) * (S::TOT * 256)) * 4;   // tile row ms + 4 role: the second half of wave-stream ms
     const unsigned lane_bytes = (unsigned)lane * 16u;
     // B fragment of stream block r for joint tile t
     auto read_b = [&](int r, int t) -> f32x4 {
@@ -351,7 +408,11 @@ __device__ __forceinline__ void fused_conv_op(const A& a, const FusedLay& lay, c
     // this lane's 4 output channels in tile t (M-passes: tile t is tile row ms + 4 t)
     int c0t[NTW], mst[NTW];
 #pragma unroll
-    for (int t = 0; t < NTW; ++t) { mst[t] = (S::MP > 1) ? ms + t * S::MSW : ms; c0t[t] = mst[t] * 16 + q * 4; }
+    for (int t = 0; t < NTW; ++t) {
+        mst[t] = (S::MP > 1) ? ms + t * S::MSW : ms;
+        if constexpr (S::kSplit) mst[t] = ms + kFusedWaves * sx.role;
+        c0t[t] = mst[t] * 16 + q * 4;
+    }
     f32x4 y[NTW];
     if (S::GN) {
         // ---- GroupNorm statistics + affine + Mish, round-4 form (instruction diet: fp32 MFMA and VALU share the SIMD's issue port).
@@ -458,6 +519,13 @@ __device__ __forceinline__ void fused_conv_op(const A& a, const FusedLay& lay, c
     for (int t = 0; t < NTW; ++t) {
         if (!col_ok) continue;
         if (op.dst_off4 >= 0) sm4[op.dst_off4 + (npos[t] + 2) * op.dst_rs4 + (c0t[t] >> 2)] = y[t];
+        if constexpr (XOUT) {
+            static_assert(NTW == 1 && S::LOUT == 16 && S::NSn == 1 && S::MSW == kFusedWaves, "XOUT: one tile per wave, 16 positions");
+            if (op.dst_off4 >= 0) {
+                const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)xdst, 0, 0x7fffffff, 0x00020000);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y[t]), xrs, ((ms * 16 + j) * 16 + q * 4) * 4, 0, 16);   // sc1
+            }
+        }
         if (op.gdst >= 0) *(f32x4*)(a.gout[op.gdst] + ((size_t)b * S::LOUT + npos[t]) * S::COUT + c0t[t]) = y[t];
         if constexpr (SAVE) if (op.save_out >= 0) *(f32x4*)(a.save + op.save_out + ((size_t)b * S::LOUT + npos[t]) * S::COUT + c0t[t]) = y[t];
     }
@@ -471,9 +539,22 @@ __device__ __forceinline__ void fused_conv_op(const A& a, const FusedLay& lay, c
     }
     FOP_STAMP();   // epilogue done (this wave)
     __builtin_amdgcn_s_setprio(0);
+    if constexpr (S::kSplit) {
+        if (op.dst_off4 >= 0) {
+            // publish this half, wait for the partner's, fetch it into the destination buffer's other columns
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            if (wave == 0 && lane == 0) __hip_atomic_fetch_add(sx.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            FOP_STAMP();   // published
+            const bool ok = fused_split_poll(sx, (int*)(smem + lay.stat_off), wave, lane);
+            FOP_STAMP();   // the partner's half is published
+            if (!ok) return false;
+            fused_split_load(sx.xsrc, sm4, op.dst_off4, op.dst_rs4, (sx.role ^ 1) * 16, wave, lane);
+        }
+    }
     lds_barrier();
     FOP_STAMP();
 #undef FOP_STAMP
+    return true;
 }
 
 // ---- prologue of a fused program (shared by the generic and the static kernels).  GEOM: the program's geometry table (fused_geom.hpp) -
@@ -931,6 +1012,115 @@ __device__ __forceinline__ void fused_join_down_from(const FusedJoinDown& dn, co
     }
 }
 
+// fused_join_split_kernel's primary: down ops [I, END) as fused_join_down_from runs them; ops END.. follow in half-row form - the ring of op END - 1 runs on into
+// role 0's stream of op END, and op END - 1's output also goes to `xdst`.
+template <class SD, int I, int END>
+__device__ __forceinline__ void fused_join_down_to(const FusedJoinDown& dn, const FusedLay& lay, f32x4 (&ring)[kFusedRing], float* smem, int wave, int lane, int b,
+                                                   long long* tr_base, int& tr, float* xdst) {
+    static_assert(END < SD::N, "half-row ops follow");
+    if constexpr (I < END) {
+        const FusedOp op = fused_static_desc<typename SD::GEOM, I, false>(dn);
+        int nbase = dn.sbase[I] * 4;
+        int nmax = 0;
+        if constexpr (I + 1 < SD::N) {
+            using N = typename FusedShapeOf<SD::ids[I + 1 < SD::N ? I + 1 : I]>::type;
+            if constexpr (I + 1 == END) {
+                nbase = (dn.sbase[I + 1] + wave * 2 * (N::TOT * 256)) * 4;
+                nmax = N::TOT - 1;
+            } else {
+                nbase = (dn.sbase[I + 1] + (wave & (N::MSn < kFusedWaves ? N::MSn - 1 : kFusedWaves - 1)) * (N::SLEN * 256)) * 4;
+                nmax = N::SLEN - 1;
+            }
+        }
+        // (a wave's 128 trace slots end inside the down part: its later ops go unstamped)
+        fused_conv_op<typename FusedShapeOf<SD::ids[I]>::type, false, FusedJoinDown, I + 1 == END>(dn, lay, op, ring, smem, wave, lane, b, nbase, nmax,
+                                                                                                    tr + 5 <= 128 ? tr_base : nullptr, tr, xdst);
+        fused_join_down_to<SD, I + 1, END>(dn, lay, ring, smem, wave, lane, b, tr_base, tr, xdst);
+    }
+}
+
+// ---- junction.  The final op has written x_{t-1} to `out` (the next up part's final op reads x_in there; the chain row likewise) and into the
+// interior rows of the down program's staged-input buffer; here the rest of what fused_prologue produces: zero halo rows, zero channel padding.
+//
+// Global memory: the down part below overwrites workspace slots (its gout[0..2]: the two skip tensors and the L = 8 output) that the up part
+// of THIS launch has read as gsrc2 / gsrc3 (and possibly gsrc1, when slots are re-used).  That is safe because (1) the up part reads its three
+// global inputs in fused_prologue only - they are in LDS before the prologue's barrier - and its ops have no global source or destination
+// (GeomUpAB: every gdst is -1; the final op reads x_in / noise / hard conditions and writes out / chain, none of them a workspace slot), and (2) every
+// global address of either part is indexed by this workgroup's trajectory b: no workgroup reads or writes another trajectory's rows.
+template <class SD>
+__device__ __forceinline__ void fused_join_junction(const FusedArgs& a, float* smem, int tid) {
+    f32x4* const sm4 = (f32x4*)smem;
+    {
+        constexpr FusedGeom gd = SD::GEOM::g;
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        if (tid < 2 * gd.in_rs4) {
+            sm4[gd.in_off4 + tid] = z;
+            sm4[gd.in_off4 + (gd.in_rows - 2) * gd.in_rs4 + tid] = z;
+        }
+        const int D = a.D;
+#pragma unroll
+        for (int k = 0; k < (gd.L0 * gd.in_rs4 + kFusedThreads - 1) / kFusedThreads; ++k) {
+            const int i = tid + k * kFusedThreads;
+            if (i >= gd.L0 * gd.in_rs4) continue;
+            const int l = i / gd.in_rs4, c = (i - l * gd.in_rs4) * 4;      // row, first channel of this float4 column
+            const int at = gd.in_off4 + (l + 2) * gd.in_rs4 + (c >> 2);
+            if (c >= D) sm4[at] = z;
+            else if (c + 4 > D) {
+#pragma unroll
+                for (int e = 1; e < 4; ++e)
+                    if (c + e >= D) smem[at * 4 + e] = 0.f;
+            }
+        }
+    }
+}
+
+// The primary workgroup of fused_join_split_kernel: fused_join_kernel's statements (below) for trajectory b, in its order, down to down op END - 1, whose
+// output also goes to `xdst`; the ring runs on into role 0's stream of op END.  (Two copies on purpose: with fused_join_kernel as a wrapper of this function
+// hipcc allocates that kernel's registers differently - 15 405 instructions against 15 338 -, and the unpaired kernel stays the code it was measured as.)
+template <class SU, class SD, int END>
+__device__ __forceinline__ void fused_join_body(const FusedJoinArgs& ja, float* smem, f32x4 (&ring)[kFusedRing], const int b, float* xdst) {
+    using JL = FusedJoinLay<SU, SD>;
+    f32x4* const sm4 = (f32x4*)smem;
+    const FusedArgs& a = ja.up;
+    const FusedJoinDown& dn = ja.dn;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int tr = 0;
+    long long* const tr_base = (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wave * 128 : nullptr;
+    if (tr_base) tr_base[tr] = (long long)__builtin_readcyclecounter();
+    ++tr;
+    // the down part's parameter block and its slice of the next timestep's conditioning row: requested with the up prologue's loads, so
+    // that their cold first touch (~1.4 us) is one round trip with everything else the launch touches first
+    f32x4 jv[JL::JK];
+#pragma unroll
+    for (int k = 0; k < JL::JK; ++k) {
+        const int idx = tid + k * kFusedThreads;
+        const int it = idx - JL::npar4 < JL::ntt4 ? idx - JL::npar4 : 0;   // (clamped: the last pass is partial)
+        const float* src = idx < JL::npar4 ? dn.packed + dn.gpar_off + (size_t)idx * 4 : dn.tt_row + dn.tt_lo + (size_t)it * 4;
+        jv[k] = *(const f32x4*)src;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    FinalPre fp;
+    const FusedLay lay = fused_lay<typename SU::GEOM>(a);
+    fused_prologue<typename SU::GEOM>(a, lay, smem, ring, tid, lane, wave, b, tr_base, tr);
+    // (region [kJoinTail, ...) belongs to nobody else; first read after the junction's barrier)
+#pragma unroll
+    for (int k = 0; k < JL::JK; ++k) {
+        const int idx = tid + k * kFusedThreads;
+        if (idx < JL::npar4) sm4[(JL::par_off >> 2) + idx] = jv[k];
+        else if (idx - JL::npar4 < JL::ntt4) sm4[(JL::tt_off >> 2) + idx - JL::npar4] = jv[k];
+    }
+    fused_join_up_from<SU, SD, 0>(a, dn, lay, ring, fp, smem, tid, wave, lane, b, tr_base, tr);
+
+    fused_join_junction<SD>(a, smem, tid);
+    lds_barrier();
+    if (tr_base) tr_base[tr] = (long long)__builtin_readcyclecounter();
+    ++tr;
+    FusedLay dlay = {};
+    dlay.stat_off = JL::stat_off; dlay.par_off = JL::par_off; dlay.tt_off = JL::tt_off;
+    fused_join_down_to<SD, 0, END>(dn, dlay, ring, smem, wave, lane, b, tr_base, tr, xdst);
+}
+
 template <class SU, class SD>
 __global__ __launch_bounds__(kFusedThreads) void fused_join_kernel(const FusedJoinArgs ja) {
 #ifndef MPDX_NO_WARM_KERNARG
@@ -971,15 +1161,7 @@ __global__ __launch_bounds__(kFusedThreads) void fused_join_kernel(const FusedJo
         else if (idx - JL::npar4 < JL::ntt4) sm4[(JL::tt_off >> 2) + idx - JL::npar4] = jv[k];
     }
     fused_join_up_from<SU, SD, 0>(a, dn, lay, ring, fp, smem, tid, wave, lane, b, tr_base, tr);
-
-    // ---- junction.  The final op has written x_{t-1} to `out` (the next up part's final op reads x_in there; the chain row likewise) and into the
-    // interior rows of the down program's staged-input buffer; here the rest of what fused_prologue produces: zero halo rows, zero channel padding.
-    //
-    // Global memory: the down part below overwrites workspace slots (its gout[0..2]: the two skip tensors and the L = 8 output) that the up part
-    // of THIS launch has read as gsrc2 / gsrc3 (and possibly gsrc1, when slots are re-used).  That is safe because (1) the up part reads its three
-    // global inputs in fused_prologue only - they are in LDS before the prologue's barrier - and its ops have no global source or destination
-    // (GeomUpAB: every gdst is -1; the final op reads x_in / noise / hard conditions and writes out / chain, none of them a workspace slot), and (2) every
-    // global address of either part is indexed by this workgroup's trajectory b: no workgroup reads or writes another trajectory's rows.
+    // ---- junction (fused_join_junction's statements)
     {
         constexpr FusedGeom gd = SD::GEOM::g;
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
@@ -1008,6 +1190,181 @@ __global__ __launch_bounds__(kFusedThreads) void fused_join_kernel(const FusedJo
     FusedLay dlay = {};
     dlay.stat_off = JL::stat_off; dlay.par_off = JL::par_off; dlay.tt_off = JL::tt_off;
     fused_join_down_from<SD, 0>(dn, dlay, ring, smem, wave, lane, b, tr_base, tr);
+}
+
+// ---- PAIRED form of the joined launch: the 128-channel level of the down part (downs[2]: ops kSplitFrom .. of FusedSeqDown3, 8 tile rows on one position
+// tile each) on TWO compute units per trajectory.  The primary workgroup of trajectory b is fused_join_kernel's up to down op kSplitFrom - 1; a helper
+// workgroup on another compute unit of the same XCD stages the down parameters, waits for the level's input and then both run the level's ops in half-row
+// form (FusedHalfShape): role 0 rows 0 - 3, role 1 rows 4 - 7, a wave one tile for the whole K - the k-loops halve, no summation order changes, the chain is
+// bit-identical.  After each of the level's first four ops the roles trade their halves of the output (FusedSplitCtx); the last op's output and the level's
+// skip tensor go to global memory from each role for its own 64 channels (plain stores: the next launch reads them).
+//
+// The launch geometry, stated once for kernel and host: a grid of 2 nb8 blocks, nb8 = 8 ceil(B / 8); block x < nb8 is the primary of trajectory x, block
+// x >= nb8 the helper of trajectory x - nb8; a trajectory >= B leaves at once.  Workgroups are dealt round-robin over the 8 XCDs and nb8 is a multiple of 8,
+// so both roles of a trajectory sit on one XCD (as run_slot arranges for clusters).
+struct SplitSlot { int b, role; };
+constexpr int split_nb8(int B) { return 8 * ((B + 7) / 8); }
+constexpr int split_grid(int B) { return 2 * split_nb8(B); }
+constexpr int split_block(int b, int role, int nb8) { return b + role * nb8; }
+__host__ __device__ constexpr SplitSlot split_slot(int block, int nb8) { return block < nb8 ? SplitSlot{block, 0} : SplitSlot{block - nb8, 1}; }
+// every (trajectory, role) of a batch of up to 128 is exactly one block of the grid, every other block names a trajectory >= B (it leaves), and the two
+// blocks of a trajectory share block % 8 - their XCD
+constexpr bool split_map_ok() {
+    for (int B = 1; B <= 128; ++B) {
+        const int nb8 = split_nb8(B), grid = split_grid(B);
+        int live = 0;
+        for (int x = 0; x < grid; ++x) {
+            const SplitSlot s = split_slot(x, nb8);
+            if (s.b < 0 || s.role < 0 || s.role > 1) return false;
+            if (s.b >= B) continue;
+            if (split_block(s.b, s.role, nb8) != x || (x & 7) != (s.b & 7)) return false;
+            ++live;
+        }
+        if (live != 2 * B || nb8 % 8 || nb8 < B) return false;
+    }
+    return true;
+}
+static_assert(split_map_ok(), "block <-> (trajectory, role): a bijection on the live blocks, one XCD per trajectory");
+
+// The exchange area of a trajectory: kSplitSlots slots of two halves.  Slot 0: the level's input (down op kSplitFrom - 1's output, 64 channels: one half, written
+// by the primary); slot 1 + i: the output of the level's op i, half r written by role r.  One slot per op: nothing is overwritten inside a launch.
+// The trajectory's counter (a 128-byte line of its own, never reset between launches) counts publications: the primary's entry hand-off makes it base + 1,
+// both roles' publications of the level's op i make it base + 1 + 2 (i + 1); a launch leaves it at base + kSplitAdvance.
+constexpr int kSplitFrom = 10, kSplitSlots = 5;
+constexpr int kSplitTrajFloats = kSplitSlots * 2 * kSplitHalfFloats;   // 40 KB
+constexpr unsigned kSplitAdvance = 1 + 2 * (kSplitSlots - 1);
+constexpr int kSplitMaxB = 128;
+struct FusedSplitArgs {
+    float* xch;           // [B][kSplitSlots][2][4][16][16]
+    unsigned* counters;   // [B * kInnerRunCounterStride]
+    unsigned* status;     // the handle's sticky give-up word
+    long long budget;     // s_memtime ticks of 4 ms
+    unsigned base;        // every live counter's value when the launch starts
+    int nb8;
+};
+
+template <class SD, int I>
+__device__ __forceinline__ int fused_split_from(const FusedJoinDown& dn, const FusedSplitArgs& sa, const FusedLay& lay, f32x4 (&ring)[kFusedRing], float* smem, int wave,
+                                                int lane, int b, int role, long long* tr_base, int& tr) {
+    if constexpr (I < SD::N) {
+        using S = FusedHalfShape<typename FusedShapeOf<SD::ids[I]>::type>;
+        static_assert(S::TOT >= kFusedRing, "every ring slot holds a block of this op when it starts");
+        const FusedOp op = fused_static_desc<typename SD::GEOM, I, false>(dn);
+        int nbase = dn.sbase[I] * 4;
+        int nmax = 0;
+        if constexpr (I + 1 < SD::N) {
+            using N = typename FusedShapeOf<SD::ids[I + 1 < SD::N ? I + 1 : I]>::type;
+            nbase = (dn.sbase[I + 1] + (wave * 2 + role) * (N::TOT * 256)) * 4;
+            nmax = N::TOT - 1;
+        }
+        constexpr int slot = I - kSplitFrom + 1;
+        float* const xt = sa.xch + (size_t)b * kSplitTrajFloats + slot * 2 * kSplitHalfFloats;
+        FusedSplitCtx sx;
+        sx.role = role; sx.counter = sa.counters + (size_t)b * kInnerRunCounterStride; sx.target = sa.base + 1u + 2u * (unsigned)slot; sx.budget = sa.budget;
+        sx.xsrc = xt + (role ^ 1) * kSplitHalfFloats;
+        if (!fused_conv_op<S, false, FusedJoinDown, S::LOUT == 16>(dn, lay, op, ring, smem, wave, lane, b, nbase, nmax, tr_base, tr, xt + role * kSplitHalfFloats, sx)) return I;
+        return fused_split_from<SD, I + 1>(dn, sa, lay, ring, smem, wave, lane, b, role, tr_base, tr);
+    } else {
+        return -1;
+    }
+}
+
+// A workgroup gave up its wait at down op `at` (uniform): the status word, poison for the partner, NaN into this role's channels of the level's two outputs.
+template <class SD>
+__device__ __forceinline__ void fused_split_give_up(const FusedJoinDown& dn, const FusedSplitArgs& sa, int b, int role, int at, unsigned target) {
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        __hip_atomic_fetch_or(sa.status, 1u | ((unsigned)at << 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(sa.counters + (size_t)b * kInnerRunCounterStride, target + kRunPoison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    constexpr FusedGeom gd = SD::GEOM::g;
+    constexpr int g1 = gd.ops[SD::N - 2].gdst, g2 = gd.ops[SD::N - 1].gdst;   // the level's skip tensor [B][16][128] and its output [B][8][128]
+    for (int e = tid; e < 24 * 64; e += kFusedThreads) {
+        const int p = e >> 6, c = role * 64 + (e & 63);
+        if (p < 16) dn.gout[g1][((size_t)b * 16 + p) * 128 + c] = __builtin_nanf("");
+        else dn.gout[g2][((size_t)b * 8 + (p - 16)) * 128 + c] = __builtin_nanf("");
+    }
+}
+
+template <class SU, class SD>
+__global__ __launch_bounds__(kFusedThreads) void fused_join_split_kernel(const FusedJoinArgs ja, const FusedSplitArgs sa) {
+    const SplitSlot slot = split_slot((int)blockIdx.x, sa.nb8);
+    if (slot.b >= ja.up.B) return;
+#ifndef MPDX_NO_WARM_KERNARG
+    warm_kernarg<(int)(sizeof(FusedJoinArgs) + sizeof(FusedSplitArgs))>();
+#endif
+    using JL = FusedJoinLay<SU, SD>;
+    constexpr FusedGeom gd = SD::GEOM::g;
+    constexpr FusedGeomOp g0 = gd.ops[kSplitFrom];   // the level's first op: its source buffer holds the level's input
+    using S0 = typename FusedShapeOf<SD::ids[kSplitFrom]>::type;
+    static_assert(SD::N == kSplitFrom + kSplitSlots && gd.ops[kSplitFrom - 1].dst_off4 == g0.src_off4 && S0::NC16 == 4, "the level: the program's last five ops, 64 channels in");
+    static_assert(gd.ops[SD::N - 1].dst_off4 < 0 && gd.ops[SD::N - 2].gdst >= 0 && gd.ops[SD::N - 1].gdst >= 0, "the level's last op leaves through global memory only");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    f32x4* const sm4 = (f32x4*)smem;
+    const FusedJoinDown& dn = ja.dn;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = slot.b, role = slot.role;
+    float* const x0 = sa.xch + (size_t)b * kSplitTrajFloats;   // slot 0
+    unsigned* const counter = sa.counters + (size_t)b * kInnerRunCounterStride;
+    FusedLay dlay = {};
+    dlay.stat_off = JL::stat_off; dlay.par_off = JL::par_off; dlay.tt_off = JL::tt_off;
+    // the level's stamps of trajectory 0 (dev tool): behind the 4 x 128 slots of the primary's waves, 64 per wave, the primary's first
+    int tr = 0;
+    long long* const tr_base = (MPDX_TRACE_PTR(ja.up.trace) && b == 0 && lane == 0) ? ja.up.trace + 512 + (role * kFusedWaves + wave) * 64 : nullptr;
+    f32x4 ring[kFusedRing];
+    if (role == 0) {
+        fused_join_body<SU, SD, kSplitFrom>(ja, smem, ring, b, x0);
+        // entry hand-off: the level's input is in LDS and - every wave drains its write-through stores - in slot 0
+        if (tr_base) tr_base[tr] = (long long)__builtin_readcyclecounter();
+        ++tr;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0) __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tr_base) tr_base[tr] = (long long)__builtin_readcyclecounter();
+        ++tr;
+    } else {
+        // the helper's entry: the down parameter block and conditioning slice (the primary's loads), the first ring blocks of its own rows of the level's
+        // first op, zero halo rows - all before the poll -, then the level's input from slot 0
+        if (tr_base) tr_base[tr] = (long long)__builtin_readcyclecounter();
+        ++tr;
+        f32x4 jv[JL::JK];
+#pragma unroll
+        for (int k = 0; k < JL::JK; ++k) {
+            const int idx = tid + k * kFusedThreads;
+            const int it = idx - JL::npar4 < JL::ntt4 ? idx - JL::npar4 : 0;
+            const float* src = idx < JL::npar4 ? dn.packed + dn.gpar_off + (size_t)idx * 4 : dn.tt_row + dn.tt_lo + (size_t)it * 4;
+            jv[k] = *(const f32x4*)src;
+        }
+        fused_ring_request(ring, fused_weights_rsrc(dn.packed), (dn.sbase[kSplitFrom] + (wave * 2 + 1) * (S0::TOT * 256)) * 4, S0::TOT, (unsigned)lane * 16u);
+#pragma unroll
+        for (int k = 0; k < JL::JK; ++k) {
+            const int idx = tid + k * kFusedThreads;
+            if (idx < JL::npar4) sm4[(JL::par_off >> 2) + idx] = jv[k];
+            else if (idx - JL::npar4 < JL::ntt4) sm4[(JL::tt_off >> 2) + idx - JL::npar4] = jv[k];
+        }
+        if (tid < 2 * g0.src_rs4) {
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            sm4[g0.src_off4 + tid] = z;
+            sm4[g0.src_off4 + (16 + 2) * g0.src_rs4 + tid] = z;
+        }
+        FusedSplitCtx sx;
+        sx.counter = counter; sx.target = sa.base + 1u; sx.budget = sa.budget;
+        if (tr_base) tr_base[tr] = (long long)__builtin_readcyclecounter();
+        ++tr;
+        if (!fused_split_poll(sx, (int*)(smem + dlay.stat_off), wave, lane)) {
+            fused_split_give_up<SD>(dn, sa, b, role, kSplitFrom - 1, sx.target);
+            return;
+        }
+        if (tr_base) tr_base[tr] = (long long)__builtin_readcyclecounter();
+        ++tr;
+        fused_split_load(x0, sm4, g0.src_off4, g0.src_rs4, 0, wave, lane);
+        lds_barrier();
+    }
+    if (tr_base) tr_base[tr] = (long long)__builtin_readcyclecounter();
+    ++tr;
+    const int at = fused_split_from<SD, kSplitFrom>(dn, sa, dlay, ring, smem, wave, lane, b, role, tr_base, tr);
+    if (at >= 0) fused_split_give_up<SD>(dn, sa, b, role, at, sa.base + 1u + 2u * (unsigned)(at - kSplitFrom + 1));
 }
 
 }  // namespace mpdx

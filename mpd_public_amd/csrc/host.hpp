@@ -148,6 +148,20 @@ struct mpdx_unet {
         unsigned status_host = 0;     // stands in for *status until the device state exists
         unsigned status_word() const { return status ? __atomic_load_n(status, __ATOMIC_RELAXED) : status_host; }
     } run;
+    // mpdx_unet_set_level_split: mpdx_plan may run a joined launch in its paired form (fused_join_split_kernel: the 128-channel down level on two compute
+    // units per trajectory) - 0 never, 1 wherever it is admitted, -1 automatic (by batch)
+    int level_split = -1;
+    int plan_split = 0;       // paired launches of the last mpdx_plan call (mpdx_unet_plan_split)
+    // The paired launch's device state, made at the first mpdx_plan call that may take it (mpdx.hip level_split_create / _begin / _free)
+    struct LevelSplitState {
+        int capacity = -1;            // compute units (-1: not asked yet; 0: no paired launch on this handle)
+        int wgs = 0;                  // workgroups per compute unit the kernel's occupancy query answered
+        float* xch = nullptr;         // exchange area [kSplitMaxB][kSplitTrajFloats]
+        unsigned* counters = nullptr; // one 128-byte line per trajectory, not reset between launches: base advances by kSplitAdvance per launch
+        unsigned base = 0;
+        int live = 1 << 30;           // trajectories whose counters hold base (all of them while every counter is zero)
+        bool rezero = false;          // a give-up's poison: zero the counters (and base) before the next launch
+    } split;
     // launch units: fused whole-trajectory segments (fused_level.hpp) or single layers
     struct CopyJob { size_t src, dst; int n0, ss0, ds0, n1, ss1, ds1, n_inner; };   // strided copy inside `packed` (float units)
     struct Fused {
@@ -226,6 +240,8 @@ int launch_fused_args(const mpdx_unet::Fused& f, const FusedArgs& a, int B, hipS
 int launch_fused_train(const mpdx_unet::Fused& f, const FusedArgs& a, int B, hipStream_t st);
 int launch_fused_join(const FusedJoinArgs& ja, int B, hipStream_t st);   // fused_join_kernel<FusedSeqUpAB, FusedSeqDown3> (programs 3 and 5)
 size_t fused_join_lds_bytes();
+int launch_fused_join_split(const FusedJoinArgs& ja, const FusedSplitArgs& sa, int B, hipStream_t st);   // fused_join_split_kernel, split_grid(B) workgroups
+int fused_join_split_workgroups_per_cu();   // one occupancy query; 0: failed
 // ---- k_guide.hip
 struct NoiseRng;
 int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const float* hs, const float* hg, const uint32_t* amax_in,

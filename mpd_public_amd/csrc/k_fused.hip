@@ -49,4 +49,18 @@ int launch_fused_join(const FusedJoinArgs& ja, int B, hipStream_t st) {
     return 0;
 }
 
+// its paired form: two workgroups per trajectory (fused_level.hpp, fused_join_split_kernel)
+int fused_join_split_workgroups_per_cu() {
+    const void* kern = (const void*)fused_join_split_kernel<FusedSeqUpAB, FusedSeqDown3>;
+    if (raise_lds_limit(kern)) return 0;
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, kFusedThreads, fused_join_lds_bytes()) != hipSuccess) return (void)hipGetLastError(), 0;
+    return n;
+}
+int launch_fused_join_split(const FusedJoinArgs& ja, const FusedSplitArgs& sa, int B, hipStream_t st) {
+    if (int rc = raise_lds_limit((const void*)fused_join_split_kernel<FusedSeqUpAB, FusedSeqDown3>)) return rc;
+    hipLaunchKernelGGL((fused_join_split_kernel<FusedSeqUpAB, FusedSeqDown3>), dim3(split_grid(B)), dim3(kFusedThreads), fused_join_lds_bytes(), st, ja, sa);
+    return 0;
+}
+
 }  // namespace mpdx

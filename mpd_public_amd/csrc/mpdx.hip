@@ -772,23 +772,6 @@ static int run_fused(mpdx_unet* u, const mpdx_unet::Fused& f, const float* packe
     if (int rc = fill_fused_args(u, f, packed, tt_row, x, ws, B, fa, a)) return rc;
     return launch_fused_args(f, a, B, st);
 }
-// mpdx_plan only: the up program `up` of a pass (row `tt_row`, step `fa`) and the down program `dn` of the NEXT pass (row `tt_next`) as one launch
-// (fused_join_kernel).  The down part starts from the x_{t-1} the up part has just computed, so its global input pointer is not used.
-static int run_fused_join(mpdx_unet* u, const mpdx_unet::Fused& up, const mpdx_unet::Fused& dn, const float* packed, const float* tt_row, const float* tt_next,
-                          const float* x, float* ws, int B, const FinalArgs* fa, hipStream_t st, long long* trace = nullptr) {
-    if (int rc = ensure_fused_streams(u, packed, st)) return rc;
-    FusedJoinArgs ja;
-    FusedArgs d;
-    if (int rc = fill_fused_args(u, up, packed, tt_row, x, ws, B, fa, ja.up)) return rc;
-    if (int rc = fill_fused_args(u, dn, packed, tt_next, x, ws, B, nullptr, d)) return rc;
-    ja.up.trace = trace;   // dev tool (mpdx_fused_trace with seg == number of segments); null in the plan
-    ja.dn.packed = d.packed; ja.dn.tt_row = d.tt_row;
-    for (int k = 0; k < 3; ++k) ja.dn.gout[k] = d.gout[k];
-    ja.dn.gpar_off = d.gpar_off; ja.dn.tt_lo = d.tt_lo;
-    for (int k = 0; k < kMaxFusedOps; ++k) ja.dn.sbase[k] = k < d.nops ? d.ops[k].sbase : 0;
-    return launch_fused_join(ja, B, st);
-}
-
 // ---- the device state of the inner-level run (mpdx_unet::InnerRunState, host.hpp)
 // Workgroups of a run launch of `width` that are resident at once on `cus` compute units, given the occupancy answer for that instantiation: the
 // wide form stays at one workgroup per compute unit (the batches the per-layer tiles were measured at), the narrow form takes up to two.
@@ -851,9 +834,65 @@ static void inner_run_free(mpdx_unet::InnerRunState& r) {
 static int handle_status_error(const mpdx_unet* u, const char* fn) {
     const unsigned w = u->run.status_word();
     if (!w) return 0;
-    return fail(MPDX_E_DEVICE, "%s: a workgroup of the inner-level run gave up its wait (status 0x%x: layer %u of the run); the outputs of that plan hold NaN. "
-                "mpdx_unet_set_status(u, 0) clears the word", fn, w, w >> 8);
+    return fail(MPDX_E_DEVICE, "%s: a workgroup of an inner-level run or of the paired joined launch gave up its wait (status 0x%x: layer %u of the run, or down op %u of the paired launch); the outputs of that plan hold NaN. "
+                "mpdx_unet_set_status(u, 0) clears the word", fn, w, w >> 8, w >> 8);
 }
+// ---- the device state of the paired joined launch (mpdx_unet::LevelSplitState, host.hpp; fused_join_split_kernel): one occupancy query, then the exchange
+// area and the counters of kSplitMaxB trajectories.  The status word and the budget are the runs' (inner_run_create).  capacity 0: no paired launch here.
+static int level_split_create(mpdx_unet* u, int cus) {
+    mpdx_unet::LevelSplitState& s = u->split;
+    if (s.capacity >= 0) return 0;
+    s.capacity = 0;
+    if (int rc = inner_run_create(u->run, cus)) return rc;
+    if (u->run.capacity <= 0 || !u->run.status_dev) return 0;
+    s.wgs = fused_join_split_workgroups_per_cu();
+    if (s.wgs < 1) return 0;
+    HIP_TRY(hipMalloc((void**)&s.xch, (size_t)kSplitMaxB * kSplitTrajFloats * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&s.counters, (size_t)kSplitMaxB * kInnerRunCounterStride * sizeof(unsigned)));
+    HIP_TRY(hipMemset(s.counters, 0, (size_t)kSplitMaxB * kInnerRunCounterStride * sizeof(unsigned)));
+    s.capacity = cus;
+    return 0;
+}
+static void level_split_free(mpdx_unet::LevelSplitState& s) {
+    if (s.xch) (void)hipFree(s.xch);
+    if (s.counters) (void)hipFree(s.counters);
+}
+// A paired launch of B trajectories starts: every counter of its trajectories holds *base_out.  A launch advances the counters of ITS trajectories only, so a
+// larger batch than the launch before (a give-up's poison likewise) zeroes them all, stream-ordered, and starts from base 0 again.
+static int level_split_begin(mpdx_unet::LevelSplitState& s, int B, hipStream_t st, unsigned* base_out) {
+    if (B > kSplitMaxB) return fail(MPDX_E_STATE, "paired joined launch of %d trajectories (at most %d)", B, kSplitMaxB);
+    if (s.rezero || B > s.live) {
+        HIP_TRY(hipMemsetAsync(s.counters, 0, (size_t)kSplitMaxB * kInnerRunCounterStride * sizeof(unsigned), st));
+        s.base = 0; s.rezero = false;
+    }
+    s.live = B;
+    *base_out = s.base;
+    s.base += kSplitAdvance;
+    return 0;
+}
+// mpdx_plan only: the up program `up` of a pass (row `tt_row`, step `fa`) and the down program `dn` of the NEXT pass (row `tt_next`) as one launch
+// (fused_join_kernel; split: its paired form, fused_join_split_kernel).  The down part starts from the x_{t-1} the up part has just computed, so its global
+// input pointer is not used.
+static int run_fused_join(mpdx_unet* u, const mpdx_unet::Fused& up, const mpdx_unet::Fused& dn, const float* packed, const float* tt_row, const float* tt_next,
+                          const float* x, float* ws, int B, const FinalArgs* fa, hipStream_t st, long long* trace = nullptr, bool split = false) {
+    if (int rc = ensure_fused_streams(u, packed, st)) return rc;
+    FusedJoinArgs ja;
+    FusedArgs d;
+    if (int rc = fill_fused_args(u, up, packed, tt_row, x, ws, B, fa, ja.up)) return rc;
+    if (int rc = fill_fused_args(u, dn, packed, tt_next, x, ws, B, nullptr, d)) return rc;
+    ja.up.trace = trace;   // dev tool (mpdx_fused_trace with seg == number of segments); null in the plan
+    ja.dn.packed = d.packed; ja.dn.tt_row = d.tt_row;
+    for (int k = 0; k < 3; ++k) ja.dn.gout[k] = d.gout[k];
+    ja.dn.gpar_off = d.gpar_off; ja.dn.tt_lo = d.tt_lo;
+    for (int k = 0; k < kMaxFusedOps; ++k) ja.dn.sbase[k] = k < d.nops ? d.ops[k].sbase : 0;
+    if (!split) return launch_fused_join(ja, B, st);
+    FusedSplitArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    if (int rc = level_split_begin(u->split, B, st, &sa.base)) return rc;
+    sa.xch = u->split.xch; sa.counters = u->split.counters; sa.status = u->run.status_dev; sa.budget = u->run.budget; sa.nb8 = split_nb8(B);
+    return launch_fused_join_split(ja, sa, B, st);
+}
+
 // mpdx_plan only: the seven 256 -> 256 Conv1dBlocks of the innermost level, layers [first, first + kInnerRunLayers), as ONE persistent launch (inner_run.hpp)
 static long long* g_run_trace = nullptr;   // dev tool (mpdx_fused_trace on a run): kRunTraceSlots stamps per layer of the run kind g_run_trace_kind
 static int g_run_trace_kind = -1;
@@ -952,7 +991,7 @@ static int no_hook(PassEvent, int) { return 0; }
 template <class Hook>
 static int walk_pass(mpdx_unet* u, const std::vector<mpdx_unet::Unit>& units, const float* packed, const float* row, const float* x, float* ws,
                      int B, FinalArgs& fa, hipStream_t st, Hook&& hook, bool first_done = false, const float* next_row = nullptr,
-                     long long* join_trace = nullptr) {
+                     long long* join_trace = nullptr, bool split = false) {
     const int n = (int)units.size();
     bool final_done = false;
     for (int i = first_done ? 1 : 0; i < n; ++i) {
@@ -960,7 +999,7 @@ static int walk_pass(mpdx_unet* u, const std::vector<mpdx_unet::Unit>& units, co
         if (un.kind == mpdx_unet::kProgram) final_done |= u->fused[un.fused].has_final;
         if (hook(kSkipUnit, i)) continue;
         if (int rc = hook(kBeforeLaunch, i)) return rc;
-        const int rc = next_row && i == n - 1 ? run_fused_join(u, u->fused[un.fused], u->fused[units[0].fused], packed, row, next_row, x, ws, B, &fa, st, join_trace)
+        const int rc = next_row && i == n - 1 ? run_fused_join(u, u->fused[un.fused], u->fused[units[0].fused], packed, row, next_row, x, ws, B, &fa, st, join_trace, split)
                                               : run_unit(u, un, packed, row, x, ws, B, &fa, st);
         if (rc) return rc;
         if (int rc = hook(kAfterLaunch, i)) return rc;
@@ -1102,10 +1141,13 @@ static int inner_run_auto_width(int B) { return (void)B, kRunNarrow; }
 static int tail_run_auto_width(int B) { return B <= 64 ? kRunNarrow : kRunWide; }
 // What mpdx_plan enqueues per pass at batch B, made once per call (the switches and the device are read here, not per pass): the launch units with the
 // seven run layers as ONE unit where the run is selected, and whether passes can be joined.
+// The batches at which the paired joined launch is taken when the handle leaves the choice open: read from profiles/level_split_ab.md.
+static bool level_split_auto(int B) { return B <= kSplitMaxB; }
 struct PlanSchedule {
     std::vector<mpdx_unet::Unit> units;
     bool run = false;    // units holds a kInnerRun or a kTailRun unit
     bool join = false;   // an unguided pass that has a successor ends in fused_join_kernel; the successor starts at its second unit
+    bool split = false;  // ... in its paired form, fused_join_split_kernel
     int build(mpdx_unet* u, int B, bool with_run = true) {   // with_run = false: the per-layer units whatever the handle says (mpdx_fused_trace)
         units = current_units(u, B, nullptr);
         const int cus = device_cus();
@@ -1146,6 +1188,13 @@ struct PlanSchedule {
         if (first.kind != mpdx_unet::kProgram || last.kind != mpdx_unet::kProgram || first.fused == last.fused) return 0;
         const mpdx_unet::Fused &dn = u->fused[first.fused], &up = u->fused[last.fused];
         join = dn.program == 5 && dn.in1 == SRC_X && dn.in2 == SRC_NONE && !dn.has_final && up.program == 3 && up.has_final && B <= cus;
+        // The paired form: both workgroups of every trajectory resident at once - 2 nb8 <= compute units, B <= 128 on 256 - on a handle that has not
+        // switched it off.  Automatic (level_split < 0): by batch, level_split_auto.
+        const bool want = u->level_split > 0 || (u->level_split < 0 && level_split_auto(B));
+        if (join && want && u->cfg.state_dim <= 16 && split_grid(B) <= cus && B <= kSplitMaxB && sw::geo() && !sw::debug()) {
+            if (int rc = level_split_create(u, cus)) return rc;
+            split = u->split.capacity > 0 && split_grid(B) <= u->split.capacity * std::min(1, u->split.wgs);
+        }
         return 0;
     }
 };
@@ -1224,6 +1273,21 @@ int mpdx_unet_set_plan_join(mpdx_unet* u, int on) {
     return 0;
 }
 int mpdx_unet_plan_joined(const mpdx_unet* u) { return u ? u->plan_joined : 0; }
+int mpdx_unet_set_level_split(mpdx_unet* u, int on) {
+    if (!u) return fail(MPDX_E_INVALID, "null argument");
+    u->level_split = on < 0 ? -1 : on ? 1 : 0;
+    return 0;
+}
+int mpdx_unet_plan_split(const mpdx_unet* u) { return u ? u->plan_split : 0; }
+int mpdx_level_split_block(int B, int block, int32_t* trajectory, int32_t* role) {
+    if (B <= 0 || B > kSplitMaxB) return fail(MPDX_E_INVALID, "mpdx_level_split_block: B=%d", B);
+    const int grid = split_grid(B);
+    if (block < 0 || block >= grid) return fail(MPDX_E_INVALID, "mpdx_level_split_block: block %d of %d", block, grid);
+    const SplitSlot s = split_slot(block, split_nb8(B));
+    if (trajectory) *trajectory = s.b < B ? s.b : -1;
+    if (role) *role = s.role;
+    return grid;
+}
 
 int mpdx_unet_set_inner_run(mpdx_unet* u, int on) {
     if (!u) return fail(MPDX_E_INVALID, "null argument");
@@ -1264,6 +1328,7 @@ int mpdx_unet_set_status(mpdx_unet* u, unsigned word) {
     if (u->run.status) __atomic_store_n(u->run.status, word, __ATOMIC_RELAXED);
     u->run.status_host = word;
     if (!word && u->run.counters) u->run.ctr[0].rezero = u->run.ctr[1].rezero = true;   // whatever a give-up left in the counters goes before the next run
+    if (!word) u->split.rezero = true;
     return 0;
 }
 
@@ -1272,6 +1337,7 @@ void mpdx_unet_destroy(mpdx_unet* u) {
     if (u && u->pack_chunks_dev) (void)hipFree(u->pack_chunks_dev);
     if (u && u->jobs_dev) (void)hipFree(u->jobs_dev);
     if (u) inner_run_free(u->run);
+    if (u) level_split_free(u->split);
     delete u;
 }
 
@@ -1430,7 +1496,7 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
     // innermost level are one persistent launch in guided iterations too: the inner levels do not see the guide.
     PlanSchedule ps;
     if (int rc = ps.build(u, B)) return rc;
-    u->inner_runs = u->inner_run_layers = u->plan_joined = 0;
+    u->inner_runs = u->inner_run_layers = u->plan_joined = u->plan_split = 0;
     hipStream_t st = (hipStream_t)stream;
     const int H = u->cfg.n_support_points, D = u->cfg.state_dim;
     const size_t n = (size_t)B * H * D;
@@ -1474,10 +1540,11 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
         } else {
             fa.mode = 2; fa.absmax = fl;  // posterior mean + its max|.| per context
         }
-        if (int rc = walk_pass(u, ps.units, packed, timetab + (size_t)t * u->tt_row, padded_input(u, x, ws, B, st), ws, B, fa, st, no_hook, down_done, tt_next))
+        if (int rc = walk_pass(u, ps.units, packed, timetab + (size_t)t * u->tt_row, padded_input(u, x, ws, B, st), ws, B, fa, st, no_hook, down_done, tt_next, nullptr, ps.split))
             return rc;
         down_done = join;
         u->plan_joined += join ? 1 : 0;
+        u->plan_split += join && ps.split ? 1 : 0;
         if (guided) {
             for (int j = 0; j < n_guide_steps; ++j) {
                 const bool last = j == n_guide_steps - 1;  // the last iteration also adds the noise term and appends to the chain
@@ -1497,7 +1564,7 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
         }
     }
     HIP_TRY(hipGetLastError());
-    return ps.run ? handle_status_error(u, "mpdx_plan") : 0;   // (what has already given up by now; the rest shows at the next call or in mpdx_unet_status)
+    return ps.run || ps.split ? handle_status_error(u, "mpdx_plan") : 0;   // (what has already given up by now; the rest shows at the next call or in mpdx_unet_status)
 }
 
 int mpdx_randn(float* out, size_t n, uint64_t seed, uint64_t offset, void* stream) {

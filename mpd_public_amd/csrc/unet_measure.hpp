@@ -156,7 +156,7 @@ int mpdx_fused_trace(mpdx_unet* u, const float* packed, const float* timetab, co
         if (pass == 2 && run_kind >= 0) { g_run_trace = dev.p; g_run_trace_kind = run_kind; }
         else if (pass == 2 && !joined) { g_fused_trace = dev.p; g_fused_trace_seg = seg; }
         const float* next_row = pass == 2 && joined ? timetab : nullptr;
-        if (int rc = walk_pass(u, ps.units, packed, timetab, padded_input(u, x, ws, B, st), ws, B, fa, st, no_hook, false, next_row, dev.p)) return rc;
+        if (int rc = walk_pass(u, ps.units, packed, timetab, padded_input(u, x, ws, B, st), ws, B, fa, st, no_hook, false, next_row, dev.p, ps.split)) return rc;
     }
     HIP_TRY(hipStreamSynchronize(st));
     const int n = std::min(cap, 1024);   // 8 waves x 128 slots

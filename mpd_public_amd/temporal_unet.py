@@ -186,6 +186,16 @@ class TemporalUnet(nn.Module):
         """Joined launches of the last fused plan on this model (mpdx_unet_plan_joined)."""
         return int(_lib.load().mpdx_unet_plan_joined(self._handle()))
 
+    def set_level_split(self, on):
+        """mpdx_unet_set_level_split: may a joined launch of the fused planning loop run the 128-channel down level on two compute units per trajectory
+        (the paired form)?  True: wherever it is admitted (B <= 128 on 256 compute units), False: never, None: automatic by batch (the default).
+        Results are bit-identical either way.  A handle option, like set_plan_join."""
+        _lib.check(_lib.load().mpdx_unet_set_level_split(self._handle(), -1 if on is None else int(bool(on))), "mpdx_unet_set_level_split")
+
+    def plan_split(self) -> int:
+        """Paired joined launches of the last fused plan on this model (mpdx_unet_plan_split): 0 or plan_joined()."""
+        return int(_lib.load().mpdx_unet_plan_split(self._handle()))
+
     def set_inner_run(self, on: bool):
         """mpdx_unet_set_inner_run: may the fused planning loop run the seven 256 -> 256 layers of the innermost level, and the tail of up level 0
         (three 128 -> 128 layers + Upsample1d), as one persistent launch each (default: yes, where the network and the batch admit it)?  Results are
