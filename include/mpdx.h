@@ -272,8 +272,41 @@ typedef struct mpdx_field {
      *   MPDX_GRID_NEAREST: GridMapSDF AS RECALLED - node i_j = rint(c_j) (half to even, as torch.round / rintf); sdf = the node's value, gradient =
      *                      the node's STORED gradient (first-order surrogate), the edge node's for a clamped point.
      * The guide applies the hinge relu(margin - sdf) to it exactly as to an OBJECTS field. */
-    int32_t grid_sdf_off;               /* float offset of the sdf plane in grids */
-    int32_t grid_grad_off;              /* float offset of the gradient plane in grids, or -1: none (LINEAR only) */
+    /* --- MPDX_FIELD_OBJECTS: moving obstacles, time-indexed translation tracks (an extension: the reference's collision fields are static).  Both
+     * members zero: the field does not move - the block behaves exactly as before the members existed (they lie where an OBJECTS field never
+     * carried anything: the words a GRID field uses for its plane offsets; the caller zeroes the block as for every appended member).
+     * An MPDX_FIELD_OBJECTS field may carry a track: track_len = H rows of 4 floats (ox, oy, oz, 0) at prims + track_off, behind the primitive
+     * tables (the kernels stage it into LDS with them; n_prim_floats covers it).  Row h is the rigid translation of ALL the field's primitives at
+     * the time of support point h (h * dt), relative to the positions in the primitive table.  In 2-D oz is ignored.
+     * On point i of a trajectory - the guide's n_interp interpolated points, the metrics' n_check points, the supports themselves with
+     * interpolation off - the kernels form the interpolation pair (i0, i1, l0, l1) of q_i = l0 * x[i0] + l1 * x[i1]; the field's offset there is
+     *     o_i = l0 * track[i0] + l1 * track[i1]        (the same pair, the same arithmetic, fp32 throughout)
+     * and every link point p of that trajectory point is tested as p' = p - o_i: from there on the field's arithmetic is unchanged (hinge,
+     * arg-min primitive, gradient, all on p').  The force on the link point is the one computed at p' (a translation has an identity Jacobian; for
+     * the Panda the moment of the force is taken about the link point p itself).  No velocity of the obstacle enters the cost.
+     * A NaN or infinite track entry cannot fault: no index is formed from p'.  What the field then reports is NOT defined: against a sphere every
+     * comparison with NaN is false (no hit, no force), but the box distance goes through fmaxf, which drops a NaN operand - a box whose p' is NaN on
+     * every axis reads as deep inside (a hit, an active hinge), and one that is NaN on some axes acts as a slab along the others.  Keep tracks finite
+     * (the Python side refuses a non-finite track; the C ABI does not read the table and cannot).
+     * Checked on the host before any launch, on members only (MPDX_E_INVALID, message naming the member): track_len neither 0 nor H of the launch;
+     * a track_len != 0 on a MPDX_FIELD_WORKSPACE or MPDX_FIELD_SELF field; track_off negative, not a multiple of 4, or the track not ending inside
+     * n_prim_floats; a track overlapping a primitive table of any field or another track; n_scenes > 1; robot == MPDX_ROBOT_CHAIN.  Tracks next to a
+     * MPDX_FIELD_GRID field are allowed (a grid itself does not move: its two words are its plane offsets).  Fields at and beyond n_fields are not
+     * looked at.
+     * Entry points that take tracks: mpdx_guide_step, mpdx_guide_step_scaled, mpdx_guide_time, mpdx_guide_variant, mpdx_traj_metrics,
+     * mpdx_traj_metrics_mask, mpdx_plan; mpdx_gpmp_step, mpdx_rrt_connect, mpdx_rrt_paths and mpdx_sdf_grid_bake refuse any OBJECTS field with
+     * track_len != 0 (the baseline planners would silently plan among the obstacles' positions at time 0). */
+    /* The two words below are read by the field's kind: a MPDX_FIELD_GRID field has no primitives that could move and a MPDX_FIELD_OBJECTS field
+     * no planes, so the track members of an OBJECTS field (moving obstacles, below) share their storage - mpdx_field and mpdx_guide_params keep
+     * their size and every member its offset.  Two consequences.  (1) These words used to be ignored for every kind but MPDX_FIELD_GRID: a caller that
+     * wrote something into them on an OBJECTS, WORKSPACE or SELF field (grid_grad_off = -1 on every field, say) now states a track, and the host
+     * checks refuse the block (a track_len that is not H, or a track on a WORKSPACE / SELF field) rather than ignore it - zero them, as every appended
+     * member of the block asks.  (2) Anonymous unions need C11 (or C++); a C99 caller compiles the header with its compiler's extension
+     * (gcc and clang accept them in every mode). */
+    union { int32_t grid_sdf_off;       /* MPDX_FIELD_GRID: float offset of the sdf plane in grids */
+            int32_t track_len; };       /* MPDX_FIELD_OBJECTS: 0: the field does not move; otherwise it must equal H of the launch */
+    union { int32_t grid_grad_off;      /* MPDX_FIELD_GRID: float offset of the gradient plane in grids, or -1: none (LINEAR only) */
+            int32_t track_off; };       /* MPDX_FIELD_OBJECTS: float offset of the field's track in prims: track_len rows of 4 floats, offset a multiple of 4 */
     int32_t n[3];                       /* nodes along x, y, z (>= 2 along a used axis; n[2] = 1 in 2-D) */
     float   origin[3];                  /* position of node (0, 0, 0) */
     float   cell;                       /* edge of the cubic cell (> 0) */

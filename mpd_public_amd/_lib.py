@@ -43,11 +43,21 @@ ROBOT_CHAIN_HEADER_FLOATS, ROBOT_CHAIN_JOINT_FLOATS, ROBOT_CHAIN_SPHERE_FLOATS =
 ROBOT_CHAIN_REVOLUTE, ROBOT_CHAIN_PRISMATIC = 0, 1
 
 
+class _FieldWord0(C.Union):     # by the field's kind: a grid's sdf plane offset | the rows of an OBJECTS field's translation track (0: it does not move)
+    _fields_ = [("grid_sdf_off", C.c_int32), ("track_len", C.c_int32)]
+
+
+class _FieldWord1(C.Union):     # a grid's gradient plane offset | the float offset in prims of an OBJECTS field's track
+    _fields_ = [("grid_grad_off", C.c_int32), ("track_off", C.c_int32)]
+
+
 class Field(C.Structure):
+    _anonymous_ = ("_word0", "_word1")
     _fields_ = [("kind", C.c_int32), ("weight", C.c_float), ("sphere_off", C.c_int32), ("n_spheres", C.c_int32),
                 ("box_off", C.c_int32), ("n_boxes", C.c_int32), ("ws_min", C.c_float * 3), ("ws_max", C.c_float * 3),
-                # MPDX_FIELD_GRID (planes in GuideParams.grids; lookup formulas in include/mpdx.h)
-                ("grid_sdf_off", C.c_int32), ("grid_grad_off", C.c_int32), ("n", C.c_int32 * 3), ("origin", C.c_float * 3),
+                # MPDX_FIELD_GRID (planes in GuideParams.grids; lookup formulas in include/mpdx.h); the first two words are the track members of a
+                # MPDX_FIELD_OBJECTS field (moving obstacles): the anonymous unions of the header
+                ("_word0", _FieldWord0), ("_word1", _FieldWord1), ("n", C.c_int32 * 3), ("origin", C.c_float * 3),
                 ("cell", C.c_float), ("mode", C.c_int32)]
 
 

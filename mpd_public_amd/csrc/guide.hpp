@@ -25,6 +25,7 @@
 #include "conv_block.hpp"
 #include "grid_field.hpp"
 #include "guide_common.hpp"
+#include "motion.hpp"
 #include "scene_table.hpp"
 
 namespace mpdx {
@@ -62,6 +63,13 @@ struct GuideArgs {
     dev_grids grid;         // MPDX_FIELD_GRID descriptors (grid_field.hpp): read by the HAS_GRID instantiations only
     dev_scenes scene;       // per-scene primitive tables (scene_table.hpp): last, read by the MULTI_SCENE instantiations only
 };
+// the arguments of the MOVING instantiations: the same block with the track descriptor (motion.hpp) behind it - the static instantiations keep,
+// byte for byte, the arguments they had
+struct GuideArgsMoving : GuideArgs {
+    dev_motion motion;
+};
+template <bool MOVING>
+using guide_args_t = std::conditional_t<MOVING, GuideArgsMoving, GuideArgs>;
 
 // d cost / d p  for  cost = relu(margin - min_prims sdf(p)).
 // The scan over primitives only tracks the minimum signed distance and its index: batched (4 primitives' data are read
@@ -330,9 +338,17 @@ __device__ __forceinline__ float objects_sdf(const float* __restrict__ prims, co
 // field is a grid, so that the primitive-only instantiations compile from exactly the code they had before grids existed.
 // MULTI_SCENE (here and in the guide kernels): the workgroup stages the block of ITS scene (scene_table.hpp) and scans the OBJECTS fields with that
 // scene's counts; chosen by the launcher when n_scenes > 1, for the same reason.
-template <int QD, int DIM, int ROBOT, bool HAS_GRID = false, bool MULTI_SCENE = false>
+// MOVING (here and in the guide kernels): OBJECTS fields may carry a track (motion.hpp): the offset o_i of a moving field is formed once per
+// point and every link point is tested as p - o_i; the branch on the field's track length is scalar.  Chosen by the launcher when a field carries a
+// track, for the same reason; never together with MULTI_SCENE (refused on the host).
+// The track descriptor is a trailing argument of the MOVING instantiations alone (Motion = dev_motion; the static ones take none: their arguments are,
+// byte for byte, what they were).
+template <int QD, int DIM, int ROBOT, bool HAS_GRID = false, bool MULTI_SCENE = false, bool MOVING = false, class... Motion>
 __global__ __launch_bounds__(64) void traj_metrics_kernel(const dev_guide_params gp, const float* __restrict__ x, float* __restrict__ out,
-                                                          int B, int H, int n_check, uint8_t* __restrict__ mask, const dev_grids grid, const dev_scenes scene) {
+                                                          int B, int H, int n_check, uint8_t* __restrict__ mask, const dev_grids grid, const dev_scenes scene,
+                                                          const Motion... motion) {
+    static_assert(!(MOVING && MULTI_SCENE), "tracks with several scenes are refused on the host");
+    static_assert(sizeof...(Motion) == (MOVING ? 1 : 0), "the track descriptor travels with the MOVING instantiations only");
     constexpr int D = 2 * QD;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int lane = threadIdx.x, b = blockIdx.x;
@@ -368,6 +384,18 @@ __global__ __launch_bounds__(64) void traj_metrics_kernel(const dev_guide_params
             for (int f = 0; f < gp.n_fields; ++f) {
                 if (gp.fields[f].kind == MPDX_FIELD_OBJECTS) {
                     if constexpr (MULTI_SCENE) hit |= objects_sdf<DIM>(sprim, scene_field(gp, sc_n, f), p) < gp.link_margin;
+                    else if constexpr (MOVING) {
+                        float pm[DIM];
+#pragma unroll
+                        for (int j = 0; j < DIM; ++j) pm[j] = p[j];
+                        if (track_len_of(f, motion...) != 0) {   // (scalar: f is uniform)
+                            float o[DIM];
+                            track_offset<DIM, false>(sprim, track_off_of(f, motion...), ip, o);
+#pragma unroll
+                            for (int j = 0; j < DIM; ++j) pm[j] = p[j] - o[j];
+                        }
+                        hit |= objects_sdf<DIM>(sprim, gp.fields[f], pm) < gp.link_margin;
+                    }
                     else hit |= objects_sdf<DIM>(sprim, gp.fields[f], p) < gp.link_margin;
                 }
                 else if (gp.fields[f].kind == MPDX_FIELD_WORKSPACE) {
@@ -398,6 +426,14 @@ __global__ __launch_bounds__(64) void traj_metrics_kernel(const dev_guide_params
                     for (int s = 0; s < kPandaNS; ++s) {
                         const float p3[3] = {P[s][0], P[s][1], P[s][2]};
                         hit |= grid_sdf<3>(grid.grids, grid.g[f], p3) < kPandaSR[s];
+                    }
+                } else if (MOVING && kind == MPDX_FIELD_OBJECTS && track_len_of(f, motion...) != 0) {   // a moving field: o_i once per point, then every link sphere at p - o_i
+                    float o[3];
+                    track_offset<3, false>(sprim, track_off_of(f, motion...), ip, o);
+#pragma unroll
+                    for (int s = 0; s < kPandaNS; ++s) {
+                        const float p3[3] = {P[s][0] - o[0], P[s][1] - o[1], P[s][2] - o[2]};
+                        hit |= objects_sdf<3>(sprim, gp.fields[f], p3) < kPandaSR[s];
                     }
                 } else {
 #pragma unroll
@@ -612,9 +648,13 @@ __device__ __forceinline__ void sum_fields_and_apply(const GuideArgs& a, int n_s
 // wave 0 then gathers, clips, adds the GP term and applies the update.  WPT = 8 (2 point halves x up to 4 fields): the
 // single-wave version is a long serial latency chain (2-D: 19 us per launch; 8 waves: 9 us).  The Panda has its own
 // kernel below (guide_step_panda_kernel).
-template <int QD, int DIM, int ROBOT, int WPT, bool HAS_GRID = false, bool MULTI_SCENE = false>
-__global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a) {
+// MOVING: a wave serves ONE field (FW = MAXF), so the offset o_i of that field, if it moves, is formed once per point with the point itself: its two
+// LDS reads are issued with the reads of the point's supports.
+template <int QD, int DIM, int ROBOT, int WPT, bool HAS_GRID = false, bool MULTI_SCENE = false, bool MOVING = false>
+__global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const guide_args_t<MOVING> a) {
     static_assert(ROBOT == MPDX_ROBOT_POINTMASS, "the Panda has its own kernel (guide_step_panda_kernel)");
+    static_assert(!(MOVING && MULTI_SCENE), "tracks with several scenes are refused on the host");
+    static_assert(!MOVING || WPT / (WPT >= 2 ? 2 : 1) >= MPDX_MAX_FIELDS, "MOVING: one field per wave");
     constexpr int D = 2 * QD;
     constexpr int MAXF = MPDX_MAX_FIELDS;
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -662,6 +702,18 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
         float q[QD];
 #pragma unroll
         for (int j = 0; j < QD; ++j) q[j] = l0 * sx[ip.i0 * D + j] + l1 * sx[ip.i1 * D + j];
+        float pm[DIM];   // MOVING: the point as this wave's field sees it, q_i - o_i
+        if constexpr (MOVING) {
+            const int fw = wv / PW;   // this wave's field (scalar)
+#pragma unroll
+            for (int j = 0; j < DIM; ++j) pm[j] = q[j];
+            if (fw < gp.n_fields && a.motion.len[fw] != 0) {
+                float o[DIM];
+                track_offset<DIM, false>(sprim, a.motion.off[fw], ip, o);
+#pragma unroll
+                for (int j = 0; j < DIM; ++j) pm[j] = q[j] - o[j];
+            }
+        }
 
         if (ROBOT == MPDX_ROBOT_POINTMASS) {
             float p[DIM];
@@ -673,6 +725,7 @@ __global__ __launch_bounds__(64 * WPT) void guide_step_kernel(const GuideArgs a)
                 float force[DIM];
                 if (gp.fields[f].kind == MPDX_FIELD_OBJECTS) {
                     if constexpr (MULTI_SCENE) objects_force<DIM>(sprim, scene_field(gp, sc_n, f), p, margin, force);
+                    else if constexpr (MOVING) objects_force<DIM>(sprim, gp.fields[f], pm, margin, force);   // (f is this wave's field: pm = p where it does not move)
                     else objects_force<DIM>(sprim, gp.fields[f], p, margin, force);
                 }
                 else if (gp.fields[f].kind == MPDX_FIELD_WORKSPACE) workspace_force<DIM>(gp.fields[f], p, margin, force);
@@ -786,9 +839,12 @@ constexpr int panda_group_joints(int part) { return part == 0 ? 3 : part == 1 ? 
 // FKREG: the forward kinematics of the point are evaluated HERE from the LDS-staged state (sx, H, D, scale) instead of being read from
 // the per-point FK table of phase 1 (sfk): 4 x the FK work, no 38-KB table - the large-batch variant of the kernel (below).
 // MULTI_SCENE: the OBJECTS fields are scanned with the counts of the workgroup's scene (sc_n; scene_table.hpp)
-template <int PART, bool FKREG, bool HAS_GRID = false, bool MULTI_SCENE = false>
+// MOVING: a field with a track (mo, motion.hpp) is scanned at P_s - o_i; o_i is formed once per point and field (its two 16-byte LDS reads are
+// issued in front of the scan's first batch), the force acts on P_s itself; a field without a track takes one scalar branch
+template <int PART, bool FKREG, bool HAS_GRID = false, bool MULTI_SCENE = false, bool MOVING = false>
 __device__ __forceinline__ void panda_group_forces(const dev_guide_params& gp, const dev_grids& grid, const float* sprim, const float* sfk, float* sG, int half, int lane, int N,
-                                                   long long* tr, const float* sx = nullptr, int H = 0, float scale = 0.f, const SceneCounts* sc_n = nullptr) {
+                                                   long long* tr, const float* sx = nullptr, int H = 0, float scale = 0.f, const SceneCounts* sc_n = nullptr,
+                                                   const dev_motion* mo = nullptr) {
     constexpr int QD = 7, NP = kPandaParts, D = 14;
     constexpr int s_beg = panda_group_first(PART), s_end = panda_group_first(PART + 1), NG = s_end - s_beg;
     constexpr int NJ = panda_group_joints(PART);
@@ -870,6 +926,18 @@ __device__ __forceinline__ void panda_group_forces(const dev_guide_params& gp, c
             }
             if (kind == MPDX_FIELD_OBJECTS) {
                 if constexpr (MULTI_SCENE) objects_force_n<3, NG>(sprim, scene_field(gp, *sc_n, f), pg, mg, fg);
+                else if constexpr (MOVING) {
+                    float pm[NG][3];
+#pragma unroll
+                    for (int n = 0; n < NG; ++n) { pm[n][0] = pg[n][0]; pm[n][1] = pg[n][1]; pm[n][2] = pg[n][2]; }
+                    if (mo->len[f] != 0) {   // (scalar: f is uniform)
+                        float o[3];
+                        track_offset<3, true>(sprim, mo->off[f], interp_pair(gp.interpolate, scale, i, H), o);
+#pragma unroll
+                        for (int n = 0; n < NG; ++n) { pm[n][0] = pg[n][0] - o[0]; pm[n][1] = pg[n][1] - o[1]; pm[n][2] = pg[n][2] - o[2]; }
+                    }
+                    objects_force_n<3, NG>(sprim, gp.fields[f], pm, mg, fg);
+                }
                 else objects_force_n<3, NG>(sprim, gp.fields[f], pg, mg, fg);
             }
             else if (HAS_GRID && kind == MPDX_FIELD_GRID) grid_force_n<3, NG>(grid.grids, grid.g[f], pg, mg, fg);
@@ -894,8 +962,9 @@ __device__ __forceinline__ void panda_group_forces(const dev_guide_params& gp, c
 // DENSE (large batches): no FK table in LDS (the forces phase evaluates the FK in registers, four times per point) and registers capped
 // at 128: 70 KB of LDS and 4 waves per SIMD -> TWO workgroups per CU, where the latency-bound phases of one overlap the other's
 // (the default variant: 107 KB, 166 VGPRs, one workgroup per CU; at B = 100 there is one workgroup per CU anyway).  Same arithmetic.
-template <bool DENSE, bool HAS_GRID = false, bool MULTI_SCENE = false>
-__global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(const GuideArgs a) {
+template <bool DENSE, bool HAS_GRID = false, bool MULTI_SCENE = false, bool MOVING = false>
+__global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(const guide_args_t<MOVING> a) {
+    static_assert(!(MOVING && MULTI_SCENE), "tracks with several scenes are refused on the host");
     constexpr int QD = 7, D = 14, MAXF = MPDX_MAX_FIELDS, NP = kPandaParts, WPT = 8;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const dev_guide_params& gp = a.gp;
@@ -995,11 +1064,13 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void guide_step_panda_kernel(co
     {
         const int half = wv & 1;
         long long* trf = (MPDX_TRACE_PTR(a.trace) && b == 0 && lane == 0) ? a.trace + wv * 16 + 8 : nullptr;  // slots 8..: per-field stamps
+        const dev_motion* mo = nullptr;
+        if constexpr (MOVING) mo = &a.motion;
         switch (wv >> 1) {  // the group is a template parameter: sphere -> frame is static, no per-joint masks
-            case 0: panda_group_forces<0, DENSE, HAS_GRID, MULTI_SCENE>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale, &sc_n); break;
-            case 1: panda_group_forces<1, DENSE, HAS_GRID, MULTI_SCENE>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale, &sc_n); break;
-            case 2: panda_group_forces<2, DENSE, HAS_GRID, MULTI_SCENE>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale, &sc_n); break;
-            default: panda_group_forces<3, DENSE, HAS_GRID, MULTI_SCENE>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale, &sc_n); break;
+            case 0: panda_group_forces<0, DENSE, HAS_GRID, MULTI_SCENE, MOVING>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale, &sc_n, mo); break;
+            case 1: panda_group_forces<1, DENSE, HAS_GRID, MULTI_SCENE, MOVING>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale, &sc_n, mo); break;
+            case 2: panda_group_forces<2, DENSE, HAS_GRID, MULTI_SCENE, MOVING>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale, &sc_n, mo); break;
+            default: panda_group_forces<3, DENSE, HAS_GRID, MULTI_SCENE, MOVING>(gp, a.grid, sprim, sfk, sG, half, lane, N, trf, sx, H, scale, &sc_n, mo); break;
         }
     }
     G_STAMP();  // 3 this wave's forces done

@@ -251,7 +251,8 @@ const char* chain_params_problem(const mpdx_guide_params& gp);   // nullptr, or 
 const char* tool_params_problem(const mpdx_guide_params& gp);    // nullptr, or why the tool members are refused (tool_frame == 0: nullptr); chain.hpp
 struct ChainInfo;
 // The checks every launcher applies to a guide parameter block: D == 2 q_dim, n_fields, the primitive table; with chain_info (the guide, its timer
-// and the metrics; filled for a chain robot, else zeroed) also the chain, grid and scene members.  0, or fail(MPDX_E_INVALID, ...).
-int guide_block_problem(const mpdx_guide_params* gp, int D, ChainInfo* chain_info);
+// and the metrics; filled for a chain robot, else zeroed) also the track (H: the support points of the launch; motion.hpp), chain, grid and scene members;
+// without it (the baseline planners) any track is refused.  0, or fail(MPDX_E_INVALID, ...).
+int guide_block_problem(const mpdx_guide_params* gp, int D, ChainInfo* chain_info, int H);
 
 }  // namespace mpdx

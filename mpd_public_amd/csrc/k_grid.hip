@@ -5,6 +5,7 @@
 #include "edt.hpp"
 #include "mesh_sdf.hpp"
 #include "scene_table.hpp"   // has_scenes
+#include "motion.hpp"        // field_track_len
 
 namespace mpdx {
 
@@ -71,6 +72,8 @@ int mpdx_sdf_grid_bake(const mpdx_guide_params* gp, int field, float* sdf_out, f
     const mpdx_field& f = gp->fields[field];
     if (f.kind != MPDX_FIELD_OBJECTS) return fail(MPDX_E_INVALID, "grid bake: field %d is not an OBJECTS field", field);
     if (gp->tool_frame != 0) return fail(MPDX_E_INVALID, "grid bake: tool_frame %d (the tool-axis term belongs to the guide; a grid is baked from an OBJECTS field)", gp->tool_frame);
+    for (int k = 0; k < MPDX_MAX_FIELDS; ++k)   // a grid stands for the fixed environment: a moving field cannot be baked
+        if (field_track_len(*gp, k) != 0) return fail(MPDX_E_INVALID, "grid bake: fields[%d].track_len = %d (a grid does not move; bake the fixed objects and keep the moving field as primitives)", k, field_track_len(*gp, k));
     if (has_scenes(*gp)) return fail(MPDX_E_INVALID, "grid bake: one scene only (n_scenes = %d): a grid stands for the fixed environment", gp->n_scenes);
     if (gp->ws_dim != 2 && gp->ws_dim != 3) return fail(MPDX_E_INVALID, "grid bake: ws_dim %d", gp->ws_dim);
     if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");

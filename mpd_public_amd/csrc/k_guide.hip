@@ -91,14 +91,17 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
     if ((threadIdx.x & 63) == 0) atomicMax(out + ctx, __float_as_uint(m));
 }
 
-int guide_block_problem(const mpdx_guide_params* gp, int D, ChainInfo* chain_info) {
+int guide_block_problem(const mpdx_guide_params* gp, int D, ChainInfo* chain_info, int H) {
     if (D != 2 * gp->q_dim || D > 16) return fail(MPDX_E_INVALID, "state dim %d != 2*q_dim (%d)", D, gp->q_dim);
     if (gp->n_fields < 0 || gp->n_fields > MPDX_MAX_FIELDS) return fail(MPDX_E_INVALID, "n_fields %d", gp->n_fields);
     if (gp->n_prim_floats > 0 && !gp->prims) return fail(MPDX_E_INVALID, "primitive table missing");
     if (!chain_info) {   // (the baseline planners: built-in robots, one scene, no grid - refusals of their own)
         if (gp->tool_frame != 0) return fail(MPDX_E_INVALID, "tool_frame %d: the baseline planners do not take the tool-axis term (guide, mpdx_plan and mpdx_traj_tool_metrics only)", gp->tool_frame);
+        for (int f = 0; f < MPDX_MAX_FIELDS; ++f)   // a planner would silently plan among the obstacles' positions at time 0
+            if (field_track_len(*gp, f) != 0) return fail(MPDX_E_INVALID, "fields[%d].track_len = %d: the baseline planners do not take moving obstacles (guide, metrics and mpdx_plan only)", f, field_track_len(*gp, f));
         return 0;
     }
+    if (const char* why = motion_params_problem(*gp, H)) return fail(MPDX_E_INVALID, "%s", why);   // (members only, and before a chain table is read: a track refuses a chain)
     memset(chain_info, 0, sizeof(*chain_info));
     if (gp->robot == MPDX_ROBOT_CHAIN)   // (a chain robot's own refusals first: it takes no grid field at all)
         if (const char* why = chain_params_check(*gp, chain_info)) return fail(MPDX_E_INVALID, "%s", why);
@@ -127,7 +130,7 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
     if (!gp || !x || !amax_in) return fail(MPDX_E_INVALID, "null argument");
     if (H > 128 || H < 2) return fail(MPDX_E_INVALID, "guide kernel: one support point per lane of one or two waves: H=%d unsupported (max 128)", H);
     ChainInfo chain_info;
-    if (int rc = guide_block_problem(gp, D, &chain_info)) return rc;
+    if (int rc = guide_block_problem(gp, D, &chain_info, H)) return rc;
     if (gp->interpolate && (gp->n_interp < H || gp->n_interp > 8 * H)) return fail(MPDX_E_INVALID, "n_interp %d unsupported", gp->n_interp);
     if (gp->robot == MPDX_ROBOT_PANDA && (((uintptr_t)x & 15) || ((size_t)H * D) % 4))
         return fail(MPDX_E_INVALID, "Panda guide: x must be 16-byte aligned with H * D a multiple of 4 (the trajectory is staged with 16-byte loads)");
@@ -152,20 +155,35 @@ int launch_guide(const mpdx_guide_params* gp, float* x, float* grad_out, const f
     const size_t lds = guide_lds_bytes(staged, H, D, dense);
     if (lds > 160 * 1024) return fail(MPDX_E_INVALID, "guide needs %zu B of LDS (n_interp %d too large)", lds, gp->n_interp);
     if (gp->robot == MPDX_ROBOT_CHAIN) return launch_chain_guide(a, dev_tool_of(*gp), gp->chain, chain_info, multi, lds, B, st);   // (q_dim == n_joints, ws_dim == 3: checked above)
+    // a track selects the MOVING instantiations (motion.hpp), for the same reason; their arguments carry the track descriptor behind the block
+    const bool moving = has_motion(*gp);
+    GuideArgsMoving am;   // (filled for a MOVING launch only: the static launches pass `a`)
+    if (moving) {
+        static_cast<GuideArgs&>(am) = a;
+        am.motion = dev_motion_of(*gp);
+    }
     int rc = 0;
     const bool known = with_builtin_robot(*gp, [&](auto qd, auto, auto robot) {
         if constexpr (decltype(robot)::value == MPDX_ROBOT_PANDA)
-            rc = with_bools([&](auto dense_c, auto grid_c, auto multi_c) {
-                auto kern = guide_step_panda_kernel<decltype(dense_c)::value, decltype(grid_c)::value, decltype(multi_c)::value>;
-                if (int r = raise_lds_limit((const void*)kern)) return r;
-                hipLaunchKernelGGL(kern, dim3(B), dim3(512), lds, st, a);
-                return 0;
-            }, dense, grid, multi);
+            rc = with_bools([&](auto dense_c, auto grid_c) {
+                return with_scene_mode([&](auto multi_c, auto moving_c) {
+                    auto kern = guide_step_panda_kernel<decltype(dense_c)::value, decltype(grid_c)::value, decltype(multi_c)::value, decltype(moving_c)::value>;
+                    if (int r = raise_lds_limit((const void*)kern)) return r;
+                    if constexpr (decltype(moving_c)::value) hipLaunchKernelGGL(kern, dim3(B), dim3(512), lds, st, am);
+                    else hipLaunchKernelGGL(kern, dim3(B), dim3(512), lds, st, a);
+                    return 0;
+                }, multi, moving);
+            }, dense, grid);
         else   // (the point mass has no dense variant and stays under the default LDS limit's refusal: no raise_lds_limit)
-            with_bools([&](auto grid_c, auto multi_c) {
-                constexpr int QD = decltype(qd)::value;
-                hipLaunchKernelGGL((guide_step_kernel<QD, QD, MPDX_ROBOT_POINTMASS, 8, decltype(grid_c)::value, decltype(multi_c)::value>), dim3(B), dim3(512), lds, st, a);
-            }, grid, multi);
+            with_bools([&](auto grid_c) {
+                return with_scene_mode([&](auto multi_c, auto moving_c) {
+                    constexpr int QD = decltype(qd)::value;
+                    auto kern = guide_step_kernel<QD, QD, MPDX_ROBOT_POINTMASS, 8, decltype(grid_c)::value, decltype(multi_c)::value, decltype(moving_c)::value>;
+                    if constexpr (decltype(moving_c)::value) hipLaunchKernelGGL(kern, dim3(B), dim3(512), lds, st, am);
+                    else hipLaunchKernelGGL(kern, dim3(B), dim3(512), lds, st, a);
+                    return 0;
+                }, multi, moving);
+            }, grid);
     });
     if (!known) return fail(MPDX_E_INVALID, "unsupported robot %d / q_dim %d / ws_dim %d", gp->robot, gp->q_dim, gp->ws_dim);
     return rc;
@@ -202,10 +220,11 @@ int mpdx_traj_metrics_mask(const mpdx_guide_params* gp, const float* x_unnormali
     if (!gp || !x_unnormalised || !out4 || B <= 0) return fail(MPDX_E_INVALID, "bad argument");
     if (H > 128 || H < 2) return fail(MPDX_E_INVALID, "H=%d unsupported (max 128)", H);
     ChainInfo chain_info;
-    if (int rc = guide_block_problem(gp, D, &chain_info)) return rc;
+    if (int rc = guide_block_problem(gp, D, &chain_info, H)) return rc;
     if (n_check < 2) n_check = H;
     hipStream_t st = (hipStream_t)stream;
-    const bool grid = has_grid_field(*gp), multi = has_scenes(*gp);
+    const bool grid = has_grid_field(*gp), multi = has_scenes(*gp), moving = has_motion(*gp);
+    const dev_motion mo = dev_motion_of(*gp);
     const dev_guide_params g = dev_params_staged(*gp);   // (n_prim_floats = what a workgroup stages: the table, or one scene block + the shared tail)
     const dev_scenes sc = dev_scenes_of(*gp);
     if (gp->robot == MPDX_ROBOT_CHAIN) {
@@ -218,10 +237,17 @@ int mpdx_traj_metrics_mask(const mpdx_guide_params* gp, const float* x_unnormali
     memset(&gr, 0, sizeof(gr));
     if (grid) gr = dev_grids_of(*gp);
     const bool known = with_builtin_robot(*gp, [&](auto qd, auto dim, auto robot) {
-        with_bools([&](auto grid_c, auto multi_c) {
-            hipLaunchKernelGGL((traj_metrics_kernel<decltype(qd)::value, decltype(dim)::value, decltype(robot)::value, decltype(grid_c)::value, decltype(multi_c)::value>),
-                               dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr, sc);
-        }, grid, multi);
+        with_bools([&](auto grid_c) {
+            return with_scene_mode([&](auto multi_c, auto moving_c) {
+                if constexpr (decltype(moving_c)::value)
+                    hipLaunchKernelGGL((traj_metrics_kernel<decltype(qd)::value, decltype(dim)::value, decltype(robot)::value, decltype(grid_c)::value, false, true, dev_motion>),
+                                       dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr, sc, mo);
+                else
+                    hipLaunchKernelGGL((traj_metrics_kernel<decltype(qd)::value, decltype(dim)::value, decltype(robot)::value, decltype(grid_c)::value, decltype(multi_c)::value>),
+                                       dim3(B), dim3(64), lds, st, g, x_unnormalised, out4, B, H, n_check, mask, gr, sc);
+                return 0;
+            }, multi, moving);
+        }, grid);
     });
     if (!known) return fail(MPDX_E_INVALID, "unsupported robot %d / q_dim %d / ws_dim %d", gp->robot, gp->q_dim, gp->ws_dim);
     HIP_TRY(hipGetLastError());
@@ -234,7 +260,7 @@ int mpdx_traj_tool_metrics(const mpdx_guide_params* gp, const float* x_unnormali
     if (H > 128 || H < 2) return fail(MPDX_E_INVALID, "H=%d unsupported (max 128)", H);
     if (gp->tool_frame == 0) return fail(MPDX_E_INVALID, "tool_frame 0: mpdx_traj_tool_metrics needs the tool members of the block");
     ChainInfo chain_info;
-    if (int rc = guide_block_problem(gp, D, &chain_info)) return rc;   // (a built-in robot with tool_frame != 0 is refused there)
+    if (int rc = guide_block_problem(gp, D, &chain_info, H)) return rc;   // (a built-in robot with tool_frame != 0 is refused there)
     if (n_check < 2) n_check = H;
     if (int rc = launch_chain_tool_metrics(dev_tool_of(*gp), x_unnormalised, out2, mask, n_check, B, H, gp->chain, chain_info, (hipStream_t)stream)) return rc;
     HIP_TRY(hipGetLastError());
@@ -245,7 +271,7 @@ int mpdx_guide_time(const mpdx_guide_params* gp, float* x, float* grad_out, cons
                     int reps, void* stream, float* ms_avg) {
     if (!gp || !x || !grad_out || !absmax_in || !ms_avg || reps < 1) return fail(MPDX_E_INVALID, "bad argument");
     ChainInfo chain_info;
-    if (int rc = guide_block_problem(gp, D, &chain_info)) return rc;   // (before the events: nothing is created for a refused block)
+    if (int rc = guide_block_problem(gp, D, &chain_info, H)) return rc;   // (before the events: nothing is created for a refused block)
     hipStream_t st = (hipStream_t)stream;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
@@ -287,7 +313,7 @@ int mpdx_guide_trace(const mpdx_guide_params* gp, float* x, const uint32_t* absm
 int mpdx_guide_variant(const mpdx_guide_params* gp, int B, int H, int D) {
     if (!gp) return fail(MPDX_E_INVALID, "null argument");
     ChainInfo chain_info;
-    if (int rc = guide_block_problem(gp, D, &chain_info)) return rc;
+    if (int rc = guide_block_problem(gp, D, &chain_info, H)) return rc;
     return guide_takes_dense(guide_params_staged(*gp, chain_info), B, H, D) ? 1 : 0;
 }
 

@@ -7,6 +7,7 @@
 #include "inner_run.hpp"
 #include "loss.hpp"
 #include "scene_table.hpp"
+#include "motion.hpp"
 
 namespace mpdx {
 
@@ -1484,6 +1485,8 @@ int mpdx_plan(mpdx_unet* u, const float* packed, const float* timetab, int T, co
     if (!u || !packed || !timetab || !coefs || !x || !ws || T <= 0 || n_without_noise < 0 || B <= 0)
         return fail(MPDX_E_INVALID, "bad argument");
     if (int rc = handle_status_error(u, "mpdx_plan")) return rc;   // sticky: a run of an earlier plan on this handle gave up (no synchronisation: a host read)
+    if (guide)   // the tracks of moving obstacles first, as guide_block_problem orders the checks (members only; H is the network's)
+        if (const char* why = motion_params_problem(*guide, u->cfg.n_support_points)) return fail(MPDX_E_INVALID, "%s", why);
     if (guide)   // the scene members are checked here, before the first launch of the loop (launch_guide checks them again per launch)
         if (const char* why = scene_params_problem(*guide)) return fail(MPDX_E_INVALID, "%s", why);
     if (guide)   // ... and so is a chain robot's table (a device table is read here, once, outside the loop)

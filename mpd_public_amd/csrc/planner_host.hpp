@@ -6,7 +6,7 @@ namespace mpdx {
 // the argument checks launch_guide applies to a guide parameter block, for the planners that copy it into their kernel arguments
 // (gn_point / config_hit index gp.fields; the GPMP2 kernel's support-window arithmetic assumes n_interp >= H).  H == 0: no horizon (RRT).
 static int check_planner_params(const mpdx_guide_params* gp, int H, int D) {
-    if (int rc = guide_block_problem(gp, D, nullptr)) return rc;
+    if (int rc = guide_block_problem(gp, D, nullptr, H)) return rc;
     if (gp->n_scenes > 1) return fail(MPDX_E_INVALID, "the baseline planners take one scene (n_scenes = %d): scene batches are for the guide and metrics kernels", gp->n_scenes);
     for (int f = 0; f < gp->n_fields; ++f)   // gn_point / config_hit scan primitive tables: a grid field would be skipped silently
         if (gp->fields[f].kind == MPDX_FIELD_GRID) return fail(MPDX_E_INVALID, "grid fields: guide and metrics only (field %d is a MPDX_FIELD_GRID)", f);

@@ -137,14 +137,15 @@ class TrajectoryDataset:
 
     def __init__(self, env_id="EnvDense2D", robot_id="RobotPointMass", n_support_points=64, include_velocity=True,
                  obstacle_cutoff_margin=0.05, use_extra_objects=True, tensor_args=None, base_dir=None, normalizer="LimitsNormalizer",
-                 sdf_grid=None, **kw):
+                 sdf_grid=None, moving_objects=None, **kw):
         self.tensor_args = tensor_args or {"device": "cpu", "dtype": torch.float32}
         # robot_id: one of the reference's names, or (extension) a planning.RobotChain - a serial chain described by a table
         chain = isinstance(robot_id, RobotChain)
         self.env, self.robot = make_env(env_id), (robot_id if chain else make_robot(robot_id))
         # sdf_grid (extension, default None: primitive tables): the task's fixed objects as a baked signed-distance grid - a dict - or a grid_sdf.GridSDF used as it is (planning.PlanningTask)
         self.task = PlanningTask(self.env, self.robot, obstacle_cutoff_margin=obstacle_cutoff_margin,
-                                 use_extra_objects=use_extra_objects, tensor_args=self.tensor_args, sdf_grid=sdf_grid)
+                                 use_extra_objects=use_extra_objects, tensor_args=self.tensor_args, sdf_grid=sdf_grid,
+                                 moving_objects=moving_objects)   # (extension, default None: an ObjectSet on a track, planning.PlanningTask)
         self.n_support_points, self.include_velocity = n_support_points, include_velocity
         self.state_dim = self.robot.q_dim * (2 if include_velocity else 1)
         # `normalizer`: one of the reference's five class names (trajectories.py:26,78).  Without a dataset directory the limits are this package's

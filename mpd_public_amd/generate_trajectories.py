@@ -39,10 +39,18 @@ from .guides import build_device_params
 from .planning import CostCollision, CostGPTrajectory
 
 
+def _refuse_tracks(task, who):
+    """The baseline planners work on configurations without a time: they would silently plan among a moving obstacle's positions at time 0."""
+    if getattr(task, "has_tracks", False):
+        raise ValueError(f"{who}: the task has a moving obstacle (a track); the baseline planners do not take it - moving obstacles are for the guide, "
+                         f"the metrics and the plan loop")
+
+
 # ------------------------------------------------------------------------------------------------ collision checking of edges
 def edges_free(task, qa: torch.Tensor, qb: torch.Tensor, n_edge_checks: int = 16) -> torch.Tensor:
     """qa, qb: [n, q] configurations on the GPU -> bool [n]: the straight segment qa -> qb is collision free (checked on
     n_edge_checks interpolated configurations with the metrics kernel, link margin only - as task.get_trajs_collision_and_free)."""
+    _refuse_tracks(task, "edges_free")
     z = torch.zeros_like(qa)
     traj = torch.stack([torch.cat([qa, z], -1), torch.cat([qb, z], -1)], dim=1).contiguous()   # [n, 2, 2q]
     return task.trajectory_metrics(traj, n_check=n_edge_checks)[:, 0] == 0
@@ -56,6 +64,7 @@ class RRTConnectBatch:
 
     def __init__(self, task, start: torch.Tensor, goal: torch.Tensor, n: int, step_size: float = 0.1, max_nodes: int = 2048,
                  n_edge_checks: int = 16, generator: Optional[torch.Generator] = None):
+        _refuse_tracks(task, "RRTConnectBatch")
         dev = start.device
         if dev.type != "cuda":
             raise RuntimeError("RRTConnectBatch runs on the GPU (libmpdx RRT-Connect kernel); there is no CPU fallback")
@@ -211,6 +220,7 @@ class GPMP2:
                  lambda_init: float = 1e-2, lambda_up: float = 10.0, lambda_down: float = 0.2, lambda_min: float = 1e-7, lambda_max: float = 1e7,
                  step: float = 1.0, adaptive: bool = True, device="cuda"):
         rob, task = dataset.robot, dataset.task
+        _refuse_tracks(task, "GPMP2")
         H = dataset.n_support_points
         costs = [CostCollision(rob, H, field=f, sigma_coll=1.0) for f in task.get_collision_fields()]
         costs.append(CostGPTrajectory(rob, H, dt, sigma_gp=sigma_gp))

@@ -72,6 +72,9 @@ class GridSDF:
     @classmethod
     def for_primitives(cls, objects, ws_min, ws_max, cell_size, mode="linear", padding=0.3):
         """A grid still to be baked (on the device, on first use) from the spheres and boxes of `objects`, on the box `grid_spec_for` places around the workspace."""
+        if getattr(objects, "track", None) is not None:
+            raise ValueError("GridSDF.for_primitives: the object set carries a track, and a grid does not move - keep a moving set as primitives "
+                             "(PlanningTask(moving_objects=...)) and bake the fixed objects only")
         shape, origin = grid_spec_for(ws_min, ws_max, cell_size, padding)
         return cls(None, origin, cell_size, mode=mode, source=objects, shape=shape)
 

@@ -26,7 +26,10 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
     scenes (a planning.PlanningScenes, or None = one scene, the table as before): the OBJECTS fields it varies get one table per scene - the blocked
     layout of include/mpdx.h (per-scene header + tables at the same offsets in every scene block, capacity = the largest scene, the other OBJECTS
     fields once in the shared tail).  n_scenes / scene_stride are set; the caller binds scene_of_ctx / scene_n_per_ctx per call
-    (`params.table_host`: the host copy of the table, for tests)."""
+    (`params.table_host`: the host copy of the table, for tests).
+    Moving obstacles: an OBJECTS field whose ObjectSet carries a `track` gets its [H, 4] rows packed behind the primitive tables (offset rounded up to
+    a multiple of 4) and track_len / track_off of the field set; H is the cost's n_support_points (ValueError when the track has another number of
+    rows, for a RobotChain and with scenes)."""
     gp = _lib.GuideParams()
     gp.robot, gp.q_dim, gp.ws_dim = robot.robot_id, robot.q_dim, ws_dim
     gp.interpolate, gp.n_interp = int(bool(interpolate)), int(n_interp)
@@ -42,6 +45,7 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
             gp.mins[d], gp.maxs[d] = float(mins[d]), float(maxs[d])
     gp.cutoff_margin, gp.link_margin = float(cutoff_margin), float(robot.link_margin)
     prims, nf, off = [], 0, 0
+    tracks = []    # (field index, [H, 4] rows) of the OBJECTS fields that move
     varied = []    # scenes: (field index, [ObjectSet per scene]) of the fields that differ per scene
     shared = []    # scenes: (field index, sphere floats, box floats) of the OBJECTS fields every scene sees
     planes, goff = [], 0     # grid planes, each padded to a multiple of 4 floats (16-byte aligned gradient planes)
@@ -54,12 +58,18 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
             f, fld = gp.fields[nf], c.field
             f.kind, f.weight = fld.kind, float(w)
             per_scene = scenes.objects_for(fld) if scenes is not None else None
+            if fld.kind == _lib.FIELD_OBJECTS and scenes is not None and getattr(fld.objects, "track", None) is not None:
+                raise ValueError(f"field {fld.name!r} carries a track: scene batches and tracks do not combine")
             if fld.kind == _lib.FIELD_OBJECTS and scenes is not None:
                 if per_scene is not None:
                     varied.append((nf, per_scene))
                 else:
                     shared.append((nf,) + tuple(fld.objects.prim_floats()))
             elif fld.kind == _lib.FIELD_OBJECTS:
+                if getattr(fld.objects, "track", None) is not None:
+                    if robot.robot_id == _lib.ROBOT_CHAIN:
+                        raise ValueError(f"field {fld.name!r} carries a track: a RobotChain takes no moving obstacles")
+                    tracks.append((nf, fld.objects.track_rows(c.n_support_points)))
                 sp, bx = fld.objects.prim_floats()
                 f.sphere_off, f.n_spheres = off, sp.size // 4
                 off += sp.size
@@ -112,6 +122,13 @@ def build_device_params(robot, ws_dim, cutoff_margin, mins, maxs, cost_l, weight
     if scenes is not None:
         table, n_floats = _scene_table(gp, scenes.n_scenes, varied, shared)
     else:
+        for fi, rows in tracks:   # behind the tables, each at a multiple of 4 floats
+            if off % 4:
+                prims.append(np.zeros(4 - off % 4, np.float32))
+                off += prims[-1].size
+            gp.fields[fi].track_off, gp.fields[fi].track_len = off, rows.shape[0]
+            prims.append(rows.reshape(-1))
+            off += rows.size
         n_floats = int(sum(p.size for p in prims))
         table = np.concatenate(prims).astype(np.float32) if n_floats else np.zeros(4, np.float32)
     gp.table_host = table

@@ -66,6 +66,27 @@ def _tool_axis_endpoints(task, dataset, cost, gen, seed, device, max_tries=100):
     raise ValueError("No pair of collision free configurations satisfies the tool-axis constraint")
 
 
+N_SUPPORT_POINTS = 64   # the horizon of every shipped configuration (TrajectoryDataset's default)
+
+
+def _moving_sphere_set(moving_sphere, env_id, n_support_points=N_SUPPORT_POINTS):
+    """experiment(moving_sphere=(c0, c1, r)): the sphere at c0 as an ObjectSet on the straight track to c1."""
+    import numpy as np
+    from .planning import ObjectSet, make_env, _pad3
+    dim = make_env(env_id).dim
+    try:
+        c0, c1, r = moving_sphere
+        c0, c1, r = np.asarray(c0, np.float64).reshape(-1), np.asarray(c1, np.float64).reshape(-1), float(r)
+    except (TypeError, ValueError):
+        raise ValueError(f"moving_sphere takes (c0, c1, r): two centres and a radius, got {moving_sphere!r}") from None
+    if c0.shape != (dim,) or c1.shape != (dim,) or not (np.isfinite(c0).all() and np.isfinite(c1).all()):
+        raise ValueError(f"moving_sphere: c0 and c1 must be finite points of the {dim}-D workspace of {env_id}, got {c0.tolist()} and {c1.tolist()}")
+    if not (r > 0 and np.isfinite(r)):
+        raise ValueError(f"moving_sphere: the radius must be positive and finite, got {r!r}")
+    z = ObjectSet.empty()
+    return ObjectSet(_pad3(c0, dim), np.array([r], np.float32), z.box_centers, z.box_half).with_linear_motion(np.zeros(dim), c1 - c0, n_support_points)
+
+
 def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mpd", use_guide_on_extra_objects_only: bool = False,
                n_samples: int = 50, start_guide_steps_fraction: float = 0.25, n_guide_steps: int = 5,
                n_diffusion_steps_without_noise: int = 5, weight_grad_cost_collision: float = 1e-2,
@@ -73,8 +94,14 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
                trajectory_duration: float = 5.0, device: str = "cuda", debug: bool = True, render: bool = False, seed: int = 30,
                results_dir: str = "logs", model_dir: str = None, model_args: dict = None, sdf_grid_cell_size: float = None,
                sdf_grid_mode: str = "linear", robot=None, goal_ee_pos=None, goal_ee_rot=None, goal_ee_frame=None, tool_axis=None,
-               weight_grad_cost_tool_axis: float = 1e-2, sdf_grid=None, **kwargs):
-    """tool_axis (extension; None = no such term, as before): dict(frame=, axis=, world_axis=, max_tilt=) - the arguments of planning.CostToolAxis, every
+               weight_grad_cost_tool_axis: float = 1e-2, sdf_grid=None, moving_sphere=None, **kwargs):
+    """moving_sphere (extension; None = every obstacle is static, as before): (c0, c1, r) - one more sphere of radius r that moves at constant velocity
+    from centre c0 at the first support point to c1 at the last (2 or 3 coordinates each, the workspace's).  It is a further collision field of the task
+    (planning.PlanningTask(moving_objects=...)): its cost enters the composite as the extra objects' does, the guide pushes every support away from
+    the sphere's position at that support's own time, and the reported figures (free / colliding trajectories, collision intensity) are time-aware.
+    A task that is already full (the Panda: self, fixed, workspace, extra) gives the extras' place to the moving sphere.  Start and goal are drawn
+    against the static fields.
+    tool_axis (extension; None = no such term, as before): dict(frame=, axis=, world_axis=, max_tilt=) - the arguments of planning.CostToolAxis, every
     key optional - adds the tool-axis constraint to the guide with weight `weight_grad_cost_tool_axis` ("carry it upright": the frame's axis stays
     within max_tilt radians of the world axis along the whole trajectory).  A chain robot (the Panda as robot=RobotChain.panda()).  Start and goal are
     then task.ik_coll_free_q solutions for two reachable end-effector targets whose orientation satisfies the constraint exactly (the pose of a random
@@ -114,8 +141,13 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
         raise ValueError("sdf_grid (a GridSDF) and sdf_grid_cell_size (bake one from the primitives) exclude each other")
     if sdf_grid is None and sdf_grid_cell_size is not None:
         sdf_grid = dict(cell_size=float(sdf_grid_cell_size), mode=sdf_grid_mode)
-    dataset = TrajectoryDataset(env_id=env_id, robot_id=robot if robot is not None else robot_id, use_extra_objects=True, obstacle_cutoff_margin=0.05,
-                                include_velocity=args["include_velocity"], tensor_args=tensor_args, sdf_grid=sdf_grid)
+    moving_objects, use_extra = None, True
+    if moving_sphere is not None:
+        moving_objects = _moving_sphere_set(moving_sphere, env_id)
+        use_extra = not (robot is None and robot_id == "RobotPanda")   # (self + fixed + workspace + extra: full - the moving sphere takes the extras' place)
+    dataset = TrajectoryDataset(env_id=env_id, robot_id=robot if robot is not None else robot_id, use_extra_objects=use_extra, obstacle_cutoff_margin=0.05,
+                                include_velocity=args["include_velocity"], tensor_args=tensor_args, sdf_grid=sdf_grid, n_support_points=N_SUPPORT_POINTS,
+                                moving_objects=moving_objects)
     n_support_points, robot, task = dataset.n_support_points, dataset.robot, dataset.task
     dt = trajectory_duration / n_support_points
     robot.dt = dt
@@ -195,6 +227,8 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
 
     hard_conds = dataset.get_hard_conditions(torch.vstack((start_state_pos, goal_state_pos)), normalize=True)
     collision_fields = task.get_collision_fields_extra_objects() if use_guide_on_extra_objects_only else task.get_collision_fields()
+    if use_guide_on_extra_objects_only and moving_objects is not None:   # (the moving sphere's cost enters the composite the way the extra objects' does)
+        collision_fields = [f for f in collision_fields if f is not None] + task.get_collision_fields_moving_objects()
     cost_l = [CostCollision(robot, n_support_points, field=f, sigma_coll=1.0, tensor_args=tensor_args) for f in collision_fields]
     weights = [weight_grad_cost_collision] * len(cost_l)
     if tool_cost is not None:
@@ -336,7 +370,16 @@ if __name__ == "__main__":
                     help="plan to this end-effector position (inverse kinematics) instead of a random goal configuration")
     ap.add_argument("--tool_upright", type=float, default=None, metavar="MAX_TILT_DEG",
                     help="carry the tool upright: the last frame's z axis stays within this many degrees of the world's z (a chain robot; RobotPanda runs as RobotChain.panda())")
+    ap.add_argument("--moving_sphere", type=float, nargs="+", default=None, metavar="V",
+                    help="one more sphere that moves at constant velocity during the plan: the coordinates of its centre at the first support point, then those "
+                         "at the last, then its radius (5 numbers in a 2-D workspace, 7 in 3-D)")
     a = _mesh_grid_args(vars(ap.parse_args()))
+    ms = a.pop("moving_sphere")
+    if ms is not None:
+        if len(ms) not in (5, 7):
+            raise SystemExit("--moving_sphere takes the coordinates of c0, then those of c1, then the radius: 5 numbers (2-D) or 7 (3-D)")
+        k = len(ms) // 2
+        a["moving_sphere"] = (ms[:k], ms[k: 2 * k], ms[-1])
     upright = a.pop("tool_upright")
     if upright is not None:
         import math

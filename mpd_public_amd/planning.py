@@ -25,16 +25,45 @@ from .grid_sdf import GRID_MODES, MESH_SIGNS, GridSDF, grid_spec_for, _check_mes
 
 @dataclass
 class ObjectSet:
-    """sphere + axis-aligned box primitives; rows padded to 3-D (z = 0 in 2-D)."""
+    """sphere + axis-aligned box primitives; rows padded to 3-D (z = 0 in 2-D).
+
+    track (extension; None = the set does not move): [H, dim] or [H, 3] - row h is the rigid translation of ALL the set's primitives at the time of
+    support point h, relative to the centres above (include/mpdx.h, the track members of mpdx_field).  No rotation, one track per set."""
     sphere_centers: np.ndarray  # [ns, 3]
     sphere_radii: np.ndarray    # [ns]
     box_centers: np.ndarray     # [nb, 3]
     box_half: np.ndarray        # [nb, 3]
+    track: Optional[np.ndarray] = None
 
     @staticmethod
     def empty():
         z3, z1 = np.zeros((0, 3), np.float32), np.zeros((0,), np.float32)
         return ObjectSet(z3, z1, z3.copy(), z3.copy())
+
+    def with_linear_motion(self, start_offset, end_offset, n_support_points):
+        """A copy of the set on a straight constant-velocity track: translated by start_offset at the first support point and by end_offset at the
+        last of n_support_points (offsets of 2 or 3 coordinates)."""
+        H = int(n_support_points)
+        if H < 2:
+            raise ValueError(f"n_support_points={n_support_points}: a track has at least 2 rows")
+        a, b = (np.asarray(v, np.float64).reshape(-1) for v in (start_offset, end_offset))
+        if a.shape != b.shape or a.size not in (2, 3):
+            raise ValueError(f"start_offset / end_offset: two vectors of 2 or 3 coordinates are expected, got {a.shape} and {b.shape}")
+        s = np.linspace(0.0, 1.0, H)[:, None]
+        return ObjectSet(self.sphere_centers, self.sphere_radii, self.box_centers, self.box_half, ((1.0 - s) * a + s * b).astype(np.float32))
+
+    def track_rows(self, n_support_points):
+        """The track as the kernels read it: [H, 4] float32 rows (ox, oy, oz, 0).  ValueError unless it has n_support_points rows of 2 or 3 entries."""
+        t = np.asarray(self.track, np.float32)
+        if t.ndim != 2 or t.shape[1] not in (2, 3):
+            raise ValueError(f"track: [H, dim] or [H, 3] is expected, got {t.shape}")
+        if not np.isfinite(t).all():
+            raise ValueError("track: non-finite entry (the kernels do not fault on one, but what the field then reports is not defined)")
+        if t.shape[0] != int(n_support_points):
+            raise ValueError(f"track has {t.shape[0]} rows for n_support_points={n_support_points}: one row per support point")
+        rows = np.zeros((t.shape[0], 4), np.float32)
+        rows[:, : t.shape[1]] = t
+        return rows
 
     def prim_floats(self):
         sp = np.concatenate([self.sphere_centers, self.sphere_radii[:, None]], 1).astype(np.float32).reshape(-1)
@@ -301,8 +330,15 @@ class CollisionField:
 class PlanningTask:
     """The attribute / method surface inference.py reads from `task` (inference.py:161,191-193,288-297)."""
 
-    def __init__(self, env: Env, robot, obstacle_cutoff_margin=0.05, use_extra_objects=True, tensor_args=None, sdf_grid=None, **kw):
-        """sdf_grid (extension; None = the primitive tables, as before): dict(cell_size=..., mode='linear' | 'nearest', padding=0.3) - the FIXED
+    def __init__(self, env: Env, robot, obstacle_cutoff_margin=0.05, use_extra_objects=True, tensor_args=None, sdf_grid=None, moving_objects=None, **kw):
+        """moving_objects (extension; None = as before): an ObjectSet with a `track` (ObjectSet.with_linear_motion, or a [H, dim] array of its own) -
+        a further OBJECTS field named 'moving_objects' whose primitives translate along the track during the plan; the guide and the metrics test
+        every trajectory point against the obstacle's position at that point's own time (include/mpdx.h, the track members).  The fixed and the
+        extra set may carry a track as well (not a fixed set that becomes a grid).  At most MPDX_MAX_FIELDS fields: a Panda task with fixed, extra,
+        workspace and self fields is full - build it with use_extra_objects=False and the moving set takes the extras' place.  Not for a RobotChain,
+        PlanningScenes or the baseline planners.  random_coll_free_q / ik_coll_free_q, whose configurations have no time, test against the
+        fields that do not move.
+        sdf_grid (extension; None = the primitive tables, as before): dict(cell_size=..., mode='linear' | 'nearest', padding=0.3) - the FIXED
         objects become a signed-distance grid (baked from the primitives on the device on first use, mpdx_sdf_grid_bake) and
         get_collision_fields() returns a FIELD_GRID field in their place; extra objects, workspace and self fields stay as they are (as
         torch_robotics does, as recalled: the precomputed grid is for the fixed objects only).  An environment that already carries a grid
@@ -314,8 +350,14 @@ class PlanningTask:
                 raise ValueError("a RobotChain lives in a 3-D workspace (a planar arm is a chain whose axes are all z, among 3-D primitives)")
             if sdf_grid is not None or getattr(env, "grid_fixed", None) is not None:
                 raise ValueError("a RobotChain takes primitive, workspace and self fields: no signed-distance grid")
+            if moving_objects is not None or any(getattr(o, "track", None) is not None for o in (env.obj_fixed, env.obj_extra if use_extra_objects else None)):
+                raise ValueError("a RobotChain takes no moving obstacles: tracks are for the point mass and the Panda (the chain kernels have no MOVING instantiation)")
         self.tensor_args = tensor_args or {"device": "cpu", "dtype": torch.float32}
         self.ws_min, self.ws_max = env.limits
+        if moving_objects is not None:
+            _check_object_set(moving_objects, env.dim, "moving_objects")
+            if moving_objects.track is None:
+                raise ValueError("moving_objects: the set has no track (ObjectSet.with_linear_motion, or set .track to a [H, dim] array)")
         given = sdf_grid if isinstance(sdf_grid, GridSDF) else None
         self.sdf_grid = given if given is not None else dict(sdf_grid) if sdf_grid is not None else None
         if given is not None:
@@ -337,16 +379,52 @@ class PlanningTask:
         self.df_collision_ws_boundaries = CollisionField(_lib.FIELD_WORKSPACE, ws_min=self.ws_min, ws_max=self.ws_max, name="workspace")
         has_self = robot.name == "RobotPanda" or (isinstance(robot, RobotChain) and robot.n_pairs > 0)
         self.df_collision_self = CollisionField(_lib.FIELD_SELF, name="self") if has_self else None
+        self.df_collision_moving_objects = CollisionField(_lib.FIELD_OBJECTS, objects=moving_objects, name="moving_objects") if moving_objects is not None else None
+        fields = self.get_collision_fields()
+        if len(fields) > _lib.MAX_FIELDS:
+            raise ValueError(f"{len(fields)} collision fields ({', '.join(f.name for f in fields)}); the kernels take at most {_lib.MAX_FIELDS} - build the task with "
+                             f"use_extra_objects=False and the moving set takes the extras' place")
+        self._gp_by_h = {}
 
     def get_collision_fields(self) -> List[CollisionField]:
-        out = [self.df_collision_self, self.df_collision_objects, self.df_collision_ws_boundaries, self.df_collision_extra_objects]
+        out = [self.df_collision_self, self.df_collision_objects, self.df_collision_ws_boundaries, self.df_collision_extra_objects,
+               getattr(self, "df_collision_moving_objects", None)]
         return [f for f in out if f is not None]
 
     def get_collision_fields_extra_objects(self) -> List[CollisionField]:
         return [self.df_collision_extra_objects]
 
+    def get_collision_fields_moving_objects(self) -> List[CollisionField]:
+        return [self.df_collision_moving_objects]
+
+    @property
+    def has_tracks(self) -> bool:
+        """a field of the task moves (its ObjectSet carries a track): the metrics need the horizon of the trajectories they check"""
+        return any(field_track(f) is not None for f in self.get_collision_fields())
+
     # ---- collision checking / metrics (inference.py:161,288-297); arithmetic in csrc/guide.hpp::traj_metrics_kernel
-    def _params(self, device):
+    def _params(self, device, n_support_points=None, static_only=False):
+        """The metrics' parameter block.  A task with a track keeps one block per horizon (a track has one row per support point; ValueError when the
+        rows differ from n_support_points) and one of its static fields alone (static_only: configurations without a time).  A block is keyed by
+        (device, horizon, the identity of every track array): assigning a new array to `objects.track` builds a new block at the next call;
+        writing INTO a track array, or changing the primitives of a set, is not seen - build a new task (the one-block cache of a task without
+        tracks has the same limit).  At most 8 blocks are kept (the oldest goes first).  refresh_grids() reaches every one of them."""
+        if self.has_tracks:
+            if n_support_points is None and not static_only:
+                raise ValueError("this task has a moving obstacle (a track): its parameter block belongs to one horizon, and the baseline planners "
+                                 "(RRTConnectBatch, GPMP2, edges_free) do not take it")
+            from .guides import build_device_params
+            tracks = tuple(id(field_track(f)) for f in self.get_collision_fields() if field_track(f) is not None)
+            key = (torch.device(device), None if static_only else int(n_support_points), () if static_only else tracks)
+            store = self.__dict__.setdefault("_gp_by_h", {})
+            if key not in store:
+                while len(store) >= 8:
+                    del store[next(iter(store))]
+                fields = [f for f in self.get_collision_fields() if not (static_only and field_track(f) is not None)]
+                costs = [CostCollision(self.robot, key[1] or 64, field=f) for f in fields]
+                store[key] = build_device_params(self.robot, self.env.dim, self.obstacle_cutoff_margin, None, None, costs, [1.0] * len(costs), True, 128,
+                                                 True, 1.0, device)
+            return store[key][0]
         if getattr(self, "_gp", None) is None or self._gp_prims.device != torch.device(device):
             from .guides import build_device_params
             costs = [CostCollision(self.robot, 64, field=f) for f in self.get_collision_fields()]
@@ -357,14 +435,22 @@ class PlanningTask:
 
     def refresh_grids(self):
         """after GridSDF.update_occupancy / update_mesh: copy the planes again where the metrics' grid buffer is a concatenation (guides.refresh_grid_planes)"""
+        from .guides import refresh_grid_planes
         if getattr(self, "_gp", None) is not None:
-            from .guides import refresh_grid_planes
             refresh_grid_planes(self._gp)
+        for gp, _prims in self.__dict__.get("_gp_by_h", {}).values():   # a task with a track: one block per horizon, each with a grid buffer of its own
+            refresh_grid_planes(gp)
 
-    def trajectory_metrics(self, trajs, n_check=None, return_mask=False):
+    def trajectory_metrics(self, trajs, n_check=None, return_mask=False, static_only=False):
         """trajs: UNNORMALISED [B,H,D] on the GPU -> float tensor [B,4]: (#colliding waypoints, path length, smoothness,
-        #waypoints checked); with return_mask also the per-waypoint collision flags [B, n_check] (bool) the count is made of."""
+        #waypoints checked); with return_mask also the per-waypoint collision flags [B, n_check] (bool) the count is made of.
+        A task with a moving obstacle checks every point against the obstacle's position at the point's own time (H must be the track's length:
+        ValueError otherwise, before any device work); static_only leaves the moving fields out."""
         import ctypes as C
+        if self.has_tracks and not static_only:   # (before any device work)
+            for f in self.get_collision_fields():
+                if field_track(f) is not None:
+                    f.objects.track_rows(trajs.shape[1])
         trajs = trajs.to(torch.float32).contiguous()
         if not trajs.is_cuda:
             raise RuntimeError("trajectory metrics run on the GPU (libmpdx); there is no CPU fallback")
@@ -372,7 +458,7 @@ class PlanningTask:
         n_check = int(n_check or 4 * H)
         out = torch.empty((B, 4), dtype=torch.float32, device=trajs.device)
         mask = torch.empty((B, n_check), dtype=torch.uint8, device=trajs.device) if return_mask else None
-        gp = self._params(trajs.device)
+        gp = self._params(trajs.device, H, static_only) if self.has_tracks else self._params(trajs.device)
         _lib.check(_lib.load().mpdx_traj_metrics_mask(C.byref(gp), trajs.data_ptr(), out.data_ptr(), mask.data_ptr() if return_mask else None,
                                                       n_check, B, H, D, _lib.current_stream()), "mpdx_traj_metrics_mask")
         return (out, mask.bool()) if return_mask else out
@@ -428,7 +514,7 @@ class PlanningTask:
         for _ in range(max_tries):
             q = lo + (hi - lo) * torch.rand((4 * n_samples, self.robot.q_dim), device=device, generator=generator)
             traj = torch.cat([q, torch.zeros_like(q)], -1)[:, None, :].expand(-1, 2, -1).contiguous()
-            free = self.trajectory_metrics(traj, n_check=2)[:, 0] == 0
+            free = self.trajectory_metrics(traj, n_check=2, static_only=True)[:, 0] == 0
             got.append(q[free])
             if sum(g.shape[0] for g in got) >= n_samples:
                 return torch.cat(got)[:n_samples]
@@ -447,7 +533,7 @@ class PlanningTask:
         q, perr = res.q[res.converged], res.pos_err[res.converged]
         if q.shape[0]:
             traj = torch.cat([q, torch.zeros_like(q)], -1)[:, None, :].expand(-1, 2, -1).contiguous()
-            free = self.trajectory_metrics(traj, n_check=2)[:, 0] == 0
+            free = self.trajectory_metrics(traj, n_check=2, static_only=True)[:, 0] == 0
             q, perr = q[free], perr[free]
         if not q.shape[0]:
             raise ValueError("No collision free configuration reaches the target")
@@ -468,6 +554,11 @@ class PlanningTask:
         if self.robot.name == "RobotPointMass":
             lo, hi = np.concatenate([self.ws_min, lo[qd:]]), np.concatenate([self.ws_max, hi[qd:]])
         return torch.tensor(lo[:qd], device=device), torch.tensor(hi[:qd], device=device)
+
+
+def field_track(f):
+    """the track of a collision field's ObjectSet, or None (the field does not move)"""
+    return getattr(getattr(f, "objects", None), "track", None) if getattr(f, "kind", None) == _lib.FIELD_OBJECTS else None
 
 
 def _check_object_set(o, dim, what):
@@ -501,12 +592,16 @@ class PlanningScenes:
     def __init__(self, task: PlanningTask, extra_objects, fixed_objects=None):
         if task.df_collision_extra_objects is None:
             raise ValueError("PlanningScenes replaces the task's extra-objects field: build the task with use_extra_objects=True")
+        if task.has_tracks:
+            raise ValueError("the task has a moving obstacle (a track): scene batches and tracks do not combine (the kernels have no instantiation for both)")
         extra_objects = list(extra_objects)
         if not extra_objects:
             raise ValueError("at least one scene")
         dim = task.env.dim
         for s, o in enumerate(extra_objects):
             _check_object_set(o, dim, f"extra_objects[{s}]")
+            if o.track is not None:
+                raise ValueError(f"extra_objects[{s}] carries a track: scene batches and tracks do not combine")
         if fixed_objects is not None:
             if task.df_collision_objects.kind == _lib.FIELD_GRID:
                 raise ValueError("the task's fixed field is a signed-distance grid, which every scene shares: fixed_objects cannot replace it")
@@ -515,6 +610,8 @@ class PlanningScenes:
                 raise ValueError(f"{len(fixed_objects)} fixed object sets for {len(extra_objects)} scenes")
             for s, o in enumerate(fixed_objects):
                 _check_object_set(o, dim, f"fixed_objects[{s}]")
+                if o.track is not None:
+                    raise ValueError(f"fixed_objects[{s}] carries a track: scene batches and tracks do not combine")
         self.task, self.extra_objects, self.fixed_objects = task, extra_objects, fixed_objects
         self._gp = None
         # sizes: what a workgroup stages must fit the kernels' table budget (the same rule the launchers apply)

@@ -1,0 +1,310 @@
+"""fp64 reference of moving obstacles (include/mpdx.h, the track members of mpdx_field; csrc/motion.hpp) and the case table of
+tests/test_moving_cpu.py / tests/test_gpu_moving.py - test infrastructure, nothing here touches the GPU.
+
+`MovingField` has the duck type oracle.costs.CostCollision reads (`kind == "objects"`, `sdf(points)`), the way tests/grid_ref.GridField has:
+    sdf(pts [B, N, K, dim]) = inner.sdf(pts - o[None, :, None, :]),    o [N, dim] = the track interpolated to the N points (align_corners, as the
+                                                                       trajectory itself: oracle.guide.interpolate_points_v1), in the dtype of the points
+so it plugs into the unchanged fp64 oracle guide and its autograd: d sdf / d p at p is the inner field's gradient at p - o (identity Jacobian).
+"""
+import copy
+import functools
+
+import numpy as np
+import torch
+
+import guide_ref as gr
+from grid_ref import GridField
+from helpers import oracle_guide
+
+DELTA = gr.DELTA
+EPS_CELL = 1e-4                                              # tests/test_gpu_grid_sdf.py: a link point within 1e-4 cell of a discontinuity of the lookup
+GRID_CAP = {"RobotPointMass": 0.01, "RobotPanda": 0.05}     # the caps of tests/test_gpu_grid_sdf.py, for the HAS_GRID cases
+GRID_CELL = {2: 0.01, 3: 0.02}
+
+
+class MovingField:
+    kind = "objects"
+
+    def __init__(self, inner, track, dim, nearest=False):
+        """inner: an oracle.costs.ObjectField; track [H, >= dim]; nearest: the deliberately WRONG variant - the offset of the nearest support's row
+        instead of the interpolated one (what a kernel would compute that forgot the interpolation)"""
+        self.inner, self.dim, self.nearest = inner, dim, nearest
+        self.track = torch.as_tensor(np.asarray(track, np.float32)[:, :dim].copy())     # fp32 values, as the table carries them
+
+    def offsets(self, N, dtype):
+        """o [N, dim]: the track at the N points of a trajectory"""
+        from oracle.guide import interpolate_points_v1
+        tr = self.track.to(dtype)
+        H = tr.shape[0]
+        if N == H:
+            return tr
+        if self.nearest:
+            u = torch.arange(N, dtype=torch.float64) * (H - 1) / (N - 1)
+            return tr[torch.floor(u + 0.5).long().clamp(max=H - 1)]
+        return interpolate_points_v1(tr.unsqueeze(0), N)[0]
+
+    def sdf(self, pts):
+        o = self.offsets(pts.shape[-3], pts.dtype)
+        return self.inner.sdf(pts - o[:, None, :])
+
+
+class _ShiftedRobot:
+    """the robot as a moving field sees it: link points minus the field's offset at the point's time (for guide_ref.decision_distance, whose
+    decisions are those of the inner field at the shifted points)"""
+
+    def __init__(self, robot, field):
+        self.robot, self.field, self.q_dim, self.radii, self.name = robot, field, robot.q_dim, robot.radii, robot.name
+
+    def link_points(self, q):
+        pts = self.robot.link_points(q)
+        return pts - self.field.offsets(pts.shape[-3], pts.dtype)[:, None, :]
+
+
+# ------------------------------------------------------------------------------------------------------------ the moving set and its track
+def bend_track(H, dim, amp=0.3):
+    """[H, dim]: along +x in the first half of the plan, along +y in the second (a bend at mid-time, so that the interpolation between the two rows
+    around it matters), a slow drift along z in 3-D; centred on the table positions"""
+    s = np.linspace(0.0, 1.0, H)
+    o = np.stack([amp * (2 * np.minimum(s, 0.5) - 0.5), amp * (2 * np.maximum(s - 0.5, 0.0) - 0.5), 0.1 * (s - 0.5)], 1)
+    return o[:, :dim].astype(np.float32)
+
+
+_MOVING_SPHERES = ((0.10, 0.20, 0.45, 0.10), (-0.20, -0.10, 0.65, 0.08))
+_MOVING_BOXES = (((0.25, -0.25, 0.40), (0.06, 0.09, 0.10)),)
+
+
+def moving_set(dim, H, track="bend"):
+    """two spheres and one box; track: 'bend', 'zero' (H rows of zeros), None (no track: a static set) or an array"""
+    o = gr._object_set(_MOVING_SPHERES, _MOVING_BOXES, dim)
+    if track is None:
+        return o
+    o.track = bend_track(H, dim) if isinstance(track, str) and track == "bend" else np.zeros((H, dim), np.float32) if isinstance(track, str) else np.asarray(track, np.float32)
+    return o
+
+
+# ------------------------------------------------------------------------------------------------------------ the GPU cases
+# name -> robot, H, interpolated points (None: interpolation off), fixed objects as a linear grid.  All B = 4 on the coverage environments
+# (guide_ref.cover_env) with the moving set above; the Panda gives the extras' place to the moving set (a full task).
+CASES = {
+    "pm2-H6": dict(robot_id="RobotPointMass", H=6, n_interp=12, grid=False),          # the smallest window arithmetic
+    "pm2-H64": dict(robot_id="RobotPointMass", H=64, n_interp=128, grid=False),
+    "pm2-H96": dict(robot_id="RobotPointMass", H=96, n_interp=128, grid=False),        # two waves of supports
+    "pm2-H64-nointerp": dict(robot_id="RobotPointMass", H=64, n_interp=None, grid=False),
+    "pm3-H24": dict(robot_id="RobotPointMass3D", H=24, n_interp=128, grid=False),
+    "panda-H64": dict(robot_id="RobotPanda", H=64, n_interp=128, grid=False),          # sparse here, dense in a child process
+    "pm2-H64-grid": dict(robot_id="RobotPointMass", H=64, n_interp=128, grid=True),
+    "panda-H64-grid": dict(robot_id="RobotPanda", H=64, n_interp=128, grid=True),
+}
+B = 4
+WEIGHTS = (1e-2, 1e-7)
+# which of guide_ref.cover_trajs' trajectories a case takes (its first B by default); chosen so that the moving field's hinges are reached and the
+# ambiguous share stays under the cap - conditions, asserted by tests/test_moving_cpu.py from the reference alone
+SELECT = {}
+
+
+def cap_of(case):
+    c = CASES[case]
+    return GRID_CAP["RobotPanda" if c["robot_id"] == "RobotPanda" else "RobotPointMass"] if c["grid"] else gr.cap_of(c["robot_id"])
+
+
+def dataset(case, device="cpu", track="bend"):
+    """the case's TrajectoryDataset: the robot's own normaliser, the coverage environment, the moving set as the task's moving_objects (track=None:
+    the same primitives as a static extra field in the same slot - the block without tracks)"""
+    import mpd_public_amd as m
+    from mpd_public_amd.planning import PlanningTask
+    c = CASES[case]
+    env_id, dim = gr.ROBOTS[c["robot_id"]]
+    ds = m.TrajectoryDataset(env_id, c["robot_id"], n_support_points=c["H"], tensor_args={"device": device, "dtype": torch.float32})
+    d = copy.copy(ds)
+    d.env = gr.cover_env(dim)
+    mv = moving_set(dim, c["H"], track)
+    kw = dict(obstacle_cutoff_margin=ds.task.obstacle_cutoff_margin, tensor_args=ds.tensor_args, use_extra_objects=c["robot_id"] != "RobotPanda")
+    if c["grid"]:
+        kw["sdf_grid"] = dict(cell_size=GRID_CELL[dim], mode="linear")
+    if track is None:
+        d.task = PlanningTask(d.env, d.robot, **kw)
+        from mpd_public_amd import _lib
+        from mpd_public_amd.planning import CollisionField
+        d.task.df_collision_moving_objects = CollisionField(_lib.FIELD_OBJECTS, objects=mv, name="moving_objects")
+    else:
+        d.task = PlanningTask(d.env, d.robot, moving_objects=mv, **kw)
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def trajs(case):
+    """normalised fp32 [B, H, D]"""
+    c = CASES[case]
+    x = gr.cover_trajs(c["robot_id"], c["H"])
+    sel = SELECT.get(case, tuple(range(B)))
+    return x[list(sel)].contiguous()
+
+
+def cpu_grid_field(ds):
+    """grid_ref.GridField of the task's fixed-objects grid with node values from the fp64 primitive SDF at the bake's node positions, rounded to fp32:
+    the device bake to 2e-6 (tests/test_gpu_grid_sdf.py), for the reference-only conditions; the GPU tests download the device's values instead"""
+    from oracle import costs as oc
+    g = ds.task.df_collision_objects.grid
+    dim, o = ds.env.dim, ds.env.obj_fixed
+    fld = oc.ObjectField(torch.tensor(o.sphere_centers[:, :dim], dtype=torch.float64), torch.tensor(o.sphere_radii, dtype=torch.float64),
+                         torch.tensor(o.box_centers[:, :dim], dtype=torch.float64), torch.tensor(o.box_half[:, :dim], dtype=torch.float64))
+    shape = tuple(reversed(g.shape))
+    pos = GridField(torch.zeros(shape), g.origin, g.cell).node_positions()
+    return GridField(fld.sdf(pos.reshape(-1, dim)).reshape(shape).float(), g.origin, g.cell, "linear")
+
+
+def oracle(ds, weights=WEIGHTS, n_interp=128, dtype=torch.float64, grid_field=None, nearest=False, clip_grad=True):
+    """(guide, composite, index of the grid term or None) of the unchanged oracle for a dataset of `dataset`: every field with a track becomes a
+    MovingField around the oracle's own ObjectField, a grid field `grid_field`.  n_interp None: interpolation off."""
+    from mpd_public_amd import _lib
+    from mpd_public_amd.planning import field_track
+    og, comp = oracle_guide(ds, *weights, clip_grad=clip_grad, interpolate=n_interp is not None, n_interp=n_interp or 128, dtype=dtype)
+    k_grid = None
+    for k, f in enumerate(ds.task.get_collision_fields()):
+        if f.kind == _lib.FIELD_GRID:
+            comp.cost_l[k].field, k_grid = grid_field, k
+        elif field_track(f) is not None:
+            comp.cost_l[k].field = MovingField(comp.cost_l[k].field, field_track(f), ds.env.dim, nearest=nearest)
+    return og, comp, k_grid
+
+
+def product(ds, weights=WEIGHTS, n_interp=128):
+    """the product guide (not yet on a device) with the case's interpolation"""
+    import mpd_public_amd as m
+    H = ds.n_support_points
+    costs = [m.CostCollision(ds.robot, H, field=f, sigma_coll=1.0) for f in ds.task.get_collision_fields()]
+    w = [weights[0]] * len(costs)
+    costs.append(m.CostGPTrajectory(ds.robot, H, 5.0 / H, sigma_gp=1.0))
+    w.append(weights[1])
+    comp = m.CostComposite(ds.robot, H, costs, weights_cost_l=w)
+    return m.GuideManagerTrajectoriesWithVelocity(ds, comp, clip_grad=True, interpolate_trajectories_for_collision=n_interp is not None,
+                                                  num_interpolated_points_for_collision=n_interp or 128)
+
+
+def interpolated(og, x, n_interp):
+    from oracle.guide import interpolate_points_v1
+    xu = og.normalizer.unnormalize(x.double())
+    return interpolate_points_v1(xu, n_interp) if n_interp is not None else xu
+
+
+def _band(term, xi, cutoff, eps=DELTA):
+    """[B, N] bool: a hinge of the term within eps of zero at margin = radius + cutoff"""
+    keep = term.cutoff
+    term.cutoff = cutoff + eps
+    hi = term.factors(xi) > 0
+    term.cutoff = cutoff - eps
+    lo = term.factors(xi) > 0
+    term.cutoff = keep
+    return (hi & ~lo).any(-1)
+
+
+def decision_distance(comp, xi, k_grid=None):
+    """guide_ref.decision_distance with every MovingField term judged as its inner field on the SHIFTED points; the grid term is left out (it has
+    discontinuities of its own: grid_ambiguous)"""
+    from oracle import costs as oc
+    c2 = copy.copy(comp)
+    c2.cost_l = []
+    for k, term in enumerate(comp.cost_l):
+        if k == k_grid:
+            continue
+        if isinstance(term, oc.CostCollision) and isinstance(term.field, MovingField):
+            t2 = copy.copy(term)
+            t2.robot, t2.field = _ShiftedRobot(term.robot, term.field), term.field.inner
+            term = t2
+        c2.cost_l.append(term)
+    return gr.decision_distance(c2, xi)
+
+
+def moving_hinges(comp, xi):
+    """number of interpolated points at which a hinge of a moving field is active (the trajectories must reach the new code)"""
+    from oracle import costs as oc
+    n = 0
+    for term in comp.cost_l:
+        if isinstance(term, oc.CostCollision) and isinstance(term.field, MovingField):
+            n += int((term.factors(xi) > 0).any(-1).sum())
+    return n
+
+
+def ambiguous(comp, xi, H, k_grid=None, cutoff=0.05):
+    """[B, H] numpy bool: the ambiguous support waypoints of a guide comparison, from fp64 alone"""
+    amb = gr.ambiguous_supports(decision_distance(comp, xi, k_grid), H)
+    if k_grid is not None:
+        term = comp.cost_l[k_grid]
+        pts = term.robot.link_points(xi[..., : term.robot.q_dim])
+        pt = (term.field.discontinuity_distance(pts) < EPS_CELL).any(-1) | _band(term, xi, cutoff)
+        amb = amb | gr.ambiguous_supports(torch.where(pt, 0.0, 1.0), H)
+    return amb.numpy()
+
+
+def metrics_reference(comp, xi, k_grid=None):
+    """(hit [B, N] bool, band [B, N] bool) of the metrics flags on the checked points xi: a point collides iff a hinge with margin = link radius (no
+    cutoff margin) is active; band: a hinge within 1e-5 of zero (or, with a grid, a link point within EPS_CELL of a cell face)"""
+    from oracle import costs as oc
+    hit = torch.zeros(xi.shape[:2], dtype=torch.bool)
+    band = torch.zeros(xi.shape[:2], dtype=torch.bool)
+    for k, term in enumerate(comp.cost_l):
+        if not isinstance(term, oc.CostCollision):
+            continue
+        keep, term.cutoff = term.cutoff, 0.0
+        hit |= (term.factors(xi) > 0).any(-1)
+        term.cutoff = keep
+        band |= _band(term, xi, 0.0)
+        if k == k_grid:
+            pts = term.robot.link_points(xi[..., : term.robot.q_dim])
+            band |= (term.field.discontinuity_distance(pts) < EPS_CELL).any(-1)
+    return hit.numpy(), band.numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """everything the reference says about a GPU case, computed once (read-only): ds (CPU), x, og, comp, k_grid, xi, amb [B, H], ref (fp64 increment),
+    hinges (active moving-field hinges)"""
+    c = CASES[name]
+    ds = dataset(name)
+    x = trajs(name)
+    og, comp, k_grid = oracle(ds, n_interp=c["n_interp"], grid_field=cpu_grid_field(ds) if c["grid"] else None)
+    xi = interpolated(og, x, c["n_interp"])
+    amb = ambiguous(comp, xi, c["H"], k_grid, ds.task.obstacle_cutoff_margin)
+    amb.setflags(write=False)
+    return dict(ds=ds, x=x, og=og, comp=comp, k_grid=k_grid, xi=xi, amb=amb, hinges=moving_hinges(comp, xi))
+
+
+# ------------------------------------------------------------------------------------------------------------ the hand-built crossing
+CROSS_H = 64
+
+
+def crossing_dataset(kind, device="cpu"):
+    """2-D point mass, one sphere of radius 0.2 and nothing else but the workspace: 'static' at (0, -0.8); 'crossing' the same sphere on a linear track of
+    (0, +1.6) - it meets a robot that runs along y = 0 at mid-time; 'parked' static at (0, 0); 'leaving' at (0, 0) on a track that has left
+    (to (0, 1.2) by a third of the plan) before the robot arrives"""
+    import mpd_public_amd as m
+    from mpd_public_amd.planning import Env, ObjectSet, PlanningTask
+    ds = m.TrajectoryDataset("EnvSimple2D", "RobotPointMass", n_support_points=CROSS_H, tensor_args={"device": device, "dtype": torch.float32})
+    d = copy.copy(ds)
+    z = ObjectSet.empty()
+    cy = -0.8 if kind in ("static", "crossing") else 0.0
+    sph = ObjectSet(np.array([[0.0, cy, 0.0]], np.float32), np.array([0.2], np.float32), z.box_centers, z.box_half)
+    if kind == "crossing":
+        sph = sph.with_linear_motion((0.0, 0.0), (0.0, 1.6), CROSS_H)
+    elif kind == "leaving":
+        s = np.linspace(0.0, 1.0, CROSS_H)
+        sph.track = np.stack([np.zeros(CROSS_H), 1.2 * np.minimum(3.0 * s, 1.0)], 1).astype(np.float32)
+    corner = ObjectSet(np.array([[0.9, 0.9, 0.0]], np.float32), np.array([0.03], np.float32), z.box_centers.copy(), z.box_half.copy())   # (the oracle's field takes no empty set)
+    d.env = Env("Crossing2D", 2, corner, ObjectSet.empty())
+    if sph.track is None:
+        d.env.obj_extra = sph
+        d.task = PlanningTask(d.env, d.robot, obstacle_cutoff_margin=ds.task.obstacle_cutoff_margin, tensor_args=ds.tensor_args)
+    else:
+        d.task = PlanningTask(d.env, d.robot, obstacle_cutoff_margin=ds.task.obstacle_cutoff_margin, tensor_args=ds.tensor_args, use_extra_objects=False,
+                              moving_objects=sph)
+    return d
+
+
+def crossing_traj(ds):
+    """normalised fp32 [1, H, 4]: the straight line from (-0.8, 0) to (0.8, 0) at constant speed (duration 5: the oracle's dt = 5 / H)"""
+    H = CROSS_H
+    q = torch.stack([torch.linspace(-0.8, 0.8, H, dtype=torch.float64), torch.zeros(H, dtype=torch.float64)], 1)
+    v = torch.tensor([1.6 / 5.0, 0.0], dtype=torch.float64).expand(H, 2)
+    xu = torch.cat([q, v], 1).unsqueeze(0)
+    lo, hi = ds.normalizer.mins.cpu().double(), ds.normalizer.maxs.cpu().double()
+    return (2 * (xu - lo) / (hi - lo) - 1).float().contiguous()

@@ -1,0 +1,331 @@
+"""GPU tests of moving obstacles (time-indexed translation tracks; include/mpdx.h, csrc/motion.hpp): the MOVING instantiations of the guide and metrics
+kernels against the blocks without tracks (a zero track changes no bit), against the fp64 oracle with tests/moving_ref.MovingField in place of the
+moving field, a hand-built crossing, the fused plan against the step-by-step loop, the refusals, and inference.experiment(moving_sphere=...).
+
+The cases, their trajectories and their reference live in tests/moving_ref.py; the conditions a comparison presupposes (the share of ambiguous
+support waypoints under its cap, active hinges of the moving field) are asserted from the fp64 reference before the kernel's output is looked at, and
+by tests/test_moving_cpu.py without a GPU.  The yardstick is guide_ref.judge's, unchanged: the only new arithmetic is one interpolation and one
+subtraction of workspace-sized fp32 numbers (about 1e-7 relative), the rounding the link points already carry."""
+import ctypes as C
+import os
+import subprocess
+import sys
+from math import ceil
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+import guide_ref as gr
+import moving_ref as mr
+from grid_ref import GridField
+from helpers import synth_sd, t, DIM_MULTS
+
+pytestmark = pytest.mark.gpu
+
+ROOT = Path(__file__).resolve().parent.parent
+
+
+def _track_lens(gp):
+    """track_len of the block's fields (0 for a field that is no OBJECTS field: a grid field keeps its plane offset in that word)"""
+    from mpd_public_amd import _lib
+    return [int(gp.fields[i].track_len) if i < gp.n_fields and gp.fields[i].kind == _lib.FIELD_OBJECTS else 0 for i in range(_lib.MAX_FIELDS)]
+
+
+# ------------------------------------------------------------------------------------------------------------------------ 1. zero track
+@pytest.mark.parametrize("name", ["pm2-H64", "pm3-H24", "panda-H64"])
+def test_zero_track_changes_no_bit(name):
+    """p - 0 = p bit for bit: with a track of zeros the MOVING instantiations give the increment, the in-place update and the metrics of the same
+    block without tracks"""
+    from mpd_public_amd import _lib
+    lib, st = _lib.load(), _lib.current_stream()
+    cs = mr.CASES[name]
+    Hh = cs["H"]
+    static, zero = mr.dataset(name, "cuda", track=None), mr.dataset(name, "cuda", track="zero")
+    x = mr.trajs(name).cuda()
+    Bn, _, D = x.shape
+    ga, gb = mr.product(static, n_interp=cs["n_interp"]).cuda(), mr.product(zero, n_interp=cs["n_interp"]).cuda()
+    inc_a, inc_b = ga(x), gb(x)
+    pa, pb = ga.device_params("cuda"), gb.device_params("cuda")
+    assert not any(_track_lens(pa)) and Hh in _track_lens(pb) and pa.n_fields == pb.n_fields           # (the launcher picks MOVING for pb)
+    assert float(inc_a.abs().max()) > 0 and torch.equal(inc_a, inc_b)
+    # in place, with hard conditions and the next range test's max|x|
+    outs = []
+    for gp in (pa, pb):
+        xx = x.clone()
+        hs, hg = xx[:, 0].contiguous().clone(), xx[:, -1].contiguous().clone()
+        flag, nxt = torch.zeros(1, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
+        _lib.check(lib.mpdx_absmax(xx.data_ptr(), flag.data_ptr(), Bn, Bn, Hh, D, st), "mpdx_absmax")
+        _lib.check(lib.mpdx_guide_step(C.byref(gp), xx.data_ptr(), None, hs.data_ptr(), hg.data_ptr(), flag.data_ptr(), nxt.data_ptr(), Bn, Bn, Hh, D, st), "mpdx_guide_step")
+        outs.append((xx, nxt))
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]) and not torch.equal(outs[0][0], x)
+    # metrics
+    xu = static.unnormalize_trajectories(x)
+    for n_check in (64, 256):
+        ma, ka = static.task.trajectory_metrics(xu, n_check=n_check, return_mask=True)
+        mb, kb = zero.task.trajectory_metrics(xu, n_check=n_check, return_mask=True)
+        assert torch.equal(ma, mb) and torch.equal(ka, kb) and bool(ka.any())
+    assert zero.task.has_tracks and not static.task.has_tracks
+
+
+# ------------------------------------------------------------------------------------------------------------------------ 2. guide increment
+def _device_grid_field(ds):
+    """grid_ref.GridField over the node values of the DEVICE bake (tests/test_gpu_grid_sdf.py::_reference_field)"""
+    g = ds.task.df_collision_objects.grid
+    sdf, grad = g.node_values("cuda")
+    return GridField(sdf.cpu(), g.origin, g.cell, g.mode, None if grad is None else grad.cpu())
+
+
+def _reference(name, ds_gpu):
+    """(x, amb, ref): the case's reference - for a grid case with the device's node values - and its conditions, asserted before anything is compared"""
+    cs, c = mr.CASES[name], mr.case(name)
+    og, comp, k_grid, amb = c["og"], c["comp"], c["k_grid"], c["amb"]
+    if cs["grid"]:
+        og, comp, k_grid = mr.oracle(c["ds"], n_interp=cs["n_interp"], grid_field=_device_grid_field(ds_gpu))
+        amb = mr.ambiguous(comp, mr.interpolated(og, c["x"], cs["n_interp"]), cs["H"], k_grid, c["ds"].task.obstacle_cutoff_margin)
+    share = float(amb.mean())
+    print(f"{name}: ambiguous support waypoints {100 * share:.2f} % (cap {100 * mr.cap_of(name):.0f} %), active moving-field hinges {c['hinges']}")
+    assert share <= mr.cap_of(name) and c["hinges"] > 0
+    ref = og(c["x"].double()).numpy()
+    assert np.abs(ref).max() > 0
+    return c["x"], amb, ref
+
+
+def _increment(name):
+    ds = mr.dataset(name, "cuda")
+    pg = mr.product(ds, n_interp=mr.CASES[name]["n_interp"]).cuda()
+    got = pg(mr.trajs(name).cuda()).cpu().numpy()
+    gp = pg.device_params("cuda")
+    return ds, gp, got
+
+
+@pytest.mark.parametrize("name", list(mr.CASES))
+def test_moving_guide_increment_vs_oracle(name):
+    from mpd_public_amd import _lib
+    cs = mr.CASES[name]
+    ds, gp, got = _increment(name)
+    x, amb, ref = _reference(name, ds)
+    assert cs["H"] in _track_lens(gp) and (_lib.FIELD_GRID in [gp.fields[i].kind for i in range(gp.n_fields)]) == cs["grid"]
+    if cs["robot_id"] == "RobotPanda":
+        assert int(_lib.load().mpdx_guide_variant(C.byref(gp), x.shape[0], cs["H"], x.shape[2])) == 0       # the table variant at this batch
+    gr.judge(got, ref, amb, mr.WEIGHTS[0], what=name)
+
+
+_CHILD_CODE = """
+import sys
+sys.path[:0] = [{root!r}, {tests!r}]
+import ctypes as C
+import numpy as np
+import moving_ref as mr
+import test_gpu_moving as M
+from mpd_public_amd import _lib
+ds, gp, got = M._increment("panda-H64")
+x = mr.trajs("panda-H64")
+np.savez({out!r}, got=got, variant=np.array(int(_lib.load().mpdx_guide_variant(C.byref(gp), x.shape[0], 64, x.shape[2]))))
+"""
+
+
+def test_moving_panda_dense_variant_vs_oracle(tmp_path):
+    """guide_step_panda_kernel<DENSE, ..., MOVING>, forced on at this small batch in a child process (MPDX_GUIDE_DENSE is read once per process); the
+    variant the child took is asked of the launcher's own rule"""
+    out = tmp_path / "dense.npz"
+    code = _CHILD_CODE.format(root=str(ROOT), tests=str(ROOT / "tests"), out=str(out))
+    r = subprocess.run([sys.executable, "-c", code], cwd=str(ROOT), env={**os.environ, "MPDX_GUIDE_DENSE": "1"}, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    with np.load(out) as z:
+        got, variant = z["got"], int(z["variant"])
+    assert variant == 1
+    x, amb, ref = _reference("panda-H64", None)
+    gr.judge(got, ref, amb, mr.WEIGHTS[0], what="panda-H64 dense")
+
+
+# ------------------------------------------------------------------------------------------------------------------------ 3. metrics flags
+@pytest.mark.parametrize("name", ["pm2-H64", "panda-H64"])
+@pytest.mark.parametrize("n_check", [64, 256])
+def test_moving_metrics_flags_vs_fp64_reference(name, n_check):
+    """trajectory_metrics(..., return_mask=True) on a task with a track: the flags equal an fp64 evaluation of the same hinges (margin = link radius, no
+    cutoff) at the obstacle's position at each point's own time, outside the points whose fp64 slack is within 1e-5 of zero"""
+    from oracle.guide import interpolate_points_v1
+    c = mr.case(name)
+    ds = mr.dataset(name, "cuda")
+    xu = c["og"].normalizer.unnormalize(c["x"].double()).float()          # the un-normalised fp32 trajectories both sides see
+    hit, band = mr.metrics_reference(c["comp"], interpolate_points_v1(xu.double(), n_check))
+    assert band.mean() <= 0.01 and (hit & ~band).any() and (~hit & ~band).any()
+    out, mask = ds.task.trajectory_metrics(xu.cuda(), n_check=n_check, return_mask=True)
+    out, mask = out.cpu().numpy(), mask.cpu().numpy()
+    print(f"{name} n_check {n_check}: {int(hit.sum())} of {hit.size} collide; flags differing outside the band {int((mask != hit)[~band].sum())}, inside "
+          f"{int((mask != hit)[band].sum())} of {int(band.sum())}")
+    assert (mask == hit)[~band].all()
+    np.testing.assert_array_equal(out[:, 0], mask.sum(1))
+    np.testing.assert_array_equal(out[:, 3], n_check)
+    # the static set in the same slot gives other flags: the track is in use
+    _, mask_static = mr.dataset(name, "cuda", track=None).task.trajectory_metrics(xu.cuda(), n_check=n_check, return_mask=True)
+    assert (mask_static.cpu().numpy() != mask)[~band].any()
+    # everything built on the same block is time-aware
+    task = ds.task
+    tc, tf = task.get_trajs_collision_and_free(xu.cuda())
+    n_coll = int((out[:, 0] > 0).sum())
+    assert (0 if tc is None else tc.shape[0]) == n_coll and (0 if tf is None else tf.shape[0]) == xu.shape[0] - n_coll
+    m4 = task.trajectory_metrics(xu.cuda()).cpu().numpy()
+    assert task.compute_fraction_free_trajs(xu.cuda()) == pytest.approx(float((m4[:, 0] == 0).mean()))
+    assert task.compute_collision_intensity_trajs(xu.cuda()) == pytest.approx(float((m4[:, 0] / m4[:, 3]).mean()))
+    assert task.compute_success_free_trajs(xu.cuda()) == int((m4[:, 0] == 0).any())
+
+
+# ------------------------------------------------------------------------------------------------------------------------ 4. the crossing
+def test_hand_built_crossing():
+    """Why the feature exists.  The robot runs the straight line (-0.8, 0) -> (0.8, 0) at constant speed; a sphere of radius 0.2 starts at (0, -0.8).
+    Static it leaves the line free; on a linear track of (0, +1.6) it meets the robot at mid-time: exactly the waypoints the fp64 reference names are
+    flagged, and the guide pushes those supports away from the sphere's position at their own time.  Parked on the line at (0, 0) it blocks it; on a
+    track that leaves before the robot arrives nothing is flagged."""
+    from oracle.guide import interpolate_points_v1
+    n_check, got_flags, ref_flags = 256, {}, {}
+    for kind in ("static", "crossing", "parked", "leaving"):
+        cpu, ds = mr.crossing_dataset(kind), mr.crossing_dataset(kind, "cuda")
+        x = mr.crossing_traj(cpu)
+        og, comp, _ = mr.oracle(cpu)
+        xu = og.normalizer.unnormalize(x.double()).float()
+        hit, band = mr.metrics_reference(comp, interpolate_points_v1(xu.double(), n_check))
+        assert not band.any(), kind                                        # none of the expectations lies in the 1e-5 band
+        _, mask = ds.task.trajectory_metrics(xu.cuda(), n_check=n_check, return_mask=True)
+        got_flags[kind], ref_flags[kind] = mask.cpu().numpy()[0], hit[0]
+        np.testing.assert_array_equal(got_flags[kind], ref_flags[kind], err_msg=kind)
+    assert not got_flags["static"].any() and not got_flags["leaving"].any()
+    assert got_flags["parked"].any() and got_flags["crossing"].any()
+    idx = np.nonzero(got_flags["crossing"])[0]
+    assert idx.min() > 64 and idx.max() < 192                              # met around mid-time, not at the ends
+    # the guide on the crossing: against fp64, and away from where the sphere IS at each support's time
+    cpu, ds = mr.crossing_dataset("crossing"), mr.crossing_dataset("crossing", "cuda")
+    x = mr.crossing_traj(cpu)
+    og, comp, _ = mr.oracle(cpu)
+    amb = mr.ambiguous(comp, mr.interpolated(og, x, 128), mr.CROSS_H)
+    assert amb.mean() <= gr.CAP["RobotPointMass"]
+    ref = og(x.double()).numpy()
+    got = mr.product(ds).cuda()(x.cuda()).cpu().numpy()
+    gr.judge(got, ref, amb, mr.WEIGHTS[0], what="crossing")
+    xu = og.normalizer.unnormalize(x.double()).numpy()[0]
+    mv = cpu.task.df_collision_moving_objects.objects
+    centre = mv.sphere_centers[0, :2].astype(np.float64) + mv.track.astype(np.float64)                     # [H, 2]: the sphere at each support's time
+    pushed = np.nonzero(np.abs(ref[0, :, :2]).max(-1) > 1e-4)[0]                                              # the supports the reference pushes (w = 1e-2, clipped to 1)
+    assert pushed.size >= 3 and (np.abs(pushed - (mr.CROSS_H - 1) / 2) < 12).all()
+    away = ((got[0, pushed, :2]) * (xu[pushed, :2] - centre[pushed])).sum(-1)
+    assert (away > 0).all(), away
+    before = pushed[pushed < (mr.CROSS_H - 1) / 2]     # before mid-time the sphere is still below the line (push up), after it above (push down)
+    assert before.size and (got[0, before, 1] > 0).all() and (got[0, pushed[pushed > (mr.CROSS_H - 1) / 2], 1] < 0).all()
+    # ... while the static sphere, 0.8 below the line, pushes nothing
+    st_cpu, st_gpu = mr.crossing_dataset("static"), mr.crossing_dataset("static", "cuda")
+    got_static = mr.product(st_gpu).cuda()(x.cuda()).cpu().numpy()
+    assert np.abs(got_static[0, :, :2]).max() < 1e-5 < np.abs(got[0, :, :2]).max()
+
+
+# ------------------------------------------------------------------------------------------------------------------------ 5. the plan loop
+def test_moving_guided_plan_fused_equals_stepwise():
+    """mpdx_plan launches the guide through launch_guide and so takes tracks without changes of its own: the fused plan and the step-by-step protocol
+    loop agree bit for bit (tests/test_gpu_grid_sdf.py::test_grid_guided_plan_fused_equals_stepwise), T = 5 + 2 steps on synthetic weights"""
+    import mpd_public_amd as m
+    T, n0, B, opt = 5, 2, 4, 0
+    ds = mr.dataset("pm2-H64", "cuda")
+    D = ds.state_dim
+    net = m.TemporalUnet(n_support_points=64, state_dim=D, unet_input_dim=32, dim_mults=DIM_MULTS[opt])
+    net.load_state_dict(synth_sd(D, opt), strict=True)
+    dm = m.GaussianDiffusionModel(model=net, variance_schedule="cosine", n_diffusion_steps=T, predict_epsilon=True).cuda().eval()
+    noise = t("moving_plan_noise", (T + n0 + 1, B, 64, D))
+    start = ds.normalizer.normalize(torch.cat([torch.tensor([-0.45, -0.1]).cuda(), torch.zeros(2, device="cuda")]))
+    goal = ds.normalizer.normalize(torch.cat([torch.tensor([0.45, 0.2]).cuda(), torch.zeros(2, device="cuda")]))
+    hc = {0: start, 63: goal}
+    kw = dict(n_samples=B, horizon=64, return_chain=True, sample_fn=m.ddpm_sample_fn, n_guide_steps=3, t_start_guide=ceil(0.5 * T),
+              n_diffusion_steps_without_noise=n0, noise_std_extra_schedule_fn=lambda tt: 0.5, noise=noise.cuda())
+    pg = mr.product(ds, weights=(1e-1, 1e-7)).cuda()
+    a = dm.run_inference(None, hc, fused=True, guide=pg, **kw)
+    b = dm.run_inference(None, hc, fused=False, guide=pg, **kw)
+    assert bool(torch.isfinite(a).all()) and torch.equal(a, b)
+    assert 64 in _track_lens(pg.device_params("cuda"))
+    # the same plan among the same primitives standing still ends elsewhere: the track is in use inside the plan loop
+    ps = mr.product(mr.dataset("pm2-H64", "cuda", track=None), weights=(1e-1, 1e-7)).cuda()
+    s = dm.run_inference(None, hc, fused=True, guide=ps, **kw)
+    assert torch.equal(s[0], a[0]) and not torch.equal(s[-1], a[-1])
+
+
+# ------------------------------------------------------------------------------------------------------------------------ 6. refusals
+def test_refused_track_blocks_launch_nothing():
+    """tracks with the planners, with scenes, with a chain robot, and a track_len other than H: refused on the host, the output buffers keep their
+    sentinel; the restored block runs"""
+    from mpd_public_amd import _lib
+    lib, st = _lib.load(), _lib.current_stream()
+    ds = mr.dataset("pm2-H64", "cuda")
+    pg = mr.product(ds).cuda()
+    gp = pg.device_params("cuda")
+    B, H, D = 4, 64, 4
+    x = mr.trajs("pm2-H64").cuda()
+    sentinel = 123.0
+    out = torch.full_like(x, sentinel)
+    flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+    o = _lib.GpmpOpts(1.0, 10.0, 0.1, 1e-6, 1e6, 1.0, 1)
+    state = torch.full((B, 4), sentinel, device="cuda")
+    assert lib.mpdx_gpmp_step(C.byref(gp), C.byref(o), x.data_ptr(), out.data_ptr(), state.data_ptr(), B, H, D, 1, st) == -1
+    assert "track_len" in lib.mpdx_last_error().decode()
+    r = _lib.RrtOpts()
+    r.step, r.max_nodes, r.max_iters, r.max_connect_steps, r.n_edge_checks = 0.1, 64, 16, 4, 4
+    ibuf = torch.full((B, 2 * 64), 77, dtype=torch.int32, device="cuda")
+    nodes = torch.full((B, 2, 64, 2), sentinel, device="cuda")
+    assert lib.mpdx_rrt_connect(C.byref(gp), C.byref(r), x.data_ptr(), x.data_ptr(), nodes.data_ptr(), ibuf.data_ptr(), ibuf.data_ptr(), ibuf.data_ptr(),
+                                ibuf.data_ptr(), B, st) == -1
+    assert "track_len" in lib.mpdx_last_error().decode()
+    assert lib.mpdx_rrt_paths(C.byref(gp), x.data_ptr(), x.data_ptr(), nodes.data_ptr(), ibuf.data_ptr(), ibuf.data_ptr(), out.data_ptr(), None, B, 64, H,
+                              0.1, 4, 1, st) == -1
+    assert "track_len" in lib.mpdx_last_error().decode()
+    m4 = torch.full((B, 4), sentinel, device="cuda")
+
+    def refused(member):
+        assert lib.mpdx_guide_step(C.byref(gp), x.data_ptr(), out.data_ptr(), None, None, flag.data_ptr(), None, B, B, H, D, st) == -1
+        assert member in lib.mpdx_last_error().decode(), lib.mpdx_last_error()
+        assert lib.mpdx_traj_metrics_mask(C.byref(gp), x.data_ptr(), m4.data_ptr(), None, 64, B, H, D, st) == -1
+        assert member in lib.mpdx_last_error().decode(), lib.mpdx_last_error()
+    k = _track_lens(gp).index(H)
+    gp.n_scenes, gp.scene_stride, gp.scene_n_per_ctx = 2, 28, 2
+    refused("track_len")
+    gp.n_scenes, gp.scene_stride, gp.scene_n_per_ctx = 0, 0, 0
+    gp.robot = _lib.ROBOT_CHAIN
+    refused("track_len")
+    gp.robot = _lib.ROBOT_POINTMASS
+    gp.fields[k].track_len = H - 1
+    refused("track_len")
+    gp.fields[k].track_len = H
+    # ... and the same block at another horizon (32 supports of the same buffer)
+    assert lib.mpdx_guide_step(C.byref(gp), x.data_ptr(), out.data_ptr(), None, None, flag.data_ptr(), None, B, B, 32, D, st) == -1
+    assert "track_len" in lib.mpdx_last_error().decode()
+    torch.cuda.synchronize()
+    assert bool((out == sentinel).all()) and bool((state == sentinel).all()) and bool((nodes == sentinel).all()) and bool((ibuf == 77).all())
+    assert bool((m4 == sentinel).all())
+    assert lib.mpdx_guide_step(C.byref(gp), x.data_ptr(), out.data_ptr(), None, None, flag.data_ptr(), None, B, B, H, D, st) == 0
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(out).all()) and not bool((out == sentinel).any())
+    # the Python surface refuses before it reaches the device
+    from mpd_public_amd import generate_trajectories as gt
+    with pytest.raises(ValueError, match="RRTConnectBatch"):
+        gt.RRTConnectBatch(ds.task, x[0, 0, :2], x[0, -1, :2], 3)
+    with pytest.raises(ValueError, match="n_support_points"):
+        ds.task.trajectory_metrics(x[:, :32].contiguous())
+
+
+# ------------------------------------------------------------------------------------------------------------------------ 7. the entry
+def test_experiment_entry_with_a_moving_sphere(tmp_path):
+    """inference.experiment(moving_sphere=(c0, c1, r)) on a synthetic point-mass model at reduced n_diffusion_steps: it runs, reports the usual figures
+    (time-aware), and its guided trajectories differ from the run without the option"""
+    from mpd_public_amd.inference import experiment
+    n = 6
+    kw = dict(model_id="EnvSimple2D-RobotPointMass", planner_alg="mpd", n_samples=n, debug=False, seed=3, weight_grad_cost_collision=1e-1,
+              model_args=dict(n_diffusion_steps=8, variance_schedule="cosine", unet_dim_mults_option=0))
+    r = experiment(results_dir=str(tmp_path / "moving"), moving_sphere=((-0.6, -0.6), (0.6, 0.6), 0.3), **kw)
+    base = experiment(results_dir=str(tmp_path / "static"), **kw)
+    assert r["trajs_iters"].shape == base["trajs_iters"].shape and torch.isfinite(r["trajs_iters"]).all()
+    assert 0.0 <= r["fraction_free_trajs"] <= 1.0 and 0.0 <= r["collision_intensity_trajs"] <= 1.0
+    nf = 0 if r["trajs_final_free"] is None else r["trajs_final_free"].shape[0]
+    nc = 0 if r["trajs_final_coll"] is None else r["trajs_final_coll"].shape[0]
+    assert nf + nc == n
+    xs = r["trajs_iters"]
+    assert torch.equal(xs[:, :, 0, :], base["trajs_iters"][:, :, 0, :]) and torch.equal(xs[:, :, -1, :], base["trajs_iters"][:, :, -1, :])   # hard conditions
+    assert torch.equal(xs[0], base["trajs_iters"][0])                # same noise: the chains start equal ...
+    assert not torch.equal(xs[-1], base["trajs_iters"][-1])          # ... and the moving sphere is in use: the guided results differ
