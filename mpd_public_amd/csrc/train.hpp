@@ -1428,12 +1428,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                    float max_norm, float* __restrict__ norm, const int* __restrict__ cnt) {
     float coef = 1.0f;
     __shared__ float red[4];
-    if (cnt) {   // graph replay: 1-based step count from device memory; the corrections as mpdx_adam_step computes them on the host (double pow, float result)
+    if (cnt) {   // graph replay: 1-based step count from device memory; the corrections as mpdx_adam_step computes them on the host (in double, rounded once)
         __shared__ float s_bc[2];
         if (threadIdx.x == 0) {
             const double st = (double)cnt[0];
-            s_bc[0] = 1.0f - (float)pow((double)b1, st);
-            s_bc[1] = sqrtf(1.0f - (float)pow((double)b2, st));
+            s_bc[0] = (float)(1.0 - pow((double)b1, st));
+            s_bc[1] = (float)sqrt(1.0 - pow((double)b2, st));
         }
         __syncthreads();
         bc1 = s_bc[0]; bc2_sqrt = s_bc[1];

@@ -1125,9 +1125,11 @@ int mpdx_adam_step(float* params, const float* grads, float* exp_avg, float* exp
             n_part = nb;
         }
     }
-    const float bc1 = step > 0 ? 1.0f - (float)pow((double)beta1, step) : 1.0f, bc2 = step > 0 ? 1.0f - (float)pow((double)beta2, step) : 1.0f;
+    // the bias corrections 1 - beta^t and sqrt(1 - beta2^t) in double, rounded ONCE (torch.optim.Adam computes them in Python doubles): 1.0f - (float)pow(..)
+    // rounds beta^t at 2^-25 absolute first, which is 1.5e-5 of 1 - 0.999^2 - the whole update of step 2 was off by 50 fp32 roundings
+    const float bc1 = step > 0 ? (float)(1.0 - pow((double)beta1, step)) : 1.0f, bc2_sqrt = step > 0 ? (float)sqrt(1.0 - pow((double)beta2, step)) : 1.0f;
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, n, lr,
-                       beta1, beta2, eps, bc1, sqrtf(bc2), clip, n_part, max_norm, scratch, (const int*)cnt);
+                       beta1, beta2, eps, bc1, bc2_sqrt, clip, n_part, max_norm, scratch, (const int*)cnt);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -133,11 +133,14 @@ def q_sample(buf: dict, x_start: torch.Tensor, t: torch.Tensor, noise: torch.Ten
 
 
 def p_losses(sd: dict, x_start: torch.Tensor, t: torch.Tensor, hard_conds: dict, noise: torch.Tensor, T: int,
-             variance_schedule: str = "exponential", predict_epsilon: bool = True, loss_type: str = "l2") -> torch.Tensor:
-    """diffusion_model_base.py:331-352 with the unweighted WeightedL1 / WeightedL2 of helpers.py:71-99 (loss.mean())."""
+             variance_schedule: str = "exponential", predict_epsilon: bool = True, loss_type: str = "l2", weights=None) -> torch.Tensor:
+    """diffusion_model_base.py:331-352 with the WeightedL1 / WeightedL2 of helpers.py:71-99: loss.mean() without a weight table,
+    (loss * weights).mean() with `weights` [H, D] (WeightedLoss.forward, helpers.py:71-87)."""
     buf = _sched.make_buffers(T, variance_schedule)
     x_noisy = apply_hard_conditioning(q_sample(buf, x_start, t, noise), hard_conds)
     x_recon = apply_hard_conditioning(unet_forward(sd, x_noisy, t), hard_conds)
     targ = noise if predict_epsilon else x_start
     err = (x_recon - targ).abs() if loss_type == "l1" else torch.nn.functional.mse_loss(x_recon, targ, reduction="none")
-    return err.mean()
+    if weights is None:
+        return err.mean()
+    return (err * weights).mean()

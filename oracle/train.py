@@ -16,12 +16,14 @@ from . import diffusion
 
 
 def loss_and_grads(sd: dict, x_start, t, hard_conds, noise, T, variance_schedule="exponential", predict_epsilon=True, loss_type="l2",
-                   dtype=torch.float32):
-    """-> (loss, {name: d loss / d sd[name]}) ; sd values are leaf copies in `dtype` (float64 gives a tight reference)."""
+                   dtype=torch.float32, weights=None):
+    """-> (loss, {name: d loss / d sd[name]}) ; sd values are leaf copies in `dtype` (float64 gives a tight reference).
+    `weights`: the [H, D] table of the weighted loss (helpers.py:71-87), or None for the unweighted mean."""
     leaf = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in sd.items()}
     cast = lambda v: v.to(dtype) if torch.is_floating_point(v) else v
     hc = {k: cast(v) for k, v in (hard_conds or {}).items()}
-    loss = diffusion.p_losses(leaf, cast(x_start), t, hc, cast(noise), T, variance_schedule, predict_epsilon, loss_type)
+    loss = diffusion.p_losses(leaf, cast(x_start), t, hc, cast(noise), T, variance_schedule, predict_epsilon, loss_type,
+                              None if weights is None else cast(weights))
     names = list(leaf)
     grads = torch.autograd.grad(loss, [leaf[k] for k in names])
     return loss.detach(), dict(zip(names, grads))
