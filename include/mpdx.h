@@ -546,6 +546,52 @@ int mpdx_sdf_grid_from_mesh(const float* vertices, int n_vertices, const int32_t
                             float* wind_out /* or NULL: w per node, for tests */, const int n[3], const float origin[3], float cell, float inflate,
                             int sign_mode, void* stream);
 
+/* ---- depth-camera fusion: projective TSDF integration (KinectFusion-style truncated signed distance) into per-node planes on the device
+ * (csrc/tsdf.hpp).  Replaces nothing in the reference; it fuses depth frames into the occupancy bytes mpdx_sdf_grid_from_occupancy turns into the
+ * sdf and gradient planes.  Every step is exactly reproducible in numpy (tests/tsdf_ref.py): tsdf, weight and occ are held to it bit for bit.
+ * Every fp32 operation below is one rounded operation (the library builds with -ffp-contract=on; the kernel spells them out).
+ *   camera  pinhole, no distortion (undistort first); OpenCV frame: x right, y down, z forward; depth [height][width] fp32 on the device, metres
+ *           along z; pixel (iu, iv) has its centre at image coordinate (iu, iv).  cam_from_world and world_from_cam are row-major 3x4 [R | t], formed
+ *           in float64 by the caller and rounded to fp32 (one need not be the exact inverse of the other in fp32).
+ *   p       node (ix, iy, iz) sits at origin_j + (float)i_j * cell (one rounded product, one rounded sum, as for mpdx_sdf_grid_bake).
+ * Per node, for each camera in the order given (A = cam_from_world, B = world_from_cam):
+ *   1. x_j = ((A[j][0] p0 + A[j][1] p1) + A[j][2] p2) + A[j][3]; the camera is skipped unless x2 > 0 (false for NaN).
+ *   2. u = fx * (x0 / x2) + cx, v = fy * (x1 / x2) + cy; ru = rintf(u), rv = rintf(v) (half to even); the pixel must satisfy 0 <= ru <= width - 1
+ *      and 0 <= rv <= height - 1, tested on the floats before any conversion (a non-finite u or v is no measurement); iu = (int)ru, iv = (int)rv.
+ *   3. d = depth[iv * width + iu] is a measurement only if min_depth <= d <= max_depth (NaN, +-inf, 0 and negative values are rejected).
+ *   4. robot mask (n_spheres > 0): P_cam = (((float)iu - cx) / fx * d, ((float)iv - cy) / fy * d, d), P_j = ((B[j][0] P0 + B[j][1] P1) + B[j][2] P2)
+ *      + B[j][3]; the measurement is skipped (it neither carves nor occupies) if (dx * dx + dy * dy) + dz * dz < r * r for any sphere (c, r),
+ *      d = P - c.  r is the padded radius.
+ *   5. s = d - x2; skipped if s < -trunc (the node is occluded); o = fminf(s, trunc) / trunc.
+ *   6. T = (T * W + o) / (W + 1), then W = fminf(W + 1, max_weight).
+ * After all cameras, occ = (W > 0 && T < 0) for EVERY node, nodes no camera saw in this call included.  So an unobserved node (W == 0) is free: a
+ * solid's unseen interior is free behind an occupied shell about trunc thick, and the inflate of the transform still applies.  Start a map with
+ * tsdf = weight = 0 (a NaN tsdf at W = 0 would stay NaN: 0 * NaN).
+ *
+ * One thread per node (256 per workgroup, x fastest: the plane reads and writes are coalesced); the camera records and the spheres are kernel
+ * arguments (uniform: scalar loads, no copy).  No atomics, no workspace, no scratch; the library allocates nothing and never synchronises.
+ * tsdf, weight [nz][ny][nx] fp32 and occ [nz][ny][nx] bytes are device pointers, read and written in place; spheres is a HOST array [n][4]
+ * (centre, radius), copied into the launch.  3-D grids only.
+ *
+ * Refused on the host, before any launch (MPDX_E_INVALID, the message names the argument): n outside 2 ... 4096 along every axis or more than 2^29
+ * nodes (n[2] = 1: "3-D only"); n_cams outside 1 ... 8 or cams null; a null or not 4-byte aligned depth, width or height outside 1 ... 8192; fx or
+ * fy not positive and finite; a non-finite cx, cy or matrix entry; min_depth < 0, max_depth <= min_depth or a non-finite bound; n_spheres outside
+ * 0 ... 64, spheres null with n_spheres > 0, a non-finite sphere value or a negative radius; cell not positive and finite; a non-finite origin; trunc
+ * not positive and finite; max_weight outside 1 ... 2^24; a null or misaligned tsdf, weight (4 bytes) or occ. */
+#define MPDX_TSDF_MAX_CAMS     8
+#define MPDX_TSDF_MAX_SPHERES 64
+typedef struct mpdx_depth_camera {
+    const float* depth;                 /* device pointer: [height][width] fp32, metres */
+    int32_t width, height;
+    float fx, fy, cx, cy;
+    float cam_from_world[12];           /* row-major 3x4 */
+    float world_from_cam[12];           /* row-major 3x4 */
+    float min_depth, max_depth;
+} mpdx_depth_camera;
+int mpdx_tsdf_integrate(const mpdx_depth_camera* cams, int n_cams, const float* spheres /* host [n][4]: centre, radius */, int n_spheres,
+                        float* tsdf, float* weight, uint8_t* occ, const int n[3], const float origin[3], float cell, float trunc, float max_weight,
+                        void* stream);
+
 /* ---- baseline planners of the dataset-generation script: replaces `HybridPlanner(RRTConnect x n via
  * MultiSampleBasedPlanner, GPMP2).optimize()` of scripts/generate_data/generate_trajectories.py:68-120.  The planners are
  * un-vendored in the reference (mp_baselines submodule empty: PARITY UNPINNED); the published algorithms are restated

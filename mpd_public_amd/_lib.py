@@ -94,6 +94,15 @@ class IkOpts(C.Structure):
                 ("lambda_min", C.c_float), ("lambda_max", C.c_float), ("adaptive", C.c_int32), ("max_iters", C.c_int32), ("seed", C.c_uint64)]
 
 
+TSDF_MAX_CAMS, TSDF_MAX_SPHERES = 8, 64     # MPDX_TSDF_MAX_*
+
+
+class DepthCamera(C.Structure):     # mpdx_depth_camera (arithmetic of mpdx_tsdf_integrate in include/mpdx.h)
+    _fields_ = [("depth", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("cam_from_world", C.c_float * 12), ("world_from_cam", C.c_float * 12), ("min_depth", C.c_float),
+                ("max_depth", C.c_float)]
+
+
 # every symbol include/mpdx.h declares: name -> (restype, argtypes)
 _vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
 SIGNATURES = {
@@ -143,6 +152,7 @@ SIGNATURES = {
     "mpdx_sdf_grid_from_occupancy": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int * 3), _f, _f, _vp, _sz, _vp]),
     "mpdx_occupancy_from_points": (_i, [_vp, _i, _vp, C.POINTER(C.c_int * 3), C.POINTER(C.c_float * 3), _f, _vp]),
     "mpdx_sdf_grid_from_mesh": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, C.POINTER(C.c_int * 3), C.POINTER(C.c_float * 3), _f, _f, _i, _vp]),
+    "mpdx_tsdf_integrate": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, C.POINTER(C.c_int * 3), C.POINTER(C.c_float * 3), _f, _f, _f, _vp]),
     "mpdx_unet_profile": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, C.POINTER(C.c_float), C.POINTER(C.c_double),
                                 C.POINTER(C.c_char_p), C.POINTER(C.c_int)]),
     "mpdx_layer_trace": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(C.c_longlong)]),

@@ -1,9 +1,10 @@
 // k_grid.hip - the producers of signed-distance grid planes and their C-ABI entry points: the bake from primitives (sdf_grid_bake_kernel, grid_field.hpp),
 // the Euclidean distance transform and voxelisation (edt.hpp), the mesh distance / winding-number kernel (mesh_sdf.hpp), and the gradient plane by
-// differences the last two share (grid_gradient_kernel, grid_field.hpp).
+// differences the last two share (grid_gradient_kernel, grid_field.hpp), and the depth-camera fusion that feeds the transform (tsdf.hpp).
 #include "host.hpp"
 #include "edt.hpp"
 #include "mesh_sdf.hpp"
+#include "tsdf.hpp"
 #include "scene_table.hpp"   // has_scenes
 #include "motion.hpp"        // field_track_len
 
@@ -216,6 +217,63 @@ int mpdx_sdf_grid_from_mesh(const float* vertices, int n_vertices, const int32_t
         else hipLaunchKernelGGL(mesh_sdf_kernel<false>, dim3(blocks), dim3(256), 0, st, m);
     }
     if (grad_out) launch_grid_gradient(sdf_out, grad_out, n, nodes, cell, st);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int mpdx_tsdf_integrate(const mpdx_depth_camera* cams, int n_cams, const float* spheres, int n_spheres, float* tsdf, float* weight, uint8_t* occ,
+                        const int n[3], const float origin[3], float cell, float trunc, float max_weight, void* stream) {
+    using namespace mpdx;
+    const char* who = "tsdf integrate";
+    long long nodes;
+    if (int rc = check_shape(who, n, 3, &nodes)) return rc;
+    if (!cams) return fail(MPDX_E_INVALID, "%s: cams is null", who);
+    if (n_cams < 1 || n_cams > MPDX_TSDF_MAX_CAMS) return fail(MPDX_E_INVALID, "%s: n_cams %d (1 ... %d)", who, n_cams, MPDX_TSDF_MAX_CAMS);
+    TsdfArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int c = 0; c < n_cams; ++c) {
+        const mpdx_depth_camera& k = cams[c];
+        if (!k.depth) return fail(MPDX_E_INVALID, "%s: cams[%d].depth is null", who, c);
+        if (int rc = check_aligned(who, "depth", k.depth, 4)) return rc;
+        if (k.width < 1 || k.width > 8192 || k.height < 1 || k.height > 8192)
+            return fail(MPDX_E_INVALID, "%s: cams[%d] width %d x height %d (1 ... 8192 each)", who, c, k.width, k.height);
+        if (!(k.fx > 0.f && finite_f(k.fx)) || !(k.fy > 0.f && finite_f(k.fy)))
+            return fail(MPDX_E_INVALID, "%s: cams[%d] fx and fy must be positive and finite", who, c);
+        if (!finite_f(k.cx) || !finite_f(k.cy)) return fail(MPDX_E_INVALID, "%s: cams[%d] cx and cy must be finite", who, c);
+        for (int i = 0; i < 12; ++i)
+            if (!finite_f(k.cam_from_world[i]) || !finite_f(k.world_from_cam[i]))
+                return fail(MPDX_E_INVALID, "%s: cams[%d] cam_from_world and world_from_cam must be finite", who, c);
+        if (!finite_f(k.min_depth) || !finite_f(k.max_depth) || k.min_depth < 0.f || !(k.max_depth > k.min_depth))
+            return fail(MPDX_E_INVALID, "%s: cams[%d] depth bounds min_depth %g, max_depth %g (0 <= min_depth < max_depth, finite)", who, c,
+                        (double)k.min_depth, (double)k.max_depth);
+        TsdfCam& t = a.cams[c];
+        t.depth = k.depth; t.width = k.width; t.height = k.height; t.fx = k.fx; t.fy = k.fy; t.cx = k.cx; t.cy = k.cy;
+        t.min_depth = k.min_depth; t.max_depth = k.max_depth;
+        for (int i = 0; i < 12; ++i) { t.A[i] = k.cam_from_world[i]; t.B[i] = k.world_from_cam[i]; }
+    }
+    if (n_spheres < 0 || n_spheres > MPDX_TSDF_MAX_SPHERES) return fail(MPDX_E_INVALID, "%s: n_spheres %d (0 ... %d)", who, n_spheres, MPDX_TSDF_MAX_SPHERES);
+    if (n_spheres > 0 && !spheres) return fail(MPDX_E_INVALID, "%s: spheres is null with n_spheres %d", who, n_spheres);
+    for (int k = 0; k < n_spheres; ++k) {
+        for (int j = 0; j < 4; ++j)
+            if (!finite_f(spheres[4 * k + j])) return fail(MPDX_E_INVALID, "%s: spheres[%d] must be finite", who, k);
+        if (spheres[4 * k + 3] < 0.f) return fail(MPDX_E_INVALID, "%s: spheres[%d] radius is negative", who, k);
+        for (int j = 0; j < 4; ++j) a.spheres[k][j] = spheres[4 * k + j];
+    }
+    if (int rc = check_cell(who, cell)) return rc;
+    if (!origin) return fail(MPDX_E_INVALID, "%s: origin is null", who);
+    if (int rc = check_origin(who, origin, 3)) return rc;
+    if (!(trunc > 0.f && finite_f(trunc))) return fail(MPDX_E_INVALID, "%s: trunc must be positive and finite", who);
+    if (!(max_weight >= 1.f && max_weight <= 16777216.f)) return fail(MPDX_E_INVALID, "%s: max_weight %g (1 ... 2^24)", who, (double)max_weight);
+    if (!tsdf) return fail(MPDX_E_INVALID, "%s: tsdf is null", who);
+    if (!weight) return fail(MPDX_E_INVALID, "%s: weight is null", who);
+    if (!occ) return fail(MPDX_E_INVALID, "%s: occ is null", who);
+    if (int rc = check_aligned(who, "tsdf", tsdf, 4)) return rc;
+    if (int rc = check_aligned(who, "weight", weight, 4)) return rc;
+    a.tsdf = tsdf; a.weight = weight; a.occ = occ;
+    for (int j = 0; j < 3; ++j) { a.n[j] = n[j]; a.origin[j] = origin[j]; }
+    a.nodes = (int)nodes; a.n_cams = n_cams; a.n_spheres = n_spheres;
+    a.cell = cell; a.trunc = trunc; a.max_weight = max_weight;
+    hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1,6 +1,7 @@
 """Signed-distance grids (MPDX_FIELD_GRID) and the ways to make one: node values of the caller's own, a bake from sphere / box primitives, an occupancy
-map or a point cloud, a triangle mesh.  The last three run on the device (csrc/k_grid.hip); the lookups are in csrc/grid_field.hpp.  planning.py - the
-environments, robots and tasks that use a grid as a collision field - imports the names from here; this module does not import it.
+map or a point cloud, a triangle mesh, depth frames.  The last four run on the device (csrc/k_grid.hip); the lookups are in csrc/grid_field.hpp.
+planning.py - the environments, robots and tasks that use a grid as a collision field - imports the names from here; this module does not import it
+at load time (the robot mask of the depth fusion takes planning.robot_link_spheres when it is called).
 """
 from __future__ import annotations
 
@@ -29,7 +30,8 @@ class GridSDF:
     A grid made from an occupancy map or a point cloud (`from_occupancy`, `from_points`: an exact Euclidean distance transform on the device,
     mpdx_sdf_grid_from_occupancy) holds its planes on the device from the start and can be re-run in place (`update_occupancy`).
     So does a grid made from a triangle mesh (`from_mesh`: every node against every triangle on the device, mpdx_sdf_grid_from_mesh; `update_mesh`);
-    `mesh_info` says what was done to the mesh on the way (None for every other grid)."""
+    `mesh_info` says what was done to the mesh on the way (None for every other grid).  A grid made from depth frames (`from_depth`: TSDF integration,
+    mpdx_tsdf_integrate, then the transform of the occupancy it leaves) also holds its tsdf and weight planes and fuses more frames (`integrate_depth`)."""
     sdf: Optional[torch.Tensor]
     origin: np.ndarray
     cell: float
@@ -68,6 +70,8 @@ class GridSDF:
         self._ws = None
         self._mesh = None     # mesh grids: (vertices [V, 3] fp32, faces [F, 3] int32, sign mode) on the device of the planes
         self.mesh_info = None
+        self._tsdf = None     # depth grids: (tsdf [n_nodes], weight [n_nodes]) fp32 on the device of the planes, and the settings of the fusion
+        self._depth_cfg = None
 
     @classmethod
     def for_primitives(cls, objects, ws_min, ws_max, cell_size, mode="linear", padding=0.3):
@@ -119,7 +123,8 @@ class GridSDF:
         if self._made_on_device:
             here = self._planes[0].device
             if device.type != here.type or device.index not in (None, here.index):
-                raise RuntimeError(f"this GridSDF was made from {'an occupancy map' if self._occ is not None else 'a mesh'} on {here}; it is not copied to {device}")
+                what = "depth frames" if self._tsdf is not None else "an occupancy map" if self._occ is not None else "a mesh"
+                raise RuntimeError(f"this GridSDF was made from {what} on {here}; it is not copied to {device}")
             return self._planes
         if self._planes is not None and self._planes[0].device == device:
             return self._planes
@@ -279,6 +284,95 @@ class GridSDF:
             for t in (v, f):
                 t.record_stream(torch.cuda.current_stream())
 
+    # ---- depth frames: projective TSDF integration, csrc/tsdf.hpp (arithmetic in include/mpdx.h), then the transform of the occupancy it leaves
+    @classmethod
+    def from_depth(cls, depth, intrinsics, world_from_cam, ws_min, ws_max, cell_size, padding=0.3, mode="linear", inflate=0.0, trunc=None,
+                   max_weight=20.0, depth_range=(0.1, 5.0), depth_scale=1.0, robot=None, q=None, robot_padding=0.02, device="cuda"):
+        """Fuse depth frames into a grid on the box `grid_spec_for` places around the (3-D) workspace, then transform its occupancy (as from_occupancy).
+        depth        one image [h, w] or a list of them (or an [n, h, w] array), one per camera, each of its own size: float metres along the optical
+                     axis, or uint16 scaled by `depth_scale` (0.001 for millimetres).  Pixels outside depth_range (NaN, inf, 0 ...) are no measurement.
+        intrinsics   (fx, fy, cx, cy) per camera (pinhole, OpenCV frame x right / y down / z forward, pixel (iu, iv) centred at (iu, iv); undistorted)
+        world_from_cam  a 4x4 or 3x4 [R | t] per camera, checked in float64 (finite, R orthonormal to 1e-4) and inverted there
+        trunc        the truncation distance, default 3 * cell_size; max_weight caps the per-node weight (default 20: a node forgets an old surface
+                     within about that many frames).  Both defaults are plain defaults, not tuned values.
+        robot, q     mask the robot's link spheres (planning.robot_link_spheres, each padded by robot_padding) out of the frames: a pixel whose
+                     back-projected point lies inside one neither carves nor occupies.  q [q_dim] or [k, q_dim]; at most 64 spheres in all.
+        Unobserved nodes are free (a solid's unseen interior is free behind an occupied shell about trunc thick); `inflate` applies as for
+        from_occupancy.  The planes (sdf, gradient for mode='nearest', tsdf, weight, occupancy) live on `device` from the start."""
+        ws_min, ws_max = np.asarray(ws_min, np.float64).reshape(-1), np.asarray(ws_max, np.float64).reshape(-1)
+        if ws_min.size != 3 or ws_max.size != 3:
+            raise ValueError(f"from_depth: a depth grid is 3-D only (the workspace has {ws_min.size} axes)")
+        cell = float(cell_size)
+        trunc = 3.0 * cell if trunc is None else float(trunc)
+        if not (trunc > 0 and np.isfinite(trunc)):
+            raise ValueError("from_depth: trunc must be positive and finite")
+        max_weight = float(max_weight)
+        if not 1.0 <= max_weight <= float(1 << 24):
+            raise ValueError("from_depth: max_weight must lie in 1 ... 2^24")
+        lo, hi = (float(v) for v in depth_range)
+        if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 <= lo < hi):
+            raise ValueError("from_depth: depth_range is (min, max) with 0 <= min < max, finite")
+        if not (float(depth_scale) > 0 and np.isfinite(float(depth_scale))):
+            raise ValueError("from_depth: depth_scale must be positive and finite")
+        if not (float(robot_padding) >= 0 and np.isfinite(float(robot_padding))):
+            raise ValueError("from_depth: robot_padding must be non-negative and finite")
+        cfg = dict(trunc=trunc, max_weight=max_weight, depth_range=(lo, hi), depth_scale=float(depth_scale), robot_padding=float(robot_padding))
+        frames = _depth_frames(depth, intrinsics, world_from_cam, cfg["depth_scale"])
+        spheres = _mask_spheres(robot, q, cfg["robot_padding"])
+        shape, origin = grid_spec_for(ws_min, ws_max, cell, padding)
+        g = cls._empty_occupancy(shape, origin, cell, mode, inflate, device)
+        g._tsdf = (torch.zeros(g.n_nodes, dtype=torch.float32, device=g.sdf.device), torch.zeros(g.n_nodes, dtype=torch.float32, device=g.sdf.device))
+        g._depth_cfg = cfg
+        g._integrate(frames, spheres)
+        g._transform()
+        return g
+
+    def integrate_depth(self, depth, intrinsics, world_from_cam, robot=None, q=None, reset=False):
+        """Fuse more frames (the arguments of from_depth, with its settings) INTO THE TSDF, WEIGHT AND OCCUPANCY PLANES THIS GRID ALREADY HOLDS, then
+        re-run the transform into its sdf and gradient planes; reset=True starts from an empty map (tsdf = weight = 0).  Returns self: a guide or task
+        copies the planes again with its refresh_grids(), as after update_occupancy."""
+        if self._tsdf is None:
+            raise ValueError("integrate_depth: this GridSDF was not made by from_depth")
+        frames = _depth_frames(depth, intrinsics, world_from_cam, self._depth_cfg["depth_scale"])
+        spheres = _mask_spheres(robot, q, self._depth_cfg["robot_padding"])
+        if reset:
+            for p in self._tsdf:
+                p.zero_()
+        self._integrate(frames, spheres)
+        self._transform()
+        return self
+
+    def tsdf(self):
+        """(tsdf, weight) [nz, ny, nx] fp32 views on the device (None for a grid that was not made from depth frames)"""
+        if self._tsdf is None:
+            return None
+        shp = tuple(reversed(self.shape))
+        return self._tsdf[0].reshape(shp), self._tsdf[1].reshape(shp)
+
+    def _integrate(self, frames, spheres):
+        """mpdx_tsdf_integrate over the frames, at most MPDX_TSDF_MAX_CAMS per call (the cameras are taken in order either way)"""
+        dev = self._occ.device
+        cfg = self._depth_cfg
+        sp = (C.c_float * max(4, spheres.size))(*spheres.reshape(-1).tolist())
+        tsdf, weight = self._tsdf
+        with torch.cuda.device(dev):
+            imgs = [img.to(dev) if isinstance(img, torch.Tensor) else torch.from_numpy(img).to(dev) for img, _, _, _ in frames]
+            for lo in range(0, len(frames), _lib.TSDF_MAX_CAMS):
+                chunk = list(range(lo, min(len(frames), lo + _lib.TSDF_MAX_CAMS)))
+                cams = (_lib.DepthCamera * len(chunk))()
+                for c, i in enumerate(chunk):
+                    _, k, A, B = frames[i]
+                    cam = cams[c]
+                    cam.depth, cam.height, cam.width = imgs[i].data_ptr(), int(imgs[i].shape[0]), int(imgs[i].shape[1])
+                    cam.fx, cam.fy, cam.cx, cam.cy = (float(v) for v in k)
+                    cam.cam_from_world[:], cam.world_from_cam[:] = A.reshape(-1).tolist(), B.reshape(-1).tolist()
+                    cam.min_depth, cam.max_depth = cfg["depth_range"]
+                _lib.check(_lib.load().mpdx_tsdf_integrate(cams, len(chunk), sp if spheres.size else None, spheres.shape[0], tsdf.data_ptr(),
+                                                           weight.data_ptr(), self._occ.data_ptr(), C.byref(self._n3()), C.byref(self._origin3()),
+                                                           self.cell, cfg["trunc"], cfg["max_weight"], _lib.current_stream()), "mpdx_tsdf_integrate")
+            for t in imgs:
+                t.record_stream(torch.cuda.current_stream())
+
     def node_values(self, device="cuda"):
         """(sdf [nz, ny, nx] | [ny, nx], grad [..., 4] or None) as the kernels read them (downloaded by the tests for their fp64 reference)."""
         sdf, grad = self.planes(device)
@@ -334,6 +428,83 @@ def _check_mesh(vertices, faces, sign):
         f = f[:, ::-1]
     info = dict(n_vertices=int(v32.shape[0]), n_faces=int(f.shape[0]), dropped_faces=dropped, flipped=bool(flipped), signed_volume=volume, sign=sign)
     return v32, np.ascontiguousarray(f.astype(np.int32)), info
+
+
+def _depth_frames(depth, intrinsics, world_from_cam, depth_scale):
+    """The host-side checks of GridSDF.from_depth / integrate_depth, in float64, before anything is uploaded -> [(image fp32 [h, w] (numpy, or the
+    caller's float tensor), (fx, fy, cx, cy) float64, cam_from_world fp32 [3, 4], world_from_cam fp32 [3, 4])], one per camera.  The inverse is
+    formed in float64 from the 4x4 pose and both matrices are rounded to fp32."""
+    if isinstance(depth, (list, tuple)):
+        imgs = list(depth)
+    elif (depth.dim() if isinstance(depth, torch.Tensor) else np.ndim(depth)) == 3:
+        imgs = list(depth)
+    else:
+        imgs = [depth]
+    n = len(imgs)
+    if n < 1:
+        raise ValueError("depth: no frames")
+    out = []
+    for i, img in enumerate(imgs):
+        if isinstance(img, torch.Tensor) and img.dtype.is_floating_point:
+            im = img.detach().to(torch.float32).contiguous()
+        else:
+            a = img.detach().cpu().numpy() if isinstance(img, torch.Tensor) else np.asarray(img)
+            if a.dtype == np.uint16:
+                a = a.astype(np.float64) * float(depth_scale)
+            elif a.dtype.kind != "f":
+                raise ValueError(f"depth[{i}]: float metres or uint16 (scaled by depth_scale) are expected, got {a.dtype}")
+            im = np.ascontiguousarray(a.astype(np.float32))
+        if im.ndim != 2 or not (1 <= im.shape[0] <= 8192 and 1 <= im.shape[1] <= 8192):
+            raise ValueError(f"depth[{i}]: an image [h, w] with 1 ... 8192 pixels along each axis is expected, got {tuple(im.shape)}")
+        out.append(im)
+    k = np.asarray(intrinsics, np.float64)
+    if k.shape == (4,) and n == 1:
+        k = k[None]
+    if k.shape != (n, 4):
+        raise ValueError(f"intrinsics: (fx, fy, cx, cy) per camera, [{n}, 4] expected, got {tuple(k.shape)}")
+    if not np.isfinite(k).all() or (k[:, :2] <= 0).any():
+        raise ValueError("intrinsics: fx, fy must be positive and finite, cx, cy finite")
+    if isinstance(world_from_cam, (list, tuple)) and any(np.ndim(v) == 2 for v in world_from_cam):
+        poses = [np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, np.float64) for v in world_from_cam]   # 4x4 and 3x4 mixed
+    else:
+        M = np.asarray(world_from_cam.detach().cpu().numpy() if isinstance(world_from_cam, torch.Tensor) else world_from_cam, np.float64)
+        poses = [M] if M.ndim == 2 else list(M)
+    if len(poses) != n or any(P.shape not in ((3, 4), (4, 4)) for P in poses):
+        raise ValueError(f"world_from_cam: a 4x4 or 3x4 pose per camera ({n}) expected, got {[tuple(P.shape) for P in poses]}")
+    if not all(np.isfinite(P).all() for P in poses):
+        raise ValueError("world_from_cam: the poses must be finite")
+    if any(P.shape[0] == 4 and (P[3] != np.array([0.0, 0.0, 0.0, 1.0])).any() for P in poses):
+        raise ValueError("world_from_cam: the last row of a 4x4 pose must be (0, 0, 0, 1)")
+    M = np.stack([P[:3] for P in poses])
+    R = M[:, :3, :3]
+    dev = np.abs(R @ np.swapaxes(R, 1, 2) - np.eye(3)).max(axis=(1, 2))
+    if (dev > 1e-4).any():
+        raise ValueError(f"world_from_cam[{int(np.argmax(dev))}]: the rotation is not orthonormal to 1e-4 (|R R^T - I| = {dev.max():.3g})")
+    H = np.zeros((n, 4, 4))
+    H[:, :3] = M[:, :3]
+    H[:, 3, 3] = 1.0
+    inv = np.linalg.inv(H)
+    return [(out[i], k[i], inv[i, :3].astype(np.float32), H[i, :3].astype(np.float32)) for i in range(n)]
+
+
+def _mask_spheres(robot, q, padding):
+    """[S, 4] fp32 (centre, radius + padding) of planning.robot_link_spheres(robot, q), S <= 64; [0, 4] without a robot"""
+    if robot is None:
+        if q is not None:
+            raise ValueError("robot mask: q without a robot")
+        return np.zeros((0, 4), np.float32)
+    if q is None:
+        raise ValueError("robot mask: give q with the robot")
+    from .planning import robot_link_spheres
+    sp = robot_link_spheres(robot, q)
+    if sp.shape[0] > _lib.TSDF_MAX_SPHERES:
+        raise ValueError(f"robot mask: {sp.shape[0]} spheres (at most {_lib.TSDF_MAX_SPHERES}: fewer configurations in q)")
+    sp = sp.copy()
+    sp[:, 3] += float(padding)
+    sp = sp.astype(np.float32)
+    if not np.isfinite(sp).all():
+        raise ValueError("robot mask: the spheres must be finite in fp32")
+    return sp
 
 
 def _occupancy_bytes(occ):

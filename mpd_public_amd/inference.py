@@ -352,6 +352,31 @@ def _mesh_grid_args(a: dict) -> dict:
     return a
 
 
+def _depth_grid_args(a: dict) -> dict:
+    """--sdf_grid_depth FILE.npz of the command line: depth [n, h, w] (metres, or uint16 millimetres), intrinsics [n, 4] (fx, fy, cx, cy) and
+    world_from_cam [n, 4, 4] are fused into a GridSDF over the task's workspace (GridSDF.from_depth, at --sdf_grid_cell_size, in --sdf_grid_mode)
+    that goes to experiment(sdf_grid=...), as _mesh_grid_args does with a mesh."""
+    path = a.pop("sdf_grid_depth", None)
+    if path is None:
+        return a
+    if a.get("sdf_grid") is not None:
+        raise SystemExit("--sdf_grid_depth and --sdf_grid_mesh exclude each other")
+    if a["sdf_grid_cell_size"] is None:
+        raise SystemExit("--sdf_grid_depth needs --sdf_grid_cell_size")
+    import numpy as np
+    from .planning import GridSDF, make_env
+    with np.load(path) as z:
+        missing = [k for k in ("depth", "intrinsics", "world_from_cam") if k not in z]
+        if missing:
+            raise SystemExit(f"--sdf_grid_depth {path}: the archive lacks {', '.join(missing)} (depth [n, h, w], intrinsics [n, 4], world_from_cam [n, 4, 4])")
+        depth, intrinsics, poses = z["depth"], z["intrinsics"], z["world_from_cam"]
+    ws_min, ws_max = make_env(a["model_id"].split("-")[0]).limits
+    a["sdf_grid"] = GridSDF.from_depth(list(depth), intrinsics, list(poses), ws_min, ws_max, a["sdf_grid_cell_size"], mode=a["sdf_grid_mode"],
+                                       depth_scale=0.001 if depth.dtype == np.uint16 else 1.0)
+    a["sdf_grid_cell_size"] = None
+    return a
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
@@ -366,6 +391,9 @@ if __name__ == "__main__":
     ap.add_argument("--sdf_grid_mode", default="linear", choices=["linear", "nearest"])
     ap.add_argument("--sdf_grid_mesh", default=None, metavar="PATH",
                     help="fixed objects from a triangle mesh (.obj / .stl, closed, in the workspace frame) as a signed-distance grid; needs --sdf_grid_cell_size")
+    ap.add_argument("--sdf_grid_depth", default=None, metavar="NPZ",
+                    help="the obstacles from depth frames (an .npz of depth [n, h, w] in metres or uint16 millimetres, intrinsics [n, 4] = fx, fy, cx, cy, "
+                         "world_from_cam [n, 4, 4]; OpenCV camera frame) fused into a signed-distance grid; needs --sdf_grid_cell_size")
     ap.add_argument("--goal_ee_pos", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
                     help="plan to this end-effector position (inverse kinematics) instead of a random goal configuration")
     ap.add_argument("--tool_upright", type=float, default=None, metavar="MAX_TILT_DEG",
@@ -373,7 +401,7 @@ if __name__ == "__main__":
     ap.add_argument("--moving_sphere", type=float, nargs="+", default=None, metavar="V",
                     help="one more sphere that moves at constant velocity during the plan: the coordinates of its centre at the first support point, then those "
                          "at the last, then its radius (5 numbers in a 2-D workspace, 7 in 3-D)")
-    a = _mesh_grid_args(vars(ap.parse_args()))
+    a = _depth_grid_args(_mesh_grid_args(vars(ap.parse_args())))
     ms = a.pop("moving_sphere")
     if ms is not None:
         if len(ms) not in (5, 7):

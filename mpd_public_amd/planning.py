@@ -304,6 +304,39 @@ class RobotChain:
         return cls(joints, spheres, PANDA_SELF_PAIRS, q_limits=(syn.PANDA_Q_MIN, syn.PANDA_Q_MAX), v_limit=2.5, name=name)
 
 
+_PANDA_CHAIN = None
+
+
+def robot_link_spheres(robot, q) -> np.ndarray:
+    """The robot's collision spheres in the world at q [q_dim] or [k, q_dim] (numpy or a torch tensor) -> [S, 4] float64 (centre, radius), the k
+    configurations' spheres one after the other.  RobotPanda: RobotChain.panda().fk; a RobotChain: its own sphere table; a 3-D RobotPointMass: one
+    sphere of link_margin at q.  The depth fusion (GridSDF.from_depth / integrate_depth) masks these, padded, out of the frames."""
+    qa = np.asarray(q.detach().cpu().numpy() if torch.is_tensor(q) else q, np.float64)
+    if qa.ndim not in (1, 2) or qa.shape[-1] != robot.q_dim:
+        raise ValueError(f"robot_link_spheres: q is [{robot.q_dim}] or [k, {robot.q_dim}] for {robot.name}, got {tuple(qa.shape)}")
+    if not np.isfinite(qa).all():
+        raise ValueError("robot_link_spheres: q must be finite")
+    qa = qa.reshape(-1, robot.q_dim)
+    if isinstance(robot, RobotPointMass):
+        if robot.q_dim != 3:
+            raise ValueError(f"robot_link_spheres: a {robot.q_dim}-D point mass (depth fusion is 3-D only)")
+        return np.concatenate([qa, np.full((qa.shape[0], 1), float(robot.link_margin))], 1)
+    if isinstance(robot, RobotPanda):
+        global _PANDA_CHAIN
+        if _PANDA_CHAIN is None:
+            _PANDA_CHAIN = RobotChain.panda()
+        chain = _PANDA_CHAIN
+    elif isinstance(robot, RobotChain):
+        chain = robot
+    else:
+        raise ValueError(f"robot_link_spheres: {type(robot).__name__} (RobotPanda, RobotChain or a 3-D RobotPointMass)")
+    out = np.zeros((qa.shape[0], chain.n_spheres, 4))
+    for k in range(chain.n_spheres):
+        out[:, k, :3] = chain.fk(qa, frame=int(chain.sphere_frame[k]), offset=chain.sphere_offset[k])[0]
+        out[:, k, 3] = chain.sphere_radius[k]
+    return out.reshape(-1, 4)
+
+
 def make_robot(robot_id: str):
     if robot_id == "RobotPointMass":
         return RobotPointMass(2)
