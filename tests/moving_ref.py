@@ -94,6 +94,7 @@ CASES = {
     "panda-H64": dict(robot_id="RobotPanda", H=64, n_interp=128, grid=False),          # sparse here, dense in a child process
     "pm2-H64-grid": dict(robot_id="RobotPointMass", H=64, n_interp=128, grid=True),
     "panda-H64-grid": dict(robot_id="RobotPanda", H=64, n_interp=128, grid=True),
+    "pm3-H24-grid": dict(robot_id="RobotPointMass3D", H=24, n_interp=128, grid=True),
 }
 B = 4
 WEIGHTS = (1e-2, 1e-7)

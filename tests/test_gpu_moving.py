@@ -142,7 +142,7 @@ def test_moving_panda_dense_variant_vs_oracle(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------------------------------ 3. metrics flags
-@pytest.mark.parametrize("name", ["pm2-H64", "panda-H64"])
+@pytest.mark.parametrize("name", ["pm2-H64", "panda-H64", "pm2-H64-grid", "panda-H64-grid", "pm3-H24-grid"])
 @pytest.mark.parametrize("n_check", [64, 256])
 def test_moving_metrics_flags_vs_fp64_reference(name, n_check):
     """trajectory_metrics(..., return_mask=True) on a task with a track: the flags equal an fp64 evaluation of the same hinges (margin = link radius, no

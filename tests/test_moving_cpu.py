@@ -469,7 +469,8 @@ def test_gpu_case_conditions_from_the_reference_alone(name):
     assert abs(amax - 1.0) > 1e-3
 
 
-@pytest.mark.parametrize("name,n_check", [("pm2-H64", 64), ("pm2-H64", 256), ("panda-H64", 64), ("panda-H64", 256)])
+@pytest.mark.parametrize("name,n_check", [("pm2-H64", 64), ("pm2-H64", 256), ("panda-H64", 64), ("panda-H64", 256)] +
+                         [(n, k) for n in ("pm2-H64-grid", "panda-H64-grid", "pm3-H24-grid") for k in (64, 256)])
 def test_metrics_case_conditions(name, n_check):
     """the metrics comparison presupposes decided points of both kinds, few points in the 1e-5 band, and points that the moving field ALONE decides"""
     from oracle.guide import interpolate_points_v1
@@ -477,7 +478,8 @@ def test_metrics_case_conditions(name, n_check):
     xu = c["og"].normalizer.unnormalize(c["x"].double()).float()
     xi = interpolate_points_v1(xu.double(), n_check)
     hit, band = mr.metrics_reference(c["comp"], xi)
-    ogs, comps, _ = mr.oracle(mr.dataset(name, track=None), n_interp=128)
+    grid = c["comp"].cost_l[c["k_grid"]].field if mr.CASES[name]["grid"] else None
+    ogs, comps, _ = mr.oracle(mr.dataset(name, track=None), n_interp=128, grid_field=grid)
     hit_static, _ = mr.metrics_reference(comps, xi)
     print(f"{name} n_check {n_check}: {int(hit.sum())} of {hit.size} collide, {int(band.sum())} in the band, {int((hit != hit_static).sum())} differ from the static set")
     assert band.mean() <= 0.01 and (hit & ~band).any() and (~hit & ~band).any()
