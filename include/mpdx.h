@@ -55,7 +55,12 @@ typedef struct mpdx_unet_cfg {
     int32_t n_support_points;           /* H: 64 in every shipped configuration; 16 ... 128 with H % 2^(n_levels-1) == 0 (powers of two run as they are, 24 / 40 / 48 / 96 ... in the next power-of-two container, zero rows kept zero) */
     int32_t unet_input_dim;             /* 32 */
     int32_t n_levels;                   /* len(dim_mults) */
-    int32_t dim_mults[MPDX_MAX_LEVELS]; /* (1,2,4,8) or (1,2,4): UNET_DIM_MULTS, temporal_unet.py:14-17 */
+    int32_t dim_mults[MPDX_MAX_LEVELS]; /* (1,2,4,8) or (1,2,4): UNET_DIM_MULTS, temporal_unet.py:14-17 - the shipped ones.  Admitted: 2 ... 8 entries >= 1 with
+                                           dim_mults[0] == 1, unet_input_dim a multiple of 16, every Conv1dBlock's GroupNorm region (group of 4 ... 32 channels x
+                                           positions of its level) a power of two in 64 ... 2048 - e.g. (1,2), (1,8), (1,1,2), (1,2,2), (1,2,4,4), (1,2,8,8),
+                                           (1,2,4,8,8), (1,1,2,2,4,8) on H = 128 (tests/shapes_ref.py holds the family the suite runs).  Refused with the layer
+                                           named: a region outside that range ((1,2) on H = 16, (1,3), (1,16), width 16 ...), and dim_mults[i] == 2 * dim_mults[i+1]
+                                           ((1,2,1), (1,4,2)): ups.<j>.0 would carry an identity residual over its whole concatenated input */
     int32_t time_emb_dim;               /* 32 */
     int32_t self_attention;             /* 0 / 1: TemporalUnet(self_attention=...), see above (appended: positional initialisers of the members above leave it 0) */
 } mpdx_unet_cfg;

@@ -1239,6 +1239,13 @@ int mpdx_unet_create(const mpdx_unet_cfg* cfg, mpdx_unet** out) {
     if (H < 16 || H > 128 || (H % (1 << (cfg->n_levels - 1))) || (H >> (cfg->n_levels - 1)) < 2)
         return fail(MPDX_E_INVALID, "n_support_points %d must be a multiple of 2^(levels-1) = %d in [16, 128] with >= 2 points at the coarsest level", H,
                     1 << (cfg->n_levels - 1));
+    // ups.j.0 reads the concatenation of the level below and the skip, 2 * dim_mults[lv] channels wide, and writes dim_mults[lv - 1]: where the two are
+    // equal the reference's block has no residual_conv and its residual is the WHOLE concatenation (layers.py:337-355).  A layer here names one residual
+    // slot of cout channels (build_model's rtb, ConvArgs::res), so such a network is refused, not run with half a residual
+    for (int lv = 1; lv < cfg->n_levels; ++lv)
+        if (2 * cfg->dim_mults[lv] == cfg->dim_mults[lv - 1])
+            return fail(MPDX_E_INVALID, "layer ups.%d.0: identity residual over a concatenation (dim_mults[%d] = %d is twice dim_mults[%d] = %d, so the block "
+                        "has no residual_conv) unsupported", cfg->n_levels - 1 - lv, lv - 1, cfg->dim_mults[lv - 1], lv, cfg->dim_mults[lv]);
     mpdx_unet* u = new mpdx_unet();
     u->cfg = *cfg;
     build_model(u);

@@ -1016,9 +1016,13 @@ struct TimeBwdArgs {
 //   blocks [B, B + ...)  cond_mlp weight / bias gradients, 32 table rows per block:  dW[c][e] = sum_b dT[b][c] * mish(temb[b][e]),
 //                        db[c] = sum_b dT[b][c]
 // Every sum runs in the order of the four kernels it replaces (b ascending; table rows by part, parts ascending).
-constexpr int kTimeBwdMaxRow = 2560;
+// Longest time-table row (sum of C_out over the residual blocks): what stage 1 can stage in the 40 KB below.  1920 / 1024 in the shipped networks, 2944 in
+// the five-level (1, 2, 4, 8, 8).  A multiple of 64 floats: the three parts keep their banks whatever the value.
+constexpr int kTimeBwdLds = 10240;
+constexpr int kTimeBwdMaxRow = (kTimeBwdLds - 32 * 32) / 2;   // 4608
+static_assert(kTimeBwdMaxRow % 64 == 0 && 2 * kTimeBwdMaxRow + 32 * 32 <= kTimeBwdLds, "stage 1 of time_bwd_all_body: [dT row | row offsets | 32 x 32 partial sums]");
 __device__ __forceinline__ void time_bwd_all_body(const TimeBwdArgs& a, const int block_id) {
-    __shared__ __attribute__((aligned(16))) float sh[10240];   // 40 KB: stage 1 [dT row | row offsets | partial sums], tail [dtm | h1m | dh1 | emb]
+    __shared__ __attribute__((aligned(16))) float sh[kTimeBwdLds];   // 40 KB: stage 1 [dT row | row offsets | partial sums], tail [dtm | h1m | dh1 | emb]
     __shared__ int s_toff[41];
     __shared__ unsigned s_woff[40];
     __shared__ unsigned s_ticket;

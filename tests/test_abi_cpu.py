@@ -70,7 +70,8 @@ def test_invalid_configurations_are_rejected_with_messages(lib):
     for kw in (dict(n_levels=1), dict(state_dim=0), dict(time_emb_dim=16), dict(unet_input_dim=24), dict(n_support_points=44),      # 44 % 2^(levels-1) != 0
                dict(n_support_points=18, n_levels=3, dim_mults=(1, 2, 4)), dict(n_support_points=256), dict(n_support_points=8),
                dict(n_support_points=16),                                       # a 32-element GroupNorm region on the up path
-               dict(n_support_points=16, n_levels=3, dim_mults=(1, 2, 4))):
+               dict(n_support_points=16, n_levels=3, dim_mults=(1, 2, 4)),
+               dict(n_levels=3, dim_mults=(1, 2, 1)), dict(n_levels=3, dim_mults=(1, 4, 2))):   # ups.0.0: identity residual over a concatenation
         rc, _ = _create(lib, **kw)
         assert rc < 0, kw
         assert lib.mpdx_last_error()
