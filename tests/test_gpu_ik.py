@@ -9,6 +9,11 @@ PlanningTask.ik_coll_free_q, experiment(goal_ee_pos=...)) against the torch refe
                  one step R3: reference fp32 vs fp64 2.199e-06; kernel vs fp64 1.370e-06; bound 8.796e-06
                  one step R8: reference fp32 vs fp64 2.294e-05; kernel vs fp64 3.577e-05; bound 9.175e-05
                  one step Panda: reference fp32 vs fp64 1.307e-05; kernel vs fp64 9.849e-06; bound 5.228e-05
+                 one step R8[:2]: reference fp32 vs fp64 5.830e-07; kernel vs fp64 9.205e-07; bound 2.479e-06
+                 one step R8[:4]: reference fp32 vs fp64 2.897e-06; kernel vs fp64 3.634e-06; bound 1.159e-05
+                 one step R8[:5]: reference fp32 vs fp64 4.996e-06; kernel vs fp64 5.121e-06; bound 1.998e-05
+                 one step R8[:6]: reference fp32 vs fp64 1.566e-05; kernel vs fp64 1.229e-05; bound 6.264e-05
+                 (R8[:k]: the 8-joint robot cut after k joints; with R1, R3, Panda and R8 every instantiation, 1 ... 8 joints, runs)
 2. independence  a target solved alone is bit-equal to the same target inside a batch of 3
 3. seeds         max_iters = 0, q_init = NULL: the seeds are fmaf(hi - lo, u, lo) of the Philox uniforms of tests/philox_ref.py to one float32 ulp
                  of the span hi - lo (with hi - lo taken in float32 as the kernel takes it, what is left is u's rounding, at most span * 2^-25 =
@@ -31,13 +36,7 @@ OFFSET = (0.05, -0.02, 0.11)
 SHAPES = [(1, 1), (3, 64), (1, 65), (3, 65)]
 
 
-def _fk_slack(name, q, frame=None, offset=(0.0, 0.0, 0.0)):
-    """twice the largest |FK_fp32 - FK_fp64| (position: L2, rotation: Frobenius) the reference shows on the configurations q"""
-    r32, r64 = ik_ref.IKRef(name, torch.float32, frame=frame, offset=offset), ik_ref.IKRef(name, torch.float64, frame=frame, offset=offset)
-    q = q.detach().cpu().float().reshape(-1, q.shape[-1])
-    p32, R32, _ = r32.pose(q)
-    p64, R64, _ = r64.pose(q.double())
-    return 2.0 * max(float((p32.double() - p64).norm(dim=-1).max()), float((R32.double() - R64).flatten(-2).norm(dim=-1).max()))
+_fk_slack = ik_ref.fk_slack   # twice the largest |FK_fp32 - FK_fp64| the reference shows on the configurations
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. one step
@@ -56,7 +55,7 @@ def _one_step_inputs(name):
     return out
 
 
-@pytest.mark.parametrize("name", ["R1", "R3", "R8", "Panda"])
+@pytest.mark.parametrize("name", ["R1", "R3", "R8", "Panda", "R8[:2]", "R8[:4]", "R8[:5]", "R8[:6]"])   # every instantiation: 1 ... 8 joints
 def test_one_step_against_the_fp64_reference(name):
     import mpd_public_amd as m
     rob = product_robot(name)
@@ -102,7 +101,7 @@ def test_a_target_alone_equals_the_target_in_a_batch(name, pose):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. seeds
-@pytest.mark.parametrize("name", ["R3", "R8"])
+@pytest.mark.parametrize("name", ["R3", "R8", "R8[:5]", "R8[:6]"])   # 5 and 6 joints: the second Philox block part-filled
 def test_philox_seeds(name):
     import mpd_public_amd as m
     rob = product_robot(name)

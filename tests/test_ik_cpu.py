@@ -1,8 +1,11 @@
 """CPU checks of the chain-robot inverse kinematics (mpdx_ik_solve, solve_ik, RobotChain.fk): the reference of tests/ik_ref.py pinned against
 autograd before any kernel is involved, the host FK against the reference FK, the C ABI's refusals (no launch, host buffers: the method of
 tests/test_chain_cpu.py), the Python refusals, and the fixture check of the GPU convergence test - the reference alone solves every target of
-every case from at least 8 of its 64 seeds, in fp64 and in fp32."""
+every case from at least 8 of its 64 seeds, in fp64 and in fp32.  Last the reference-only side of tests/test_gpu_ik_loop.py: the fp32 reference,
+standing in for the kernel, meets every condition of every loop case; a wrong damping rule in it does not; the reference's reading of the
+180-degree twin; the mix of lane kinds."""
 import ctypes as C
+import functools
 import re
 from pathlib import Path
 
@@ -213,3 +216,88 @@ def test_reference_solves_every_convergence_case(name, pose):
         assert float(ep.norm(dim=-1)[ok].max()) <= 1e-4 + 1e-5
         if pose:
             assert float(eR.norm(dim=-1)[ok].max()) <= 1e-3 + 1e-5
+
+
+# ---------------------------------------------------------------------------------------------------------------- the loop cases (tests/test_gpu_ik_loop.py)
+@functools.lru_cache(maxsize=None)
+def _stand_in(name, pose, schedule, rule="right"):
+    kw = ik_ref.loop_kw(pose, schedule)
+    q0, tpos, trot = ik_ref.loop_case(name, pose)
+    qp = ik_ref.reference_prefixes(ik_ref.IKRef(name, torch.float32, **kw), q0, tpos[:, None], trot[:, None], ik_ref.LOOP_K, rule)
+    return ik_ref.loop_report(name, kw, qp, tpos, trot)
+
+
+@pytest.mark.parametrize("schedule", ["default", "narrow"])
+@pytest.mark.parametrize("pose", [False, True], ids=["position", "pose"])
+@pytest.mark.parametrize("name", ik_ref.LOOP_ROBOTS)
+def test_fp32_reference_meets_every_condition_of_the_loop_cases(name, pose, schedule):
+    """the teacher-forced fp64 trail over the fp32 reference's own prefixes: every minimum (decidable decisions, accepts, rejects, reject runs, limit
+    joints, accepts at the clamps of the narrow schedule), the mismatch cap, the backward-error bound, the limits and the descent hold, so a
+    failure of the same conditions on the GPU is the kernel's"""
+    rep = _stand_in(name, pose, schedule)
+    what = f"ik loop {name} {'pose' if pose else 'position'} {schedule} (fp32 reference)"
+    print(ik_ref.report_line(what, rep))
+    ik_ref.assert_loop_report(what, rep, **ik_ref.loop_minimums(name, pose, schedule))
+
+
+# A missing lambda_min clamp (a damping of 1e-5 for 1e-4 changes A by 9e-5 I only) shows in the backward error where |A| is small or where the
+# next reject leaves 1e-4 for 1e-3: by a factor of 50 and more over the bound in NO_LAM_MIN_BY_ETA; elsewhere hundreds of decisions give it away,
+# but for the three cases of NO_LAM_MIN_FAINT (a handful of decisions, a factor of 2 ... 6 in eta: seen on this fixture, not asserted).
+NO_LAM_MIN_BY_ETA = {("R8[:4]", False), ("R8[:5]", True), ("Panda", True)}
+NO_LAM_MIN_FAINT = {("R3", True), ("R8[:2]", False), ("R8[:2]", True)}
+# A missing lambda_max clamp shows after four rejects in a row only (the first three lead to lambda_max under either rule): every pose case shows
+# it in the backward error by a factor of 800 and more; in these four position-only cases no checked step and no decidable decision follows such
+# a run (the pose cases of the same robots run the same kernel instantiations).
+NO_LAM_MAX_UNSEEN = {("R3", False), ("R8[:2]", False), ("R8[:4]", False), ("Panda", False)}
+
+
+@pytest.mark.parametrize("pose", [False, True], ids=["position", "pose"])
+@pytest.mark.parametrize("name", ik_ref.LOOP_ROBOTS)
+def test_a_wrong_damping_rule_is_caught(name, pose):
+    """narrow schedule, the fp32 reference with a wrong rule as the solver: up and down swapped, no lambda_min clamp, no lambda_max clamp.  The
+    accepted steps' backward error in the reference's system (at the RIGHT damping) exceeds the bound, which the right rule holds with room:
+    swapped in every case, no lambda_max clamp in every pose case, no lambda_min clamp in NO_LAM_MIN_BY_ETA; elsewhere the decisions give it away
+    (several times the 2 disagreements a case may have), with the exceptions named above"""
+    right = _stand_in(name, pose, "narrow")
+    assert right["eta_ratio"] <= 0.5 and len(right["mismatches"]) <= 2
+    for rule in ik_ref.LAMBDA_RULES[1:]:
+        wrong = _stand_in(name, pose, "narrow", rule)
+        print(f"{name} {'pose' if pose else 'position'} {rule}: worst eta / bound {wrong['eta_ratio']:.3g} (right rule {right['eta_ratio']:.3g}), "
+              f"decision mismatches {len(wrong['mismatches'])}")
+        by_eta = rule == "swapped" or (rule == "no_lam_max" and pose) or (rule == "no_lam_min" and (name, pose) in NO_LAM_MIN_BY_ETA)
+        if by_eta:
+            assert wrong["eta_ratio"] > 1.5, (name, pose, rule, wrong["eta_ratio"])
+        elif not ((rule == "no_lam_max" and (name, pose) in NO_LAM_MAX_UNSEEN) or (rule == "no_lam_min" and (name, pose) in NO_LAM_MIN_FAINT)):
+            assert wrong["eta_ratio"] > 1.5 or len(wrong["mismatches"]) > 6, (name, pose, rule, wrong["eta_ratio"], len(wrong["mismatches"]))
+
+
+@pytest.mark.parametrize("name", ik_ref.STOP_ROBOTS)
+def test_reference_reads_the_180_degree_twin_by_the_trace_alone(name):
+    """at q*: the position and e_R are inside the default tolerances for the target AND for its twin Rot(q*) diag(1, -1, -1); the traces are 3 and -1:
+    the reference stops at once on the first and never on the second (e = 0: no step moves it), in fp64 and in fp32"""
+    q_star, tpos, trot, twin = ik_ref.stop_case(name)
+    for dtype in (torch.float64, torch.float32):
+        ref = ik_ref.IKRef(name, dtype, offset=ik_ref.LOOP_OFFSET, rot_weight=ik_ref.ROT_WEIGHT)
+        for R, trace in ((trot, 3.0), (twin, -1.0)):
+            _, pe, re, tr = ref.residual(q_star.to(dtype), tpos[:, None].to(dtype), R[:, None].to(dtype))
+            assert float(pe.max()) <= 1e-5 and float(re.max()) <= 1e-5 and float((tr - trace).abs().max()) <= 1e-5, (name, dtype, trace)
+            s = ref.solve(q_star, tpos[:, None], R[:, None], max_iters=3)
+            assert bool((s["converged"] == (trace > 1)).all()) and bool((s["iters"] == (0 if trace > 1 else 3)).all()), (name, dtype, trace)
+        pos_only = ik_ref.IKRef(name, dtype, offset=ik_ref.LOOP_OFFSET).solve(q_star, tpos[:, None], twin[:, None], max_iters=3)
+        assert bool(pos_only["converged"].all()) and not bool(pos_only["iters"].any())
+
+
+@pytest.mark.parametrize("name,pose", [("R3", False), ("Panda", True)])
+def test_lane_case_mixes_the_three_kinds_of_restart(name, pose):
+    """of the 130 restarts the reference converges restart 3 at iteration 0, some after 1 ... 39 iterations and some never; both workgroup edges of
+    the GPU test (restarts 63 and 64) are not of one kind"""
+    q0, tpos, trot, kw = ik_ref.lane_case(name, pose)
+    for dtype in (torch.float64, torch.float32):
+        s = ik_ref.IKRef(name, dtype, **kw).solve(q0, tpos[:, None], trot[:, None], max_iters=ik_ref.LANE_ITERS)
+        it, cv = s["iters"][0], s["converged"][0]
+        assert bool(cv[ik_ref.LANE_AT_TARGET]) and int(it[ik_ref.LANE_AT_TARGET]) == 0 and int((it == 0).sum()) == 1
+        early, never = cv & (it > 0) & (it < ik_ref.LANE_ITERS), ~cv & (it == ik_ref.LANE_ITERS)
+        print(name, dtype, "early", int(early.sum()), "never", int(never.sum()))
+        assert int(early.sum()) >= 20 and int(never.sum()) >= 20 and int(early.sum() + never.sum()) == ik_ref.LANE_R - 1
+        lanes = torch.tensor(ik_ref.LANES)
+        assert bool(early[lanes].any()) and bool(never[lanes].any()) and bool(early[63]) != bool(early[64])
