@@ -775,6 +775,39 @@ int mpdx_unet_layer_tile(const mpdx_unet* u, int i, int B, char* buf, size_t buf
 int mpdx_attention_block(float* x, const float* to_qkv_w, const float* to_out_w, const float* to_out_b, const float* norm_g, const float* norm_b,
                          int B, int L, int Lv, int C, void* stream);
 
+/* ---- cost values and clearance per trajectory: the VALUES of the terms whose gradients mpdx_guide_step applies.  Replaces the forward half of
+ * guides.py:190, cost(x, x_interpolated=..., return_invidual_costs_and_weights=True) -> ([B] per term, [weights]), for a composite compiled into
+ * mpdx_guide_params (cost arithmetic un-vendored in the reference, restated from the published formulas: PARITY UNPINNED); the clearance replaces
+ * nothing (the reference counts colliding waypoints).  One 64-lane workgroup per trajectory, sums and minima by a fixed butterfly (no atomics:
+ * two calls on the same input give the same bits).  x_unnormalised [B,H,D] is in robot units, as for mpdx_traj_metrics: clip_grad, the normaliser
+ * members and identity_normalizer are ignored.  The weights of the block (fields[f].weight, gp_weight, tool_weight) are NOT applied.
+ * All in fp32, on the same device functions as mpdx_traj_metrics_mask (a negative clearance and a collision flag come from the same signed distance):
+ *   1. the evaluated points: N = n_points (2 ... 8192), or for n_points == 0 what the block says (interpolate ? n_interp : H); point i is the guide's
+ *      linear interpolation q_i = l0 x[i0] + l1 x[i1], u = i (H - 1) / (N - 1), i0 = (int)u, l1 = u - i0 (N == H: the supports themselves)
+ *   2. the link spheres of q_i: the point itself with r = link_margin (point mass); the Panda's 11 spheres; the chain table's spheres (sinf / cosf)
+ *   3. slot f < n_fields, cost_out[b][f] = sum over points and factors, with m = r + cutoff_margin:
+ *        MPDX_FIELD_OBJECTS / MPDX_FIELD_GRID  one relu(m - sdf(p)) per sphere; a field with a track is tested at p - o_i, o_i = l0 track[i0] + l1 track[i1]
+ *        MPDX_FIELD_WORKSPACE                  one relu(m - (p_j - ws_min_j)) and one relu(m - (ws_max_j - p_j)) per sphere and axis j < ws_dim
+ *        MPDX_FIELD_SELF                       one relu(r_a + r_b - |P_a - P_b|) per pair (Panda: its 12 pairs; chain: the table's); point mass: none
+ *      a slot at or beyond n_fields is 0
+ *   4. slot MPDX_MAX_FIELDS, the GP prior over the SUPPORTS: with eq = q_{h+1} - q_h - dt v_h, ev = v_{h+1} - v_h,
+ *        sum_{h < H-1} 12/dt^3 |eq|^2 - 12/dt^2 eq.ev + 4/dt |ev|^2, times 0.5 under gp_half_factor, divided by sigma_gp^2; 0 when use_gp == 0
+ *   5. slot MPDX_MAX_FIELDS + 1, the tool axis (chain, tool_frame != 0; arithmetic of the tool members above): sum_i relu(tool_cos_min - tool_world .
+ *      Rot_f(q_i) tool_axis); 0 when tool_frame == 0
+ *   6. clearance_out[b][f] (or NULL) = min over points and factors of: sdf - r (objects, grid), face distance - r (workspace), |P_a - P_b| - (r_a +
+ *      r_b) (self); +3.0e38 for a slot without factors
+ *   7. point_out[b][i][f] (or NULL) = the factor sum of field f at point i alone, point_out[b][i][MPDX_MAX_FIELDS] that of the tool term (the GP prior
+ *      has no points)
+ * Checked on the host before any launch (MPDX_E_INVALID, the message names the argument): gp, x_unnormalised or cost_out NULL; B <= 0; D != 2 q_dim;
+ * H < 2; n_points outside {0} and 2 ... 8192 (or, for 0, an n_interp outside it); the LDS need (state, staged tables, 64 x 49 floats of sphere centres for
+ * the Panda and a chain) above 160 KB; everything mpdx_traj_metrics refuses in the block: a bad chain table ("chain: ..."), grid, scene and track members
+ * (track_len != H), chain + grid, chain + track, track + scenes, and the checks of the tool members.
+ * Takes: the point mass (ws_dim 2 and 3), the Panda, a chain of 1 ... 8 joints; every field kind; tracks (point mass, Panda); scenes (all three). */
+#define MPDX_COST_SLOTS (MPDX_MAX_FIELDS + 2)   /* fields 0 ... 3 | GP prior | tool axis */
+int mpdx_traj_costs(const mpdx_guide_params* gp, const float* x_unnormalised, float* cost_out /* [B][MPDX_COST_SLOTS] */,
+                    float* clearance_out /* [B][MPDX_MAX_FIELDS] or NULL */, float* point_out /* [B][n_points][MPDX_MAX_FIELDS + 1] or NULL */,
+                    int n_points, int B, int H, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,7 @@ class StepCoefs(C.Structure):
 
 
 MAX_FIELDS = 4
+COST_SLOTS = MAX_FIELDS + 2              # MPDX_COST_SLOTS: fields 0 ... 3 | GP prior | tool axis
 SCENE_HEADER_WORDS = 2 * MAX_FIELDS      # MPDX_SCENE_HEADER_WORDS
 SCENE_MAX_STAGED_FLOATS = 12 * 1024      # MPDX_SCENE_MAX_STAGED_FLOATS
 FIELD_OBJECTS, FIELD_WORKSPACE, FIELD_SELF, FIELD_GRID = 0, 1, 2, 3
@@ -144,6 +145,7 @@ SIGNATURES = {
     "mpdx_traj_metrics": (_i, [C.POINTER(GuideParams), _vp, _vp, _i, _i, _i, _i, _vp]),
     "mpdx_traj_metrics_mask": (_i, [C.POINTER(GuideParams), _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mpdx_traj_tool_metrics": (_i, [C.POINTER(GuideParams), _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mpdx_traj_costs": (_i, [C.POINTER(GuideParams), _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mpdx_guide_trace": (_i, [C.POINTER(GuideParams), _vp, _vp, _i, _i, _i, _vp, C.POINTER(C.c_longlong)]),
     "mpdx_guide_variant": (_i, [C.POINTER(GuideParams), _i, _i, _i]),
     "mpdx_absmax": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),

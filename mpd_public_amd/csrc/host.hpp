@@ -2,7 +2,7 @@
 // units of libmpdx.so.  The library is built from one host TU (mpdx.hip: model building, tile choice, the launch units of a pass and the ONE walk
 // over them, mpdx_plan's launch schedule and loop, the C ABI, the small streaming kernels; it alone includes fused_build.hpp - the fused-segment builder and build_units - and
 // unet_measure.hpp - the timing / trace entry points and the launch-unit queries) and one TU per kernel family - k_conv.hip (conv_block.hpp), k_ws.hip (conv_ws.hpp), k_fused.hip /
-// k_fused_train.hip (fused_level.hpp), k_guide.hip (guide.hpp), k_chain.hip (chain.hpp), k_ik.hip (ik.hpp), k_grid.hip (the grid producers: edt.hpp, mesh_sdf.hpp, grid_field.hpp's bake), k_attn.hip (attn.hpp), k_inner_run.hip (inner_run.hpp), k_train.hip (train.hpp + train_host.hpp), k_planner.hip
+// k_fused_train.hip (fused_level.hpp), k_guide.hip (guide.hpp), k_chain.hip (chain.hpp), k_costs.hip (costs.hpp), k_ik.hip (ik.hpp), k_grid.hip (the grid producers: edt.hpp, mesh_sdf.hpp, grid_field.hpp's bake), k_attn.hip (attn.hpp), k_inner_run.hip (inner_run.hpp), k_train.hip (train.hpp + train_host.hpp), k_planner.hip
 // (planner.hpp + planner_host.hpp) - so that an edit to one kernel family recompiles that family only (mpd_public_amd/build.py
 // compiles the TUs in parallel and keeps the objects).  A kernel template is instantiated in exactly ONE TU, behind a plain function
 // declared here; no device code crosses a TU (no -fgpu-rdc).

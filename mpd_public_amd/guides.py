@@ -298,6 +298,27 @@ class GuideManagerTrajectoriesWithVelocity(nn.Module):
         if self._params is not None:
             refresh_grid_planes(self._params)
 
+    # ------------------------------------------------------------------------------------------- the values of what the guide differentiates
+    @torch.no_grad()
+    def costs(self, x_normalized, return_clearance=False, return_point_costs=False):
+        """The VALUES of this guide's cost terms on normalised trajectories [B,H,D] (GPU): a planning.TrajectoryCosts - the unweighted terms in the
+        order of cost.cost_l, the composite's weights, their total and, on request, the clearance per collision field and the factor sums per point.
+        Un-normalises with dataset.unnormalize_trajectories and evaluates the guide's own parameter block (mpdx_traj_costs): its interpolate /
+        num_interpolated_points_for_collision, its scene binding, its grids (refresh_grids reaches the block as it does for forward) - the cost the
+        guide differentiates, on the points where it differentiates it.  The reference's contract cost(x, x_interpolated=...,
+        return_invidual_costs_and_weights=True) -> (terms, weights) is (list(c.terms.T), list(c.weights))."""
+        if not self.is_native:
+            raise NotImplementedError("costs() evaluates a CostComposite of the reference's terms on the HIP kernel; this guide differentiates a Python cost "
+                                      "callable - call it directly, cost(x, x_interpolated=..., return_invidual_costs_and_weights=True), as the reference does")
+        if not x_normalized.is_cuda:
+            raise RuntimeError("the guide's costs run on the GPU (libmpdx); there is no CPU fallback")
+        from .planning import TrajectoryCosts, launch_traj_costs
+        x = x_normalized.to(torch.float32)
+        self.check_batch(x.shape[0])
+        xu = self.dataset.unnormalize_trajectories(x).to(torch.float32).contiguous()
+        gp = self.device_params(x.device)
+        return TrajectoryCosts.from_slots(self.cost, *launch_traj_costs(gp, xu, 0, return_clearance, return_point_costs))
+
     # ------------------------------------------------------------------------------------------- guide protocol
     def _forward_autograd(self, x_normalized):
         """guides.py:173-211 verbatim in behaviour, for a Python cost callable: torch autograd on the device."""

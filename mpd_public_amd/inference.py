@@ -94,8 +94,13 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
                trajectory_duration: float = 5.0, device: str = "cuda", debug: bool = True, render: bool = False, seed: int = 30,
                results_dir: str = "logs", model_dir: str = None, model_args: dict = None, sdf_grid_cell_size: float = None,
                sdf_grid_mode: str = "linear", robot=None, goal_ee_pos=None, goal_ee_rot=None, goal_ee_frame=None, tool_axis=None,
-               weight_grad_cost_tool_axis: float = 1e-2, sdf_grid=None, moving_sphere=None, **kwargs):
-    """moving_sphere (extension; None = every obstacle is static, as before): (c0, c1, r) - one more sphere of radius r that moves at constant velocity
+               weight_grad_cost_tool_axis: float = 1e-2, sdf_grid=None, moving_sphere=None, report_costs: bool = False, **kwargs):
+    """report_costs (extension; False = the results are what they were): evaluate the guide's cost composite on the final trajectories
+    (GuideManagerTrajectoriesWithVelocity.costs, mpdx_traj_costs) - the results gain `cost_guide_trajs_final` ([n_samples], the weighted total the guide
+    optimised), `cost_guide_terms_trajs_final` (dict(names=, weights=, terms=[n_samples, n_terms] unweighted)) and `min_clearance_trajs_final` ([n_samples],
+    the smallest distance less the link radius over every collision field; negative: it collides).  `idx_best_traj` keeps the reference's rule (path length
+    plus smoothness).
+    moving_sphere (extension; None = every obstacle is static, as before): (c0, c1, r) - one more sphere of radius r that moves at constant velocity
     from centre c0 at the first support point to c1 at the last (2 or 3 coordinates each, the workspace's).  It is a further collision field of the task
     (planning.PlanningTask(moving_objects=...)): its cost enters the composite as the extra objects' does, the guide pushes every support away from
     the sphere's position at that support's own time, and the reported figures (free / colliding trajectories, collision intensity) are time-aware.
@@ -327,6 +332,15 @@ def experiment(model_id: str = "EnvSpheres3D-RobotPanda", planner_alg: str = "mp
         results_data_dict["fraction_within_tilt"] = float((n_bad == 0).float().mean())
         if debug:
             print(f"tool axis: largest tilt {float(tilt.max()):.3f} rad (allowed {tool_cost.max_tilt:.3f}); within the tilt: {results_data_dict['fraction_within_tilt']*100:.2f} %")
+    if report_costs:
+        tc = guide.costs(trajs_normalized_iters[-1], return_clearance=True)
+        results_data_dict["cost_guide_trajs_final"] = tc.total
+        results_data_dict["cost_guide_terms_trajs_final"] = dict(names=list(tc.names), weights=tc.weights, terms=tc.terms)
+        results_data_dict["min_clearance_trajs_final"] = tc.min_clearance
+        if debug and idx_best_traj is not None:
+            i_best = int(trajs_final_free_idxs[idx_best_traj])
+            print(f"guide cost of the best free trajectory: {float(tc.total[i_best]):.4g}  (" + ", ".join(f"{n} {float(v):.4g}" for n, v in zip(tc.names, tc.terms[i_best]))
+                  + ")" + (f"; clearance {float(tc.min_clearance[i_best]):.4f}" if tc.min_clearance is not None else ""))
     if results_dir:
         out_dir = os.path.join(results_dir, model_id, "results_inference", str(seed))
         os.makedirs(out_dir, exist_ok=True)
@@ -401,6 +415,8 @@ if __name__ == "__main__":
     ap.add_argument("--moving_sphere", type=float, nargs="+", default=None, metavar="V",
                     help="one more sphere that moves at constant velocity during the plan: the coordinates of its centre at the first support point, then those "
                          "at the last, then its radius (5 numbers in a 2-D workspace, 7 in 3-D)")
+    ap.add_argument("--report_costs", action="store_true",
+                    help="also report the guide's cost composite on the final trajectories: the weighted total, every term, and the clearance to the obstacles")
     a = _depth_grid_args(_mesh_grid_args(vars(ap.parse_args())))
     ms = a.pop("moving_sphere")
     if ms is not None:

@@ -519,6 +519,20 @@ class PlanningTask:
         tilt, n_bad = torch.acos(out[:, 0].clamp(-1.0, 1.0)), out[:, 1]
         return (tilt, n_bad, mask.bool()) if return_mask else (tilt, n_bad)
 
+    def trajectory_costs(self, trajs, cost, n_points=None, return_clearance=False, return_point_costs=False):
+        """trajs: UNNORMALISED [B,H,D] on the GPU; cost: a CostComposite of this task's robot, or one of its terms (wrapped with weight 1) -> a
+        TrajectoryCosts: the unweighted value of every term in the order of cost.cost_l, their weighted total and - on request - the clearance per
+        collision field and the factor sums per evaluated point.  The collision and tool terms are evaluated on n_points points of the guide's linear
+        interpolation (default 4 H; H gives the supports), the GP prior on the supports.  mpdx_traj_costs (csrc/costs.hpp::traj_costs_kernel).
+        A task with a moving obstacle needs H to be the track's length (ValueError before any device work)."""
+        trajs, comp = _costs_arguments(self, trajs, cost)
+        H = trajs.shape[1]
+        n_points = int(n_points or 4 * H)
+        from .guides import build_device_params
+        gp, _keep = build_device_params(self.robot, self.env.dim, self.obstacle_cutoff_margin, None, None, comp.cost_l, comp.weight_cost_l, True, 128, True,
+                                        1.0, trajs.device)
+        return TrajectoryCosts.from_slots(comp, *launch_traj_costs(gp, trajs, n_points, return_clearance, return_point_costs))
+
     def get_trajs_collision_and_free(self, trajs, return_indices=False, **kw):
         m = self.trajectory_metrics(trajs)
         coll = m[:, 0] > 0
@@ -730,6 +744,21 @@ class PlanningScenes:
                                                       n_check, B, H, D, _lib.current_stream()), "mpdx_traj_metrics_mask")
         table.record_stream(torch.cuda.current_stream())   # (the launch is asynchronous: the allocator must not hand the table out before it ran)
         return (out, mask.bool()) if return_mask else out
+
+    def trajectory_costs(self, trajs, cost, scene_of_context, n_per_context, n_points=None, return_clearance=False, return_point_costs=False):
+        """PlanningTask.trajectory_costs where the c-th group of n_per_context trajectories is evaluated against scene scene_of_context[c] (the
+        collision terms of `cost` name the task's fields, as the guide's do)."""
+        trajs, comp = _costs_arguments(self.task, trajs, cost)
+        B, H, _ = trajs.shape
+        soc = self.check_assignment(scene_of_context, B, n_per_context)
+        n_points = int(n_points or 4 * H)
+        from .guides import build_device_params
+        gp0, _keep = build_device_params(self.task.robot, self.task.env.dim, self.task.obstacle_cutoff_margin, None, None, comp.cost_l, comp.weight_cost_l,
+                                         True, 128, True, 1.0, trajs.device, scenes=self)
+        gp, table = self.bind(gp0, soc, n_per_context, trajs.device)
+        raw = launch_traj_costs(gp, trajs, n_points, return_clearance, return_point_costs)
+        table.record_stream(torch.cuda.current_stream())   # (the launch is asynchronous: the allocator must not hand the table out before it ran)
+        return TrajectoryCosts.from_slots(comp, *raw)
 
     def get_trajs_collision_and_free(self, trajs, scene_of_context, n_per_context, return_indices=False, **kw):
         m = self.trajectory_metrics(trajs, scene_of_context, n_per_context)
@@ -952,3 +981,107 @@ class CostComposite:
         self.weight_cost_l = list(weights_cost_l) if weights_cost_l is not None else [1.0] * len(self.cost_l)
         if len(self.cost_l) != len(self.weight_cost_l):
             raise ValueError("one weight per cost term")
+
+
+# ------------------------------------------------------------------------------------------------ cost values (mpdx_traj_costs)
+
+
+def as_cost_composite(cost) -> CostComposite:
+    """`cost` itself if it is a CostComposite; a single term wrapped with weight 1; TypeError for anything else"""
+    if isinstance(cost, CostComposite):
+        return cost
+    if isinstance(cost, (CostCollision, CostGPTrajectory, CostToolAxis)):
+        return CostComposite(cost.robot, cost.n_support_points, [cost], weights_cost_l=[1.0])
+    raise TypeError(f"cost: a CostComposite or one of its terms is expected, got {type(cost).__name__}")
+
+
+def cost_term_slots(cost_l):
+    """(names, slots) of the terms of a composite in the order of cost_l: a collision term is named after its field and takes the next of the slots
+    0 ... MPDX_MAX_FIELDS - 1 (the order build_device_params fills fields[] in), the GP prior 'gp' slot MPDX_MAX_FIELDS, the tool-axis term 'tool_axis'
+    the slot behind it (the layout of mpdx_traj_costs' cost_out)."""
+    names, slots, nf = [], [], 0
+    for c in cost_l:
+        if isinstance(c, CostCollision):
+            names.append(getattr(c.field, "name", "") or f"field{nf}")
+            slots.append(nf)
+            nf += 1
+        elif isinstance(c, CostGPTrajectory):
+            names.append("gp")
+            slots.append(_lib.MAX_FIELDS)
+        elif isinstance(c, CostToolAxis):
+            names.append("tool_axis")
+            slots.append(_lib.MAX_FIELDS + 1)
+        else:
+            raise NotImplementedError(type(c))
+    if nf > _lib.MAX_FIELDS:
+        raise NotImplementedError(f"at most {_lib.MAX_FIELDS} collision fields")
+    return names, slots
+
+
+@dataclass
+class TrajectoryCosts:
+    """The values of a cost composite on a batch of trajectories (PlanningTask.trajectory_costs, GuideManagerTrajectoriesWithVelocity.costs): what the
+    reference's cost(x, x_interpolated=..., return_invidual_costs_and_weights=True) returns, plus how close each trajectory comes to each field."""
+    names: List[str]                               # the terms in the order of cost.cost_l: field names, 'gp', 'tool_axis'
+    weights: torch.Tensor                          # [n_terms] the composite's weights
+    terms: torch.Tensor                            # [B, n_terms] UNWEIGHTED term values
+    total: torch.Tensor                            # [B] = terms @ weights
+    clearance: Optional[torch.Tensor] = None       # [B, n_collision_terms]: smallest distance less the link radius per field (negative: it collides)
+    point_costs: Optional[torch.Tensor] = None     # [B, n_points, n_collision_terms (+ 1 with a tool term)]: the unweighted factor sum per evaluated point
+
+    @property
+    def min_clearance(self):
+        """[B] the smallest clearance over the collision terms (None without return_clearance, or without a collision term)"""
+        if self.clearance is None or self.clearance.shape[-1] == 0:
+            return None
+        return self.clearance.amin(-1)
+
+    @classmethod
+    def from_slots(cls, comp: CostComposite, cost_raw, clearance_raw=None, point_raw=None):
+        """From the raw outputs of mpdx_traj_costs: cost_raw [B, MPDX_COST_SLOTS], clearance_raw [B, MPDX_MAX_FIELDS] or None, point_raw
+        [B, n_points, MPDX_MAX_FIELDS + 1] or None - the slots picked and ordered as comp.cost_l lists the terms."""
+        names, slots = cost_term_slots(comp.cost_l)
+        idx = torch.tensor(slots, dtype=torch.long, device=cost_raw.device)
+        terms = cost_raw.index_select(-1, idx)
+        weights = torch.tensor([float(w) for w in comp.weight_cost_l], dtype=terms.dtype, device=terms.device)
+        coll = [s for s in slots if s < _lib.MAX_FIELDS]     # (ascending: the collision terms take the slots in their order)
+        cols = coll + ([_lib.MAX_FIELDS] if _lib.MAX_FIELDS + 1 in slots else [])
+        clearance = clearance_raw[:, :len(coll)].contiguous() if clearance_raw is not None else None
+        points = point_raw.index_select(-1, torch.tensor(cols, dtype=torch.long, device=point_raw.device)) if point_raw is not None else None
+        return cls(names, weights, terms, terms @ weights, clearance, points)
+
+
+def launch_traj_costs(gp, trajs, n_points, return_clearance=False, return_point_costs=False):
+    """mpdx_traj_costs on UNNORMALISED float32 [B,H,D] GPU trajectories with the block gp; n_points = 0: the block's own points.  Returns the raw
+    (cost [B, COST_SLOTS], clearance [B, MAX_FIELDS] or None, point costs [B, n_points, MAX_FIELDS + 1] or None)."""
+    import ctypes as C
+    B, H, D = trajs.shape
+    n_eval = int(n_points) if n_points else (int(gp.n_interp) if gp.interpolate else H)
+    cost = torch.empty((B, _lib.COST_SLOTS), dtype=torch.float32, device=trajs.device)
+    clr = torch.empty((B, _lib.MAX_FIELDS), dtype=torch.float32, device=trajs.device) if return_clearance else None
+    pts = torch.empty((B, max(n_eval, 0), _lib.MAX_FIELDS + 1), dtype=torch.float32, device=trajs.device) if return_point_costs else None
+    _lib.check(_lib.load().mpdx_traj_costs(C.byref(gp), trajs.data_ptr(), cost.data_ptr(), _lib.ptr(clr), _lib.ptr(pts), int(n_points or 0), B, H, D,
+                                           _lib.current_stream()), "mpdx_traj_costs")
+    return cost, clr, pts
+
+
+def _costs_arguments(task, trajs, cost):
+    """the checks PlanningTask.trajectory_costs and PlanningScenes.trajectory_costs make before any device work; returns (trajs float32, composite)"""
+    comp = as_cost_composite(cost)
+    robot = task.robot
+    for c in comp.cost_l:
+        if not isinstance(c, (CostCollision, CostGPTrajectory, CostToolAxis)):
+            raise TypeError(f"cost term {type(c).__name__}: CostCollision, CostGPTrajectory or CostToolAxis is expected")
+        same_chain = isinstance(robot, RobotChain) and isinstance(c.robot, RobotChain) and c.robot.q_dim == robot.q_dim
+        if c.robot is not robot and not same_chain:
+            raise ValueError(f"the {type(c).__name__} term was built for another robot than this task's")
+    cost_term_slots(comp.cost_l)
+    if trajs.dim() != 3:
+        raise ValueError(f"trajs: [B, H, D] is expected, got {tuple(trajs.shape)}")
+    if task.has_tracks:   # (before any device work, as trajectory_metrics)
+        for f in task.get_collision_fields():
+            if field_track(f) is not None:
+                f.objects.track_rows(trajs.shape[1])
+    if not trajs.is_cuda:
+        raise RuntimeError("trajectory costs run on the GPU (libmpdx); there is no CPU fallback")
+    return trajs.to(torch.float32).contiguous(), comp
